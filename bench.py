@@ -7,7 +7,11 @@ DAISY x2 -> per-cell exact 5-NN proposals -> neighbour proposals -> 4 BCD sweeps
 N > 1: one process per GPU (torch.distributed over RCCL); every rank processes its own pairs (weak scaling,
 no data-path collective) and the flow fields are gathered on rank 0 over xGMI after every step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+The timed region is exactly K steps.  --dump-outputs DIR writes what the last timed step returned (the flow field, and on
+rank 0 of a multi-rank run the fields gathered from every rank) as DIR/<name>.npy; the inputs depend only on the arguments,
+so two builds can be compared output for output.
 
 `python bench.py --gpus N` (N > 1, no RANK in the environment) starts its N ranks itself -- before anything touches the
 GPU -- and relays rank 0's JSON line; under `python -m torch.distributed.run ... bench.py --gpus N` the ranks are the
@@ -27,7 +31,8 @@ sys.path.insert(0, ROOT)
 PKG = "lk-s-2022-estimacija-pokreta_amd"
 
 H, W, BCD_TIMES = 436, 1024, 4
-LONG_STEPS = 98                # the default --steps; a run with another --steps adds one timed region of this length
+LONG_STEPS = 98                # the default --steps; --long-run adds one timed region of this length to a run with another --steps
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: all files together
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/F16 MFMA ~2.5 PF dense (the kNN screen runs on f16 MFMA)
 PMC_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")   # rocprofv3 --pmc passes of this command (tracked)
@@ -363,6 +368,7 @@ class GpuEngine:
         self.bcd_events = []
         self.gather = None
         self.jobs = None
+        self.last = None                        # (flow, gather slot) of the latest step
 
     def like(self):
         return self.flows[0].flow
@@ -386,6 +392,7 @@ class GpuEngine:
             flow = df.vratiKonacniFlow()
             if self.gather is not None:
                 self.gather(flow, i % self.P)
+        self.last = (flow, i % self.P)
         return flow
 
     def begin(self, nsteps):
@@ -441,6 +448,7 @@ class BatchEngine:
         self.group_no = 0
         self.nsteps = None
         self.jobs = None                        # explicit (image 1, image 2) per step (the fixed batch); None: the two resident pairs in turn
+        self.last = None                        # (flow, gather slot) of the latest step
 
     def like(self):
         return self.flows[0].flow
@@ -513,6 +521,7 @@ class BatchEngine:
                 flow = df.vratiKonacniFlow()
                 if self.gather is not None:
                     self.gather(flow, j)
+                self.last = (flow, j)
             done = torch.cuda.Event()
             done.record()
             self.set_free[k] = done
@@ -535,6 +544,7 @@ class StubEngine:
         self.field = torch.full((8, 8, 2), float(rank), dtype=torch.float32)
         self.gather = None
         self.jobs = None
+        self.last = None
 
     def make_jobs(self, passes):
         return [None] * len(passes)
@@ -548,6 +558,7 @@ class StubEngine:
     def step(self, i, timed):
         if self.gather is not None:
             self.gather(self.field, 0)
+        self.last = (self.field, 0)
         return self.field
 
     def begin(self, nsteps):
@@ -623,6 +634,33 @@ def run_fixed_batch(eng, npasses, world, rank, use_dist, sync_all):
     return rec
 
 
+# ---------------------------------------------------------------------------------------------------- outputs
+def dump_outputs(dirname, eng, gathered, world):
+    """--dump-outputs: the arrays the last timed step handed back, read before anything else reuses their buffers.
+    flow.npy = this rank's (H,W,2) float32 [dy,dx] field; flow_by_rank.npy = the (world,H,W,2) fields rank 0 gathered in
+    that step (multi-rank runs).  An array that would take the files past DUMP_BYTES_MAX is replaced by a fixed, seeded
+    sample of its elements (<name>.npy) and their flat indices (<name>_index.npy, float64)."""
+    import numpy as np
+    eng.sync()
+    flow, slot = eng.last
+    arrays = [("flow", flow)]
+    if gathered is not None and world > 1:
+        arrays.append(("flow_by_rank", eng.torch.stack(gathered[slot])))
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES_MAX - 4 * 4096            # .npy headers
+    for name, t in arrays:
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > left:
+            k = max(0, left // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+
+
 # ---------------------------------------------------------------------------------------------------- worker
 def worker(args):
     import torch
@@ -639,6 +677,7 @@ def worker(args):
     # under a launcher (ours or torch.distributed.run) the process group is always created, also for one rank, which
     # exercises the same RCCL gather path; a plain `python bench.py` runs without torch.distributed
     use_dist = "RANK" in os.environ
+    bufs = None
     if use_dist:
         # the communication libraries print banners (RCCL: version / host, gloo: connection lines) on STDOUT when the first
         # communicator comes up; stdout must carry the JSON line only, so fd 1 points at stderr until that has happened
@@ -685,9 +724,11 @@ def worker(args):
         return d
 
     dt = timed_region(args.steps, True)
-    # the driver's 20 steps are 0.2 s: one more region of the default length (98 steps, 14 groups of 7: fill and drain of the
-    # two-group pipeline weigh < 10 %) right behind it, reported beside the headline, never instead of it
-    dt_long = timed_region(LONG_STEPS, False) if (args.steps != LONG_STEPS and not args.no_long_run and not args.stub) else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, bufs, world)
+    # --long-run: the driver's 20 steps are 0.2 s; one more region of the default length (98 steps, 14 groups of 7: fill and
+    # drain of the two-group pipeline weigh < 10 %) right behind it, reported beside the headline, never instead of it
+    dt_long = timed_region(LONG_STEPS, False) if (args.steps != LONG_STEPS and args.long_run and not args.stub) else None
 
     fixed = run_fixed_batch(eng, args.fixed_batch, world, rank, use_dist, sync_all) if args.fixed_batch > 0 else None
 
@@ -934,7 +975,11 @@ def main():
     ap.add_argument("--steps", type=int, default=LONG_STEPS)       # 14 groups of 7: the fill and drain of the two-group pipeline weigh < 10 %
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-long-run", action="store_true", help="skip the extra timed region of %d steps (ms_per_step_%d)" % (LONG_STEPS, LONG_STEPS))
+    ap.add_argument("--long-run", action="store_true",
+                    help="after the --steps region, time one more region of %d steps (ms_per_step_%d)" % (LONG_STEPS, LONG_STEPS))
+    ap.add_argument("--no-long-run", action="store_true", help=argparse.SUPPRESS)   # the default; kept for recorded commands
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the one-GPU timings of BASELINE configs[2] and [4]")
     ap.add_argument("--inflight", type=int, default=3,
                     help="independent pairs in flight per GPU (each on its own HIP stream and workspace)")

@@ -33,6 +33,22 @@ def test_bench_self_launches_two_ranks():
     assert abs(fb["Mpix/s"] - 16 * 436 * 1024 / (fb["ms"] * 1e-3) / 1e6) < 1e-6 * fb["Mpix/s"]
 
 
+def test_dump_outputs_of_the_last_step(tmp_path):
+    # rank 0's own field and the fields it gathered from both ranks in the last timed step
+    import numpy as np
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert sorted(os.listdir(tmp_path)) == ["flow.npy", "flow_by_rank.npy"]
+    flow, by_rank = np.load(tmp_path / "flow.npy"), np.load(tmp_path / "flow_by_rank.npy")
+    assert flow.dtype == by_rank.dtype == np.float32 and flow.shape == (8, 8, 2) and by_rank.shape == (2, 8, 8, 2)
+    assert (flow == 0).all() and (by_rank[0] == 0).all() and (by_rank[1] == 1).all()
+    # one process without a launcher: no gather, the field alone
+    one = tmp_path / "one"
+    out = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--stub", "--dump-outputs", str(one)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert sorted(os.listdir(one)) == ["flow.npy"]
+
+
 def test_fixed_batch_with_a_ragged_share():
     # 5 passes over 2 ranks: rank 0 has 3, rank 1 has 2 and must still take part in the third gather
     out = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--stub", "--fixed-batch", "5"])

@@ -874,6 +874,32 @@ def test_bench_two_ranks_rehearsal(torch_, tmp_path):
     assert d["config"]["mode"] == "batch" and d["roofline"]["kernel"] in ("bcd_chain_kernel", "knn_screen_kernel")
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(torch_, oracle, synth, tmp_path):
+    """--dump-outputs writes the flow the LAST timed step returned (4 steps in groups of 2: step 3 = resident pair 1, the
+    second pass of the second batched group), every pixel equal to the oracle's pass over that pair; --steps alone sets
+    the timed steps (no extra long region in the line)."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "2",
+                          "--no-cpu-baseline", "--no-other-configs", "--fixed-batch", "0", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
+    assert d["steps"] == 4 and not any(k.startswith(("ms_per_step_", "value_")) for k in d)
+    assert sorted(os.listdir(dump)) == ["flow.npy"]
+    got = np.load(dump / "flow.npy")
+    assert got.dtype == np.float32 and got.shape == (436, 1024, 2)
+    O = oracle
+    O.set_threads(16)
+    try:
+        img1, img2, _ = synth.make_pair(436, 1024, seed=synth.pair_seed(1, 0))
+        ref = O.full_pass(O.make_params(436, 1024, 27, 64, seed=0), img1, img2, 4)
+    finally:
+        O.set_threads(1)
+    assert np.array_equal(got.astype(np.float64), ref["flows"][-1])
+
+
 def test_cli_kitti_png_branch(torch_, oracle, synth, tmp_path, monkeypatch):
     """The reference's own input path (daisy i flann.py:19-27,34-35,52-53): 8-bit PNGs under
     ../data_scene_flow/training/image_2/0001<idx>_1{0,1}.png, cropped to 1241x375 at (0,0), cells 73x25; backward swaps the
