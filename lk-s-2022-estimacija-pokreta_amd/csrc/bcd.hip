@@ -80,8 +80,6 @@ struct BcdPlanes {
     uint32_t pool_rows;
 };
 
-template <int V> struct BcdC { static constexpr int value = V; };
-
 // ------------------------------------------------------------------------------------------------ lists
 // grid: one wave per pixel q, as the PREDECESSOR: q's labels are the wave-uniform side of the tests for both pixels that
 // have q in front of them -- its successor on the column chain (dir 0) and on the row chain (dir 1) -- so the scalar loads
@@ -172,7 +170,7 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
             }
         }
     };
-    if (fifth) build(BcdC<1>()); else build(BcdC<0>());
+    if (fifth) build(IntC<1>()); else build(IntC<0>());
 
     // One group of 64 labels: member lists, blocks, pool rows.  MERGED = the fifth group (two pixels, 32 labels each): label,
     // count and output rows are per lane, ranks are taken inside each half.
@@ -227,10 +225,10 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
                 }
             };
             // slots 5..9 / 10..14 only if some label of the wave has that many members (wave-uniform: 97 % / 25 % of the waves)
-            slots(BcdC<0>(), BcdC<BCD_BLK>());
+            slots(IntC<0>(), IntC<BCD_BLK>());
             if (__ballot(n > BCD_BLK)) {
-                slots(BcdC<BCD_BLK>(), BcdC<2 * BCD_BLK>());
-                if (__ballot(n > 2 * BCD_BLK)) slots(BcdC<2 * BCD_BLK>(), BcdC<BCD_LIST>());
+                slots(IntC<BCD_BLK>(), IntC<2 * BCD_BLK>());
+                if (__ballot(n > 2 * BCD_BLK)) slots(IntC<2 * BCD_BLK>(), IntC<BCD_LIST>());
             }
         }
         // bytes 0..3 | 4, 5..8 | 9, 10..13 | 14 and nibbles 0..4, 5..9, 10..14 -> the three blocks
@@ -280,14 +278,14 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
     };
     const size_t pd0 = (size_t)p0 * 2 + 0, pd1 = (size_t)p1 * 2 + 1;
     if (v0) {
-        emit(BcdC<0>(), m[0], f[0], 0, lane, tn0, true, pd0);
-        if (LP > 64) emit(BcdC<0>(), m[1], f[1], 1, 64 + lane, tn0, true, pd0);
+        emit(IntC<0>(), m[0], f[0], 0, lane, tn0, true, pd0);
+        if (LP > 64) emit(IntC<0>(), m[1], f[1], 1, 64 + lane, tn0, true, pd0);
     }
     if (v1) {
-        emit(BcdC<0>(), m[2], f[2], 0, lane, tn1, true, pd1);
-        if (LP > 64) emit(BcdC<0>(), m[3], f[3], 1, 64 + lane, tn1, true, pd1);
+        emit(IntC<0>(), m[2], f[2], 0, lane, tn1, true, pd1);
+        if (LP > 64) emit(IntC<0>(), m[3], f[3], 1, 64 + lane, tn1, true, pd1);
     }
-    if (LP > 128) emit(BcdC<1>(), m[4], f[4], 2, 128 + (lane & 31), half ? tn1 : tn0, half ? v1 : v0, half ? pd1 : pd0);
+    if (LP > 128) emit(IntC<1>(), m[4], f[4], 2, 128 + (lane & 31), half ? tn1 : tn0, half ? v1 : v0, half ? pd1 : pd0);
 }
 
 // ------------------------------------------------------------------------------------------------ chains
@@ -387,8 +385,6 @@ __device__ static inline unsigned long long wave_key_min_asm(unsigned long long 
     *first_lane = fl;
     return ((unsigned long long)mh << 32) | ml;
 }
-
-template <int V> struct IntC { static constexpr int value = V; };
 
 __device__ static inline uint32_t lane_rank(unsigned long long mask)
 {

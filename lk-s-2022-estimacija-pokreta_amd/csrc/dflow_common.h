@@ -16,7 +16,26 @@ struct Geom {
     __host__ __device__ int y0(int cj) const { return cj * ch; }
     __host__ __device__ int x1(int ci) const { return ci == ncx - 1 ? W : (ci + 1) * cw; }
     __host__ __device__ int y1(int cj) const { return cj == ncy - 1 ? H : (cj + 1) * ch; }
+    // the candidate cells of query cell (qci, qcj): [imin, imax] x [jmin, jmax]; slot = its place in the reference order
+    // (ci outer, cj inner: Q2)
+    struct Window {
+        int imin, imax, jmin, jmax;
+        __host__ __device__ int slot(int ci, int cj) const { return (ci - imin) * (jmax - jmin + 1) + (cj - jmin); }
+    };
+    __host__ __device__ Window window(int qci, int qcj) const
+    {
+        return {max(0, qci - win), min(ncx - 1, qci + win), max(0, qcj - win), min(ncy - 1, qcj + win)};
+    }
 };
+
+// pixels of the largest cell (the last one: the ragged cells are the larger ones)
+__host__ __device__ static inline int max_cell_points(const Geom &g)
+{
+    return (g.x1(g.ncx - 1) - g.x0(g.ncx - 1)) * (g.y1(g.ncy - 1) - g.y0(g.ncy - 1));
+}
+
+// a compile-time int as a type (selects an instantiation of a generic lambda)
+template <int V> struct IntC { static constexpr int value = V; };
 
 static inline Geom make_geom(const dflow_params *p)
 {
@@ -80,6 +99,43 @@ __device__ static inline float np_pairwise_sum68(const float *a)
 #pragma unroll
     for (int i = 64; i < DFLOW_DESC; i++) res = __fadd_rn(res, a[i]);
     return res;
+}
+
+// The canonical pair arithmetic of the kNN stage, for query q and candidate c (as 17 float4): l2 = squared L2 of q - c as a
+// sequential fmaf chain over k = 0..67; l1() = sum_k |q[k]-c[k]| in numpy's float32 pairwise order (8 running sums, a tree,
+// then the 4-element tail; l1_cost_np), summed where it is used so that a kernel that needs it only for some pairs pays
+// the tree only for those.  Every kernel that must agree bit for bit with the brute-force search uses it.
+struct PairDist {
+    float l2, rs[8], tl[4];
+    __device__ float l1() const
+    {
+        float l1 = ((rs[0] + rs[1]) + (rs[2] + rs[3])) + ((rs[4] + rs[5]) + (rs[6] + rs[7]));
+        l1 = l1 + tl[0]; l1 = l1 + tl[1]; l1 = l1 + tl[2]; l1 = l1 + tl[3];
+        return l1;
+    }
+};
+typedef float dflow_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ static PairDist pair_dist(const float (&q)[DFLOW_DESC], const float4 (&c)[DFLOW_DESC / 4])
+{
+    PairDist d;
+    d.l2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < DFLOW_DESC / 4; k++) {
+        const float4 v = c[k];
+        // two differences per instruction (v_pk_add_f32 with negated operand: the same IEEE subtraction per half)
+        const dflow_f2 ea = (dflow_f2){q[4 * k], q[4 * k + 1]} - (dflow_f2){v.x, v.y};
+        const dflow_f2 eb = (dflow_f2){q[4 * k + 2], q[4 * k + 3]} - (dflow_f2){v.z, v.w};
+        const float e[4] = {ea.x, ea.y, eb.x, eb.y};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            d.l2 = __fmaf_rn(e[i], e[i], d.l2);
+            const int j = (4 * k + i) & 7;
+            if (k < 2) d.rs[j] = fabsf(e[i]);
+            else if (k < 16) d.rs[j] = d.rs[j] + fabsf(e[i]);
+            else d.tl[i] = fabsf(e[i]);
+        }
+    }
+    return d;
 }
 
 // sum_k |a[k]-b[k]| in numpy's float32 pairwise order (np.sum(np.absolute(..)), daisy i flann.py:179-180).

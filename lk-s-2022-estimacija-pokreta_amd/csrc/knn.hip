@@ -152,13 +152,20 @@ __global__ void __launch_bounds__(KNN_THREADS, 4) knn_exact_kernel(KnnArgs a, co
 #define KNN_FIX_CHUNK 64              // candidates per LDS chunk (four per wave)
 #define KNN_FIX_BLOCKS 256            // one per CU: a launch that finds no item costs 4 096 wave starts (1 024 blocks: 16 384, which
                                   // delayed the stream by a millisecond when other kernels held the CUs)
-__device__ static inline void top5_insert(Top5 &t, float cd, int cidx)
+// sorted insertion into an ascending top 5: the entry goes in front of the first slot it beats, and every later entry shifts
+// down unconditionally (a displaced entry must stay in front of an equal one that followed it).  top5_insert: beats = a
+// smaller distance (a sequential scan, where equal distances arrive in index order); top5_merge: a smaller distance, or an
+// equal one with a smaller index (entries of another scan, the (distance, index) rule applied explicitly).
+template <bool BY_INDEX> __device__ static inline void top5_place(Top5 &t, float cd, int cidx)
 {
     bool sh = false;
-#define CSWAP(D, I) if (sh || cd < D) { float td = D; int ti = I; D = cd; I = cidx; cd = td; cidx = ti; sh = true; }
-    CSWAP(t.d0, t.i0) CSWAP(t.d1, t.i1) CSWAP(t.d2, t.i2) CSWAP(t.d3, t.i3) CSWAP(t.d4, t.i4)
-#undef CSWAP
+    auto slot = [&](float &d, int &i) {
+        if (sh || cd < d || (BY_INDEX && cd == d && cidx < i)) { const float td = d; const int ti = i; d = cd; i = cidx; cd = td; cidx = ti; sh = true; }
+    };
+    slot(t.d0, t.i0); slot(t.d1, t.i1); slot(t.d2, t.i2); slot(t.d3, t.i3); slot(t.d4, t.i4);
 }
+__device__ static inline void top5_insert(Top5 &t, float cd, int cidx) { top5_place<false>(t, cd, cidx); }
+__device__ static inline void top5_merge(Top5 &t, float cd, int cidx) { top5_place<true>(t, cd, cidx); }
 
 template <typename T>
 __global__ void __launch_bounds__(64 * KNN_FIX_WAVES) knn_fix_kernel(KnnArgs a, const T *__restrict__ gd1, const T *__restrict__ gd2,
@@ -181,11 +188,10 @@ __global__ void __launch_bounds__(64 * KNN_FIX_WAVES) knn_fix_kernel(KnnArgs a, 
             int b = item;
             const int wslot = b % (win * win); b /= win * win;
             qstart = (b % qwaves) * 64; qcell = b / qwaves;
-            const int qci = qcell % g.ncx, qcj = qcell / g.ncx;
-            const int cimin = max(0, qci - g.win), cjmin = max(0, qcj - g.win), cjmax = min(g.ncy - 1, qcj + g.win);
-            const int ncyw = cjmax - cjmin + 1;
-            ci = cimin + wslot / ncyw; cj = cjmin + wslot % ncyw;
-            if (ci > min(g.ncx - 1, qci + g.win)) continue;
+            const Geom::Window w = g.window(qcell % g.ncx, qcell / g.ncx);
+            const int ncyw = w.jmax - w.jmin + 1;
+            ci = w.imin + wslot / ncyw; cj = w.jmin + wslot % ncyw;
+            if (ci > w.imax) continue;
         } else {
             int4 e = ovf_list[item];
             qcell = e.x; qstart = e.y; ci = e.z; cj = e.w;
@@ -198,8 +204,7 @@ __global__ void __launch_bounds__(64 * KNN_FIX_WAVES) knn_fix_kernel(KnnArgs a, 
         if (!active) qi = qnpts - 1;
         const int qy = qy0 + qi / qcw, qx = qx0 + qi % qcw;
         const size_t pix = (size_t)qy * g.W + qx;
-        const int cimin = max(0, qci - g.win), cjmin = max(0, qcj - g.win), cjmax = min(g.ncy - 1, qcj + g.win);
-        const int slot = 5 * ((ci - cimin) * (cjmax - cjmin + 1) + (cj - cjmin));
+        const int slot = 5 * g.window(qci, qcj).slot(ci, cj);
         float q[DFLOW_DESC];
         desc_load_row(q, gd1, pix);
         constexpr int P = DescPitch<T>::value;
@@ -272,14 +277,8 @@ __global__ void __launch_bounds__(64 * KNN_FIX_WAVES) knn_fix_kernel(KnnArgs a, 
             // with a smaller index.  Slots still at their initial (inf, 0) hold no candidate and are skipped.
             for (int w = 1; w < KNN_FIX_WAVES; w++)
 #pragma unroll
-                for (int j = 0; j < 5; j++) {
-                    float cd = pd[w][j][lane]; int cidx = pi[w][j][lane];
-                    if (!(cd < INFINITY)) continue;
-                    bool sh = false;
-#define CSWAP(D, I) if (sh || cd < D || (cd == D && cidx < I)) { float td = D; int ti = I; D = cd; I = cidx; cd = td; cidx = ti; sh = true; }
-                    CSWAP(t.d0, t.i0) CSWAP(t.d1, t.i1) CSWAP(t.d2, t.i2) CSWAP(t.d3, t.i3) CSWAP(t.d4, t.i4)
-#undef CSWAP
-                }
+                for (int j = 0; j < 5; j++)
+                    if (pd[w][j][lane] < INFINITY) top5_merge(t, pd[w][j][lane], pi[w][j][lane]);
             float c[5];
             emit_cell(t, g, ci, cj, pix, qy, qx, slot, a.LP, a.tphi, active, gd1, gd2, gproposals, glcosts, c);
         }
@@ -293,8 +292,7 @@ int launch_knn(const dflow_params *p, const void *d1, const void *d2, uint32_t *
     KnnArgs a;
     a.g = make_geom(p);
     a.LP = p->label_pitch; a.tphi = p->tphi;
-    int maxpts = (a.g.x1(a.g.ncx - 1) - a.g.x0(a.g.ncx - 1)) * (a.g.y1(a.g.ncy - 1) - a.g.y0(a.g.ncy - 1));
-    a.chunks = (maxpts + KNN_THREADS - 1) / KNN_THREADS;
+    a.chunks = (max_cell_points(a.g) + KNN_THREADS - 1) / KNN_THREADS;
     int nblocks = a.g.ncx * a.g.ncy * a.chunks;
     if (descr_f16(p))
         hipLaunchKernelGGL(knn_exact_kernel<_Float16>, dim3(nblocks), dim3(KNN_THREADS), 0, s, a, (const _Float16 *)d1, (const _Float16 *)d2, proposals, lcosts, nprop, bestlabels);
@@ -309,8 +307,7 @@ int launch_knn_fix(const dflow_params *p, const void *d1, const void *d2, uint32
     KnnArgs a;
     a.g = make_geom(p);
     a.LP = p->label_pitch; a.tphi = p->tphi; a.chunks = 0;
-    int maxpts = (a.g.x1(a.g.ncx - 1) - a.g.x0(a.g.ncx - 1)) * (a.g.y1(a.g.ncy - 1) - a.g.y0(a.g.ncy - 1));
-    int qwaves = (maxpts + 63) / 64;
+    int qwaves = (max_cell_points(a.g) + 63) / 64;
     if (descr_f16(p))
         hipLaunchKernelGGL(knn_fix_kernel<_Float16>, dim3(KNN_FIX_BLOCKS), dim3(64 * KNN_FIX_WAVES), 0, s, a, (const _Float16 *)d1, (const _Float16 *)d2, proposals,
                            lcosts, ovf_count, ovf_list, ovf_cap, flags, qwaves);

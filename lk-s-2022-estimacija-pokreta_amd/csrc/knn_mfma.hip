@@ -61,7 +61,6 @@
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int V> struct KmC { static constexpr int value = V; };
 
 #define KM_ALPHA 64.0f
 #define KM_K 48                 // f16 per prepared row (96 bytes)
@@ -120,6 +119,7 @@ __device__ static inline size_t list_id(const KmGeom &a, int qcell, int qwave, i
 // (tile, row) of cell c holds candidate row * ntiles + tile of that cell (see the screen kernel), positions without a
 // candidate hold the sentinel row.  The screen then stages a chunk as one contiguous 18 KB read.
 __host__ __device__ static inline int km_pad(int npts) { return (npts + KM_CHUNK - 1) / KM_CHUNK * KM_CHUNK; }
+__host__ __device__ static inline int km_ntiles(int npts) { return km_pad(npts) / 32; }     // 32-row tiles of a padded cell
 __host__ __device__ static inline size_t km_cell_base(const Geom &g, int ci, int cj)
 {
     const int wl = g.x1(g.ncx - 1) - g.x0(g.ncx - 1), hl = g.y1(g.ncy - 1) - g.y0(g.ncy - 1);
@@ -181,8 +181,7 @@ __global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d, 
         const int pos = blockIdx.x * blockDim.x + threadIdx.x;
         if (pos >= km_pad(cnpts)) return;
         orow = km_cell_base(g, ci, cj) + pos;
-        const int ntiles = km_pad(cnpts) / 32;
-        const int idx = (pos & 31) * ntiles + (pos >> 5);
+        const int idx = (pos & 31) * km_ntiles(cnpts) + (pos >> 5);
         if (idx >= cnpts) {
             km_store_sentinel(h + orow * KM_K);
             z0[orow] = make_float2(INFINITY, 0.0f);
@@ -194,21 +193,11 @@ __global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d, 
     float x[DFLOW_DESC];
     desc_load_row(x, d, (size_t)pix);
     if (which == 1) {
-        // what an all-zero query would compute for this candidate: e = 0 - c_k, acc = fmaf(e, e, acc) over k = 0..67, and
-        // sum |e| in numpy's pairwise order (knn_resolve_kernel, l1_cost_np)
-        float acc = 0.0f, rs[8];
-#pragma unroll
-        for (int k = 0; k < DFLOW_DESC; k++) acc = __fmaf_rn(x[k], x[k], acc);
-#pragma unroll
-        for (int j = 0; j < 8; j++) rs[j] = fabsf(x[j]);
-#pragma unroll
-        for (int i = 8; i < 64; i += 8)
-#pragma unroll
-            for (int j = 0; j < 8; j++) rs[j] = rs[j] + fabsf(x[i + j]);
-        float l1 = ((rs[0] + rs[1]) + (rs[2] + rs[3])) + ((rs[4] + rs[5]) + (rs[6] + rs[7]));
-#pragma unroll
-        for (int i = 64; i < DFLOW_DESC; i++) l1 = l1 + fabsf(x[i]);
-        z0[orow] = make_float2(acc, l1);
+        // what an all-zero query computes for this candidate (knn_resolve_kernel).  The pair arithmetic is symmetric bit for
+        // bit (squares and |.| of q - c and c - q are equal), and with the zero as the second row x - 0 folds to x.
+        const float4 zero[DFLOW_DESC / 4] = {};
+        const PairDist zd = pair_dist(x, zero);
+        z0[orow] = make_float2(zd.l2, zd.l1());
     }
     double sxall = 0.0;
     bool bad = false;
@@ -292,7 +281,7 @@ __global__ void __launch_bounds__(256) knn_cell_post_kernel(_Float16 *__restrict
     __shared__ unsigned long long wmin[4];
     const int ci = blockIdx.x % g.ncx, cj = blockIdx.x / g.ncx;
     const int cnpts = (g.x1(ci) - g.x0(ci)) * (g.y1(cj) - g.y0(cj));
-    const int npad = km_pad(cnpts), ntiles = npad / 32;
+    const int npad = km_pad(cnpts), ntiles = km_ntiles(cnpts);
     const size_t base = km_cell_base(g, ci, cj);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int running = 0;
@@ -405,8 +394,7 @@ __global__ void __launch_bounds__(KM_THREADS, 4) knn_screen_kernel(KmGeom a, KmS
     if (!wave_active) { qci = fqci; qcj = fqcj; qwave = 0; }         // they shadow a valid query wave and store nothing
     const int qcell = qcj * g.ncx + qci;
     const int qx0 = g.x0(qci), qy0 = g.y0(qcj), qcw = g.x1(qci) - qx0, qnpts = qcw * (g.y1(qcj) - qy0);
-    const int cimin = max(0, qci - g.win), cjmin = max(0, qcj - g.win), cjmax = min(g.ncy - 1, qcj + g.win);
-    const int wslot = (ci - cimin) * (cjmax - cjmin + 1) + (cj - cjmin);   // reference order: ci outer, cj inner (Q2)
+    const int wslot = g.window(qci, qcj).slot(ci, cj);
     const int cx0 = g.x0(ci), cy0 = g.y0(cj), ccw = g.x1(ci) - cx0, cnpts = ccw * (g.y1(cj) - cy0);
     (void)cx0; (void)cy0;
 
@@ -593,7 +581,7 @@ __global__ void __launch_bounds__(KM_THREADS, 4) knn_screen_kernel(KmGeom a, KmS
             const int buf = chunk % KM_NBUF;
             stage(chunk + KM_NBUF - 1, (chunk + KM_NBUF - 1) % KM_NBUF);                // that buffer was released by the previous barrier
             const char *ab = abuf + (size_t)buf * KM_ABUF;
-            if (wave_active) { if (pass == 0) tiles(KmC<0>(), chunk, ab); else tiles(KmC<1>(), chunk, ab); }
+            if (wave_active) { if (pass == 0) tiles(IntC<0>(), chunk, ab); else tiles(IntC<1>(), chunk, ab); }
             else if (pass == 1) dummy_stores();
             wait_ring(pass);
         }
@@ -700,6 +688,48 @@ __device__ static inline void key_insert(unsigned long long (&k)[5], float (&c)[
         k[i] = lo; c[i] = clo; x = hi; xc = chi;
     }
 }
+static constexpr unsigned long long KM_NO_KEY = 0x7F800000FFFFFFFFull;    // an empty top-5 entry: (+inf, no index)
+
+// accumulator register r of half-lane h is tile row 4 h + (r & 3) + 8 (r >> 2) of the screen's MFMA, and tile row `row`
+// holds candidate row * ntiles + tile of the cell (knn_prep_kernel)
+__device__ static inline int km_event_cand(int h, int r, int tile, int ntiles) { return (4 * h + (r & 3) + 8 * (r >> 2)) * ntiles + tile; }
+
+// the descriptor of image-1 pixel qpix into q[]
+template <bool F16>
+__device__ __forceinline__ void km_load_query(typename RowsOf<F16>::type &rows, const void *d1, size_t qpix, float (&q)[DFLOW_DESC])
+{
+    rows.issue((rs_gptr)d1, (uint32_t)qpix * RowsOf<F16>::PIECES, true);
+    float4 qv[DFLOW_DESC / 4];
+    rows.fetch(qv);
+#pragma unroll
+    for (int k = 0; k < DFLOW_DESC / 4; k++) { q[4 * k] = qv[k].x; q[4 * k + 1] = qv[k].y; q[4 * k + 2] = qv[k].z; q[4 * k + 3] = qv[k].w; }
+}
+
+// one round of a resolve kernel for this lane's candidate idx (act: the lane has one): wait for its row, issue the next
+// round (next(): its fetch overlaps this round's arithmetic), then the canonical pair arithmetic, and the candidate enters
+// the top 5 by its (distance, index) key unless it is farther than the fifth
+template <class Rows, class Next>
+__device__ __forceinline__ void km_eval(Rows &rows, Next &&next, const float (&q)[DFLOW_DESC], bool act, int idx,
+                                        unsigned long long (&keys)[5], float (&costs)[5])
+{
+    float4 cv[DFLOW_DESC / 4];
+    rows.fetch(cv);
+    next();
+    const float worst = __uint_as_float((unsigned)(keys[4] >> 32));
+    const PairDist d = pair_dist(q, cv);
+    if (act && !(d.l2 > worst)) key_insert(keys, costs, ((unsigned long long)__float_as_uint(d.l2) << 32) | (unsigned)idx, d.l1());
+}
+
+// winner j (key, cost) of the query at pixel qpix = (qy, qx) in window slot wslot: label [dy, dx] and the cost truncated at
+// tphi (daisy i flann.py:174-180); the candidate cell starts at (cx0, cy0) and is ccw pixels wide
+__device__ static inline void km_emit(const KmGeom &a, const KmResolve &p, size_t qpix, int qy, int qx, int cx0, int cy0, int ccw,
+                                      int wslot, int j, unsigned long long key, float cost)
+{
+    const int idx = (int)(key & 0xFFFFFFFFu);
+    const int ty = cy0 + idx / ccw, tx = cx0 + idx % ccw;
+    p.proposals[qpix * a.LP + 5 * wslot + j] = pack_flow(ty - qy, tx - qx);
+    p.lcosts[qpix * a.LP + 5 * wslot + j] = cost < a.tphi ? cost : a.tphi;
+}
 
 // ------------------------------------------------------------------------------------------------ resolve, staged rows
 // Round 1's kernel (one wave per (candidate cell, 64 queries) event list, every lane fetching its own rows with 17 dwordx4
@@ -736,7 +766,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
     if (ci < 0 || ci >= g.ncx) return;
     const int qx0 = g.x0(qci), qy0 = g.y0(qcj), qcw = g.x1(qci) - qx0, qnpts = qcw * (g.y1(qcj) - qy0);
     if (qwave * KM_QPW >= qnpts) return;
-    const int cimin = max(0, qci - g.win), cjmin = max(0, qcj - g.win), cjmax = min(g.ncy - 1, qcj + g.win);
+    const Geom::Window w = g.window(qci, qcj);
     const int cx0 = g.x0(ci), ccw = g.x1(ci) - cx0;
 
     __shared__ __attribute__((aligned(1024))) char stage[F16 ? 16 : ROW_STAGE_BYTES];   // row_stage.h (float32 rows only)
@@ -753,39 +783,32 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
     const int qy = qy0 + qi / qcw, qx = qx0 + qi % qcw;
     const size_t qpix = (size_t)qy * g.W + qx;
     const bool qzero = p.qs[qpix].x == KM_Q_ZERO;          // all-zero descriptor: no events, the cell's own list is the answer
-    {
-        rows.issue((rs_gptr)p.d1, (uint32_t)qpix * PIECES, true);
-        float4 qv[17];
-        rows.fetch(qv);
-#pragma unroll
-        for (int k = 0; k < 17; k++) { q[4 * k] = qv[k].x; q[4 * k + 1] = qv[k].y; q[4 * k + 2] = qv[k].z; q[4 * k + 3] = qv[k].w; }
-    }
+    km_load_query<F16>(rows, p.d1, qpix, q);
     const rs_gptr d2g = (rs_gptr)p.d2;
 
     // counts and first entries of the query's two event lists (half-lane 0: tile rows 0..3, 8..11, ...; half-lane 1: rows
     // 4..7, 12..15, ...) of a candidate cell; fetched one cell ahead
-    const int nrows = cjmax - cjmin + 1;
     int nA_n, nB_n; uint32_t entA_n[4], entB_n[4];
     auto prefetch = [&](int cj) {
-        const size_t lid = list_id(a, qcell, qwave, (ci - cimin) * nrows + (cj - cjmin));
+        const size_t lid = list_id(a, qcell, qwave, w.slot(ci, cj));
         nA_n = p.ev_cnt[lid * 128 + gq * 64 + col]; nB_n = p.ev_cnt[lid * 128 + gq * 64 + col + 32];
         const uint32_t *ev = p.ev + lid * KM_LIST_WORDS(a.evrows) + (size_t)gq * a.evrows * 64 + col;
 #pragma unroll
         for (int e = 0; e < 4; e++) { entA_n[e] = ev[e * 64]; entB_n[e] = ev[e * 64 + 32]; }     // entries past the count are ignored below
     };
-    prefetch(cjmin);
-    for (int cj = cjmin; cj <= cjmax; cj++) {
-        const int wslot = (ci - cimin) * nrows + (cj - cjmin);   // reference order: ci outer, cj inner (Q2)
+    prefetch(w.jmin);
+    for (int cj = w.jmin; cj <= w.jmax; cj++) {
+        const int wslot = w.slot(ci, cj);
         const size_t lid = list_id(a, qcell, qwave, wslot);
         const int cy0 = g.y0(cj);
-        const int ntiles = (ccw * (g.y1(cj) - cy0) + KM_CHUNK - 1) / KM_CHUNK * (KM_CHUNK / 32);   // as in the screen kernel
+        const int ntiles = km_ntiles(ccw * (g.y1(cj) - cy0));
         int nA = nA_n, nB = nB_n;
         bool ovf = nA == 255 || nB == 255;
         const uint32_t *evA = p.ev + (size_t)lid * KM_LIST_WORDS(a.evrows) + (size_t)gq * a.evrows * 64 + col;
         uint32_t entA[4], entB[4];
 #pragma unroll
         for (int e = 0; e < 4; e++) { entA[e] = e < nA && !ovf ? entA_n[e] : 0u; entB[e] = e < nB && !ovf ? entB_n[e] : 0u; }
-        if (cj < cjmax) prefetch(cj + 1);
+        if (cj < w.jmax) prefetch(cj + 1);
         if (__ballot(ovf)) {                             // an event list ran out of entries in the screen: exact redo by knn_fix_kernel
             if (lane == 0) {
                 int pos = atomicAdd(p.ovf_count, 1);
@@ -811,7 +834,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
         unsigned long long keys[5];
         float costs[5];
 #pragma unroll
-        for (int i = 0; i < 5; i++) { keys[i] = 0x7F800000FFFFFFFFull; costs[i] = 0.0f; }   // (+inf, no index)
+        for (int i = 0; i < 5; i++) { keys[i] = KM_NO_KEY; costs[i] = 0.0f; }
         // The LDS list holds KM_EVLIST2 candidates per query; a query with more events (flat or repetitive image regions)
         // takes further passes over its entries: `done` events have been evaluated, the next KM_EVLIST2 are listed.
         int done = 0, total;
@@ -823,8 +846,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
             while (mask) {
                 const int r = __ffs(mask) - 1;
                 mask &= mask - 1;
-                // accumulator register r of half-lane h = tile row 4 h + (r & 3) + 8 (r >> 2) = candidate row * ntiles + tile
-                if (seen >= done && nev < KM_EVLIST2) { evl[nev][lane] = (uint16_t)((4 * h + (r & 3) + 8 * (r >> 2)) * ntiles + tile); nev++; }
+                if (seen >= done && nev < KM_EVLIST2) { evl[nev][lane] = (uint16_t)km_event_cand(h, r, tile, ntiles); nev++; }
                 seen++;
             }
         };
@@ -845,35 +867,11 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
             int e = 0;
             int idx_next = issue_cand(0);
             while (true) {
-                float4 cv[17];
-                rows.fetch(cv);
                 const bool act = e < nev;
                 const int idx = idx_next;
                 e++;
                 const bool more = __ballot(e < nev) != 0;
-                if (more) idx_next = issue_cand(e);
-                // ---- canonical distance (sequential fmaf chain) and L1 cost (numpy pairwise order), as in knn_resolve_kernel
-                const float worst = __uint_as_float((unsigned)(keys[4] >> 32));
-                float acc = 0.0f, rs[8], tl[4];
-#pragma unroll
-                for (int k = 0; k < 17; k++) {
-                    const float4 v = cv[k];
-                    // two differences per instruction (v_pk_add_f32 with negated operand: the same IEEE subtraction per half)
-                    const km_f2 ea = (km_f2){q[4 * k], q[4 * k + 1]} - (km_f2){v.x, v.y};
-                    const km_f2 eb = (km_f2){q[4 * k + 2], q[4 * k + 3]} - (km_f2){v.z, v.w};
-                    const float e0 = ea.x, e1 = ea.y, e2 = eb.x, e3 = eb.y;
-                    acc = __fmaf_rn(e0, e0, acc); acc = __fmaf_rn(e1, e1, acc);
-                    acc = __fmaf_rn(e2, e2, acc); acc = __fmaf_rn(e3, e3, acc);
-                    const int j = (4 * k) & 7;
-                    if (k < 2) { rs[j] = fabsf(e0); rs[j + 1] = fabsf(e1); rs[j + 2] = fabsf(e2); rs[j + 3] = fabsf(e3); }
-                    else if (k < 16) { rs[j] = rs[j] + fabsf(e0); rs[j + 1] = rs[j + 1] + fabsf(e1); rs[j + 2] = rs[j + 2] + fabsf(e2); rs[j + 3] = rs[j + 3] + fabsf(e3); }
-                    else { tl[0] = fabsf(e0); tl[1] = fabsf(e1); tl[2] = fabsf(e2); tl[3] = fabsf(e3); }
-                }
-                if (act && !(acc > worst)) {
-                    float l1 = ((rs[0] + rs[1]) + (rs[2] + rs[3])) + ((rs[4] + rs[5]) + (rs[6] + rs[7]));
-                    l1 = l1 + tl[0]; l1 = l1 + tl[1]; l1 = l1 + tl[2]; l1 = l1 + tl[3];
-                    key_insert(keys, costs, ((unsigned long long)__float_as_uint(acc) << 32) | (unsigned)idx, l1);
-                }
+                km_eval(rows, [&] { if (more) idx_next = issue_cand(e); }, q, act, idx, keys, costs);
                 if (!more) break;
             }
         }
@@ -884,18 +882,9 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_kernel(KmGeom a, KmResolve 
 #pragma unroll
             for (int i = 0; i < 5; i++) { keys[i] = zt.idx[i]; costs[i] = zt.cost[i]; }
         }
-        // ---- emit (daisy i flann.py:174-180)
         if (qvalid && !heavy) {
-            const size_t pix = (size_t)qy * g.W + qx;
-            const int slot_base = 5 * wslot;
 #pragma unroll
-            for (int j = 0; j < 5; j++) {
-                const int idx = (int)(keys[j] & 0xFFFFFFFFu);
-                const float s = costs[j];
-                const int ty = cy0 + idx / ccw, tx = cx0 + idx % ccw;
-                p.proposals[pix * a.LP + slot_base + j] = pack_flow(ty - qy, tx - qx);
-                p.lcosts[pix * a.LP + slot_base + j] = s < a.tphi ? s : a.tphi;
-            }
+            for (int j = 0; j < 5; j++) km_emit(a, p, qpix, qy, qx, cx0, cy0, ccw, wslot, j, keys[j], costs[j]);
         }
     }
 }
@@ -926,32 +915,23 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
         const int qx0 = g.x0(qci), qy0 = g.y0(qcj), qcw = g.x1(qci) - qx0;
         const int qy = qy0 + qi / qcw, qx = qx0 + qi % qcw;
         const size_t qpix = (size_t)qy * g.W + qx;
-        const int cimin = max(0, qci - g.win), cjmin = max(0, qcj - g.win), cjmax = min(g.ncy - 1, qcj + g.win);
-        const int wslot = (ci - cimin) * (cjmax - cjmin + 1) + (cj - cjmin);
+        const int wslot = g.window(qci, qcj).slot(ci, cj);
         const int cx0 = g.x0(ci), cy0 = g.y0(cj), ccw = g.x1(ci) - cx0;
-        const int ntiles = (ccw * (g.y1(cj) - cy0) + KM_CHUNK - 1) / KM_CHUNK * (KM_CHUNK / 32);
+        const int ntiles = km_ntiles(ccw * (g.y1(cj) - cy0));
         const size_t lid = list_id(a, qcell, qi / KM_QPW, wslot);
         const int ql = qi % KM_QPW, gq = ql >> 5, col = ql & 31;            // the query's lane in its list
         const uint32_t *ev = p.ev + (size_t)lid * KM_LIST_WORDS(a.evrows) + (size_t)gq * a.evrows * 64 + col;
-        // the query's row, in every lane; the list lengths and the first 64 entries of both lists are requested beside it
-        // (one memory round trip instead of three)
+        // the list lengths and the first 64 entries of both lists, requested with the query's row (one memory round trip
+        // instead of three); the row goes to every lane
+        const int nA = p.ev_cnt[lid * 128 + gq * 64 + col], nB = p.ev_cnt[lid * 128 + gq * 64 + col + 32];
+        const int te = min(lane, a.evrows - 1);
+        const uint32_t pre_a = ev[(size_t)te * 64], pre_b = ev[(size_t)te * 64 + 32];
         float q[DFLOW_DESC];
-        int nA, nB;
-        uint32_t pre_a, pre_b;
-        {
-            rows.issue((rs_gptr)p.d1, (uint32_t)qpix * PIECES, true);
-            nA = p.ev_cnt[lid * 128 + gq * 64 + col]; nB = p.ev_cnt[lid * 128 + gq * 64 + col + 32];
-            const int te = min(lane, a.evrows - 1);
-            pre_a = ev[(size_t)te * 64]; pre_b = ev[(size_t)te * 64 + 32];
-            float4 qv[17];
-            rows.fetch(qv);
-#pragma unroll
-            for (int k = 0; k < 17; k++) { q[4 * k] = qv[k].x; q[4 * k + 1] = qv[k].y; q[4 * k + 2] = qv[k].z; q[4 * k + 3] = qv[k].w; }
-        }
+        km_load_query<F16>(rows, p.d1, qpix, q);
         unsigned long long keys[5];
         float costs[5];
 #pragma unroll
-        for (int i = 0; i < 5; i++) { keys[i] = 0x7F800000FFFFFFFFull; costs[i] = 0.0f; }
+        for (int i = 0; i < 5; i++) { keys[i] = KM_NO_KEY; costs[i] = 0.0f; }
         // batches of 64 list entries (first list, then second): lane = entry, its events' candidate indices go to LDS at the
         // wave-wide prefix of the popcounts
         for (int e0 = 0; e0 < nA + nB; e0 += 64) {
@@ -970,7 +950,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
                 int o = incl - cntl;
                 const int tile = (int)(en >> 16);
                 uint32_t m = t < nA + nB ? (en & 0xFFFFu) : 0u;
-                while (m) { const int r = __ffs(m) - 1; m &= m - 1; cand[o++] = (uint16_t)((4 * h + (r & 3) + 8 * (r >> 2)) * ntiles + tile); }
+                while (m) { const int r = __ffs(m) - 1; m &= m - 1; cand[o++] = (uint16_t)km_event_cand(h, r, tile, ntiles); }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // rounds of 64 candidates; the fetch of the next round overlaps this round's arithmetic
@@ -982,41 +962,18 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
             };
             int idx_next = issue_cand(0);
             for (int c0 = 0; c0 < nc; c0 += 64) {
-                float4 cv[17];
-                rows.fetch(cv);
-                const bool act = c0 + lane < nc;
                 const int idx = idx_next;
-                if (c0 + 64 < nc) idx_next = issue_cand(c0 + 64);
-                const float worst = __uint_as_float((unsigned)(keys[4] >> 32));
-                float acc = 0.0f, rs[8], tl[4];
-#pragma unroll
-                for (int k = 0; k < 17; k++) {
-                    const float4 v = cv[k];
-                    const km_f2 ea = (km_f2){q[4 * k], q[4 * k + 1]} - (km_f2){v.x, v.y};
-                    const km_f2 eb = (km_f2){q[4 * k + 2], q[4 * k + 3]} - (km_f2){v.z, v.w};
-                    const float d0 = ea.x, d1 = ea.y, d2 = eb.x, d3 = eb.y;
-                    acc = __fmaf_rn(d0, d0, acc); acc = __fmaf_rn(d1, d1, acc);
-                    acc = __fmaf_rn(d2, d2, acc); acc = __fmaf_rn(d3, d3, acc);
-                    const int j = (4 * k) & 7;
-                    if (k < 2) { rs[j] = fabsf(d0); rs[j + 1] = fabsf(d1); rs[j + 2] = fabsf(d2); rs[j + 3] = fabsf(d3); }
-                    else if (k < 16) { rs[j] = rs[j] + fabsf(d0); rs[j + 1] = rs[j + 1] + fabsf(d1); rs[j + 2] = rs[j + 2] + fabsf(d2); rs[j + 3] = rs[j + 3] + fabsf(d3); }
-                    else { tl[0] = fabsf(d0); tl[1] = fabsf(d1); tl[2] = fabsf(d2); tl[3] = fabsf(d3); }
-                }
-                if (act && !(acc > worst)) {
-                    float l1 = ((rs[0] + rs[1]) + (rs[2] + rs[3])) + ((rs[4] + rs[5]) + (rs[6] + rs[7]));
-                    l1 = l1 + tl[0]; l1 = l1 + tl[1]; l1 = l1 + tl[2]; l1 = l1 + tl[3];
-                    key_insert(keys, costs, ((unsigned long long)__float_as_uint(acc) << 32) | (unsigned)idx, l1);
-                }
+                km_eval(rows, [&] { if (c0 + 64 < nc) idx_next = issue_cand(c0 + 64); }, q, c0 + lane < nc, idx, keys, costs);
             }
         }
         // ---- merge: five times the smallest head of the 64 sorted partial lists (keys are unique: the index is part of them)
-        unsigned long long rkey = 0x7F800000FFFFFFFFull;
+        unsigned long long rkey = KM_NO_KEY;
         float rcost = 0.0f;
         for (int r = 0; r < 5; r++) {
             unsigned long long m = keys[0];
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(m, off); m = o < m ? o : m; }
-            const unsigned long long own = __ballot(keys[0] == m && m != 0x7F800000FFFFFFFFull);
+            const unsigned long long own = __ballot(keys[0] == m && m != KM_NO_KEY);
             float c = 0.0f;
             if (own) {
                 const int wl = __ffsll((long long)own) - 1;
@@ -1024,18 +981,12 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
                 if (lane == wl) {                                 // pop
 #pragma unroll
                     for (int i = 0; i < 4; i++) { keys[i] = keys[i + 1]; costs[i] = costs[i + 1]; }
-                    keys[4] = 0x7F800000FFFFFFFFull; costs[4] = 0.0f;
+                    keys[4] = KM_NO_KEY; costs[4] = 0.0f;
                 }
             }
             if (lane == r) { rkey = m; rcost = c; }
         }
-        // ---- emit (daisy i flann.py:174-180): lane j writes winner j
-        if (lane < 5) {
-            const int idx = (int)(rkey & 0xFFFFFFFFu);
-            const int ty = cy0 + idx / ccw, tx = cx0 + idx % ccw;
-            p.proposals[qpix * a.LP + 5 * wslot + lane] = pack_flow(ty - qy, tx - qx);
-            p.lcosts[qpix * a.LP + 5 * wslot + lane] = rcost < a.tphi ? rcost : a.tphi;
-        }
+        if (lane < 5) km_emit(a, p, qpix, qy, qx, cx0, cy0, ccw, wslot, lane, rkey, rcost);     // lane j writes winner j
     }
 }
 
@@ -1043,6 +994,13 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
 // nprop = 5 x window cells (daisy i flann.py:189), WTA label = first minimum of the costs with strict '<'
 // from 1000.0 (:93,181-184), fills beyond nprop (:89-90).  16 lanes per pixel: coalesced reads of the cost row,
 // (cost, slot) lexicographic minimum over the 16 lanes with DPP row shifts, coalesced fills.
+// the (cost, slot) of the lane DPP control word CTRL selects, merged into this lane's lexicographic minimum
+template <int CTRL> __device__ static inline void dpp_lexmin(float &mind, int &best)
+{
+    const float om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), CTRL, 0xF, 0xF, false));
+    const int ob = __builtin_amdgcn_update_dpp(best, best, CTRL, 0xF, 0xF, false);
+    if (om < mind || (om == mind && ob < best)) { mind = om; best = ob; }
+}
 __global__ void __launch_bounds__(256) knn_finalize_kernel(Geom g, int LP, uint32_t *__restrict__ proposals, float *__restrict__ lcosts,
                                                            int32_t *__restrict__ nprop, int32_t *__restrict__ bestlabels)
 {
@@ -1062,17 +1020,8 @@ __global__ void __launch_bounds__(256) knn_finalize_kernel(Geom g, int LP, uint3
     for (int j = 0; j < DFLOW_MAX_LABELS / 16; j++) cs[j] = sub + 16 * j < n ? lc[sub + 16 * j] : 1000.0f;
 #pragma unroll
     for (int j = 0; j < DFLOW_MAX_LABELS / 16; j++) if (cs[j] < mind) { mind = cs[j]; best = sub + 16 * j; }
-#pragma unroll
-    for (int sh = 1; sh < 16; sh <<= 1) {       // row_shl 1,2,4,8: lane 0 of every 16-lane row ends with the row minimum
-        const int ctrl = 0x100 + sh;
-        float om; int ob;
-        if (sh == 1) { om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), 0x101, 0xF, 0xF, false)); ob = __builtin_amdgcn_update_dpp(best, best, 0x101, 0xF, 0xF, false); }
-        else if (sh == 2) { om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), 0x102, 0xF, 0xF, false)); ob = __builtin_amdgcn_update_dpp(best, best, 0x102, 0xF, 0xF, false); }
-        else if (sh == 4) { om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), 0x104, 0xF, 0xF, false)); ob = __builtin_amdgcn_update_dpp(best, best, 0x104, 0xF, 0xF, false); }
-        else { om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), 0x108, 0xF, 0xF, false)); ob = __builtin_amdgcn_update_dpp(best, best, 0x108, 0xF, 0xF, false); }
-        (void)ctrl;
-        if (om < mind || (om == mind && ob < best)) { mind = om; best = ob; }
-    }
+    // row_shl 1, 2, 4, 8: lane 0 of every 16-lane row ends with the row minimum
+    dpp_lexmin<0x101>(mind, best); dpp_lexmin<0x102>(mind, best); dpp_lexmin<0x104>(mind, best); dpp_lexmin<0x108>(mind, best);
     if (ok) {
         if (sub == 0) { nprop[pix] = n; bestlabels[pix] = best == 0x7fffffff ? 0 : best; }
         for (int l = n + sub; l < LP; l += 16) { proposals[(size_t)pix * LP + l] = DFLOW_FILL_PROPOSAL; lcosts[(size_t)pix * LP + l] = DFLOW_FILL_COST; }
@@ -1080,11 +1029,6 @@ __global__ void __launch_bounds__(256) knn_finalize_kernel(Geom g, int LP, uint3
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int max_cell_points(const Geom &g)
-{
-    return (g.x1(g.ncx - 1) - g.x0(g.ncx - 1)) * (g.y1(g.ncy - 1) - g.y0(g.ncy - 1));
-}
-
 static size_t num_lists(const dflow_params *p)
 {
     Geom g = make_geom(p);
@@ -1098,7 +1042,7 @@ static size_t num_lists(const dflow_params *p)
 // that no list can run out; cells beyond KM_EVROWS_MAX - 1 tiles: KM_EVROWS_MAX
 static int km_evrows(const dflow_params *p)
 {
-    const int tiles = km_pad(max_cell_points(make_geom(p))) / 32;
+    const int tiles = km_ntiles(max_cell_points(make_geom(p)));
     return tiles + 1 < KM_EVROWS_MAX ? tiles + 1 : KM_EVROWS_MAX;
 }
 
@@ -1291,8 +1235,8 @@ int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_ou
     for (int qcj = 0; qcj < g.ncy; qcj++)
         for (int qci = 0; qci < g.ncx; qci++) {
             const long long qn = (long long)(g.x1(qci) - g.x0(qci)) * (g.y1(qcj) - g.y0(qcj));
-            const int nx = min(g.ncx - 1, qci + g.win) - max(0, qci - g.win) + 1, ny = min(g.ncy - 1, qcj + g.win) - max(0, qcj - g.win) + 1;
-            pairs += qn * nx * ny;
+            const Geom::Window w = g.window(qci, qcj);
+            pairs += qn * (w.imax - w.imin + 1) * (w.jmax - w.jmin + 1);
         }
     h_out[0] = ctr[0]; h_out[1] = ctr[1]; h_out[2] = (int64_t)k.nl; h_out[3] = (int64_t)c[0]; h_out[4] = (int64_t)c[1]; h_out[5] = (int64_t)c[2];
     h_out[6] = (int64_t)c[3]; h_out[7] = (int64_t)c[4]; h_out[8] = (int64_t)c[5]; h_out[9] = (int64_t)c[6]; h_out[10] = pairs; h_out[11] = k.evrows;
@@ -1314,7 +1258,7 @@ double knn_mfma_issued(const dflow_params *p)
                 for (int cj = qcj - g.win; cj <= qcj + g.win; cj++) {
                     if (ci < 0 || ci >= g.ncx || cj < 0 || cj >= g.ncy) continue;
                     const int cnpts = (g.x1(ci) - g.x0(ci)) * (g.y1(cj) - g.y0(cj));
-                    n += (double)qgroups * (km_pad(cnpts) / 32) * 2.0 * KM_KSTEPS;
+                    n += (double)qgroups * km_ntiles(cnpts) * 2.0 * KM_KSTEPS;
                 }
         }
     return n;
