@@ -104,15 +104,24 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
 
 /* Measurement aid (bench.py's other_configs, the low-texture tests): what the MFMA screen of the LAST dflow_knn_proposals call on
  * this workspace did, read back from the workspace (WAITS for the stream; call it before another stage reuses the workspace).
- * h_stats[DFLOW_KNN_STATS_N] (host): [0] event lists handed to the exact brute-force search (rows outside the f16 range / NaN),
- * [1] flags (bit 0: the whole pass went to the exact search: the basis failed its orthonormality check), [2] event lists of the
- * pass, [3] list entries written, [4] events = (query, candidate) pairs evaluated exactly, [5] most entries in one lane's list,
+ * h_stats[DFLOW_KNN_STATS_N] (host): [0] event lists handed to the exact brute-force search (rows outside the f16 range / NaN, or
+ * a lane's list ran out), [1] flags (bit 0: the whole pass went to the exact search: the basis failed its orthonormality check),
+ * [2] event lists the workspace holds (every (query cell, 64-query wave, window slot), the unused ones of clipped windows and
+ * smaller cells included), [3] list entries written, [4] events = (query, candidate) pairs evaluated exactly, [5] most entries in one lane's list,
  * [6] all-zero queries (answered from their cells' own lists), [7] queries outside the screen's range, [8] all-zero candidate
  * rows, [9] of those removed as duplicates, [10] (query, cell) pairs of the pass, [11] list capacity per lane, [12] (query, cell)
- * pairs with so many events that one wave took the query alone (its 64 lanes over the events).
+ * pairs with so many events that one wave took the query alone (its 64 lanes over the events).  [3], [4] and [5] count the
+ * lists that did not run out ([0] counts those that did).
  * No reference counterpart. */
 #define DFLOW_KNN_STATS_N 13
 int dflow_knn_screen_stats(const dflow_params *p, void *d_ws, size_t ws_bytes, void *stream, int64_t *h_stats);
+
+/* The same statistics followed by those added since, into a caller array of n_stats values (1 <= n_stats <=
+ * DFLOW_KNN_STATS_ALL_N; the first n_stats are written): [0..12] as above, [13] (query, cell) pairs with that many events that
+ * stayed in the lane-per-query kernel because the list of [12] was full.  dflow_knn_screen_stats keeps writing exactly
+ * DFLOW_KNN_STATS_N values, the array size its callers were built with. */
+#define DFLOW_KNN_STATS_ALL_N 14
+int dflow_knn_screen_stats_n(const dflow_params *p, void *d_ws, size_t ws_bytes, void *stream, int64_t *h_stats, int n_stats);
 
 /* nasumicni, daisy i flann.py:205-233: appends up to ngauss neighbour proposals per pixel (in place).
  * d_bestlabels must still hold the WTA labels written by dflow_knn_proposals.  Uses 4 bytes per pixel of the workspace

@@ -117,14 +117,24 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
     return rc;
 }
 
-int dflow_knn_screen_stats(const dflow_params *p, void *d_ws, size_t ws_bytes, void *stream, int64_t *h_stats)
+int dflow_knn_screen_stats_n(const dflow_params *p, void *d_ws, size_t ws_bytes, void *stream, int64_t *h_stats, int n_stats)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(h_stats);
+    if (n_stats < 1 || n_stats > DFLOW_KNN_STATS_ALL_N)
+        return dflow_set_error(DFLOW_EINVAL, "%s: n_stats = %d outside 1..%d", __func__, n_stats, DFLOW_KNN_STATS_ALL_N);
     if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
         return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
     CHECK_WS(knn_mfma_ws_bytes(p));
-    return knn_mfma_stats(p, d_ws, (hipStream_t)stream, h_stats);
+    int64_t all[DFLOW_KNN_STATS_ALL_N];
+    rc = knn_mfma_stats(p, d_ws, (hipStream_t)stream, all);
+    if (rc == DFLOW_OK) memcpy(h_stats, all, (size_t)n_stats * sizeof(int64_t));
+    return rc;
+}
+
+int dflow_knn_screen_stats(const dflow_params *p, void *d_ws, size_t ws_bytes, void *stream, int64_t *h_stats)
+{
+    return dflow_knn_screen_stats_n(p, d_ws, ws_bytes, stream, h_stats, DFLOW_KNN_STATS_N);
 }
 
 int dflow_neighbour_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2, uint32_t *d_proposals,

@@ -32,7 +32,8 @@
 //             candidate cell).  Every lane keeps the 5 largest maxima of its 16-value tile columns -> a5 <= the 5th largest
 //             tau of the query.  pass 2: v = G^ + bounds - h + S_c >= tau.  Only candidates with v >= a5 - s (s: rounding
 //             of the canonical float32 distance) can be among the exact 5 NN: these "events" (a 16-bit row mask per lane
-//             and tile) go to per-lane lists in the workspace (capacity = the tiles of a cell: a list cannot overflow).
+//             and tile) go to per-lane lists in the workspace (capacity = the tiles of the largest cell + 1, at most
+//             KM_EVROWS_MAX: a list can overflow only in cells of more than 2880 points).
 //             Events per (query, cell) on the bench frame: 5.7 (5 is the minimum).
 //   hard rows candidate rows that are all zero (saturated / constant regions: exactly-zero DAISY) tie with each other for
 //             every query, and the canonical order breaks ties by index: only the 5 of lowest index in a cell can enter
@@ -94,8 +95,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define KM_SPC (2 * (KM_CHUNK / 32))                           // event stores of a wave per chunk in pass 2 (tiles x groups)
 #define KM_EVROWS_MAX 96        // event entries (tile, 16-bit row mask) per lane, group and candidate cell: one per tile of the largest
                                 // cell + 1 (km_evrows), so that no list can run out (mean 2.7, 99 % <= 7 on dense texture, but every
-                                // tile of a cell in flat regions); cells of more than 95 tiles (3040 points): 96, and a list
-                                // that does run out is redone by knn_fix_kernel
+                                // tile of a cell in flat regions).  Tiles come in chunks of 6: up to 90 tiles (2880 points) a list
+                                // cannot run out; a cell of more than 2880 points has 96 tiles or more, each with a candidate in
+                                // row 0, so a lane with an event in every tile fills its 96 entries, and that list is redone by knn_fix_kernel
 #define KM_MAXPTS 65535         // candidate index must fit 16 bits
 #define KM_LIST_WORDS(evrows) (2 * (evrows) * 64)       // one event list: [group][entry][lane] uint32
 #define KM_ETA 7.62939453125e-6                  // eta = 2^-17: allowance for the f32 accumulation inside the matrix core
@@ -1039,7 +1041,8 @@ static size_t num_lists(const dflow_params *p)
 #define KM_HEAVY_BLOCKS 2048      // waves of knn_resolve_heavy_kernel (grid-stride over the pairs; 8 per CU)
 #define KM_HEAVY_CAP (1 << 20)    // (query, cell) pairs the cooperative kernel can take per pass (16 MB); more stay with knn_resolve_kernel
 // entries per lane of the event lists: one per tile of the largest cell, + 1 (the last entry of a list is never valid), so
-// that no list can run out; cells beyond KM_EVROWS_MAX - 1 tiles: KM_EVROWS_MAX
+// that no list can run out; cells beyond KM_EVROWS_MAX - 1 tiles (in practice 96 tiles and more: cells of more than 2880
+// points): KM_EVROWS_MAX, and a lane with an event in every tile overflows
 static int km_evrows(const dflow_params *p)
 {
     const int tiles = km_ntiles(max_cell_points(make_geom(p)));
@@ -1102,6 +1105,15 @@ static KmWs km_ws(const dflow_params *p, void *ws)
 
 size_t knn_mfma_ws_bytes(const dflow_params *p) { return km_ws(p, nullptr).bytes; }
 
+static KmGeom km_geom(const dflow_params *p, const KmWs &k)
+{
+    KmGeom a;
+    a.g = make_geom(p); a.LP = p->label_pitch; a.tphi = p->tphi;
+    a.qwaves = (max_cell_points(a.g) + KM_QPW - 1) / KM_QPW;
+    a.evrows = k.evrows;
+    return a;
+}
+
 bool knn_mfma_supported(const dflow_params *p)
 {
     Geom g = make_geom(p);
@@ -1140,10 +1152,7 @@ int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint3
     if (rc) return rc;
 
     mark(2);
-    KmGeom a;
-    a.g = g; a.LP = p->label_pitch; a.tphi = p->tphi;
-    a.qwaves = (max_cell_points(g) + KM_QPW - 1) / KM_QPW;
-    a.evrows = k.evrows;
+    const KmGeom a = km_geom(p, k);
     int win = 2 * g.win + 1;
     int wgs_per_cell = (win * win * a.qwaves + KM_WAVES - 1) / KM_WAVES;
     KmScreen sc;
@@ -1177,11 +1186,22 @@ int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint3
 
 // ------------------------------------------------------------------------------------------------ statistics (measurement aid)
 // What the screen left in the workspace: one block per event list (threads = 2 groups x 64 lanes), then one pass over the
-// image-1 records and the image-2 positions.
-__global__ void __launch_bounds__(128) knn_stats_lists_kernel(const uint32_t *__restrict__ ev, const uint8_t *__restrict__ ev_cnt, int evrows,
+// image-1 records and the image-2 positions.  Only the lists the screen writes are read: window slots outside the clipped
+// window and 64-query waves beyond a smaller query cell hold whatever the workspace held before.
+__global__ void __launch_bounds__(128) knn_stats_lists_kernel(KmGeom a, const uint32_t *__restrict__ ev, const uint8_t *__restrict__ ev_cnt,
                                                               unsigned long long *__restrict__ out)
 {
+    const Geom g = a.g;
+    const int evrows = a.evrows, win = 2 * g.win + 1;
     const size_t lid = blockIdx.x;
+    {
+        // lid = list_id(qcell, qwave, wslot)
+        const int wslot = (int)(lid % (size_t)(win * win)), qwave = (int)(lid / (win * win) % a.qwaves), qcell = (int)(lid / (win * win) / a.qwaves);
+        const int qci = qcell % g.ncx, qcj = qcell / g.ncx;
+        const Geom::Window w = g.window(qci, qcj);
+        const int qnpts = (g.x1(qci) - g.x0(qci)) * (g.y1(qcj) - g.y0(qcj));
+        if (qwave * KM_QPW >= qnpts || wslot >= (w.imax - w.imin + 1) * (w.jmax - w.jmin + 1)) return;     // block-uniform
+    }
     const int gq = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int cnt = ev_cnt[lid * 128 + threadIdx.x];
     unsigned long long entries = 0, events = 0;
@@ -1211,7 +1231,7 @@ __global__ void __launch_bounds__(256) knn_stats_rows_kernel(const float2 *__res
     }
 }
 
-// h_out[KNN_STATS_N] (host), after a dflow_knn_proposals call on the same workspace: see include/dflow.h
+// h_out[DFLOW_KNN_STATS_ALL_N] (host), after a dflow_knn_proposals call on the same workspace: see include/dflow.h
 int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_out)
 {
     const KmWs k = km_ws(p, ws);
@@ -1219,7 +1239,8 @@ int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_ou
     const size_t N = (size_t)g.H * g.W, rows2 = km_total_rows(g);
     unsigned long long *dev = (unsigned long long *)(k.ctr + 16);            // 8 counters inside the zeroed control block
     if (hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), s) != hipSuccess) return dflow_set_error(DFLOW_EHIP, "hipMemsetAsync failed");
-    hipLaunchKernelGGL(knn_stats_lists_kernel, dim3((unsigned)k.nl), dim3(128), 0, s, (const uint32_t *)k.ev, (const uint8_t *)k.ev_cnt, k.evrows, dev);
+    const KmGeom a = km_geom(p, k);
+    hipLaunchKernelGGL(knn_stats_lists_kernel, dim3((unsigned)k.nl), dim3(128), 0, s, a, (const uint32_t *)k.ev, (const uint8_t *)k.ev_cnt, dev);
     const size_t m = N > rows2 ? N : rows2;
     hipLaunchKernelGGL(knn_stats_rows_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const float2 *)k.qs, (int)N, (const uint8_t *)k.zflag,
                        (const _Float16 *)k.h2, rows2, dev);
@@ -1241,6 +1262,7 @@ int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_ou
     h_out[0] = ctr[0]; h_out[1] = ctr[1]; h_out[2] = (int64_t)k.nl; h_out[3] = (int64_t)c[0]; h_out[4] = (int64_t)c[1]; h_out[5] = (int64_t)c[2];
     h_out[6] = (int64_t)c[3]; h_out[7] = (int64_t)c[4]; h_out[8] = (int64_t)c[5]; h_out[9] = (int64_t)c[6]; h_out[10] = pairs; h_out[11] = k.evrows;
     h_out[12] = ctr[2] < KM_HEAVY_CAP ? ctr[2] : KM_HEAVY_CAP;
+    h_out[13] = ctr[2] > KM_HEAVY_CAP ? ctr[2] - KM_HEAVY_CAP : 0;     // the counter keeps counting past the cap
     return DFLOW_OK;
 }
 

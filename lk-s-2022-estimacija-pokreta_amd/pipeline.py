@@ -135,12 +135,14 @@ class DiscreteFlow:
 
     KNN_STATS = ("lists_exact", "flags", "lists", "entries", "events", "max_entries_per_lane", "zero_queries", "bad_queries",
                  "zero_candidates", "zero_candidates_removed", "query_cell_pairs", "list_capacity", "heavy_pairs")
+    KNN_STATS_ALL = KNN_STATS + ("heavy_pairs_left",)      # dflow_knn_screen_stats_n: DFLOW_KNN_STATS_ALL_N values
 
     def knn_stats(self):
-        """dflow_knn_screen_stats: what the MFMA screen of the last generisi() did (call before the next stage reuses the workspace)."""
-        out = (C.c_int64 * len(self.KNN_STATS))()
-        _lib.check(_lib.lib().dflow_knn_screen_stats(self._pp(), self.ws.data_ptr(), self.ws_bytes, self._stream(), out), "dflow_knn_screen_stats")
-        st = dict(zip(self.KNN_STATS, (int(v) for v in out)))
+        """dflow_knn_screen_stats_n: what the MFMA screen of the last generisi() did (call before the next stage reuses the workspace)."""
+        out = (C.c_int64 * len(self.KNN_STATS_ALL))()
+        _lib.check(_lib.lib().dflow_knn_screen_stats_n(self._pp(), self.ws.data_ptr(), self.ws_bytes, self._stream(), out, len(out)),
+                   "dflow_knn_screen_stats_n")
+        st = dict(zip(self.KNN_STATS_ALL, (int(v) for v in out)))
         st["events_per_query_cell"] = round(st["events"] / max(1, st["query_cell_pairs"]), 3)
         return st
 

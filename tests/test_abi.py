@@ -102,6 +102,27 @@ def test_knn_measurement_aids_validate_before_touching_the_gpu(L):
     assert lib.dflow_workspace_bytes(C.byref(big)) > nl * 2 * (tiles + 1) * 256
 
 
+def test_knn_stats_with_a_count_validate_before_touching_the_gpu(L):
+    """dflow_knn_screen_stats_n writes the first n_stats statistics of DFLOW_KNN_STATS_ALL_N (the 13 of dflow_knn_screen_stats
+    and those added since): a count outside 1..DFLOW_KNN_STATS_ALL_N, a null output, DFLOW_FLAG_KNN_EXACT or a workspace that is
+    too small fail on the host; the host mirror names every statistic, the first DFLOW_KNN_STATS_N in the old order."""
+    lib = L.lib()
+    header = open(os.path.join(ROOT, "include", "dflow.h")).read()
+    n = int(re.search(r"#define\s+DFLOW_KNN_STATS_N\s+(\d+)", header).group(1))
+    n_all = int(re.search(r"#define\s+DFLOW_KNN_STATS_ALL_N\s+(\d+)", header).group(1))
+    DF = pkg("pipeline").DiscreteFlow
+    assert n_all == 14 and n_all == len(DF.KNN_STATS_ALL) and DF.KNN_STATS_ALL[:n] == DF.KNN_STATS
+    assert DF.KNN_STATS_ALL[n:] == ("heavy_pairs_left",)
+    p = L.default_params(64, 64, 8, 8)
+    out = (C.c_int64 * (n_all + 1))()
+    for bad in (0, -1, n_all + 1):
+        assert lib.dflow_knn_screen_stats_n(C.byref(p), 1, 1 << 40, None, out, bad) == -1 and b"n_stats" in lib.dflow_last_error()
+    assert lib.dflow_knn_screen_stats_n(C.byref(p), 1, 16, None, out, n_all) == -2 and b"workspace" in lib.dflow_last_error()
+    assert lib.dflow_knn_screen_stats_n(C.byref(p), 1, 1 << 40, None, None, n_all) == -1 and b"NULL" in lib.dflow_last_error()
+    q = L.default_params(64, 64, 8, 8, flags=L.FLAG_KNN_EXACT)
+    assert lib.dflow_knn_screen_stats_n(C.byref(q), 1, 1 << 40, None, out, n_all) == -1 and b"MFMA" in lib.dflow_last_error()
+
+
 def test_no_cpu_fallback(L):
     import torch
     if torch.cuda.is_available():
