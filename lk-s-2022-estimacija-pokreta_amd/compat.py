@@ -26,8 +26,10 @@ def packedksets(df):
 
 def replay_border_scratch(packed, nprop, L):
     """The loops over the bottom row (daisy i flann.py:283-293) and the right column (:294-307) never clear ksets4:
-    entries outside [0:nprop[pixel], 0:nprop[neighbour]] keep what earlier pixels of the same loop left there."""
+    entries outside [0:nprop[pixel], 0:nprop[neighbour]] keep what earlier pixels of the same loop left there.
+    A matrix fills ceil(L*L/8) bytes of the kdim = L*L//8+1 of a row: where 8 divides L*L the last byte stays 0."""
     H, W = nprop.shape
+    nbytes = (L * L + 7) // 8
     for slot, pixels in ((1, [(H - 1, tx, H - 1, tx + 1) for tx in range(W - 1)]),
                          (0, [(ty, W - 1, ty + 1, W - 1) for ty in range(H - 1)])):
         scratch = np.zeros((L, L), bool)
@@ -35,7 +37,7 @@ def replay_border_scratch(packed, nprop, L):
             fresh = np.unpackbits(packed[ty, tx, slot])[:L * L].reshape(L, L).astype(bool)
             r, c = int(nprop[ty, tx]), int(nprop[ny, nx])
             scratch[:r, :c] = fresh[:r, :c]
-            packed[ty, tx, slot] = np.packbits(scratch.reshape(-1))
+            packed[ty, tx, slot, :nbytes] = np.packbits(scratch.reshape(-1))
 
 
 def pakovani_za_c(packed):

@@ -102,6 +102,32 @@ def test_pakovani_za_c_and_border_replay_match_reference(oracle, golden):
         assert digest(arr, np.uint8) == str(g["za_c%d_sha" % k]), "pakovani za c %d" % k
 
 
+@pytest.mark.parametrize("ngauss", (7, 8))
+def test_border_replay_when_eight_divides_the_matrix(oracle, synth, ngauss):
+    """maxnprop = 52: a 52 x 52 matrix packs into exactly 338 bytes, one fewer than the 339 of a packedksets row (L*L//8+1), whose
+    last byte stays 0; maxnprop = 53 for comparison, where the last byte holds the last bits.  The border replay must write
+    the packed bits of that many bytes (it raised ValueError for every maxnprop divisible by 4, the default pitch 160 included)."""
+    H, W, ch, cw = 12, 14, 4, 4
+    p = oracle.make_params(H, W, ch, cw, seed=4, window=1, ngauss=ngauss, maxnprop=45 + ngauss)
+    img1, img2, _ = synth.make_pair(H, W, seed=6, amp_x=1.5, amp_y=1.0)
+    d1, d2 = oracle.daisy(img1), oracle.daisy(img2)
+    pr, lc, npr, bl = oracle.knn_proposals(p, d1, d2)
+    oracle.neighbour_proposals(p, d1, d2, pr, lc, npr, bl)
+    L = p.maxnprop
+    clean = np.zeros((H, W, 2, L * L // 8 + 1), np.uint8)
+    for y in range(H):
+        for x in range(W):
+            for slot, (ny, nx) in enumerate(((y + 1, x), (y, x + 1))):
+                if ny >= H or nx >= W:
+                    continue
+                a, b = pr[y, x, :npr[y, x]], pr[ny, nx, :npr[ny, nx]]
+                m = np.zeros((L, L), bool)
+                m[:len(a), :len(b)] = p.tpsi > np.abs(a[:, None, :] - b[None, :, :]).sum(-1)
+                clean[y, x, slot, :(L * L + 7) // 8] = np.packbits(m.reshape(-1))
+    pkg("compat").replay_border_scratch(clean, npr, L)
+    assert np.array_equal(clean, oracle.pack_compat(p, pr, npr))
+
+
 def test_ucitajflow_dispatch(golden, tmp_path):
     """evaluate.ucitajFlow = FlowImage.ucitajFlow (visualization.py:97-124) for the three file kinds."""
     g, ev, fio = golden("extras"), pkg("evaluate"), pkg("flowio")
