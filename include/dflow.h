@@ -179,6 +179,17 @@ int dflow_pack_compat(const dflow_params *p, const uint32_t *d_proposals, const 
  * field, in place.  Host code: the reference's region growing depends on its scan order. */
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size);
 
+/* Canny edge map, canny_ivice, edge.py:19-35: cv2.cvtColor(BGR2GRAY) -> cv2.GaussianBlur(gray, (3,3), 0) ->
+ * cv2.Canny(threshold1=low, threshold2=high) (aperture 3, L1 gradient) -> np.array((255 - edges) / 255, float32), the
+ * ivice.bin that spremiZaEpic.py:26 hands to epicflow-static.  Plain sizes instead of dflow_params: an edge map is not tied
+ * to the flow geometry.  1 <= h, w <= 8192; low, high finite and >= 0 (swapped when low > high, then floored).
+ * d_bgr (h,w,3) uint8 BGR -> d_edges (h,w) uint8 0/255 (required) and, if d_ivice is not NULL, d_ivice (h,w) float32 = 0.0 on
+ * edges, 1.0 elsewhere.  Integer arithmetic restated from the algorithm; parity with a cv2 build is not pinned (DESIGN.md
+ * "Canny edge maps").  dflow_canny_workspace_bytes returns 0 (and sets dflow_last_error) for sizes outside the range. */
+size_t dflow_canny_workspace_bytes(int32_t h, int32_t w);
+int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, double high, uint8_t *d_edges, float *d_ivice,
+                      void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

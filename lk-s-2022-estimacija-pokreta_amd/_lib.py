@@ -11,7 +11,8 @@ LIB_PATH = os.path.join(CSRC, "libdflow.so")
 SYMBOLS = ("dflow_version", "dflow_last_error", "dflow_default_params", "dflow_workspace_bytes", "dflow_daisy",
            "dflow_knn_proposals", "dflow_knn_proposals_timed", "dflow_knn_screen_stats", "dflow_knn_screen_stats_n", "dflow_neighbour_proposals", "dflow_bcd_prepare", "dflow_bcd_phase", "dflow_bcd_sweep",
            "dflow_bcd_phase_batch", "dflow_bcd_sweep_batch",
-           "dflow_labels_to_flow", "dflow_fb_consistency", "dflow_pack_compat", "dflow_remove_small_segments_host")
+           "dflow_labels_to_flow", "dflow_fb_consistency", "dflow_pack_compat", "dflow_remove_small_segments_host",
+           "dflow_canny_workspace_bytes", "dflow_canny_edges")
 
 
 FLAG_KNN_EXACT = 1      # DFLOW_FLAG_KNN_EXACT
@@ -77,8 +78,11 @@ def lib():
         L.dflow_fb_consistency.argtypes = [pp, vp, vp, C.c_float, vp, vp]
         L.dflow_pack_compat.argtypes = [pp, vp, vp, vp, vp]
         L.dflow_remove_small_segments_host.argtypes = [vp, i32, i32, C.c_float, i32]
+        L.dflow_canny_edges.argtypes = [i32, i32, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
         for n in SYMBOLS[4:]:
             getattr(L, n).restype = C.c_int
+        L.dflow_canny_workspace_bytes.argtypes = [i32, i32]
+        L.dflow_canny_workspace_bytes.restype = sz
         _lib = L
     return _lib
 

@@ -1,5 +1,6 @@
 // C-ABI entry points of libdflow.so (declared in include/dflow.h): parameter validation, workspace
 // accounting and dispatch to the per-stage launchers.  No torch types, no allocation, no synchronisation.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -219,6 +220,31 @@ int dflow_pack_compat(const dflow_params *p, const uint32_t *d_proposals, const 
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_packed);
     return launch_pack_compat(p, d_proposals, d_nprop, d_packed, (hipStream_t)stream);
+}
+
+static int canny_check_size(const char *fn, int32_t h, int32_t w)
+{
+    if (h < 1 || w < 1 || h > 8192 || w > 8192) return dflow_set_error(DFLOW_EINVAL, "%s: image size %dx%d outside [1,8192]", fn, w, h);
+    return DFLOW_OK;
+}
+
+size_t dflow_canny_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return canny_ws_bytes(h, w);
+}
+
+int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, double high, uint8_t *d_edges, float *d_ivice,
+                      void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (!isfinite(low) || !isfinite(high) || low < 0.0 || high < 0.0)
+        return dflow_set_error(DFLOW_EINVAL, "%s: thresholds %g, %g must be finite and >= 0", __func__, low, high);
+    CHECK_PTR(d_bgr); CHECK_PTR(d_edges); CHECK_WS(canny_ws_bytes(h, w));
+    if (low > high) { const double t = low; low = high; high = t; }      // cv::Canny swaps them
+    // m <= 4 * 255 * 2: larger thresholds all mean "no candidate" / "no strong pixel"
+    const int lo = (int)floor(fmin(low, 1 << 20)), hi = (int)floor(fmin(high, 1 << 20));
+    return launch_canny(h, w, d_bgr, lo, hi, d_edges, d_ivice, d_ws, (hipStream_t)stream);
 }
 
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)

@@ -24,9 +24,7 @@ __device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo 
 
 __device__ static inline float gray_of(const uint8_t *__restrict__ bgr, int W, int y, int x)
 {
-    const uint8_t *px = bgr + ((size_t)y * W + x) * 3;
-    const int g = (1868 * px[0] + 9617 * px[1] + 4899 * px[2] + 8192) >> 14;   // cv::cvtColor BGR2GRAY (u8)
-    return (float)g / 255.0f;
+    return (float)gray_u8(bgr, W, y, x) / 255.0f;
 }
 
 template <typename T> __device__ static inline T tmul(float k, T v);

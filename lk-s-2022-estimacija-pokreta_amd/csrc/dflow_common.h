@@ -45,6 +45,14 @@ static inline Geom make_geom(const dflow_params *p)
     return g;
 }
 
+// luma of pixel (y, x) of a (H,W,3) BGR u8 image: cv::cvtColor BGR2GRAY on u8 (fixed point, 14 fractional bits, round half
+// up).  DAISY (daisy.hip) and the Canny edge map (edges.hip) both start from it.
+__device__ static inline int gray_u8(const uint8_t *__restrict__ bgr, int W, int y, int x)
+{
+    const uint8_t *px = bgr + ((size_t)y * W + x) * 3;
+    return (1868 * px[0] + 9617 * px[1] + 4899 * px[2] + 8192) >> 14;
+}
+
 // label packing: int16 dy | int16 dx << 16
 __host__ __device__ static inline uint32_t pack_flow(int dy, int dx)
 {
@@ -213,3 +221,6 @@ int launch_pack_compat(const dflow_params *p, const uint32_t *proposals, const i
 int host_remove_small_segments(float *flow, int A, int B, float tresh, int min_segment_size);
 int launch_fb_consistency(const dflow_params *p, const float *fwd, const float *bwd, float tresh, float *sparse,
                           hipStream_t s);
+// edges.hip: Canny edge map of a (H,W,3) BGR image; thresholds already swapped and floored
+size_t canny_ws_bytes(int H, int W);
+int launch_canny(int H, int W, const uint8_t *bgr, int lo, int hi, uint8_t *edges, float *ivice, void *ws, hipStream_t s);

@@ -271,3 +271,30 @@ def fb_consistency(fwd, bwd, tresh, p=None):
     _lib.check(_lib.lib().dflow_fb_consistency(C.byref(p), fwd.contiguous().data_ptr(), bwd.contiguous().data_ptr(),
                                                float(tresh), out.data_ptr(), stream), "dflow_fb_consistency")
     return out
+
+
+def canny_edges(bgr, low=100, high=200, ivice=True):
+    """canny_ivice, edge.py:19-35 (cv2.cvtColor BGR2GRAY -> cv2.GaussianBlur((3,3), 0) -> cv2.Canny(low, high)) on a (H,W,3)
+    uint8 BGR image (numpy array or tensor; a host image is uploaded to the current device) -> (edges, ivice): device
+    tensors (H,W) uint8 0/255 and (H,W) float32 (255 - edges) / 255, or None with ivice=False.  Runs on torch's current
+    stream and does not wait for it."""
+    if not isinstance(bgr, torch.Tensor):
+        bgr = torch.from_numpy(np.ascontiguousarray(bgr))
+    if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
+        raise ValueError("canny_edges wants a (H,W,3) uint8 BGR image, got %s %s" % (tuple(bgr.shape), bgr.dtype))
+    if not bgr.is_cuda:
+        bgr = bgr.to(torch.device("cuda", torch.cuda.current_device()))
+    bgr = bgr.contiguous()
+    H, W, _ = bgr.shape
+    L = _lib.lib()
+    ws_bytes = L.dflow_canny_workspace_bytes(H, W)
+    if ws_bytes == 0:
+        raise _lib.DflowError("dflow_canny_workspace_bytes: %s" % L.dflow_last_error().decode())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=bgr.device)
+    edges = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
+    iv = torch.empty((H, W), dtype=torch.float32, device=bgr.device) if ivice else None
+    stream = C.c_void_p(torch.cuda.current_stream(bgr.device).cuda_stream)
+    _lib.check(L.dflow_canny_edges(H, W, bgr.data_ptr(), float(low), float(high), edges.data_ptr(),
+                                   iv.data_ptr() if iv is not None else None, ws.data_ptr(), ws_bytes, stream),
+               "dflow_canny_edges")
+    return edges, iv

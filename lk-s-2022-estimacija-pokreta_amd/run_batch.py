@@ -7,7 +7,8 @@ forward/backward consistency check (postprocessing.py:123-135) per pair on rank 
     python -m torch.distributed.run --nproc-per-node 8 run_batch.py --pairs 8 ...
 
 Inputs are synthetic pairs (synth.make_pair, seed 1000*pair); outputs per pair in DIR: the reference's flow .npy names
-for both directions, a .flo of the forward flow, sparse_field_<pair>.npy and parovi_<pair>.txt.
+for both directions, a .flo of the forward flow, sparse_field_<pair>.npy and parovi_<pair>.txt; with --edges also
+ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_ivice: the third EpicFlow input).
 """
 import argparse
 import importlib
@@ -31,6 +32,7 @@ def main(argv=None):
     ap.add_argument("--cell", default=None, help="cell size HxW (default: the geometry's usual cells)")
     ap.add_argument("--fp16-descriptors", action="store_true", help="DAISY values rounded to binary16 (BASELINE configs[4])")
     ap.add_argument("--time", action="store_true", help="run the passes twice and report the wall time of the second run")
+    ap.add_argument("--edges", action="store_true", help="also write ivice_NN.bin (Canny edge map of each pair's first image)")
     a = ap.parse_args(argv)
     import torch
     import torch.distributed as dist
@@ -115,6 +117,10 @@ def main(argv=None):
             flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
             np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
             evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
+            if a.edges:
+                img1 = images[pair][0] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[0]
+                _, ivice = pipeline.canny_edges(img1)
+                ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
             print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
     if world > 1:
         dist.barrier()

@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
+
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed
+
+Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
+dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
+dflow_canny_edges).  Then ../discrete_flow/external/EpicFlow_v1.00/epicflow-static img1 img2 ivice.bin parovi.txt epic.flo
+runs if that binary exists; otherwise one line says the inputs are ready and the binary is absent, and the exit status is 0.
+'sed' edges need a model the reference does not ship: it exits with status 2 and says so.
+"""
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+
+EPICFLOW = "../discrete_flow/external/EpicFlow_v1.00/epicflow-static"     # spremiZaEpic.py:28
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if len(argv) != 6:
+        print(__doc__, file=sys.stderr)
+        return 2
+    kitti1, kitti2, foward, backward, tresh, kind = argv
+    con_tresh = int(tresh)                                                 # :14
+    if kind not in ("canny", "sed"):
+        print("spremiZaEpic: edge kind must be 'canny' or 'sed', not %r" % kind, file=sys.stderr)
+        return 2
+    edge = importlib.import_module(PKG + ".edge")
+    if kind == "sed":
+        try:
+            edge.sed_ivice(kitti1, "ivice.bin")
+        except NotImplementedError as e:
+            print("spremiZaEpic: %s" % e, file=sys.stderr)
+            return 2
+    import torch
+    pipeline = importlib.import_module(PKG + ".pipeline")
+    evaluate = importlib.import_module(PKG + ".evaluate")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    fwd = torch.from_numpy(np.load(foward).astype(np.float32)).to(dev)
+    bwd = torch.from_numpy(np.load(backward).astype(np.float32)).to(dev)
+    sparse = pipeline.fb_consistency(fwd, bwd, con_tresh).cpu().numpy()    # postProcessing, :15
+    np.save("sparse_field.npy", sparse)
+    evaluate.parovi(sparse, "parovi.txt")                                  # :17
+    edge.canny_ivice(kitti1, "ivice.bin")                                  # :19-23
+    if not os.path.exists(EPICFLOW):
+        print("spremiZaEpic: sparse_field.npy, parovi.txt and ivice.bin are ready; %s is absent, EpicFlow not run" % EPICFLOW)
+        return 0
+    return subprocess.run([EPICFLOW, kitti1, kitti2, "ivice.bin", "parovi.txt", "epic.flo"]).returncode
+
+
+if __name__ == "__main__":
+    sys.exit(main())
