@@ -190,6 +190,33 @@ size_t dflow_canny_workspace_bytes(int32_t h, int32_t w);
 int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, double high, uint8_t *d_edges, float *d_ivice,
                       void *d_ws, size_t ws_bytes, void *stream);
 
+/* Edge-aware interpolation of a sparse flow field: EpicFlow's sparse-to-dense step (Revaud et al., CVPR 2015), with integer
+ * geodesics so that the result is unique (DESIGN.md "EpicFlow interpolation").  1 <= h, w <= 8192.
+ * d_sparse (h,w,3) float32 [U,V,valid] (what dflow_fb_consistency writes): a seed is a pixel with valid > 0.5 and finite U,
+ * V; its id is y*w + x.  d_edges (h,w) float32 edge strength e = clamp(E, 0, 1), NaN read as 1; pixel cost
+ * c = 1 + rint(1000 e) in float32.  S, D: the 4-connected geodesic Voronoi diagram with step cost c(p) + c(q), the
+ * lexicographic minimum of (D, seed id).  The seed graph joins the seeds of 4-neighbours p, q with weight
+ * D(p) + c(p) + c(q) + D(q); every seed keeps its nn nearest seeds by (G, id), G the graph distance, itself first, and fits
+ * with weights exp(-k G / 2000) either a Nadaraya-Watson mean (DFLOW_EPIC_NW) or a locally-weighted affine model
+ * (DFLOW_EPIC_LA; the mean when fewer than 3 seeds are listed or the smallest eigenvalue of their weighted position
+ * covariance is below DFLOW_EPIC_TAU px^2).  Every pixel takes the model of its seed: d_flow (h,w,2) float32 [dy,dx].
+ * 1 <= nn <= 256; k finite and > 0; with no seed the flow is all zeros.
+ * Optional outputs (NULL to skip): d_seed_of (h,w) S (-1 without seeds), d_dist (h,w) D (0xFFFFFFFF without seeds),
+ * d_lists (h*w, nn) int32 and d_list_g (h*w, nn) uint64: row y*w + x lists the seed's neighbours and their G in order,
+ * padded with -1 / UINT64_MAX; the rows of non-seed pixels are all padding.
+ * The call reads a change counter back after every few Voronoi rounds, so it synchronises its stream and cannot be
+ * captured into a graph.  The workspace grows linearly with h*w; the workspace-size function returns 0 (and sets
+ * dflow_last_error) for sizes outside the range.  dflow_epic_last_stats reports the Voronoi rounds and the HIP-event
+ * times of the last call on the calling thread: stage_ms[4] = seed init + Voronoi, seed graph, lists + models, dense fill. */
+#define DFLOW_EPIC_LA 0
+#define DFLOW_EPIC_NW 1
+#define DFLOW_EPIC_TAU 1e-3
+size_t dflow_epic_workspace_bytes(int32_t h, int32_t w);
+int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const float *d_edges, int32_t nn, double k,
+                           int32_t method, float *d_flow, int32_t *d_seed_of, uint32_t *d_dist, int32_t *d_lists,
+                           uint64_t *d_list_g, void *d_ws, size_t ws_bytes, void *stream);
+int dflow_epic_last_stats(int32_t *rounds, float *stage_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ SYMBOLS = ("dflow_version", "dflow_last_error", "dflow_default_params", "dflow_w
            "dflow_knn_proposals", "dflow_knn_proposals_timed", "dflow_knn_screen_stats", "dflow_knn_screen_stats_n", "dflow_neighbour_proposals", "dflow_bcd_prepare", "dflow_bcd_phase", "dflow_bcd_sweep",
            "dflow_bcd_phase_batch", "dflow_bcd_sweep_batch",
            "dflow_labels_to_flow", "dflow_fb_consistency", "dflow_pack_compat", "dflow_remove_small_segments_host",
-           "dflow_canny_workspace_bytes", "dflow_canny_edges")
+           "dflow_canny_workspace_bytes", "dflow_canny_edges",
+           "dflow_epic_workspace_bytes", "dflow_epic_interpolate", "dflow_epic_last_stats")
 
 
 FLAG_KNN_EXACT = 1      # DFLOW_FLAG_KNN_EXACT
@@ -79,10 +80,14 @@ def lib():
         L.dflow_pack_compat.argtypes = [pp, vp, vp, vp, vp]
         L.dflow_remove_small_segments_host.argtypes = [vp, i32, i32, C.c_float, i32]
         L.dflow_canny_edges.argtypes = [i32, i32, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
+        L.dflow_epic_interpolate.argtypes = [i32, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.dflow_epic_last_stats.argtypes = [vp, vp]
         for n in SYMBOLS[4:]:
             getattr(L, n).restype = C.c_int
         L.dflow_canny_workspace_bytes.argtypes = [i32, i32]
         L.dflow_canny_workspace_bytes.restype = sz
+        L.dflow_epic_workspace_bytes.argtypes = [i32, i32]
+        L.dflow_epic_workspace_bytes.restype = sz
         _lib = L
     return _lib
 

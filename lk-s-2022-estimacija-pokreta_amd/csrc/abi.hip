@@ -247,6 +247,28 @@ int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, do
     return launch_canny(h, w, d_bgr, lo, hi, d_edges, d_ivice, d_ws, (hipStream_t)stream);
 }
 
+size_t dflow_epic_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return epic_ws_bytes(h, w);
+}
+
+int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const float *d_edges, int32_t nn, double k,
+                           int32_t method, float *d_flow, int32_t *d_seed_of, uint32_t *d_dist, int32_t *d_lists,
+                           uint64_t *d_list_g, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (nn < 1 || nn > 256) return dflow_set_error(DFLOW_EINVAL, "%s: nn=%d outside [1,256]", __func__, nn);
+    if (!isfinite(k) || !(k > 0.0)) return dflow_set_error(DFLOW_EINVAL, "%s: k=%g must be finite and > 0", __func__, k);
+    if (method != DFLOW_EPIC_LA && method != DFLOW_EPIC_NW)
+        return dflow_set_error(DFLOW_EINVAL, "%s: unknown method %d", __func__, method);
+    CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow); CHECK_WS(epic_ws_bytes(h, w));
+    return launch_epic(h, w, d_sparse, d_edges, nn, k, method, d_flow, d_seed_of, d_dist, d_lists, d_list_g, d_ws,
+                       (hipStream_t)stream);
+}
+
+int dflow_epic_last_stats(int32_t *rounds, float *stage_ms) { return epic_last_stats(rounds, stage_ms); }
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

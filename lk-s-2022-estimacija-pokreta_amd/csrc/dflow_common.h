@@ -224,3 +224,8 @@ int launch_fb_consistency(const dflow_params *p, const float *fwd, const float *
 // edges.hip: Canny edge map of a (H,W,3) BGR image; thresholds already swapped and floored
 size_t canny_ws_bytes(int H, int W);
 int launch_canny(int H, int W, const uint8_t *bgr, int lo, int hi, uint8_t *edges, float *ivice, void *ws, hipStream_t s);
+// epic.hip: edge-aware interpolation of a sparse flow field (arguments validated by the caller)
+size_t epic_ws_bytes(int H, int W);
+int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, double k, int method, float *flow,
+                int32_t *seed_of, uint32_t *dist, int32_t *lists, uint64_t *list_g, void *ws, hipStream_t s);
+int epic_last_stats(int32_t *rounds, float *stage_ms);

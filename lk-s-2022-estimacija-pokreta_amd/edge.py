@@ -17,13 +17,17 @@ CANNY_LOW, CANNY_HIGH = 100, 200     # edge.py:25
 
 
 def canny_ivice(fileslike, binfile, low=CANNY_LOW, high=CANNY_HIGH):
-    read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
-    pipeline = importlib.import_module(PKG + ".pipeline")
-    _, ivice = pipeline.canny_edges(read_bgr(fileslike), low, high, ivice=True)
-    data = ivice.cpu().numpy()
+    data = canny_ivice_tensor(fileslike, low, high).cpu().numpy()
     with open(binfile, "wb") as f:
         f.write(np.ascontiguousarray(data, dtype=np.float32).tobytes())
     return data
+
+
+def canny_ivice_tensor(fileslike, low=CANNY_LOW, high=CANNY_HIGH):
+    """The (H,W) float32 ivice map of canny_ivice as a device tensor, without writing it."""
+    read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+    pipeline = importlib.import_module(PKG + ".pipeline")
+    return pipeline.canny_edges(read_bgr(fileslike), low, high, ivice=True)[1]
 
 
 def sed_ivice(fileslike, binfile):

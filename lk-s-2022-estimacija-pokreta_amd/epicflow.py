@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""Drop-in for EpicFlow's interpolation binary, the last call of the reference's spremiZaEpic.py:28:
+
+    python epicflow.py <img1> <img2> <edges.bin> <matches.txt> <out.flo> [-nw] [-nn N] [-k K]
+
+img1 and img2 give H x W (they must have the same size; read as the first CLI reads them).  edges.bin is raw float32
+(H,W), exactly H*W*4 bytes, read as edge strength.  Each line of matches.txt is "x1 y1 x2 y2": a seed at (rint(x1),
+rint(y1)) with flow (x2 - x1, y2 - y1); matches outside the image are dropped and the later of two lines for one pixel
+wins.  The dense flow (pipeline.epic_interpolate on the GPU: locally-weighted affine by default, Nadaraya-Watson with -nw;
+-nn neighbours, default 100; kernel coefficient -k, default 0.8) goes to out.flo.  EpicFlow's match pre-filter and its
+variational refinement are not built (DESIGN.md "EpicFlow interpolation"): their options are refused.  Malformed input
+and unsupported options exit with status 2.
+"""
+import importlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+
+UNSUPPORTED = ("-prefnn", "-iter", "-alpha", "-gamma", "-delta", "-sigma", "-kitti", "-sintel", "-middlebury")
+
+
+class UsageError(ValueError):
+    pass
+
+
+def read_matches(path, H, W):
+    """matches.txt -> (H,W,3) float32 [U,V,valid] sparse field."""
+    rows = []
+    with open(path) as f:
+        for lineno, line in enumerate(f, 1):
+            if not line.strip():
+                continue
+            parts = line.split()
+            if len(parts) != 4:
+                raise UsageError("%s:%d: expected 'x1 y1 x2 y2', got %r" % (path, lineno, line.rstrip("\n")))
+            try:
+                rows.append([float(v) for v in parts])
+            except ValueError:
+                raise UsageError("%s:%d: not a number in %r" % (path, lineno, line.rstrip("\n")))
+    sparse = np.zeros((H, W, 3), np.float32)
+    if not rows:
+        return sparse
+    m = np.array(rows, np.float64)
+    if not np.isfinite(m).all():
+        raise UsageError("%s: a match is not finite" % path)
+    x, y = np.rint(m[:, 0]), np.rint(m[:, 1])
+    keep = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+    m, x, y = m[keep], x[keep].astype(np.int64), y[keep].astype(np.int64)
+    pix = y * W + x
+    _, last = np.unique(pix[::-1], return_index=True)          # the later line for a pixel wins
+    sel = len(pix) - 1 - last
+    flat = sparse.reshape(-1, 3)
+    flat[pix[sel], 0] = (m[sel, 2] - m[sel, 0]).astype(np.float32)
+    flat[pix[sel], 1] = (m[sel, 3] - m[sel, 1]).astype(np.float32)
+    flat[pix[sel], 2] = 1.0
+    return sparse
+
+
+def parse_args(argv):
+    pos, nn, k, method = [], 100, 0.8, "LA"
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "-nw":
+            method = "NW"
+        elif a in ("-nn", "-k"):
+            if i + 1 >= len(argv):
+                raise UsageError("%s needs a value" % a)
+            try:
+                if a == "-nn":
+                    nn = int(argv[i + 1])
+                else:
+                    k = float(argv[i + 1])
+            except ValueError:
+                raise UsageError("%s: bad value %r" % (a, argv[i + 1]))
+            i += 1
+        elif a in UNSUPPORTED:
+            raise UsageError("%s is not supported: the match pre-filter and the variational refinement are not built" % a)
+        elif a.startswith("-") and len(a) > 1:
+            raise UsageError("unknown option %s" % a)
+        else:
+            pos.append(a)
+        i += 1
+    if len(pos) != 5:
+        raise UsageError("expected 5 positional arguments, got %d" % len(pos))
+    if not 1 <= nn <= 256:
+        raise UsageError("-nn %d outside [1,256]" % nn)
+    if not (np.isfinite(k) and k > 0):
+        raise UsageError("-k %g must be finite and > 0" % k)
+    return pos, nn, k, method
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    try:
+        (im1, im2, edges_bin, matches, out), nn, k, method = parse_args(argv)
+        read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+        H, W = read_bgr(im1).shape[:2]
+        if read_bgr(im2).shape[:2] != (H, W):
+            raise UsageError("%s and %s differ in size" % (im1, im2))
+        raw = open(edges_bin, "rb").read()
+        if len(raw) != 4 * H * W:
+            raise UsageError("%s holds %d bytes, not %d (float32 %dx%d)" % (edges_bin, len(raw), 4 * H * W, W, H))
+        edges = np.frombuffer(raw, np.float32).reshape(H, W).copy()
+        sparse = read_matches(matches, H, W)
+    except (UsageError, OSError) as e:
+        print("epicflow: %s" % e, file=sys.stderr)
+        if isinstance(e, UsageError):
+            print(__doc__, file=sys.stderr)
+        return 2
+    pipeline = importlib.import_module(PKG + ".pipeline")
+    flowio = importlib.import_module(PKG + ".flowio")
+    flow = pipeline.epic_interpolate(sparse, edges, nn=nn, k=k, method=method)
+    flowio.write_flo(out, flow.cpu().numpy())
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

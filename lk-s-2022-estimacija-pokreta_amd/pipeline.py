@@ -298,3 +298,61 @@ def canny_edges(bgr, low=100, high=200, ivice=True):
                                    iv.data_ptr() if iv is not None else None, ws.data_ptr(), ws_bytes, stream),
                "dflow_canny_edges")
     return edges, iv
+
+
+EPIC_METHODS = {"LA": 0, "NW": 1}     # DFLOW_EPIC_LA, DFLOW_EPIC_NW
+
+
+def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists=True):
+    """EpicFlow's sparse-to-dense step (dflow_epic_interpolate): a (H,W,3) float32 [U,V,valid] sparse field and a (H,W)
+    float32 edge map (device tensors or host arrays; host data is uploaded to the current device) -> (H,W,2) float32 [dy,dx]
+    device tensor.  nn neighbours per seed, kernel coefficient k, method "LA" (locally-weighted affine) or "NW"
+    (Nadaraya-Watson).  With aux=True returns (flow, S, D, lists, list_g): S (H,W) int32 seed ids (-1 without seeds),
+    D (H,W) int32 geodesic distances (the uint32 bits; -1 without seeds), lists (H*W, nn) int32 and list_g (H*W, nn) int64
+    (-1 pads; None with lists=False: they take H*W*nn*12 bytes).  Runs on torch's current stream; the call synchronises
+    that stream (the Voronoi loop reads a counter back)."""
+    if method not in EPIC_METHODS:
+        raise ValueError("epic_interpolate: method must be 'LA' or 'NW', not %r" % (method,))
+    dev = sparse.device if isinstance(sparse, torch.Tensor) and sparse.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+    def upload(a, name, shape):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        if a.dtype != torch.float32 or tuple(a.shape) != shape:
+            raise ValueError("epic_interpolate: %s must be float32 %s, got %s %s" % (name, shape, tuple(a.shape), a.dtype))
+        return a.to(dev).contiguous()
+    if not isinstance(sparse, torch.Tensor):
+        sparse = torch.from_numpy(np.ascontiguousarray(sparse))
+    if sparse.dim() != 3 or sparse.shape[2] != 3:
+        raise ValueError("epic_interpolate: sparse must be (H,W,3) [U,V,valid], got %s" % (tuple(sparse.shape),))
+    H, W = int(sparse.shape[0]), int(sparse.shape[1])
+    sparse = upload(sparse, "sparse", (H, W, 3))
+    edges = upload(edges, "edges", (H, W))
+    L = _lib.lib()
+    ws_bytes = L.dflow_epic_workspace_bytes(H, W)
+    if ws_bytes == 0:
+        raise _lib.DflowError("dflow_epic_workspace_bytes: %s" % L.dflow_last_error().decode())
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
+    S = D = lst = list_g = None
+    if aux:
+        S = torch.empty((H, W), dtype=torch.int32, device=dev)
+        D = torch.empty((H, W), dtype=torch.int32, device=dev)
+        if lists:
+            lst = torch.empty((H * W, int(nn)), dtype=torch.int32, device=dev)
+            list_g = torch.empty((H * W, int(nn)), dtype=torch.int64, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.dflow_epic_interpolate(H, W, sparse.data_ptr(), edges.data_ptr(), int(nn), float(k), EPIC_METHODS[method],
+                                        flow.data_ptr(), ptr(S), ptr(D), ptr(lst), ptr(list_g), ws.data_ptr(), ws_bytes,
+                                        stream), "dflow_epic_interpolate")
+    return (flow, S, D, lst, list_g) if aux else flow
+
+
+def epic_last_stats():
+    """(Voronoi rounds, {stage: ms}) of the last epic_interpolate on this thread, from HIP events (waits for them)."""
+    rounds, ms = C.c_int32(0), (C.c_float * 4)()
+    _lib.check(_lib.lib().dflow_epic_last_stats(C.byref(rounds), ms), "dflow_epic_last_stats")
+    return rounds.value, dict(zip(("voronoi", "graph", "lists", "fill"), (float(v) for v in ms)))

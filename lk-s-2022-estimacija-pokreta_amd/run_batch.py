@@ -8,7 +8,9 @@ forward/backward consistency check (postprocessing.py:123-135) per pair on rank 
 
 Inputs are synthetic pairs (synth.make_pair, seed 1000*pair); outputs per pair in DIR: the reference's flow .npy names
 for both directions, a .flo of the forward flow, sparse_field_<pair>.npy and parovi_<pair>.txt; with --edges also
-ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_ivice: the third EpicFlow input).
+ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_ivice: the third EpicFlow input); with
+--epic also epic_<pair>.flo, the dense flow interpolated from the pair's sparse field and that edge map
+(pipeline.epic_interpolate, EpicFlow's defaults).
 """
 import argparse
 import importlib
@@ -33,6 +35,7 @@ def main(argv=None):
     ap.add_argument("--fp16-descriptors", action="store_true", help="DAISY values rounded to binary16 (BASELINE configs[4])")
     ap.add_argument("--time", action="store_true", help="run the passes twice and report the wall time of the second run")
     ap.add_argument("--edges", action="store_true", help="also write ivice_NN.bin (Canny edge map of each pair's first image)")
+    ap.add_argument("--epic", action="store_true", help="also write epic_NN.flo (edge-aware interpolation of each pair's sparse field)")
     a = ap.parse_args(argv)
     import torch
     import torch.distributed as dist
@@ -111,16 +114,21 @@ def main(argv=None):
         os.makedirs(a.out, exist_ok=True)
         for pair in range(a.pairs):
             fwd, bwd = flows[2 * pair], flows[2 * pair + 1]
-            sparse = pipeline.fb_consistency(fwd, bwd, a.thresh).cpu().numpy()
+            sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
+            sparse = sparse_dev.cpu().numpy()
             for backward, f in ((0, fwd), (1, bwd)):
                 np.save(os.path.join(a.out, flowio.flow_name(pair, backward, a.bcd_times)), f.cpu().numpy().astype(np.float64))
             flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
             np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
             evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
-            if a.edges:
+            if a.edges or a.epic:
                 img1 = images[pair][0] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[0]
                 _, ivice = pipeline.canny_edges(img1)
+            if a.edges:
                 ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
+            if a.epic:
+                epic = pipeline.epic_interpolate(sparse_dev, ivice)
+                flowio.write_flo(os.path.join(a.out, "epic_%02d.flo" % pair), epic.cpu().numpy())
             print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
     if world > 1:
         dist.barrier()

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed [--gpu-epic]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
 dflow_canny_edges).  Then ../discrete_flow/external/EpicFlow_v1.00/epicflow-static img1 img2 ivice.bin parovi.txt epic.flo
 runs if that binary exists; otherwise one line says the inputs are ready and the binary is absent, and the exit status is 0.
 'sed' edges need a model the reference does not ship: it exits with status 2 and says so.
+With the opt-in seventh token --gpu-epic, epic.flo is written by this package's own interpolation (epicflow.py,
+pipeline.epic_interpolate) from the device-side sparse field and edge map, with EpicFlow's defaults, and the binary is not
+run.  ivice.bin is handed over as the reference writes it, (255 - edges) / 255 (DESIGN.md "EpicFlow interpolation").
 """
 import importlib
 import os
@@ -24,10 +27,11 @@ EPICFLOW = "../discrete_flow/external/EpicFlow_v1.00/epicflow-static"     # spre
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    if len(argv) != 6:
+    gpu_epic = len(argv) == 7 and argv[6] == "--gpu-epic"
+    if len(argv) != 6 and not gpu_epic:
         print(__doc__, file=sys.stderr)
         return 2
-    kitti1, kitti2, foward, backward, tresh, kind = argv
+    kitti1, kitti2, foward, backward, tresh, kind = argv[:6]
     con_tresh = int(tresh)                                                 # :14
     if kind not in ("canny", "sed"):
         print("spremiZaEpic: edge kind must be 'canny' or 'sed', not %r" % kind, file=sys.stderr)
@@ -45,9 +49,18 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     fwd = torch.from_numpy(np.load(foward).astype(np.float32)).to(dev)
     bwd = torch.from_numpy(np.load(backward).astype(np.float32)).to(dev)
-    sparse = pipeline.fb_consistency(fwd, bwd, con_tresh).cpu().numpy()    # postProcessing, :15
+    sparse_dev = pipeline.fb_consistency(fwd, bwd, con_tresh)
+    sparse = sparse_dev.cpu().numpy()                                      # postProcessing, :15
     np.save("sparse_field.npy", sparse)
     evaluate.parovi(sparse, "parovi.txt")                                  # :17
+    if gpu_epic:
+        ivice = edge.canny_ivice_tensor(kitti1)
+        with open("ivice.bin", "wb") as f:
+            f.write(ivice.cpu().numpy().tobytes())
+        flow = pipeline.epic_interpolate(sparse_dev, ivice)                # the step epicflow-static would take
+        importlib.import_module(PKG + ".flowio").write_flo("epic.flo", flow.cpu().numpy())
+        print("spremiZaEpic: sparse_field.npy, parovi.txt, ivice.bin and epic.flo written (GPU interpolation)")
+        return 0
     edge.canny_ivice(kitti1, "ivice.bin")                                  # :19-23
     if not os.path.exists(EPICFLOW):
         print("spremiZaEpic: sparse_field.npy, parovi.txt and ivice.bin are ready; %s is absent, EpicFlow not run" % EPICFLOW)

@@ -1,0 +1,41 @@
+"""dflow_epic_interpolate alone, per-stage HIP-event times and Voronoi rounds: python tools/epic_time.py [reps]
+Sizes 1024x436 (the bench frame) and 1242x375 (KITTI).  Seeds: the forward/backward consistency output of a synthetic pass
+(what the reference feeds EpicFlow: every valid pixel), and its 1-in-16 grid subsample; edges: the Canny ivice map of the
+first image, as spremiZaEpic.py writes it.  LA, nn=100, k=0.8.  Prints one JSON line: median and minimum ms per call
+(host wall time, the call synchronises) and the median of each stage."""
+import importlib, json, os, sys, time
+import numpy as np, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+pipeline = importlib.import_module("lk-s-2022-estimacija-pokreta_amd.pipeline")
+synth = importlib.import_module("lk-s-2022-estimacija-pokreta_amd.synth")
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+dev = torch.device("cuda", 0)
+out = {}
+for (H, W) in ((436, 1024), (375, 1242)):
+    img1, img2, _ = synth.make_pair(H, W, seed=1)
+    flows = []
+    for a, b in ((img1, img2), (img2, img1)):
+        df = pipeline.DiscreteFlow(H, W, device=dev, seed=0)
+        flows.append(df.run(a, b, 4).clone())
+    sparse = pipeline.fb_consistency(flows[0], flows[1], 10)           # con_tresh of the reference README.md:65
+    _, ivice = pipeline.canny_edges(img1)
+    sub = torch.zeros_like(sparse)
+    sub[::4, ::4] = sparse[::4, ::4]
+    for name, sp in (("consistency", sparse), ("grid16", sub)):
+        for _ in range(3):
+            pipeline.epic_interpolate(sp, ivice)
+        wall, stages, rounds = [], [], None
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pipeline.epic_interpolate(sp, ivice)
+            torch.cuda.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            rounds, ms = pipeline.epic_last_stats()
+            stages.append(ms)
+        wall.sort()
+        out["%dx%d_%s" % (W, H, name)] = {
+            "seeds_pct": round(100.0 * float((sp[..., 2] > 0.5).float().mean()), 1), "rounds": rounds,
+            "median_ms": round(wall[len(wall) // 2], 3), "min_ms": round(wall[0], 3),
+            "stage_median_ms": {k: round(float(np.median([s[k] for s in stages])), 3) for k in stages[0]}}
+print(json.dumps(out))
