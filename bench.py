@@ -7,11 +7,16 @@ DAISY x2 -> per-cell exact 5-NN proposals -> neighbour proposals -> 4 BCD sweeps
 N > 1: one process per GPU (torch.distributed over RCCL); every rank processes its own pairs (weak scaling,
 no data-path collective) and the flow fields are gathered on rank 0 over xGMI after every step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 The timed region is exactly K steps.  --dump-outputs DIR writes what the last timed step returned (the flow field, and on
 rank 0 of a multi-rank run the fields gathered from every rank) as DIR/<name>.npy; the inputs depend only on the arguments,
 so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the outputs, the JSON line.
+--full adds everything else after the timed region: the fixed batch (BASELINE configs[3], `fixed_batch`), the roofline with
+per-kernel and per-stage times, the single-pair latency, the EPE, the one-GPU timings of the other BASELINE configurations
+(`other_configs`) and the CPU baseline; --no-cpu-baseline, --no-other-configs and --fixed-batch 0 leave parts of it out.
 
 `python bench.py --gpus N` (N > 1, no RANK in the environment) starts its N ranks itself -- before anything touches the
 GPU -- and relays rank 0's JSON line; under `python -m torch.distributed.run ... bench.py --gpus N` the ranks are the
@@ -32,6 +37,7 @@ PKG = "lk-s-2022-estimacija-pokreta_amd"
 
 H, W, BCD_TIMES = 436, 1024, 4
 LONG_STEPS = 98                # the default --steps; --long-run adds one timed region of this length to a run with another --steps
+FIXED_BATCH_PASSES = 16        # BASELINE configs[3]: 8 pairs x (forward, backward); run by --full unless --fixed-batch says otherwise
 DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: all files together
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/F16 MFMA ~2.5 PF dense (the kNN screen runs on f16 MFMA)
@@ -730,7 +736,8 @@ def worker(args):
     # drain of the two-group pipeline weigh < 10 %) right behind it, reported beside the headline, never instead of it
     dt_long = timed_region(LONG_STEPS, False) if (args.steps != LONG_STEPS and args.long_run and not args.stub) else None
 
-    fixed = run_fixed_batch(eng, args.fixed_batch, world, rank, use_dist, sync_all) if args.fixed_batch > 0 else None
+    fixed_batch = args.fixed_batch if args.fixed_batch is not None else (FIXED_BATCH_PASSES if args.full else 0)
+    fixed = run_fixed_batch(eng, fixed_batch, world, rank, use_dist, sync_all) if fixed_batch > 0 else None
 
     if rank == 0:
         out = {
@@ -748,7 +755,9 @@ def worker(args):
         if fixed is not None:
             out["fixed_batch"] = fixed
         if not args.stub:
-            finish_report(out, eng, args, world)
+            out["config"] = workload_config(eng, args)
+            if args.full:
+                finish_report(out, eng, args, world)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()
@@ -879,18 +888,24 @@ def other_configs(eng, args):
     return res
 
 
+def workload_config(eng, args):
+    """What the headline measured: the workload and how the steps were laid out on the GPU (no GPU work)."""
+    P = eng.P
+    return {"workload": "single 1024x436 Sintel-shape pair per step per GPU, forward only, bcd_times=4 "
+                        "(BASELINE.json configs[1]); cells 64x27, 150 labels/px",
+            "pairs_in_flight_per_gpu": P, "pair_seeds_rank0": eng.seeds, "mode": args.mode,
+            "parallelism": ("one pass per step, steps in equal groups of at most %d: front end of a group's pairs (DAISY, kNN, neighbour proposals) on %d HIP streams, "
+                            "their compat lists on a fourth, the BCD sweeps of the group on a fifth: one batched launch per phase (chains x passes), two groups "
+                            "alternate so that front end and sweeps of consecutive groups overlap; flow fields gathered "
+                            "on rank 0" % (P, args.front)) if args.mode == "batch" else
+                           ("one pass per step; %d independent steps in flight per GPU on separate HIP streams; "
+                            "flow fields gathered on rank 0" % P)}
+
+
 def finish_report(out, eng, args, world):
+    """--full: everything the line carries beyond the headline, measured after the timed region."""
     torch = eng.torch
     P = eng.P
-    out["config"] = {"workload": "single 1024x436 Sintel-shape pair per step per GPU, forward only, bcd_times=4 "
-                                 "(BASELINE.json configs[1]); cells 64x27, 150 labels/px",
-                     "pairs_in_flight_per_gpu": P, "pair_seeds_rank0": eng.seeds, "mode": args.mode,
-                     "parallelism": ("one pass per step, steps in equal groups of at most %d: front end of a group's pairs (DAISY, kNN, neighbour proposals) on %d HIP streams, "
-                                     "their compat lists on a fourth, the BCD sweeps of the group on a fifth: one batched launch per phase (chains x passes), two groups "
-                                     "alternate so that front end and sweeps of consecutive groups overlap; flow fields gathered "
-                                     "on rank 0" % (P, args.front)) if args.mode == "batch" else
-                                    ("one pass per step; %d independent steps in flight per GPU on separate HIP streams; "
-                                     "flow fields gathered on rank 0" % P)}
     # ---- bcd_chain_kernel: 4 sweeps x 4 phases = 16 launches between the two events of a group
     launches = 4 * BCD_TIMES
     # (start, end, passes in the launch): a batched launch carries the chains of several passes
@@ -974,13 +989,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=LONG_STEPS)       # 14 groups of 7: the fill and drain of the two-group pipeline weigh < 10 %
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the fixed batch, the roofline, EPE, other-configuration and CPU-baseline "
+                         "measurements (a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--long-run", action="store_true",
                     help="after the --steps region, time one more region of %d steps (ms_per_step_%d)" % (LONG_STEPS, LONG_STEPS))
     ap.add_argument("--no-long-run", action="store_true", help=argparse.SUPPRESS)   # the default; kept for recorded commands
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the one-GPU timings of BASELINE configs[2] and [4]")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the one-GPU timings of BASELINE configs[2] and [4]")
     ap.add_argument("--inflight", type=int, default=3,
                     help="independent pairs in flight per GPU (each on its own HIP stream and workspace)")
     ap.add_argument("--mode", choices=("streams", "batch"), default="batch",
@@ -990,9 +1008,10 @@ def main():
     ap.add_argument("--front", type=int, default=3, help="HIP streams for the front end of a group in --mode batch")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks on device 0, gather over gloo (a multi-rank rehearsal on a one-GPU box; not a measurement)")
-    ap.add_argument("--fixed-batch", type=int, default=16,
+    ap.add_argument("--fixed-batch", type=int, default=None,
                     help="passes of the fixed batch run after the timed steps (BASELINE configs[3]: 8 pairs x 2 directions, pass p -> rank "
-                         "p mod N: strong scaling, reported under fixed_batch); 0: skip")
+                         "p mod N: strong scaling, reported under fixed_batch); default %d with --full, 0 (skip) otherwise"
+                         % FIXED_BATCH_PASSES)
     ap.add_argument("--groups", default=None, help=argparse.SUPPRESS)    # experiment: explicit group sizes of the timed region
     ap.add_argument("--no-lists-stream", action="store_true", help=argparse.SUPPRESS)   # experiment: compat lists on the BCD stream itself
     ap.add_argument("--lists-on-front", action="store_true", help=argparse.SUPPRESS)    # experiment: compat lists on the front-end streams (before round 3: the default)

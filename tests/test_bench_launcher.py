@@ -19,7 +19,7 @@ def _run(extra, env=None):
 
 
 def test_bench_self_launches_two_ranks():
-    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub"])
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout
@@ -31,6 +31,14 @@ def test_bench_self_launches_two_ranks():
     fb = d["fixed_batch"]
     assert fb["passes"] == 16 and fb["passes_per_rank"] == 8 and fb["n_gpus"] == 2 and fb["scaling"] == "strong"
     assert abs(fb["Mpix/s"] - 16 * 436 * 1024 / (fb["ms"] * 1e-3) / 1e6) < 1e-6 * fb["Mpix/s"]
+
+
+def test_plain_run_is_the_headline_alone():
+    # without --full nothing runs after the timed steps: no fixed batch (nor, on the GPU, roofline, EPE, other configs, CPU baseline)
+    out = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub"])
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and "fixed_batch" not in d
 
 
 def test_dump_outputs_of_the_last_step(tmp_path):

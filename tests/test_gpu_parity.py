@@ -813,10 +813,11 @@ def test_bench_contract(torch_, tmp_path):
     """bench.py prints ONE JSON line with the driver's keys, the roofline object (the kernel with the larger measured time per
     step of knn_screen_kernel / bcd_chain_kernel, both carried, + per-stage fractions), the one-pair latency, one-GPU timings of
     BASELINE configs[2] and [4], the CPU baseline (whole bench pair + the configs[0] geometry + the single-thread sample) and the EPE of
-    the GPU flow and of the oracle's flow on the bench pair (difference exactly 0); run as a child process, as the driver does."""
+    the GPU flow and of the oracle's flow on the bench pair (difference exactly 0), all of which --full adds to the headline; run as
+    a child process, as the driver does."""
     import json, os, subprocess, sys
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=1500, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -863,7 +864,7 @@ def test_bench_two_ranks_rehearsal(torch_, tmp_path):
     import json, os, subprocess, sys
     from conftest import ROOT
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                          "--batch", "2", "--front", "2", "--no-cpu-baseline", "--rehearse-on-one-gpu"],
+                          "--batch", "2", "--front", "2", "--full", "--no-cpu-baseline", "--rehearse-on-one-gpu"],
                          capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -887,6 +888,7 @@ def test_bench_dump_outputs_is_the_last_timed_step(torch_, oracle, synth, tmp_pa
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][0])
     assert d["steps"] == 4 and not any(k.startswith(("ms_per_step_", "value_")) for k in d)
+    assert "config" in d and not set(d) & {"roofline", "latency_ms_single_pair", "epe", "fixed_batch"}     # no --full
     assert sorted(os.listdir(dump)) == ["flow.npy"]
     got = np.load(dump / "flow.npy")
     assert got.dtype == np.float32 and got.shape == (436, 1024, 2)
