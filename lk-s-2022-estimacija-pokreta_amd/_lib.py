@@ -8,14 +8,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libdflow.so")
 
-SYMBOLS = ("dflow_version", "dflow_last_error", "dflow_default_params", "dflow_workspace_bytes", "dflow_daisy",
-           "dflow_knn_proposals", "dflow_knn_proposals_timed", "dflow_knn_screen_stats", "dflow_knn_screen_stats_n", "dflow_neighbour_proposals", "dflow_bcd_prepare", "dflow_bcd_phase", "dflow_bcd_sweep",
-           "dflow_bcd_phase_batch", "dflow_bcd_sweep_batch",
-           "dflow_labels_to_flow", "dflow_fb_consistency", "dflow_pack_compat", "dflow_remove_small_segments_host",
-           "dflow_canny_workspace_bytes", "dflow_canny_edges",
-           "dflow_epic_workspace_bytes", "dflow_epic_interpolate", "dflow_epic_last_stats")
-
-
 FLAG_KNN_EXACT = 1      # DFLOW_FLAG_KNN_EXACT
 FLAG_DESCR_F16 = 8      # DFLOW_FLAG_DESCR_F16
 DESC_PITCH_F16 = 72     # DFLOW_DESC_PITCH_F16: binary16 descriptor planes are (H,W,72)
@@ -31,6 +23,38 @@ class Params(C.Structure):
                 ("maxnprop", C.c_int32), ("knn", C.c_int32), ("window", C.c_int32), ("ngauss", C.c_int32),
                 ("tpsi", C.c_int32), ("max_attempts", C.c_int32), ("tphi", C.c_float), ("sigma", C.c_float),
                 ("lamda", C.c_double), ("seed", C.c_uint64), ("label_pitch", C.c_int32), ("flags", C.c_int32)]
+
+
+_vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
+_pp = C.POINTER(Params)
+# every C-ABI function: name -> (return type, argument types)
+_SIGNATURES = {
+    "dflow_version": (C.c_int, []),
+    "dflow_last_error": (C.c_char_p, []),
+    "dflow_default_params": (None, [_pp, _i32, _i32, _i32, _i32]),
+    "dflow_workspace_bytes": (_sz, [_pp]),
+    "dflow_daisy": (C.c_int, [_pp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_knn_proposals": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_knn_proposals_timed": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(_f32), C.POINTER(_f64)]),
+    "dflow_knn_screen_stats": (C.c_int, [_pp, _vp, _sz, _vp, C.POINTER(C.c_int64)]),
+    "dflow_knn_screen_stats_n": (C.c_int, [_pp, _vp, _sz, _vp, C.POINTER(C.c_int64), _i32]),
+    "dflow_neighbour_proposals": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_bcd_prepare": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_bcd_phase": (C.c_int, [_pp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "dflow_bcd_sweep": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_bcd_phase_batch": (C.c_int, [_pp, _i32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "dflow_bcd_sweep_batch": (C.c_int, [_pp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_labels_to_flow": (C.c_int, [_pp, _vp, _vp, _vp, _vp]),
+    "dflow_fb_consistency": (C.c_int, [_pp, _vp, _vp, _f32, _vp, _vp]),
+    "dflow_pack_compat": (C.c_int, [_pp, _vp, _vp, _vp, _vp]),
+    "dflow_remove_small_segments_host": (C.c_int, [_vp, _i32, _i32, _f32, _i32]),
+    "dflow_canny_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_canny_edges": (C.c_int, [_i32, _i32, _vp, _f64, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_epic_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_epic_interpolate": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_epic_last_stats": (C.c_int, [_vp, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES)
 
 
 def build(force=False):
@@ -56,38 +80,9 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
-        pp = C.POINTER(Params)
-        L.dflow_version.restype = C.c_int
-        L.dflow_last_error.restype = C.c_char_p
-        L.dflow_default_params.argtypes = [pp, i32, i32, i32, i32]
-        L.dflow_default_params.restype = None
-        L.dflow_workspace_bytes.argtypes = [pp]
-        L.dflow_workspace_bytes.restype = sz
-        L.dflow_daisy.argtypes = [pp, vp, vp, vp, sz, vp]
-        L.dflow_knn_proposals.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        L.dflow_knn_proposals_timed.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-        L.dflow_knn_screen_stats.argtypes = [pp, vp, sz, vp, C.POINTER(C.c_int64)]
-        L.dflow_knn_screen_stats_n.argtypes = [pp, vp, sz, vp, C.POINTER(C.c_int64), i32]
-        L.dflow_neighbour_proposals.argtypes = [pp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-        L.dflow_bcd_prepare.argtypes = [pp, vp, vp, vp, vp, sz, vp]
-        L.dflow_bcd_phase.argtypes = [pp, vp, vp, vp, i32, vp, sz, vp]
-        L.dflow_bcd_sweep.argtypes = [pp, vp, vp, vp, vp, sz, vp]
-        L.dflow_bcd_phase_batch.argtypes = [pp, i32, vp, vp, i32, vp, sz, vp]
-        L.dflow_bcd_sweep_batch.argtypes = [pp, i32, vp, vp, vp, sz, vp]
-        L.dflow_labels_to_flow.argtypes = [pp, vp, vp, vp, vp]
-        L.dflow_fb_consistency.argtypes = [pp, vp, vp, C.c_float, vp, vp]
-        L.dflow_pack_compat.argtypes = [pp, vp, vp, vp, vp]
-        L.dflow_remove_small_segments_host.argtypes = [vp, i32, i32, C.c_float, i32]
-        L.dflow_canny_edges.argtypes = [i32, i32, vp, C.c_double, C.c_double, vp, vp, vp, sz, vp]
-        L.dflow_epic_interpolate.argtypes = [i32, i32, vp, vp, i32, C.c_double, i32, vp, vp, vp, vp, vp, vp, sz, vp]
-        L.dflow_epic_last_stats.argtypes = [vp, vp]
-        for n in SYMBOLS[4:]:
-            getattr(L, n).restype = C.c_int
-        L.dflow_canny_workspace_bytes.argtypes = [i32, i32]
-        L.dflow_canny_workspace_bytes.restype = sz
-        L.dflow_epic_workspace_bytes.argtypes = [i32, i32]
-        L.dflow_epic_workspace_bytes.restype = sz
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -95,6 +90,27 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise DflowError("%s failed (%d): %s" % (what, rc, lib().dflow_last_error().decode()))
+
+
+def call(name, *args):
+    """lib().name(*args); raises DflowError (with the name and dflow_last_error()) unless it returns 0."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def stream(device):
+    """The HIP stream handle torch uses on `device` now (every C-ABI call runs on it)."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def workspace(name, h, w, device):
+    """A device buffer of lib().name(h, w) bytes (a *_workspace_bytes function of an (h, w) image) and its size; raises
+    DflowError if the function refuses the size."""
+    import torch
+    nbytes = getattr(lib(), name)(h, w)
+    if nbytes == 0:
+        raise DflowError("%s: %s" % (name, lib().dflow_last_error().decode()))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
 def default_params(pich, picw, cellh, cellw, **kw):

@@ -16,9 +16,8 @@ def packedksets(df):
     H, W, L = df.p.pich, df.p.picw, df.p.maxnprop
     kdim = L * L // 8 + 1
     dev = torch.empty((H, W, 2, kdim), dtype=torch.uint8, device=df.device)
-    stream = C.c_void_p(torch.cuda.current_stream(df.device).cuda_stream)
-    _lib.check(_lib.lib().dflow_pack_compat(C.byref(df.p), df.proposals.data_ptr(), df.nprop.data_ptr(), dev.data_ptr(), stream),
-               "dflow_pack_compat")
+    _lib.call("dflow_pack_compat", C.byref(df.p), df.proposals.data_ptr(), df.nprop.data_ptr(), dev.data_ptr(),
+              _lib.stream(df.device))
     packed = dev.cpu().numpy()
     replay_border_scratch(packed, df.nprop.cpu().numpy(), L)
     return packed
@@ -66,7 +65,6 @@ def remove_small_segments(sparse, tresh, min_segment_size):
     if not (isinstance(sparse, np.ndarray) and sparse.dtype == np.float32 and sparse.ndim == 3 and sparse.shape[2] == 3
             and sparse.flags.c_contiguous):
         raise ValueError("sparse must be a C-contiguous float32 (A,B,3) array")
-    _lib.check(_lib.lib().dflow_remove_small_segments_host(sparse.ctypes.data, sparse.shape[0], sparse.shape[1],
-                                                           float(tresh), int(min_segment_size)),
-               "dflow_remove_small_segments_host")
+    _lib.call("dflow_remove_small_segments_host", sparse.ctypes.data, sparse.shape[0], sparse.shape[1], float(tresh),
+              int(min_segment_size))
     return sparse

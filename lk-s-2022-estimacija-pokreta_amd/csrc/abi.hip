@@ -66,11 +66,10 @@ void dflow_default_params(dflow_params *p, int32_t pich, int32_t picw, int32_t c
 size_t dflow_workspace_bytes(const dflow_params *p)
 {
     if (dflow_check_params(p) != DFLOW_OK) return 0;
-    size_t a = daisy_ws_bytes(p), b = bcd_ws_bytes(p), c = knn_mfma_supported(p) ? knn_mfma_ws_bytes(p) : 0;
-    size_t d = neighbour_ws_bytes(p);
-    size_t m = a > b ? a : b;
-    if (d > m) m = d;
-    return (m > c ? m : c) + 256;
+    size_t m = daisy_ws_bytes(p);
+    for (size_t b : {bcd_ws_bytes(p), neighbour_ws_bytes(p), knn_mfma_supported(p) ? knn_mfma_ws_bytes(p) : (size_t)0})
+        if (b > m) m = b;
+    return m + DFLOW_WS_SLACK;
 }
 
 #define CHECK_PTR(x) do { if (!(x)) return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", __func__, #x); } while (0)
@@ -106,14 +105,17 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
     if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
         return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
     CHECK_WS(knn_mfma_ws_bytes(p));
-    hipEvent_t ev[KNN_MFMA_EVENTS];
-    for (int k = 0; k < KNN_MFMA_EVENTS; k++)
-        if (hipEventCreate(&ev[k]) != hipSuccess) return dflow_set_error(DFLOW_EHIP, "hipEventCreate failed");
-    rc = launch_knn_mfma(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream, ev);
-    if (rc == DFLOW_OK && hipEventSynchronize(ev[KNN_MFMA_EVENTS - 1]) != hipSuccess) rc = dflow_set_error(DFLOW_EHIP, "hipEventSynchronize failed");
-    for (int k = 0; rc == DFLOW_OK && k + 1 < KNN_MFMA_EVENTS; k++)
-        if (hipEventElapsedTime(&h_ms[k], ev[k], ev[k + 1]) != hipSuccess) rc = dflow_set_error(DFLOW_EHIP, "hipEventElapsedTime failed");
-    for (int k = 0; k < KNN_MFMA_EVENTS; k++) (void)hipEventDestroy(ev[k]);
+    hipEvent_t ev[KNN_MFMA_EVENTS] = {};
+    rc = [&]() {
+        for (hipEvent_t &e : ev) DFLOW_HIP(hipEventCreate(&e));
+        const int r = launch_knn_mfma(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream, ev);
+        if (r) return r;
+        DFLOW_HIP(hipEventSynchronize(ev[KNN_MFMA_EVENTS - 1]));
+        for (int k = 0; k + 1 < KNN_MFMA_EVENTS; k++) DFLOW_HIP(hipEventElapsedTime(&h_ms[k], ev[k], ev[k + 1]));
+        return DFLOW_OK;
+    }();
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);        // clean-up: the first error, if any, is the one reported
     if (h_mfma_issued) *h_mfma_issued = knn_mfma_issued(p);
     return rc;
 }
@@ -162,7 +164,7 @@ int dflow_bcd_phase(const dflow_params *p, const uint32_t *d_proposals, const in
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_WS(bcd_ws_bytes(p));
     if (phase < 0 || phase > 3) return dflow_set_error(DFLOW_EINVAL, "phase=%d outside [0,3]", phase);
-    return launch_bcd_phase(p, d_proposals, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
+    return launch_bcd_phase(p, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
 
 int dflow_bcd_sweep(const dflow_params *p, const uint32_t *d_proposals, const int32_t *d_nprop, int32_t *d_bestlabels,

@@ -737,55 +737,42 @@ static void phase_dims(const dflow_params *p, int phase, int &nchains, int &len)
     else { nchains = H / 2; len = W; }
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static size_t back_bytes(const dflow_params *p)
-{
-    size_t m = 0;
-    for (int ph = 0; ph < 4; ph++) {
-        int n, len;
-        phase_dims(p, ph, n, len);
-        size_t b = (size_t)n * len * BCD_BACK_PITCH;
-        if (b > m) m = b;
-    }
-    return align256(m) + 256;
-}
-
-static size_t lab_bytes(const dflow_params *p) { return align256((size_t)p->pich * p->picw * p->label_pitch * 8); }
-static size_t blka_bytes(const dflow_params *p) { return align256((size_t)p->pich * p->picw * 2 * p->label_pitch * 8); }
-static size_t blkbc_bytes(const dflow_params *p) { return align256((size_t)p->pich * p->picw * 2 * BCD_ROW_BC * 8); }
 static uint32_t pool_rows_of(const dflow_params *p)
 {
     const size_t rows = (size_t)p->pich * p->picw * 2 * p->label_pitch / BCD_POOL_DIV;
     return (uint32_t)(rows < 4096 ? 4096 : rows);
 }
-static size_t mask_bytes(const dflow_params *p) { return align256((size_t)pool_rows_of(p) * BCD_MASK_WORDS * sizeof(uint32_t)); }
 
-size_t bcd_ws_bytes(const dflow_params *p)
+static BcdPlanes planes_of(const dflow_params *p, void *ws, size_t *bytes = nullptr)
 {
-    return back_bytes(p) + lab_bytes(p) + blka_bytes(p) + blkbc_bytes(p) + mask_bytes(p) + 256;
-}
-
-static BcdPlanes planes_of(const dflow_params *p, void *ws)
-{
+    const size_t n = (size_t)p->pich * p->picw;
+    size_t back = 0;                                    // the longest phase's back-pointer rows
+    for (int ph = 0; ph < 4; ph++) {
+        int nchains, len;
+        phase_dims(p, ph, nchains, len);
+        const size_t b = (size_t)nchains * len * BCD_BACK_PITCH;
+        if (b > back) back = b;
+    }
+    WsCarver c(ws);
     BcdPlanes pl;
-    char *w = (char *)ws;
-    pl.back = (uint8_t *)w; w += back_bytes(p);
-    pl.lab = (uint2 *)w; w += lab_bytes(p);
-    pl.blkA = (uint2 *)w; w += blka_bytes(p);
-    pl.blkBC = (uint2 *)w; w += blkbc_bytes(p);
-    pl.masks = (uint32_t *)w; w += mask_bytes(p);
-    pl.cursor = (uint32_t *)w;
     pl.pool_rows = pool_rows_of(p);
+    pl.back = c.take<uint8_t>(back);
+    pl.lab = c.take<uint2>(n * p->label_pitch);
+    pl.blkA = c.take<uint2>(n * 2 * p->label_pitch);
+    pl.blkBC = c.take<uint2>(n * 2 * BCD_ROW_BC);
+    pl.masks = c.take<uint32_t>((size_t)pl.pool_rows * BCD_MASK_WORDS);
+    pl.cursor = c.take<uint32_t>(256 / sizeof(uint32_t));         // cleared by one 256-byte memset
+    if (bytes) *bytes = c.bytes;
     return pl;
 }
+
+size_t bcd_ws_bytes(const dflow_params *p) { size_t b; planes_of(p, nullptr, &b); return b; }
 
 int launch_bcd_prepare(const dflow_params *p, const uint32_t *proposals, const float *lcosts, const int32_t *nprop, void *ws,
                        hipStream_t s)
 {
     long long items = (long long)p->pich * p->picw;          // one wave per pixel (as the predecessor of two others)
-    if (hipMemsetAsync(planes_of(p, ws).cursor, 0, 256, s) != hipSuccess)
-        return dflow_set_error(DFLOW_EHIP, "hipMemsetAsync failed in launch_bcd_prepare");
+    DFLOW_HIP(hipMemsetAsync(planes_of(p, ws).cursor, 0, 256, s));
     hipLaunchKernelGGL(bcd_lists_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, s, p->pich, p->picw, p->label_pitch,
                        p->tpsi, proposals, lcosts, nprop, planes_of(p, ws));
     return dflow_check_launch("bcd_lists_kernel");
@@ -813,10 +800,8 @@ int launch_bcd_phase_batch(const dflow_params *p, int npass, const int32_t *cons
     return DFLOW_OK;
 }
 
-int launch_bcd_phase(const dflow_params *p, const uint32_t *proposals, const int32_t *nprop, int32_t *bestlabels, int phase,
-                     void *ws, hipStream_t s)
+int launch_bcd_phase(const dflow_params *p, const int32_t *nprop, int32_t *bestlabels, int phase, void *ws, hipStream_t s)
 {
-    (void)proposals;
     void *wsv = ws;
     return launch_bcd_phase_batch(p, 1, &nprop, &bestlabels, phase, &wsv, s);
 }

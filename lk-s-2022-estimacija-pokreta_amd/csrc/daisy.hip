@@ -181,19 +181,26 @@ static Taps gaussian_taps(int n, double sigma)
     return t;
 }
 
-size_t daisy_ws_bytes(const dflow_params *p)
+// DAISY's part of the workspace, (H,W) planes of float4: the 4 orientation layers (lay), the layers after the first blur
+// (tmp) and the histogram cubes of the 4 rings (cubes, 4 planes)
+struct DaisyWs { float4 *tmp, *lay, *cubes; size_t bytes; };
+static DaisyWs daisy_ws(const dflow_params *p, void *ws)
 {
-    size_t N = (size_t)p->pich * p->picw;
-    return N * sizeof(float) * (1 + 1 + 4 + 4 + 16);   // img, sm, tmp(float4), lay(float4), 4 cubes(float4)
+    const size_t N = (size_t)p->pich * p->picw;
+    WsCarver c(ws);
+    float4 *tmp = c.take<float4>(N), *lay = c.take<float4>(N), *cubes = c.take<float4>(4 * N);
+    return {tmp, lay, cubes, c.bytes};
 }
+
+size_t daisy_ws_bytes(const dflow_params *p) { return daisy_ws(p, nullptr).bytes; }
 
 int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *ws, hipStream_t s)
 {
     const double pi = 3.14159265358979323846;
     int H = p->pich, W = p->picw;
     size_t N = (size_t)H * W;
-    float *img = (float *)ws, *sm = img + N;            // (first two planes of the workspace: unused since the front kernel is fused)
-    float4 *tmp = (float4 *)(sm + N), *lay = tmp + N, *cubes = lay + N;
+    const DaisyWs w = daisy_ws(p, ws);
+    float4 *const tmp = w.tmp, *const lay = w.lay, *const cubes = w.cubes;
     dim3 blk(256);
 
     Taps t = gaussian_taps(5, 0.5);

@@ -187,10 +187,32 @@ __device__ __noinline__ static float l1_cost_np(const _Float16 *__restrict__ a, 
     return res;
 }
 
+// calls f(tag) once, with the descriptor storage of p: tag::T is float or _Float16, tag::F16 the matching bool
+template <typename T_> struct DescrType { using T = T_; static constexpr bool F16 = sizeof(T_) == 2; };
+template <typename F> static inline void with_descr_type(const dflow_params *p, F &&f)
+{
+    if (descr_f16(p)) f(DescrType<_Float16>()); else f(DescrType<float>());
+}
+
 // error plumbing (abi.hip)
 int dflow_set_error(int code, const char *fmt, ...);
 int dflow_check_launch(const char *what);
 int dflow_check_params(const dflow_params *p);
+// a HIP runtime call: on failure, return DFLOW_EHIP from the enclosing function with the call and HIP's message
+#define DFLOW_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dflow_set_error(DFLOW_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
+
+// A stage's workspace layout: regions handed out in order, each on a 256-byte boundary of the caller's (256-byte aligned)
+// buffer; bytes = their total, every region rounded up to 256 bytes.  Given nullptr as the base it only counts, so that
+// one function both sizes and carves a stage's part of the workspace.
+static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct WsCarver {
+    uintptr_t base;
+    size_t bytes = 0;
+    explicit WsCarver(void *ws) : base((uintptr_t)ws) {}
+    template <typename T> T *take(size_t count) { T *r = (T *)(base + bytes); bytes = align256(bytes + count * sizeof(T)); return r; }
+};
+// spare bytes at the end of the whole workspace (dflow_workspace_bytes), beyond the largest stage
+#define DFLOW_WS_SLACK 256
 
 // stage launchers (one per .hip file)
 int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *ws, hipStream_t s);
@@ -199,6 +221,9 @@ size_t daisy_ws_bytes(const dflow_params *p);
 int launch_knn(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                int32_t *nprop, int32_t *bestlabels, hipStream_t s);
 #define KNN_MFMA_EVENTS 7
+// the brute-force search for the lists the MFMA screen could not finish (ovf_list[0 .. *ovf_count)), knn.hip
+int launch_knn_fix(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
+                   const int *ovf_count, const int4 *ovf_list, int ovf_cap, const int *flags, hipStream_t s);
 int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                     int32_t *nprop, int32_t *bestlabels, void *ws, hipStream_t s, hipEvent_t *ev = nullptr);
 double knn_mfma_issued(const dflow_params *p);
@@ -208,8 +233,7 @@ bool knn_mfma_supported(const dflow_params *p);
 int launch_neighbour(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                      int32_t *nprop, const int32_t *bestlabels, void *ws, hipStream_t s);
 size_t neighbour_ws_bytes(const dflow_params *p);
-int launch_bcd_phase(const dflow_params *p, const uint32_t *proposals, const int32_t *nprop, int32_t *bestlabels, int phase,
-                     void *ws, hipStream_t s);
+int launch_bcd_phase(const dflow_params *p, const int32_t *nprop, int32_t *bestlabels, int phase, void *ws, hipStream_t s);
 int launch_bcd_phase_batch(const dflow_params *p, int npass, const int32_t *const *nprop, int32_t *const *bestlabels, int phase,
                            void *const *ws, hipStream_t s);
 size_t bcd_ws_bytes(const dflow_params *p);

@@ -31,24 +31,19 @@ struct CannyWs {
     uint8_t *rootflag;  // (H,W) 1 at the root of a component that holds a strong pixel
 };
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t canny_ws_bytes(int H, int W)
+static CannyWs canny_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 {
     const size_t n = (size_t)H * W;
-    return align256(n * sizeof(int32_t)) + 2 * align256(n);
-}
-
-static CannyWs canny_ws(void *ws, int H, int W)
-{
-    const size_t n = (size_t)H * W;
-    char *b = (char *)ws;
+    WsCarver c(ws);
     CannyWs w;
-    w.label = (int32_t *)b;
-    w.cls = (uint8_t *)(b + align256(n * sizeof(int32_t)));
-    w.rootflag = w.cls + align256(n);
+    w.label = c.take<int32_t>(n);
+    w.cls = c.take<uint8_t>(n);
+    w.rootflag = c.take<uint8_t>(n);
+    if (bytes) *bytes = c.bytes;
     return w;
 }
+
+size_t canny_ws_bytes(int H, int W) { size_t b; canny_ws(nullptr, H, W, &b); return b; }
 
 __device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

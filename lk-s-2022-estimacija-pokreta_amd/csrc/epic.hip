@@ -40,33 +40,27 @@ struct EpicWs {
     float *model;         // (H,W,6) per seed: u = m0 + m1 dx + m2 dy, v = m3 + m4 dx + m5 dy
 };
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // every 4-neighbour pair with different seeds gives two directed edges
 static inline size_t epic_max_edges(int H, int W) { return 2 * ((size_t)H * (W - 1) + (size_t)(H - 1) * W); }
 
-size_t epic_ws_bytes(int H, int W)
+static EpicWs epic_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 {
     const size_t n = (size_t)H * W;
-    return align256(CNT_WORDS * 4) + align256(8 * n) + align256(2 * n) + 3 * align256(4 * n)
-         + align256(8 * epic_max_edges(H, W)) + align256(24 * n);
-}
-
-static EpicWs epic_ws(void *ws, int H, int W)
-{
-    const size_t n = (size_t)H * W;
-    char *b = (char *)ws;
+    WsCarver c(ws);
     EpicWs w;
-    w.cnt = (uint32_t *)b; b += align256(CNT_WORDS * 4);
-    w.key = (uint64_t *)b; b += align256(8 * n);
-    w.cost = (uint16_t *)b; b += align256(2 * n);
-    w.rowbeg = (uint32_t *)b; b += align256(4 * n);
-    w.rowend = (uint32_t *)b; b += align256(4 * n);
-    w.seeds = (int32_t *)b; b += align256(4 * n);
-    w.edges = (uint64_t *)b; b += align256(8 * epic_max_edges(H, W));
-    w.model = (float *)b;
+    w.cnt = c.take<uint32_t>(CNT_WORDS);
+    w.key = c.take<uint64_t>(n);
+    w.cost = c.take<uint16_t>(n);
+    w.rowbeg = c.take<uint32_t>(n);
+    w.rowend = c.take<uint32_t>(n);
+    w.seeds = c.take<int32_t>(n);
+    w.edges = c.take<uint64_t>(epic_max_edges(H, W));
+    w.model = c.take<float>(6 * n);
+    if (bytes) *bytes = c.bytes;
     return w;
 }
+
+size_t epic_ws_bytes(int H, int W) { size_t b; epic_ws(nullptr, H, W, &b); return b; }
 
 __device__ static inline bool is_seed(const float *__restrict__ sparse, int p)
 {
@@ -346,8 +340,6 @@ __global__ void __launch_bounds__(256) epic_fill_kernel(int H, int W, EpicWs ws,
     if (dist) dist[p] = (uint32_t)(kp >> 32);
 }
 
-#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return dflow_set_error(DFLOW_EHIP, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
-
 // Timings of the last call on this thread (dflow_epic_last_stats).
 static thread_local int g_rounds = 0;
 static thread_local hipEvent_t g_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -357,8 +349,8 @@ int epic_last_stats(int32_t *rounds, float *stage_ms)
     if (rounds) *rounds = g_rounds;
     if (stage_ms) {
         if (!g_ev[0]) return dflow_set_error(DFLOW_EINVAL, "no interpolation has run on this thread");
-        HIPTRY(hipEventSynchronize(g_ev[4]));
-        for (int i = 0; i < 4; i++) HIPTRY(hipEventElapsedTime(&stage_ms[i], g_ev[i], g_ev[i + 1]));
+        DFLOW_HIP(hipEventSynchronize(g_ev[4]));
+        for (int i = 0; i < 4; i++) DFLOW_HIP(hipEventElapsedTime(&stage_ms[i], g_ev[i], g_ev[i + 1]));
     }
     return DFLOW_OK;
 }
@@ -373,19 +365,19 @@ int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, d
     // neighbouring pixels in different tiles at most once.
     const long long max_rounds = (long long)H * (tiles.x - 1) + (long long)W * (tiles.y - 1) + 2;
     if (!g_ev[0])
-        for (int i = 0; i < 5; i++) HIPTRY(hipEventCreate(&g_ev[i]));
+        for (int i = 0; i < 5; i++) DFLOW_HIP(hipEventCreate(&g_ev[i]));
     g_rounds = 0;
 
-    HIPTRY(hipEventRecord(g_ev[0], st));
-    HIPTRY(hipMemsetAsync(ws.cnt, 0, CNT_WORDS * 4, st));
+    DFLOW_HIP(hipEventRecord(g_ev[0], st));
+    DFLOW_HIP(hipMemsetAsync(ws.cnt, 0, CNT_WORDS * 4, st));
     epic_init_kernel<<<blocks, 256, 0, st>>>(n, sparse, edges, ws);
     uint32_t h_cnt[EPIC_CHUNK + 1];
     for (long long round = 0;;) {
-        HIPTRY(hipMemsetAsync(ws.cnt + CNT_CHANGED, 0, EPIC_CHUNK * 4, st));
+        DFLOW_HIP(hipMemsetAsync(ws.cnt + CNT_CHANGED, 0, EPIC_CHUNK * 4, st));
         for (int j = 0; j < EPIC_CHUNK; j++) epic_voronoi_kernel<<<tiles, VT_THREADS, 0, st>>>(H, W, ws, ws.cnt + CNT_CHANGED + j);
         int rc = dflow_check_launch("epic_voronoi_kernel"); if (rc) return rc;
-        HIPTRY(hipMemcpyAsync(h_cnt, ws.cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
-        HIPTRY(hipStreamSynchronize(st));
+        DFLOW_HIP(hipMemcpyAsync(h_cnt, ws.cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+        DFLOW_HIP(hipStreamSynchronize(st));
         int j = 0;
         while (j < EPIC_CHUNK && h_cnt[CNT_CHANGED + j]) j++;
         if (j < EPIC_CHUNK) { g_rounds = (int)(round + j + 1); break; }
@@ -394,18 +386,18 @@ int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, d
             return dflow_set_error(DFLOW_EHIP, "epic: the Voronoi relaxation still changed after %lld rounds", round);
     }
     const int nseeds = (int)h_cnt[CNT_NSEEDS];
-    HIPTRY(hipEventRecord(g_ev[1], st));
+    DFLOW_HIP(hipEventRecord(g_ev[1], st));
     if (nseeds) {
         epic_graph_count_kernel<<<blocks, 256, 0, st>>>(H, W, ws);
         epic_graph_alloc_kernel<<<(nseeds + 255) / 256, 256, 0, st>>>(nseeds, ws);
         epic_graph_fill_kernel<<<blocks, 256, 0, st>>>(H, W, ws);
     }
-    HIPTRY(hipEventRecord(g_ev[2], st));
-    if (lists) HIPTRY(hipMemsetAsync(lists, 0xFF, (size_t)n * nn * sizeof(int32_t), st));
-    if (list_g) HIPTRY(hipMemsetAsync(list_g, 0xFF, (size_t)n * nn * sizeof(uint64_t), st));
+    DFLOW_HIP(hipEventRecord(g_ev[2], st));
+    if (lists) DFLOW_HIP(hipMemsetAsync(lists, 0xFF, (size_t)n * nn * sizeof(int32_t), st));
+    if (list_g) DFLOW_HIP(hipMemsetAsync(list_g, 0xFF, (size_t)n * nn * sizeof(uint64_t), st));
     if (nseeds) epic_lists_kernel<<<(nseeds + 3) / 4, 256, 0, st>>>(H, W, nseeds, nn, k, method, sparse, ws, lists, list_g);
-    HIPTRY(hipEventRecord(g_ev[3], st));
+    DFLOW_HIP(hipEventRecord(g_ev[3], st));
     epic_fill_kernel<<<blocks, 256, 0, st>>>(H, W, ws, flow, seed_of, dist);
-    HIPTRY(hipEventRecord(g_ev[4], st));
+    DFLOW_HIP(hipEventRecord(g_ev[4], st));
     return dflow_check_launch("epic kernels");
 }

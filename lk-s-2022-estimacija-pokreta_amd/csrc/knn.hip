@@ -294,10 +294,10 @@ int launch_knn(const dflow_params *p, const void *d1, const void *d2, uint32_t *
     a.LP = p->label_pitch; a.tphi = p->tphi;
     a.chunks = (max_cell_points(a.g) + KNN_THREADS - 1) / KNN_THREADS;
     int nblocks = a.g.ncx * a.g.ncy * a.chunks;
-    if (descr_f16(p))
-        hipLaunchKernelGGL(knn_exact_kernel<_Float16>, dim3(nblocks), dim3(KNN_THREADS), 0, s, a, (const _Float16 *)d1, (const _Float16 *)d2, proposals, lcosts, nprop, bestlabels);
-    else
-        hipLaunchKernelGGL(knn_exact_kernel<float>, dim3(nblocks), dim3(KNN_THREADS), 0, s, a, (const float *)d1, (const float *)d2, proposals, lcosts, nprop, bestlabels);
+    with_descr_type(p, [&](auto d) {
+        using T = typename decltype(d)::T;
+        hipLaunchKernelGGL(knn_exact_kernel<T>, dim3(nblocks), dim3(KNN_THREADS), 0, s, a, (const T *)d1, (const T *)d2, proposals, lcosts, nprop, bestlabels);
+    });
     return dflow_check_launch("knn_exact_kernel");
 }
 
@@ -308,11 +308,10 @@ int launch_knn_fix(const dflow_params *p, const void *d1, const void *d2, uint32
     a.g = make_geom(p);
     a.LP = p->label_pitch; a.tphi = p->tphi; a.chunks = 0;
     int qwaves = (max_cell_points(a.g) + 63) / 64;
-    if (descr_f16(p))
-        hipLaunchKernelGGL(knn_fix_kernel<_Float16>, dim3(KNN_FIX_BLOCKS), dim3(64 * KNN_FIX_WAVES), 0, s, a, (const _Float16 *)d1, (const _Float16 *)d2, proposals,
+    with_descr_type(p, [&](auto d) {
+        using T = typename decltype(d)::T;
+        hipLaunchKernelGGL(knn_fix_kernel<T>, dim3(KNN_FIX_BLOCKS), dim3(64 * KNN_FIX_WAVES), 0, s, a, (const T *)d1, (const T *)d2, proposals,
                            lcosts, ovf_count, ovf_list, ovf_cap, flags, qwaves);
-    else
-        hipLaunchKernelGGL(knn_fix_kernel<float>, dim3(KNN_FIX_BLOCKS), dim3(64 * KNN_FIX_WAVES), 0, s, a, (const float *)d1, (const float *)d2, proposals,
-                           lcosts, ovf_count, ovf_list, ovf_cap, flags, qwaves);
+    });
     return dflow_check_launch("knn_fix_kernel");
 }

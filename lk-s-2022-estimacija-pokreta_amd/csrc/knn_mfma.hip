@@ -1072,34 +1072,26 @@ static KmWs km_ws(const dflow_params *p, void *ws)
 {
     const Geom g = make_geom(p);
     const size_t N = (size_t)g.H * g.W, rows2 = km_total_rows(g), ncells = (size_t)g.ncx * g.ncy;
-    auto align256 = [](char *w) { return (char *)(((uintptr_t)w + 255) & ~(uintptr_t)255); };
+    WsCarver c(ws);
     KmWs k;
-    char *w = (char *)ws;
     k.nl = num_lists(p);
     k.evrows = km_evrows(p);
-    k.h1 = (_Float16 *)w; w += N * KM_K * sizeof(_Float16);
-    k.h2 = (_Float16 *)w; w += rows2 * KM_K * sizeof(_Float16);
-    k.qs = (float2 *)w; w += N * sizeof(float2);
-    k.z0 = (float2 *)w; w += rows2 * sizeof(float2);
-    k.zflag = (uint8_t *)w; w += rows2;
-    w = align256(w);
-    k.ctr = (int *)w; w += 256;
-    k.cell_bad = (int *)w; w += ncells * sizeof(int);
-    k.zero_bytes = 256 + ncells * sizeof(int);
-    w = align256(w);
-    k.vt = (float *)w; w += DFLOW_DESC * DFLOW_DESC * sizeof(float);
-    w = align256(w);
-    k.pca_ws = w; w += knn_pca_ws_bytes();
-    w = align256(w);
-    k.ztop = (KmCellTop *)w; w += ncells * sizeof(KmCellTop);
-    w = align256(w);
-    k.ovf = (int4 *)w; w += k.nl * sizeof(int4);
-    w = align256(w);
-    k.heavy = (int4 *)w; w += (size_t)KM_HEAVY_CAP * sizeof(int4);
-    w = align256(w);
-    k.ev = (uint32_t *)w; w += k.nl * KM_LIST_WORDS(k.evrows) * sizeof(uint32_t);
-    k.ev_cnt = (uint8_t *)w; w += k.nl * 128;
-    k.bytes = (size_t)(w - (char *)ws) + 256;
+    k.h1 = c.take<_Float16>(N * KM_K);
+    k.h2 = c.take<_Float16>(rows2 * KM_K);
+    k.qs = c.take<float2>(N);
+    k.z0 = c.take<float2>(rows2);
+    k.zflag = c.take<uint8_t>(rows2);
+    k.zero_bytes = 256 + ncells * sizeof(int);                  // one region: cleared by one memset
+    k.ctr = c.take<int>(k.zero_bytes / sizeof(int));
+    k.cell_bad = k.ctr + 256 / sizeof(int);
+    k.vt = c.take<float>(DFLOW_DESC * DFLOW_DESC);
+    k.pca_ws = c.take<char>(knn_pca_ws_bytes());
+    k.ztop = c.take<KmCellTop>(ncells);
+    k.ovf = c.take<int4>(k.nl);
+    k.heavy = c.take<int4>(KM_HEAVY_CAP);
+    k.ev = c.take<uint32_t>(k.nl * KM_LIST_WORDS(k.evrows));
+    k.ev_cnt = c.take<uint8_t>(k.nl * 128);
+    k.bytes = c.bytes;
     return k;
 }
 
@@ -1120,38 +1112,31 @@ bool knn_mfma_supported(const dflow_params *p)
     return max_cell_points(g) <= KM_MAXPTS && p->window >= 0 && p->window <= 2;
 }
 
-int launch_knn_fix(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
-                   const int *ovf_count, const int4 *ovf_list, int ovf_cap, const int *flags, hipStream_t s);
-
 // ev (optional, profiling): KNN_MFMA_EVENTS events recorded on s at the boundaries basis | prep | screen | resolve | fix | finalize
+#define KM_MARK(i) do { if (tev) DFLOW_HIP(hipEventRecord(tev[i], s)); } while (0)
 int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                     int32_t *nprop, int32_t *bestlabels, void *ws, hipStream_t s, hipEvent_t *tev)
 {
-    auto mark = [&](int k) { if (tev) (void)hipEventRecord(tev[k], s); };
     Geom g = make_geom(p);
     const size_t N = (size_t)g.H * g.W;
     const KmWs k = km_ws(p, ws);
-    if (hipMemsetAsync(k.ctr, 0, k.zero_bytes, s) != hipSuccess)
-        return dflow_set_error(DFLOW_EHIP, "hipMemsetAsync failed in launch_knn_mfma");
+    DFLOW_HIP(hipMemsetAsync(k.ctr, 0, k.zero_bytes, s));
     int nb = (int)((N + 255) / 256);
-    mark(0);
-    const bool f16 = descr_f16(p);
-    int rc = launch_knn_pca(d2, f16, k.vt, k.ctr + 1, k.pca_ws, (int)N, s);
+    KM_MARK(0);
+    int rc = launch_knn_pca(p, d2, k.vt, k.ctr + 1, k.pca_ws, s);
     if (rc) return rc;
-    mark(1);
+    KM_MARK(1);
     const dim3 cgrid((km_pad(max_cell_points(g)) + 255) / 256, g.ncx * g.ncy);
-    if (f16) {
-        hipLaunchKernelGGL(knn_prep_kernel<_Float16>, dim3(nb), dim3(256), 0, s, (const _Float16 *)d1, (const float *)k.vt, k.h1, k.qs, (float2 *)nullptr, (uint8_t *)nullptr, (int *)nullptr, g, 0);
-        hipLaunchKernelGGL(knn_prep_kernel<_Float16>, cgrid, dim3(256), 0, s, (const _Float16 *)d2, (const float *)k.vt, k.h2, (float2 *)nullptr, k.z0, k.zflag, k.cell_bad, g, 1);
-    } else {
-        hipLaunchKernelGGL(knn_prep_kernel<float>, dim3(nb), dim3(256), 0, s, (const float *)d1, (const float *)k.vt, k.h1, k.qs, (float2 *)nullptr, (uint8_t *)nullptr, (int *)nullptr, g, 0);
-        hipLaunchKernelGGL(knn_prep_kernel<float>, cgrid, dim3(256), 0, s, (const float *)d2, (const float *)k.vt, k.h2, (float2 *)nullptr, k.z0, k.zflag, k.cell_bad, g, 1);
-    }
+    with_descr_type(p, [&](auto d) {
+        using T = typename decltype(d)::T;
+        hipLaunchKernelGGL(knn_prep_kernel<T>, dim3(nb), dim3(256), 0, s, (const T *)d1, (const float *)k.vt, k.h1, k.qs, (float2 *)nullptr, (uint8_t *)nullptr, (int *)nullptr, g, 0);
+        hipLaunchKernelGGL(knn_prep_kernel<T>, cgrid, dim3(256), 0, s, (const T *)d2, (const float *)k.vt, k.h2, (float2 *)nullptr, k.z0, k.zflag, k.cell_bad, g, 1);
+    });
     hipLaunchKernelGGL(knn_cell_post_kernel, dim3(g.ncx * g.ncy), dim3(256), 0, s, k.h2, (const float2 *)k.z0, (const uint8_t *)k.zflag, k.ztop, g);
     rc = dflow_check_launch("knn_cell_post_kernel");
     if (rc) return rc;
 
-    mark(2);
+    KM_MARK(2);
     const KmGeom a = km_geom(p, k);
     int win = 2 * g.win + 1;
     int wgs_per_cell = (win * win * a.qwaves + KM_WAVES - 1) / KM_WAVES;
@@ -1161,28 +1146,28 @@ int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint3
     hipLaunchKernelGGL(knn_screen_kernel, dim3(g.ncx * g.ncy * wgs_per_cell), dim3(KM_THREADS), shmem, s, a, sc);
     rc = dflow_check_launch("knn_screen_kernel");
     if (rc) return rc;
-    mark(3);
+    KM_MARK(3);
     KmResolve rs;
     rs.d1 = d1; rs.d2 = d2; rs.ev = k.ev; rs.ev_cnt = k.ev_cnt; rs.qs = k.qs; rs.ztop = k.ztop; rs.proposals = proposals; rs.lcosts = lcosts;
     rs.ovf_count = k.ctr; rs.ovf_list = k.ovf; rs.ovf_cap = (int)k.nl;
     rs.heavy_count = k.ctr + 2; rs.heavy_list = k.heavy; rs.heavy_cap = KM_HEAVY_CAP;
-    if (f16) hipLaunchKernelGGL(knn_resolve_kernel<true>, dim3((unsigned)(g.ncx * g.ncy * win * a.qwaves)), dim3(64), 0, s, a, rs);
-    else hipLaunchKernelGGL(knn_resolve_kernel<false>, dim3((unsigned)(g.ncx * g.ncy * win * a.qwaves)), dim3(64), 0, s, a, rs);
+    const dim3 rgrid((unsigned)(g.ncx * g.ncy * win * a.qwaves));
+    with_descr_type(p, [&](auto d) { hipLaunchKernelGGL(knn_resolve_kernel<decltype(d)::F16>, rgrid, dim3(64), 0, s, a, rs); });
     rc = dflow_check_launch("knn_resolve_kernel");
     if (rc) return rc;
     // queries with hundreds of events in a cell (knn_resolve_kernel listed them): one wave each, its lanes over the events
-    if (f16) hipLaunchKernelGGL(knn_resolve_heavy_kernel<true>, dim3(KM_HEAVY_BLOCKS), dim3(64), 0, s, a, rs);
-    else hipLaunchKernelGGL(knn_resolve_heavy_kernel<false>, dim3(KM_HEAVY_BLOCKS), dim3(64), 0, s, a, rs);
+    with_descr_type(p, [&](auto d) { hipLaunchKernelGGL(knn_resolve_heavy_kernel<decltype(d)::F16>, dim3(KM_HEAVY_BLOCKS), dim3(64), 0, s, a, rs); });
     rc = dflow_check_launch("knn_resolve_heavy_kernel");
     if (rc) return rc;
-    mark(4);
+    KM_MARK(4);
     rc = launch_knn_fix(p, d1, d2, proposals, lcosts, k.ctr, k.ovf, (int)k.nl, k.ctr + 1, s);
     if (rc) return rc;
-    mark(5);
+    KM_MARK(5);
     hipLaunchKernelGGL(knn_finalize_kernel, dim3((unsigned)((N * 16 + 255) / 256)), dim3(256), 0, s, g, a.LP, proposals, lcosts, nprop, bestlabels);
-    mark(6);
+    KM_MARK(6);
     return dflow_check_launch("knn_finalize_kernel");
 }
+#undef KM_MARK
 
 // ------------------------------------------------------------------------------------------------ statistics (measurement aid)
 // What the screen left in the workspace: one block per event list (threads = 2 groups x 64 lanes), then one pass over the
@@ -1238,7 +1223,7 @@ int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_ou
     const Geom g = make_geom(p);
     const size_t N = (size_t)g.H * g.W, rows2 = km_total_rows(g);
     unsigned long long *dev = (unsigned long long *)(k.ctr + 16);            // 8 counters inside the zeroed control block
-    if (hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), s) != hipSuccess) return dflow_set_error(DFLOW_EHIP, "hipMemsetAsync failed");
+    DFLOW_HIP(hipMemsetAsync(dev, 0, 8 * sizeof(unsigned long long), s));
     const KmGeom a = km_geom(p, k);
     hipLaunchKernelGGL(knn_stats_lists_kernel, dim3((unsigned)k.nl), dim3(128), 0, s, a, (const uint32_t *)k.ev, (const uint8_t *)k.ev_cnt, dev);
     const size_t m = N > rows2 ? N : rows2;
@@ -1248,9 +1233,9 @@ int knn_mfma_stats(const dflow_params *p, void *ws, hipStream_t s, int64_t *h_ou
     if (rc) return rc;
     unsigned long long c[8];
     int ctr[4];
-    if (hipMemcpyAsync(c, dev, sizeof(c), hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(ctr, k.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return dflow_set_error(DFLOW_EHIP, "knn_mfma_stats: copy back failed");
+    DFLOW_HIP(hipMemcpyAsync(c, dev, sizeof(c), hipMemcpyDeviceToHost, s));
+    DFLOW_HIP(hipMemcpyAsync(ctr, k.ctr, sizeof(ctr), hipMemcpyDeviceToHost, s));
+    DFLOW_HIP(hipStreamSynchronize(s));
     // (query, cell) pairs of the pass
     long long pairs = 0;
     for (int qcj = 0; qcj < g.ncy; qcj++)

@@ -220,11 +220,14 @@ __global__ void __launch_bounds__(1024) knn_jacobi_kernel(const double *__restri
 
 size_t knn_pca_ws_bytes(void) { return (size_t)PCA_BLOCKS * PCA_N * PCA_N * sizeof(double); }
 
-int launch_knn_pca(const void *d2, bool f16, float *vt, int *flags, void *ws, int npix, hipStream_t s)
+int launch_knn_pca(const dflow_params *p, const void *d2, float *vt, int *flags, void *ws, hipStream_t s)
 {
     double *partial = (double *)ws;
-    if (f16) hipLaunchKernelGGL(knn_cov_kernel<_Float16>, dim3(PCA_BLOCKS), dim3(256), 0, s, (const _Float16 *)d2, partial, npix);
-    else hipLaunchKernelGGL(knn_cov_kernel<float>, dim3(PCA_BLOCKS), dim3(256), 0, s, (const float *)d2, partial, npix);
+    const int npix = p->pich * p->picw;
+    with_descr_type(p, [&](auto d) {
+        using T = typename decltype(d)::T;
+        hipLaunchKernelGGL(knn_cov_kernel<T>, dim3(PCA_BLOCKS), dim3(256), 0, s, (const T *)d2, partial, npix);
+    });
     hipLaunchKernelGGL(knn_jacobi_kernel, dim3(1), dim3(1024), 0, s, (const double *)partial, vt, flags);
     return dflow_check_launch("knn_jacobi_kernel");
 }

@@ -159,7 +159,16 @@ static void gauss_thresholds(double sigma, uint32_t *thr)
     thr[127] = 4294967295u;
 }
 
-size_t neighbour_ws_bytes(const dflow_params *p) { return (size_t)p->pich * p->picw * sizeof(uint32_t) + 256; }
+// the neighbour stage's part of the workspace: the WTA proposal of every pixel
+struct NbrWs { uint32_t *bestflow; size_t bytes; };
+static NbrWs nbr_ws(const dflow_params *p, void *ws)
+{
+    WsCarver c(ws);
+    uint32_t *bestflow = c.take<uint32_t>((size_t)p->pich * p->picw);
+    return {bestflow, c.bytes};
+}
+
+size_t neighbour_ws_bytes(const dflow_params *p) { return nbr_ws(p, nullptr).bytes; }
 
 int launch_neighbour(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                      int32_t *nprop, const int32_t *bestlabels, void *ws, hipStream_t s)
@@ -171,11 +180,12 @@ int launch_neighbour(const dflow_params *p, const void *d1, const void *d2, uint
     a.d1 = d1; a.d2 = d2; a.proposals = proposals; a.lcosts = lcosts; a.nprop = nprop; a.bestlabels = bestlabels;
     gauss_thresholds((double)p->sigma, a.thr);
     int n = p->pich * p->picw;
-    uint32_t *bestflow = (uint32_t *)ws;
+    uint32_t *bestflow = nbr_ws(p, ws).bestflow;
     a.bestflow = bestflow;
     hipLaunchKernelGGL(nbr_bestflow_kernel, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t *)proposals, bestlabels, bestflow, n, p->label_pitch);
     const size_t shmem = (size_t)(p->ngauss > 0 ? p->ngauss : 1) * NBR_THREADS * sizeof(uint32_t);
-    if (descr_f16(p)) hipLaunchKernelGGL(neighbour_kernel<_Float16>, dim3((n + NBR_THREADS - 1) / NBR_THREADS), dim3(NBR_THREADS), shmem, s, a);
-    else hipLaunchKernelGGL(neighbour_kernel<float>, dim3((n + NBR_THREADS - 1) / NBR_THREADS), dim3(NBR_THREADS), shmem, s, a);
+    with_descr_type(p, [&](auto d) {
+        hipLaunchKernelGGL(neighbour_kernel<typename decltype(d)::T>, dim3((n + NBR_THREADS - 1) / NBR_THREADS), dim3(NBR_THREADS), shmem, s, a);
+    });
     return dflow_check_launch("neighbour_kernel");
 }

@@ -35,7 +35,8 @@ class DiscreteFlow:
         if cellh is None or cellw is None:
             cellh, cellw = default_cells(pich, picw)
         self.p = _lib.default_params(pich, picw, cellh, cellw, seed=seed, **overrides)
-        _lib.check(0 if _lib.lib().dflow_workspace_bytes(C.byref(self.p)) else -1, "dflow_workspace_bytes")
+        self.ws_bytes = int(_lib.lib().dflow_workspace_bytes(C.byref(self.p)))
+        _lib.check(0 if self.ws_bytes else -1, "dflow_workspace_bytes")
         self.device = torch.device(device)
         self._descr_f16 = bool(self.p.flags & _lib.FLAG_DESCR_F16)     # storage mode of the descriptor planes: fixed here
         H, W, LP = pich, picw, self.p.label_pitch
@@ -48,7 +49,6 @@ class DiscreteFlow:
         self.nprop = torch.empty((H, W), dtype=torch.int32, device=dev)             # :91
         self.bestlabels = torch.empty((H, W), dtype=torch.int32, device=dev)        # :95
         self.flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
-        self.ws_bytes = int(_lib.lib().dflow_workspace_bytes(C.byref(self.p)))
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         self._img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
         self._bcd_ready = False     # compat matrices in the workspace are valid for the current proposals
@@ -65,7 +65,7 @@ class DiscreteFlow:
         return torch.empty((H, W, 68), dtype=torch.float32, device=self.device)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     def _pp(self):
         # the planes were allocated for one storage mode; a flag flipped afterwards would make the kernels read or write
@@ -92,8 +92,7 @@ class DiscreteFlow:
         if out is None:
             out = self._new_descr()
         self._bcd_ready = False
-        _lib.check(_lib.lib().dflow_daisy(self._pp(), img.data_ptr(), out.data_ptr(), self.ws.data_ptr(),
-                                          self.ws_bytes, self._stream()), "dflow_daisy")
+        _lib.call("dflow_daisy", self._pp(), img.data_ptr(), out.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self._stream())
         return out
 
     def load_pair(self, pic3, pic4):
@@ -113,11 +112,9 @@ class DiscreteFlow:
     def generisi(self):
         """napraviCD2 + generisi, daisy i flann.py:144-189."""
         self._bcd_ready = False
-        _lib.check(_lib.lib().dflow_knn_proposals(self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(),
-                                                  self.proposals.data_ptr(), self.lcosts.data_ptr(),
-                                                  self.nprop.data_ptr(), self.bestlabels.data_ptr(),
-                                                  self.ws.data_ptr(), self.ws_bytes, self._stream()),
-                   "dflow_knn_proposals")
+        _lib.call("dflow_knn_proposals", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
+                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                  self._stream())
 
     KNN_KERNELS = ("basis", "prep", "knn_screen_kernel", "knn_resolve_kernel", "knn_fix_kernel", "knn_finalize_kernel")
 
@@ -126,11 +123,9 @@ class DiscreteFlow:
         self._bcd_ready = False
         ms = (C.c_float * 6)()
         issued = C.c_double()
-        _lib.check(_lib.lib().dflow_knn_proposals_timed(self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(),
-                                                        self.proposals.data_ptr(), self.lcosts.data_ptr(),
-                                                        self.nprop.data_ptr(), self.bestlabels.data_ptr(),
-                                                        self.ws.data_ptr(), self.ws_bytes, self._stream(), ms, C.byref(issued)),
-                   "dflow_knn_proposals_timed")
+        _lib.call("dflow_knn_proposals_timed", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
+                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                  self._stream(), ms, C.byref(issued))
         return dict(zip(self.KNN_KERNELS, (float(v) for v in ms))), float(issued.value)
 
     KNN_STATS = ("lists_exact", "flags", "lists", "entries", "events", "max_entries_per_lane", "zero_queries", "bad_queries",
@@ -140,8 +135,7 @@ class DiscreteFlow:
     def knn_stats(self):
         """dflow_knn_screen_stats_n: what the MFMA screen of the last generisi() did (call before the next stage reuses the workspace)."""
         out = (C.c_int64 * len(self.KNN_STATS_ALL))()
-        _lib.check(_lib.lib().dflow_knn_screen_stats_n(self._pp(), self.ws.data_ptr(), self.ws_bytes, self._stream(), out, len(out)),
-                   "dflow_knn_screen_stats_n")
+        _lib.call("dflow_knn_screen_stats_n", self._pp(), self.ws.data_ptr(), self.ws_bytes, self._stream(), out, len(out))
         st = dict(zip(self.KNN_STATS_ALL, (int(v) for v in out)))
         st["events_per_query_cell"] = round(st["events"] / max(1, st["query_cell_pairs"]), 3)
         return st
@@ -149,43 +143,38 @@ class DiscreteFlow:
     def nasumicni(self):
         """daisy i flann.py:205-233."""
         self._bcd_ready = False
-        _lib.check(_lib.lib().dflow_neighbour_proposals(self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(),
-                                                        self.proposals.data_ptr(), self.lcosts.data_ptr(),
-                                                        self.nprop.data_ptr(), self.bestlabels.data_ptr(),
-                                                        self.ws.data_ptr(), self.ws_bytes, self._stream()),
-                   "dflow_neighbour_proposals")
+        _lib.call("dflow_neighbour_proposals", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
+                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                  self._stream())
 
     def pakovanje(self):
         """daisy i flann.py:256-309: compat bit matrices, built into the workspace for the chain kernel."""
-        _lib.check(_lib.lib().dflow_bcd_prepare(self._pp(), self.proposals.data_ptr(), self.lcosts.data_ptr(),
-                                                self.nprop.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self._stream()),
-                   "dflow_bcd_prepare")
+        _lib.call("dflow_bcd_prepare", self._pp(), self.proposals.data_ptr(), self.lcosts.data_ptr(),
+                  self.nprop.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self._stream())
         self._bcd_ready = True
 
     def bcd_phase(self, phase):
         """One of the four chain loops of ceoBCD, python bcd.py:265-277."""
         if not self._bcd_ready:
             self.pakovanje()
-        _lib.check(_lib.lib().dflow_bcd_phase(self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(),
-                                              self.bestlabels.data_ptr(), phase, self.ws.data_ptr(), self.ws_bytes,
-                                              self._stream()), "dflow_bcd_phase")
+        _lib.call("dflow_bcd_phase", self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), phase,
+                  self.ws.data_ptr(), self.ws_bytes, self._stream())
 
     def ceoBCD(self, bcd_times, on_sweep=None):
         """python bcd.py:261-284.  on_sweep(w) is called after sweep w (the reference saves .npy there)."""
         if not self._bcd_ready:
             self.pakovanje()
         for w in range(1, bcd_times + 1):
-            _lib.check(_lib.lib().dflow_bcd_sweep(self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(),
-                                                  self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                                                  self._stream()), "dflow_bcd_sweep")
+            _lib.call("dflow_bcd_sweep", self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(),
+                      self.ws.data_ptr(), self.ws_bytes, self._stream())
             if on_sweep is not None:
                 on_sweep(w)
 
     def vratiKonacniFlow(self, out=None):
         """python bcd.py:90-95: (H,W,2) [dy,dx] (float32 device tensor; values are small integers)."""
         out = self.flow if out is None else out
-        _lib.check(_lib.lib().dflow_labels_to_flow(self._pp(), self.proposals.data_ptr(), self.bestlabels.data_ptr(),
-                                                   out.data_ptr(), self._stream()), "dflow_labels_to_flow")
+        _lib.call("dflow_labels_to_flow", self._pp(), self.proposals.data_ptr(), self.bestlabels.data_ptr(),
+                  out.data_ptr(), self._stream())
         return out
 
     def run(self, pic3, pic4, bcd_times):
@@ -253,8 +242,7 @@ def ceoBCD_batch(passes, bcd_times, on_sweep=None):
     best = arr(*[df.bestlabels.data_ptr() for df in passes])
     ws = arr(*[df.ws.data_ptr() for df in passes])
     for w in range(1, bcd_times + 1):
-        _lib.check(_lib.lib().dflow_bcd_sweep_batch(first._pp(), n, nprop, best, ws, first.ws_bytes, first._stream()),
-                   "dflow_bcd_sweep_batch")
+        _lib.call("dflow_bcd_sweep_batch", first._pp(), n, nprop, best, ws, first.ws_bytes, first._stream())
         if on_sweep is not None:
             on_sweep(w)
 
@@ -267,9 +255,8 @@ def fb_consistency(fwd, bwd, tresh, p=None):
         ch, cw = default_cells(H, W)
         p = _lib.default_params(H, W, ch, cw)
     out = torch.empty((H, W, 3), dtype=torch.float32, device=fwd.device)
-    stream = C.c_void_p(torch.cuda.current_stream(fwd.device).cuda_stream)
-    _lib.check(_lib.lib().dflow_fb_consistency(C.byref(p), fwd.contiguous().data_ptr(), bwd.contiguous().data_ptr(),
-                                               float(tresh), out.data_ptr(), stream), "dflow_fb_consistency")
+    _lib.call("dflow_fb_consistency", C.byref(p), fwd.contiguous().data_ptr(), bwd.contiguous().data_ptr(),
+              float(tresh), out.data_ptr(), _lib.stream(fwd.device))
     return out
 
 
@@ -286,17 +273,11 @@ def canny_edges(bgr, low=100, high=200, ivice=True):
         bgr = bgr.to(torch.device("cuda", torch.cuda.current_device()))
     bgr = bgr.contiguous()
     H, W, _ = bgr.shape
-    L = _lib.lib()
-    ws_bytes = L.dflow_canny_workspace_bytes(H, W)
-    if ws_bytes == 0:
-        raise _lib.DflowError("dflow_canny_workspace_bytes: %s" % L.dflow_last_error().decode())
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=bgr.device)
+    ws, ws_bytes = _lib.workspace("dflow_canny_workspace_bytes", H, W, bgr.device)
     edges = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
     iv = torch.empty((H, W), dtype=torch.float32, device=bgr.device) if ivice else None
-    stream = C.c_void_p(torch.cuda.current_stream(bgr.device).cuda_stream)
-    _lib.check(L.dflow_canny_edges(H, W, bgr.data_ptr(), float(low), float(high), edges.data_ptr(),
-                                   iv.data_ptr() if iv is not None else None, ws.data_ptr(), ws_bytes, stream),
-               "dflow_canny_edges")
+    _lib.call("dflow_canny_edges", H, W, bgr.data_ptr(), float(low), float(high), edges.data_ptr(),
+              iv.data_ptr() if iv is not None else None, ws.data_ptr(), ws_bytes, _lib.stream(bgr.device))
     return edges, iv
 
 
@@ -328,11 +309,7 @@ def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists
     H, W = int(sparse.shape[0]), int(sparse.shape[1])
     sparse = upload(sparse, "sparse", (H, W, 3))
     edges = upload(edges, "edges", (H, W))
-    L = _lib.lib()
-    ws_bytes = L.dflow_epic_workspace_bytes(H, W)
-    if ws_bytes == 0:
-        raise _lib.DflowError("dflow_epic_workspace_bytes: %s" % L.dflow_last_error().decode())
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _lib.workspace("dflow_epic_workspace_bytes", H, W, dev)
     flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
     S = D = lst = list_g = None
     if aux:
@@ -344,15 +321,13 @@ def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists
 
     def ptr(t):
         return t.data_ptr() if t is not None else None
-    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.dflow_epic_interpolate(H, W, sparse.data_ptr(), edges.data_ptr(), int(nn), float(k), EPIC_METHODS[method],
-                                        flow.data_ptr(), ptr(S), ptr(D), ptr(lst), ptr(list_g), ws.data_ptr(), ws_bytes,
-                                        stream), "dflow_epic_interpolate")
+    _lib.call("dflow_epic_interpolate", H, W, sparse.data_ptr(), edges.data_ptr(), int(nn), float(k), EPIC_METHODS[method],
+              flow.data_ptr(), ptr(S), ptr(D), ptr(lst), ptr(list_g), ws.data_ptr(), ws_bytes, _lib.stream(dev))
     return (flow, S, D, lst, list_g) if aux else flow
 
 
 def epic_last_stats():
     """(Voronoi rounds, {stage: ms}) of the last epic_interpolate on this thread, from HIP events (waits for them)."""
     rounds, ms = C.c_int32(0), (C.c_float * 4)()
-    _lib.check(_lib.lib().dflow_epic_last_stats(C.byref(rounds), ms), "dflow_epic_last_stats")
+    _lib.call("dflow_epic_last_stats", C.byref(rounds), ms)
     return rounds.value, dict(zip(("voronoi", "graph", "lists", "fill"), (float(v) for v in ms)))
