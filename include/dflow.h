@@ -55,6 +55,17 @@ extern "C" {
 #define DFLOW_ENOSPC (-2)        /* workspace too small */
 #define DFLOW_EHIP (-3)          /* HIP runtime error (launch failure, no device) */
 
+/* The reference starts the DP's fallback minimum (permmincost) and the end label's minimum at 800000.0 (python bcd.py:152-157,
+ * :231), and the chain kernel takes the fallback minimum over the bit patterns of tpsi + dp, which order like the doubles only
+ * while they are >= 0.  Every entry point therefore refuses (DFLOW_EINVAL) a lamda or tphi that is not finite or below 0, and
+ * any parameter set with
+ *     max(pich, picw) * (3*tpsi + lamda*tphi) >= DFLOW_DP_SENTINEL       (evaluated in double, tphi widened from float)
+ * Within it, with data costs in [0, tphi]: the chain start is dp <= 2*tpsi + lamda*tphi, each step adds at most
+ * tpsi (fallback) + 2*tpsi (side terms) + lamda*tphi, so 0 <= dp and tpsi + dp < DFLOW_DP_SENTINEL on every chain, and the
+ * sentinels never bind: the kernel, the reference and the chain's Viterbi minimum agree.  At tpsi = 8 and 8192-pixel chains this
+ * allows lamda*tphi up to about 73 (the reference constants give 0.125). */
+#define DFLOW_DP_SENTINEL 800000.0
+
 /* Algorithm constants.  Field-for-field the module globals of the reference scripts. */
 typedef struct dflow_params {
     int32_t pich, picw;          /* daisy i flann.py:34-35 */
@@ -65,9 +76,9 @@ typedef struct dflow_params {
     int32_t ngauss;              /* daisy i flann.py:207  (25) */
     int32_t tpsi;                /* daisy i flann.py:47   (8; kernels support 1..8) */
     int32_t max_attempts;        /* bound on draws per pixel in the neighbour sampler (65536) */
-    float tphi;                  /* daisy i flann.py:46   (2.5) */
+    float tphi;                  /* daisy i flann.py:46   (2.5; finite, >= 0, and see DFLOW_DP_SENTINEL) */
     float sigma;                 /* daisy i flann.py:208  (8)  */
-    double lamda;                /* daisy i flann.py:48   (0.05) */
+    double lamda;                /* daisy i flann.py:48   (0.05; finite, >= 0, and see DFLOW_DP_SENTINEL) */
     uint64_t seed;               /* key of the counter-based sampler (reference: unseeded np.random, :219) */
     int32_t label_pitch;         /* LP, elements per pixel in proposals/lcosts (160; multiple of 16) */
     int32_t flags;               /* DFLOW_FLAG_* bits (0 = defaults); per call, the library keeps no process-global switches */
@@ -135,7 +146,9 @@ int dflow_neighbour_proposals(const dflow_params *p, const void *d_descr1, const
  * on that chain and their pairwise costs, plus per pixel every label's own flow and data cost (what ucitajSvePodatkeDoBCD,
  * python bcd.py:67-81, loads for bcd()).  Must be called after proposals and lcosts are final (after
  * dflow_neighbour_proposals / an upload) and before dflow_bcd_phase / dflow_bcd_sweep; the records stay valid until
- * another dflow_* stage call (daisy, knn) reuses the same workspace. */
+ * another dflow_* stage call (daisy, knn) reuses the same workspace.  The costs of used slots (below nprop) must lie in
+ * [0, tphi], which is what the kNN and neighbour stages write (min(tphi, a sum of absolute values)): the bound of
+ * DFLOW_DP_SENTINEL assumes it, and uploaded costs outside it are not checked here (the host wrapper refuses them). */
 int dflow_bcd_prepare(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
                       void *d_ws, size_t ws_bytes, void *stream);
 

@@ -43,6 +43,18 @@ int dflow_check_params(const dflow_params *p)
         return dflow_set_error(DFLOW_EINVAL, "label_pitch=%d must be a multiple of 16 in [maxnprop,%d]", p->label_pitch, DFLOW_MAX_LABELS);
     // pair costs below tpsi travel as 3-bit fields in the BCD label records (bcd.hip)
     if (p->tpsi < 1 || p->tpsi > 8) return dflow_set_error(DFLOW_EINVAL, "tpsi=%d outside [1,8]", p->tpsi);
+    // the chain kernel picks the fallback predecessor as an unsigned minimum over the bit patterns of tpsi + dp (bcd.hip),
+    // which orders like the doubles only while they are >= 0; the reference starts that minimum (and the end label's) at
+    // 800000 (python bcd.py:152-157,231): dp stays in [0, 800000) for every chain when the last rule holds (include/dflow.h)
+    if (!isfinite(p->lamda) || p->lamda < 0.0) return dflow_set_error(DFLOW_EINVAL, "lamda=%g must be finite and >= 0", p->lamda);
+    if (!isfinite(p->tphi) || p->tphi < 0.0f) return dflow_set_error(DFLOW_EINVAL, "tphi=%g must be finite and >= 0", (double)p->tphi);
+    {
+        const double n = (double)(p->pich > p->picw ? p->pich : p->picw);
+        const double dpmax = n * (3.0 * (double)p->tpsi + p->lamda * (double)p->tphi);
+        if (!(dpmax < DFLOW_DP_SENTINEL))
+            return dflow_set_error(DFLOW_EINVAL, "max(pich,picw)*(3*tpsi+lamda*tphi)=%.17g (lamda=%g, tphi=%g, tpsi=%d) must be below %g",
+                                   dpmax, p->lamda, (double)p->tphi, p->tpsi, DFLOW_DP_SENTINEL);
+    }
     if (!(p->sigma > 0.0f) || p->sigma > 8.0f) return dflow_set_error(DFLOW_EINVAL, "sigma=%g outside (0,8]", (double)p->sigma);
     if (p->max_attempts < p->ngauss) return dflow_set_error(DFLOW_EINVAL, "max_attempts < ngauss");
     if (p->flags & ~(DFLOW_FLAG_KNN_EXACT | DFLOW_FLAG_DESCR_F16)) return dflow_set_error(DFLOW_EINVAL, "unknown flags 0x%x", (unsigned)p->flags);

@@ -211,6 +211,12 @@ class DiscreteFlow:
         # daisy i flann.py:179-180,228-229) -- anything else would silently change the DP, so it is refused
         if not np.array_equal(lc[..., :L].astype(np.float64), lcosts):
             raise ValueError("lcosts holds values that are not float32-exact (the reference's files are): refusing to round them")
+        # the costs of used slots lie in [0, tphi] (min(tphi, a sum of absolute values)); the bound that keeps the DP below
+        # the reference's 800000 sentinels assumes it (include/dflow.h, DFLOW_DP_SENTINEL)
+        used = np.arange(L)[None, None, :] < np.asarray(nprop)[..., None]
+        cu = lcosts[..., :L][used]
+        if not (np.isfinite(cu).all() and (cu >= 0).all() and (cu <= self.p.tphi).all()):
+            raise ValueError("lcosts of used slots must lie in [0, tphi=%g]" % self.p.tphi)
         if proposals.min() < -32768 or proposals.max() > 32767:
             raise ValueError("proposals outside the int16 range of the packed device layout")
         self.proposals.copy_(torch.from_numpy(packed.view(np.int32)))

@@ -458,3 +458,129 @@ def bcd_phase_check(proposals, lcosts, nprop, before, after, phase, lamda=0.05, 
         bad.append("phase %d chain %d (starting at (%d,%d)): energy %.12g, Viterbi minimum %.12g"
                    % (phase, ids[c], ys[ids[c], 0], xs[ids[c], 0], e[c], vmin[c]))
     return bad
+
+
+# ------------------------------------------------------------------------------------------------------ neighbour sampler
+
+
+def _normal_mass(a, b, sigma):
+    """P(a < sigma Z < b), Z standard normal, from tail differences with math.erfc (accurate far out in either tail)."""
+    s = sigma * math.sqrt(2.0)
+    if a + b >= 0:
+        return 0.5 * (math.erfc(a / s) - math.erfc(b / s))           # upper tails
+    return 0.5 * (math.erfc(-b / s) - math.erfc(-a / s))             # lower tails
+
+
+def gauss_offset_law(c, n, sigma):
+    """The law of int(c + sigma Z) (daisy i flann.py:219,221: np.random.normal, then int()) for an integer centre c, given
+    0 <= value < n, as a float64 (n,) array; returns (law, clip).  int() truncates toward zero, so value 0 takes
+    P(-1 < c + sigma Z < 1) and value v >= 1 takes P(v <= c + sigma Z < v + 1).
+
+    The sampler draws floor(sigma Z) from a 127-entry table of offsets -64..62 plus the catch-all 63 (DESIGN.md §2 "RNG"):
+    draws with |sigma Z| >= 64 land on -64 or 63 instead.  `clip` = P(|sigma Z| >= 64) = erfc(64 / (sigma sqrt 2)) is the most
+    mass that moves: 1.2e-15 at sigma = 8 and smaller below, far under what any sample size here resolves.  The table's
+    thresholds are floor(Phi * 2^32), which moves each bin by at most 2^-32 more."""
+    p = np.array([_normal_mass(-1 - c, 1 - c, sigma) if v == 0 else _normal_mass(v - c, v + 1 - c, sigma)
+                  for v in range(n)])
+    return p / p.sum(), math.erfc(64.0 / (sigma * math.sqrt(2.0)))
+
+
+def normal_upper_quantile(alpha):
+    """z with P(Z > z) = alpha, by bisection on math.erfc (no scipy)."""
+    lo, hi = 0.0, 40.0
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if 0.5 * math.erfc(mid / math.sqrt(2.0)) > alpha:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def chi2_upper_quantile(df, alpha):
+    """The chi-square quantile with upper tail alpha on df degrees of freedom, by the Wilson-Hilferty approximation
+    df (1 - 2/(9 df) + z sqrt(2/(9 df)))^3, z the normal quantile."""
+    z = normal_upper_quantile(alpha)
+    h = 2.0 / (9.0 * df)
+    return df * (1.0 - h + z * math.sqrt(h)) ** 3
+
+
+def g_test(counts, probs, min_expected=5.0):
+    """G statistic 2 sum O ln(O/E) of observed counts against a law (arrays of one shape), after merging: the bins whose
+    expected count N p is below min_expected are pooled into one bin, and that bin, if still below, into the smallest of the
+    others.  The merge depends on the law alone, never on the counts.  Bins of probability 0 take no part; a count in one
+    makes G inf.  Returns (G, degrees of freedom)."""
+    O = np.asarray(counts, np.float64).ravel()
+    E = O.sum() * np.asarray(probs, np.float64).ravel()
+    if (O[E == 0] > 0).any():
+        return math.inf, int((E > 0).sum()) - 1
+    O, E = O[E > 0], E[E > 0]
+    small = E < min_expected
+    Ob, Eb = list(O[~small]), list(E[~small])
+    if small.any():
+        o, e = O[small].sum(), E[small].sum()
+        if e < min_expected and Eb:
+            j = int(np.argmin(Eb))
+            o, e = o + Ob.pop(j), e + Eb.pop(j)
+        Ob.append(o)
+        Eb.append(e)
+    Ob, Eb = np.array(Ob), np.array(Eb)
+    k = Ob > 0
+    return 2.0 * float((Ob[k] * np.log(Ob[k] / Eb[k])).sum()), len(Ob) - 1
+
+
+SAMPLER_ALPHA = 1e-6
+"""Rejection level of the sampler-law G-tests.  The draws are a fixed function of (seed, pixel, attempt), so a test either
+always passes or always fails; the level only sets how far from the law a stream must be before it fails."""
+
+
+def sampler_state(H, W, maxknn, L):
+    """Reference-dtype state (proposals, lcosts, nprop, bestlabels) in which the neighbour stage with ngauss = 1 appends exactly
+    the position of its first draw that lands inside the image: every kNN slot 0..maxknn-1 holds (-30000, -30000), whose
+    components no position in [0, 8191] shares, so the component-wise duplicate test (`tv in`, daisy i flann.py:226, SURVEY
+    Q5) never fires; slot maxknn holds the pixel's own position (y, x) and is its WTA label.  The appended label then lands
+    in slot maxknn + 1.  Costs are 0.
+    That slot maxknn stays out of the duplicate test's first slice, proposals[broj:broj+K] (:223-226), needs cells of at
+    least NEIGHBOUR_REACH px, so that a draw lands at most one cell away, and window >= 1: broj + K then stays at or below
+    K (3 + 3 ncellyl) <= 35 < maxknn = 45 at window 1.  (At window 0 the draw one cell down gives broj = K = maxknn.)"""
+    proposals = np.full((H, W, L, 2), -1, np.int64)
+    proposals[:, :, :maxknn] = -30000
+    yy, xx = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    proposals[:, :, maxknn, 0] = yy
+    proposals[:, :, maxknn, 1] = xx
+    lcosts = np.full((H, W, L), 1000.0)
+    lcosts[:, :, :maxknn + 1] = 0.0
+    nprop = np.full((H, W), maxknn + 1, np.int64)
+    return proposals, lcosts, nprop, np.full((H, W), maxknn, np.int64)
+
+
+def sampler_law_check(draws, sigma, border=16, alpha=SAMPLER_ALPHA):
+    """G-tests of the sampled positions `draws` ((H,W,2) [ty, tx], one per pixel) against gauss_offset_law:
+      * interior (pixels at least 64 px from every border, where no draw leaves the image): the joint histogram of the
+        offsets (ty - y, tx - x) against the product of the offset laws -- which also tests that the two are independent;
+      * for each distance d = 0..border-1 from the top and left borders: the rows drawn by the pixels of row d and the columns
+        drawn by the pixels of column d, pooled, against gauss_offset_law(d, n, sigma) (with the other coordinate independent,
+        its conditioning on landing inside the image does not change this law).  There int() truncation shows: value 0
+        takes both sides of the centre line.
+    Each test rejects at G > chi2_upper_quantile(df, alpha).  H = W = n is required.  Returns (failures, results), results
+    a list of (name, G, df, threshold)."""
+    H, W = draws.shape[:2]
+    assert H == W, "the border classes pool rows and columns of one length"
+    n, R = H, NEIGHBOUR_REACH
+    res = []
+    off = draws[R:H - R, R:W - R] - np.stack(np.meshgrid(np.arange(R, H - R), np.arange(R, W - R), indexing="ij"), -1)
+    q = gauss_offset_law(R, 2 * R, sigma)[0]                         # value R + k  <->  offset k in -64..63
+    inside = (off >= -R).all(-1) & (off < R).all(-1)
+    hist = np.zeros((2 * R, 2 * R))
+    np.add.at(hist, (off[inside][:, 0] + R, off[inside][:, 1] + R), 1)
+    G, df = g_test(np.append(hist.ravel(), (~inside).sum()), np.append(np.outer(q, q).ravel(), 0.0))
+    res.append(("interior (dy, dx)", G, df))
+    for d in range(border):
+        vals = np.concatenate([draws[d, :, 0], draws[:, d, 1]])
+        cnt = np.bincount(np.clip(vals, -1, n) + 1, minlength=n + 2)                 # bin 0: value -1, bin n + 1: value n
+        law = np.concatenate([[0.0], gauss_offset_law(d, n, sigma)[0], [0.0]])      # -1 and n collect impossible values
+        G, df = g_test(cnt, law)
+        res.append(("distance %d from the top/left border" % d, G, df))
+    res = [(name, G, df, chi2_upper_quantile(max(df, 1), alpha)) for name, G, df in res]
+    bad = ["sigma %g, %s: G = %.1f on %d df > %.1f" % (sigma, name, G, df, t) for name, G, df, t in res if not G <= t]
+    return bad, res

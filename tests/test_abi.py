@@ -4,6 +4,7 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
 import pytest
 
 from conftest import ROOT, pkg
@@ -129,3 +130,54 @@ def test_no_cpu_fallback(L):
         pytest.skip("GPU present")
     with pytest.raises(L.DflowError):
         pkg("pipeline").DiscreteFlow(64, 64, 8, 8)
+
+
+def test_lamda_and_tphi_contract(L):
+    """lamda and tphi must be finite and >= 0, and max(pich, picw) (3 tpsi + lamda tphi) < 800000 (include/dflow.h,
+    DFLOW_DP_SENTINEL): outside it the chain kernel's unsigned minimum over tpsi + dp stops ordering like the doubles, or the
+    reference's 800000 sentinels bind.  Refused on the host, with the field named in the message."""
+    lib = L.lib()
+    header = open(os.path.join(ROOT, "include", "dflow.h")).read()
+    assert re.search(r"#define\s+DFLOW_DP_SENTINEL\s+800000\.0\b", header)
+
+    def refused(msg, geom=(436, 1024, 27, 64), **kw):
+        q = L.default_params(*geom, **kw)
+        return lib.dflow_workspace_bytes(C.byref(q)) == 0 and msg in lib.dflow_last_error()
+
+    for field in ("lamda", "tphi"):
+        for bad in (float("nan"), float("inf"), -float("inf"), -1.0, -1e-30):
+            assert refused(field.encode() + b"=", **{field: bad}), (field, bad, lib.dflow_last_error())
+    for field, edge in (("lamda", 0.0), ("tphi", 0.0), ("lamda", -0.0), ("tphi", -0.0)):
+        q = L.default_params(436, 1024, 27, 64, **{field: edge})
+        assert lib.dflow_workspace_bytes(C.byref(q)) > 0, (field, edge, lib.dflow_last_error())
+    # 8000 * (3*8 + 38 * 2) = 800000 exactly: refused; one double below lamda = 38, accepted.  tphi = 2 is float32-exact.
+    assert refused(b"must be below", (8, 8000, 8, 64), lamda=38.0, tphi=2.0)
+    assert refused(b"lamda", (8000, 8, 64, 8), lamda=38.0, tphi=2.0)       # max(pich, picw) either way
+    under = L.default_params(8, 8000, 8, 64, lamda=float(np.nextafter(38.0, 0.0)), tphi=2.0)
+    assert lib.dflow_workspace_bytes(C.byref(under)) > 0, lib.dflow_last_error()
+    # the same in tphi (lamda = 2): 38 is the bound, the next float32 below it is accepted
+    assert refused(b"tphi", (8, 8000, 8, 64), lamda=2.0, tphi=38.0)
+    under = L.default_params(8, 8000, 8, 64, lamda=2.0, tphi=float(np.nextafter(np.float32(38.0), np.float32(0.0))))
+    assert lib.dflow_workspace_bytes(C.byref(under)) > 0, lib.dflow_last_error()
+    # and one pixel longer chains at the same lamda: refused
+    assert refused(b"must be below", (8, 8001, 8, 64), lamda=float(np.nextafter(38.0, 0.0)), tphi=2.0)
+    # the largest chains at the defaults: 8192 (24 + 0.05 * 2.5) = 197 632
+    assert lib.dflow_workspace_bytes(C.byref(L.default_params(8192, 8192, 512, 512))) > 0
+
+
+def test_set_host_state_refuses_costs_outside_zero_tphi():
+    """DiscreteFlow.set_host_state refuses used-slot costs that are negative, not finite or above tphi before touching the
+    device (unused slots may hold anything: the reference fills them with 1000.0).  Checked on an object without a device."""
+    DF = pkg("pipeline").DiscreteFlow
+    df = DF.__new__(DF)
+    df.p = pkg("_lib").default_params(8, 8, 8, 8)
+    H = W = 8
+    L = df.p.maxnprop
+    proposals = np.zeros((H, W, L, 2), np.int64)
+    nprop = np.full((H, W), 3, np.int64)
+    for bad in (-0.5, float("nan"), float("inf"), 2.5000002384185791):      # the float32 just above tphi = 2.5
+        lcosts = np.full((H, W, L), 1000.0)
+        lcosts[..., :3] = 1.0
+        lcosts[3, 4, 2] = bad
+        with pytest.raises(ValueError, match="tphi|float32"):
+            df.set_host_state(proposals, lcosts, nprop, np.zeros((H, W), np.int64))
