@@ -230,6 +230,34 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
                            uint64_t *d_list_g, void *d_ws, size_t ws_bytes, void *stream);
 int dflow_epic_last_stats(int32_t *rounds, float *stage_ms);
 
+/* Variational refinement of a dense flow: the second half of EpicFlow (Revaud et al., CVPR 2015, section 4, after Brox et al.,
+ * ECCV 2004): a one-level minimisation of a robust, normalised gradient- (gamma) and colour-constancy (delta) energy with an
+ * image-driven smoothness term (alpha), started from d_flow_in.  This build's own definition (DESIGN.md "Variational
+ * refinement"): niter_outer warps, niter_inner updates of the lagged weights per warp, niter_solver iterations of RED-BLACK SOR
+ * per update, so the result is a function of the inputs alone; it is not bit-matched to epicflow-static, and the defaults are
+ * EpicFlow's documented ones as recalled, not checked against that binary.  1 <= h, w <= 8192.
+ * d_bgr1, d_bgr2 (h,w,3) uint8 BGR; d_flow_in, d_flow_out (h,w,2) float32 [dy,dx], which may be the same buffer.  A pixel
+ * whose flow is not finite is treated as unmatched in the data term (it is sampled at itself), but the smoothness term still
+ * reads it.  alpha, gamma, delta finite and >= 0; sigma (Gaussian presmoothing) in [0,5]; sor_omega in (0,2); niter_outer in
+ * 0..1000 (0: the output is a copy of the input); niter_inner in 1..1000; niter_solver in 1..10000.
+ * A value outside these bounds, a NULL pointer or an unknown flag bit returns DFLOW_EINVAL; a NULL or too small workspace
+ * returns DFLOW_ENOSPC, as for every stage; both before anything is launched.  The Gaussian taps are computed in double from
+ * the float32 sigma the struct carries.  dflow_var_default_params ignores a NULL p.
+ * DFLOW_VAR_FLAG_SOR_UNFUSED runs the solver as one launch per half-sweep instead of the LDS-tiled kernel that does 8 per
+ * launch: the same result bit for bit (the cross-check and A/B partner).  The call is asynchronous on `stream` and reads
+ * nothing back.  The workspace grows linearly with h*w; the workspace-size function returns 0 (and sets dflow_last_error) for
+ * sizes outside the range. */
+#define DFLOW_VAR_FLAG_SOR_UNFUSED 1u
+typedef struct dflow_var_params {
+    float alpha, gamma, delta, sigma, sor_omega;
+    int32_t niter_outer, niter_inner, niter_solver;
+    uint32_t flags;
+} dflow_var_params;
+void dflow_var_default_params(dflow_var_params *p);
+size_t dflow_var_workspace_bytes(int32_t h, int32_t w);
+int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow_in,
+                     const dflow_var_params *p, float *d_flow_out, void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(CSRC, "libdflow.so")
 FLAG_KNN_EXACT = 1      # DFLOW_FLAG_KNN_EXACT
 FLAG_DESCR_F16 = 8      # DFLOW_FLAG_DESCR_F16
 DESC_PITCH_F16 = 72     # DFLOW_DESC_PITCH_F16: binary16 descriptor planes are (H,W,72)
+VAR_FLAG_SOR_UNFUSED = 1    # DFLOW_VAR_FLAG_SOR_UNFUSED
 
 
 class DflowError(RuntimeError):
@@ -23,6 +24,13 @@ class Params(C.Structure):
                 ("maxnprop", C.c_int32), ("knn", C.c_int32), ("window", C.c_int32), ("ngauss", C.c_int32),
                 ("tpsi", C.c_int32), ("max_attempts", C.c_int32), ("tphi", C.c_float), ("sigma", C.c_float),
                 ("lamda", C.c_double), ("seed", C.c_uint64), ("label_pitch", C.c_int32), ("flags", C.c_int32)]
+
+
+class VarParams(C.Structure):
+    """struct dflow_var_params (include/dflow.h): the parameters of dflow_var_refine."""
+    _fields_ = [("alpha", C.c_float), ("gamma", C.c_float), ("delta", C.c_float), ("sigma", C.c_float),
+                ("sor_omega", C.c_float), ("niter_outer", C.c_int32), ("niter_inner", C.c_int32),
+                ("niter_solver", C.c_int32), ("flags", C.c_uint32)]
 
 
 _vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
@@ -53,6 +61,9 @@ _SIGNATURES = {
     "dflow_epic_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_epic_interpolate": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_epic_last_stats": (C.c_int, [_vp, _vp]),
+    "dflow_var_default_params": (None, [C.POINTER(VarParams)]),
+    "dflow_var_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_var_refine": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.POINTER(VarParams), _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

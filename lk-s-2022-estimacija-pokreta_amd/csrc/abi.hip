@@ -283,6 +283,44 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
 
 int dflow_epic_last_stats(int32_t *rounds, float *stage_ms) { return epic_last_stats(rounds, stage_ms); }
 
+void dflow_var_default_params(dflow_var_params *p)
+{
+    if (!p) return;
+    memset(p, 0, sizeof(*p));
+    p->alpha = 1.0f; p->gamma = 0.71f; p->delta = 0.0f; p->sigma = 1.0f; p->sor_omega = 1.9f;
+    p->niter_outer = 5; p->niter_inner = 1; p->niter_solver = 30;
+}
+
+size_t dflow_var_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return var_ws_bytes(h, w);
+}
+
+int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow_in,
+                     const dflow_var_params *p, float *d_flow_out, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    CHECK_PTR(p); CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_flow_in); CHECK_PTR(d_flow_out);
+    const struct { const char *name; float v; } weights[] = {{"alpha", p->alpha}, {"gamma", p->gamma}, {"delta", p->delta}};
+    for (const auto &f : weights)
+        if (!isfinite(f.v) || f.v < 0.0f)
+            return dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and >= 0", __func__, f.name, (double)f.v);
+    if (!isfinite(p->sigma) || p->sigma < 0.0f || p->sigma > 5.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: sigma=%g outside [0,5]", __func__, (double)p->sigma);
+    if (!(p->sor_omega > 0.0f && p->sor_omega < 2.0f))
+        return dflow_set_error(DFLOW_EINVAL, "%s: sor_omega=%g outside (0,2)", __func__, (double)p->sor_omega);
+    if (p->niter_outer < 0 || p->niter_outer > 1000)
+        return dflow_set_error(DFLOW_EINVAL, "%s: niter_outer=%d outside [0,1000]", __func__, p->niter_outer);
+    if (p->niter_inner < 1 || p->niter_inner > 1000)
+        return dflow_set_error(DFLOW_EINVAL, "%s: niter_inner=%d outside [1,1000]", __func__, p->niter_inner);
+    if (p->niter_solver < 1 || p->niter_solver > 10000)
+        return dflow_set_error(DFLOW_EINVAL, "%s: niter_solver=%d outside [1,10000]", __func__, p->niter_solver);
+    if (p->flags & ~DFLOW_VAR_FLAG_SOR_UNFUSED) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, p->flags);
+    CHECK_WS(var_ws_bytes(h, w));
+    return launch_var(h, w, d_bgr1, d_bgr2, d_flow_in, p, d_flow_out, d_ws, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -253,3 +253,7 @@ size_t epic_ws_bytes(int H, int W);
 int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, double k, int method, float *flow,
                 int32_t *seed_of, uint32_t *dist, int32_t *lists, uint64_t *list_g, void *ws, hipStream_t s);
 int epic_last_stats(int32_t *rounds, float *stage_ms);
+// variational.hip: variational refinement of a dense flow (arguments validated by the caller)
+size_t var_ws_bytes(int H, int W);
+int launch_var(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *flow_in, const dflow_var_params *p,
+               float *flow_out, void *ws, hipStream_t s);

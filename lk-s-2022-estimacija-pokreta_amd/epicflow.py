@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """Drop-in for EpicFlow's interpolation binary, the last call of the reference's spremiZaEpic.py:28:
 
-    python epicflow.py <img1> <img2> <edges.bin> <matches.txt> <out.flo> [-nw] [-nn N] [-k K]
+    python epicflow.py <img1> <img2> <edges.bin> <matches.txt> <out.flo> [-nw] [-nn N] [-k K] [--refine] [--refine-preset NAME]
 
 img1 and img2 give H x W (they must have the same size; read as the first CLI reads them).  edges.bin is raw float32
 (H,W), exactly H*W*4 bytes, read as edge strength.  Each line of matches.txt is "x1 y1 x2 y2": a seed at (rint(x1),
 rint(y1)) with flow (x2 - x1, y2 - y1); matches outside the image are dropped and the later of two lines for one pixel
 wins.  The dense flow (pipeline.epic_interpolate on the GPU: locally-weighted affine by default, Nadaraya-Watson with -nw;
--nn neighbours, default 100; kernel coefficient -k, default 0.8) goes to out.flo.  EpicFlow's match pre-filter and its
-variational refinement are not built (DESIGN.md "EpicFlow interpolation"): their options are refused.  Malformed input
-and unsupported options exit with status 2.
+-nn neighbours, default 100; kernel coefficient -k, default 0.8) goes to out.flo.  With --refine the interpolated flow
+first goes through pipeline.variational_refine with img1 and img2 (--refine-preset sintel|kitti|middlebury implies it and
+selects that preset's values).  That step is this build's own definition of EpicFlow's variational refinement (DESIGN.md
+"Variational refinement"; red-black SOR, not bit-matched to epicflow-static), which is why it has a long option of its own:
+EpicFlow's single-dash refinement options (-iter -alpha -gamma -delta -sigma and the dataset presets) would promise that
+binary's behaviour and stay refused here, as does its match pre-filter, which is not built; variational.py takes those
+names for this build's step.  Malformed input and unsupported options exit with status 2.
 """
 import importlib
 import os
@@ -21,6 +25,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 
 UNSUPPORTED = ("-prefnn", "-iter", "-alpha", "-gamma", "-delta", "-sigma", "-kitti", "-sintel", "-middlebury")
+
+
+REFINE_PRESETS = ("sintel", "kitti", "middlebury")
 
 
 class UsageError(ValueError):
@@ -78,6 +85,12 @@ def parse_args(argv):
             except ValueError:
                 raise UsageError("%s: bad value %r" % (a, argv[i + 1]))
             i += 1
+        elif a == "--refine":                                   # the long options are read by parse_refine
+            pass
+        elif a == "--refine-preset":
+            if i + 1 >= len(argv) or argv[i + 1] not in REFINE_PRESETS:
+                raise UsageError("--refine-preset needs one of %s" % ", ".join(REFINE_PRESETS))
+            i += 1
         elif a in UNSUPPORTED:
             raise UsageError("%s is not supported: the match pre-filter and the variational refinement are not built" % a)
         elif a.startswith("-") and len(a) > 1:
@@ -94,13 +107,25 @@ def parse_args(argv):
     return pos, nn, k, method
 
 
+def parse_refine(argv):
+    """(refine, preset) of an argument list parse_args accepts: --refine, or --refine-preset NAME (which implies it; the
+    last one given counts)."""
+    preset = None
+    for i, a in enumerate(argv):
+        if a == "--refine-preset":
+            preset = argv[i + 1]
+    return "--refine" in argv or preset is not None, preset
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     try:
         (im1, im2, edges_bin, matches, out), nn, k, method = parse_args(argv)
+        refine, refine_preset = parse_refine(argv)
         read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
-        H, W = read_bgr(im1).shape[:2]
-        if read_bgr(im2).shape[:2] != (H, W):
+        img1, img2 = read_bgr(im1), read_bgr(im2)
+        H, W = img1.shape[:2]
+        if img2.shape[:2] != (H, W):
             raise UsageError("%s and %s differ in size" % (im1, im2))
         raw = open(edges_bin, "rb").read()
         if len(raw) != 4 * H * W:
@@ -115,6 +140,8 @@ def main(argv=None):
     pipeline = importlib.import_module(PKG + ".pipeline")
     flowio = importlib.import_module(PKG + ".flowio")
     flow = pipeline.epic_interpolate(sparse, edges, nn=nn, k=k, method=method)
+    if refine:
+        flow = pipeline.variational_refine(img1, img2, flow, preset=refine_preset)
     flowio.write_flo(out, flow.cpu().numpy())
     return 0
 

@@ -332,6 +332,57 @@ def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists
     return (flow, S, D, lst, list_g) if aux else flow
 
 
+# The variational part of EpicFlow's presets, as its documentation gives them; recalled, not checked against the binary.
+VAR_PRESETS = {
+    "sintel": dict(niter_outer=5, alpha=1.0, gamma=0.72, delta=0.0, sigma=1.1),
+    "kitti": dict(niter_outer=2, alpha=1.0, gamma=0.77, delta=0.0, sigma=1.7),
+    "middlebury": dict(niter_outer=25, alpha=1.0, gamma=0.72, delta=0.0, sigma=1.1),
+}
+_VAR_FIELDS = tuple(name for name, _ in _lib.VarParams._fields_)
+
+
+def var_params(preset=None, **params):
+    """struct dflow_var_params: the library's defaults, then the preset ("sintel", "kitti", "middlebury" or None), then the
+    keyword arguments (the struct's field names).  ValueError for an unknown preset or field."""
+    p = _lib.VarParams()
+    _lib.lib().dflow_var_default_params(C.byref(p))
+    if preset is not None and preset not in VAR_PRESETS:
+        raise ValueError("variational_refine: preset must be one of %s or None, not %r" % (sorted(VAR_PRESETS), preset))
+    for k, v in list(VAR_PRESETS.get(preset, {}).items()) + list(params.items()):
+        if k not in _VAR_FIELDS:
+            raise ValueError("variational_refine: unknown parameter %r (known: %s)" % (k, ", ".join(_VAR_FIELDS)))
+        setattr(p, k, v)
+    return p
+
+
+def variational_refine(img1, img2, flow, preset=None, **params):
+    """Variational refinement of a dense flow (dflow_var_refine, DESIGN.md "Variational refinement"): two (H,W,3) uint8 BGR
+    images and a (H,W,2) float32 [dy,dx] flow (device tensors or host arrays; host data is uploaded to the current device)
+    -> the refined (H,W,2) float32 [dy,dx] device tensor.  preset and params as in var_params (alpha, gamma, delta, sigma,
+    sor_omega, niter_outer, niter_inner, niter_solver, flags).  Runs on torch's current stream and does not wait for it."""
+    p = var_params(preset, **params)
+
+    def tensor(a, name, dtype, last):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        if a.dtype != dtype or a.dim() != 3 or a.shape[2] != last:
+            raise ValueError("variational_refine: %s must be (H,W,%d) %s, got %s %s" % (name, last, dtype, tuple(a.shape), a.dtype))
+        return a
+    flow = tensor(flow, "flow", torch.float32, 2)
+    img1, img2 = tensor(img1, "img1", torch.uint8, 3), tensor(img2, "img2", torch.uint8, 3)
+    H, W = int(flow.shape[0]), int(flow.shape[1])
+    if tuple(img1.shape[:2]) != (H, W) or tuple(img2.shape[:2]) != (H, W):
+        raise ValueError("variational_refine: images %s, %s and flow %s differ in size"
+                         % (tuple(img1.shape[:2]), tuple(img2.shape[:2]), (H, W)))
+    dev = flow.device if flow.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    flow, img1, img2 = (t.to(dev).contiguous() for t in (flow, img1, img2))
+    ws, ws_bytes = _lib.workspace("dflow_var_workspace_bytes", H, W, dev)
+    out = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
+    _lib.call("dflow_var_refine", H, W, img1.data_ptr(), img2.data_ptr(), flow.data_ptr(), C.byref(p), out.data_ptr(),
+              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    return out
+
+
 def epic_last_stats():
     """(Voronoi rounds, {stage: ms}) of the last epic_interpolate on this thread, from HIP events (waits for them)."""
     rounds, ms = C.c_int32(0), (C.c_float * 4)()

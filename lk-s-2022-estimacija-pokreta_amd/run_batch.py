@@ -10,7 +10,8 @@ Inputs are synthetic pairs (synth.make_pair, seed 1000*pair); outputs per pair i
 for both directions, a .flo of the forward flow, sparse_field_<pair>.npy and parovi_<pair>.txt; with --edges also
 ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_ivice: the third EpicFlow input); with
 --epic also epic_<pair>.flo, the dense flow interpolated from the pair's sparse field and that edge map
-(pipeline.epic_interpolate, EpicFlow's defaults).
+(pipeline.epic_interpolate, EpicFlow's defaults); with --epic-refine (implies --epic) that flow goes through the variational
+refinement with the pair's two images (pipeline.variational_refine, its defaults) before epic_<pair>.flo is written.
 """
 import argparse
 import importlib
@@ -36,7 +37,9 @@ def main(argv=None):
     ap.add_argument("--time", action="store_true", help="run the passes twice and report the wall time of the second run")
     ap.add_argument("--edges", action="store_true", help="also write ivice_NN.bin (Canny edge map of each pair's first image)")
     ap.add_argument("--epic", action="store_true", help="also write epic_NN.flo (edge-aware interpolation of each pair's sparse field)")
+    ap.add_argument("--epic-refine", action="store_true", help="--epic, and epic_NN.flo is the variationally refined flow")
     a = ap.parse_args(argv)
+    a.epic = a.epic or a.epic_refine
     import torch
     import torch.distributed as dist
     pipeline = importlib.import_module(PKG + ".pipeline")
@@ -122,12 +125,14 @@ def main(argv=None):
             np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
             evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
             if a.edges or a.epic:
-                img1 = images[pair][0] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[0]
+                img1, img2 = images[pair] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[:2]
                 _, ivice = pipeline.canny_edges(img1)
             if a.edges:
                 ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
             if a.epic:
                 epic = pipeline.epic_interpolate(sparse_dev, ivice)
+                if a.epic_refine:
+                    epic = pipeline.variational_refine(img1, img2, epic)
                 flowio.write_flo(os.path.join(a.out, "epic_%02d.flo" % pair), epic.cpu().numpy())
             print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
     if world > 1:
