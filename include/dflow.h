@@ -230,6 +230,38 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
                            uint64_t *d_list_g, void *d_ws, size_t ws_bytes, void *stream);
 int dflow_epic_last_stats(int32_t *rounds, float *stage_ms);
 
+/* EpicFlow's match pre-filter, the step epicflow-static takes before it interpolates: this build's own definition (DESIGN.md
+ * "EpicFlow interpolation", "Match pre-filter"), not bit-matched to that binary.  The defaults the callers use (saliency_th
+ * 0.045, pref_nn 25, pref_th 5, image smoothing sigma 0.8, tensor smoothing sigma 1.0) are EpicFlow's as
+ * recalled, not checked against the binary.  1 <= h, w <= 8192.  Seeds, d_edges, the Voronoi diagram, the seed graph, G and k
+ * as above.
+ * Stage A, saliency (skipped when saliency_th == 0; d_bgr may then be NULL and is not read): every channel of d_bgr (h,w,3)
+ * uint8 BGR as float32, smoothed by the separable Gaussian of the variational refinement (sigma 0.8), central differences
+ * 0.5 (f[+1] - f[-1]) with a replicate border, the structure tensor summed over the channels, its three planes smoothed
+ * (sigma 1.0), s = sqrt(max(0, lambda_min)), all float32.  A seed with s < saliency_th (s widened to double) is dropped,
+ * reason 2.
+ * Stage B, neighbour consistency (skipped when pref_nn == 0), over the seeds left: every seed lists its pref_nn + 1 nearest
+ * seeds by (G, id), itself first, and forms the Nadaraya-Watson estimate (u^, v^) of the others with weights exp(-k G / 2000),
+ * in double in list order; it is dropped, reason 3, when (u^ - u)^2 + (v^ - v)^2 > pref_th^2 in double.  A seed that reaches
+ * no other seed is kept (its estimate is its own flow), and so is one whose estimate is not a number (every weight 0).
+ * All seeds are judged against the same set: the result does not depend on any order.
+ * d_sparse_out (h,w,3): d_sparse_in with every dropped seed set to [0,0,0]; it may be d_sparse_in itself.  Optional outputs
+ * (NULL to skip): d_reason (h,w) uint8, 0 no seed, 1 kept, 2 saliency, 3 consistency; d_saliency (h,w) float32 s (zeros when
+ * stage A is skipped); d_estimate (h,w,2) float32 [u^, v^] at the seeds of stage B, 0 elsewhere.
+ * 0 <= pref_nn <= 255; saliency_th, pref_th finite and >= 0; k finite and > 0.  A value outside these bounds, a NULL required
+ * pointer or a NULL d_bgr with saliency_th != 0 returns DFLOW_EINVAL, a NULL or too small workspace DFLOW_ENOSPC, both before
+ * anything is launched.  Like the interpolation the call reads the Voronoi change counters back, and its own three counters at
+ * the end: it synchronises its stream and cannot be captured into a graph.  The workspace grows linearly with h*w; the
+ * workspace-size function returns 0 (and sets dflow_last_error) for sizes outside the range.
+ * dflow_epic_prefilter_last_stats: of the last call on the calling thread, counts[3] = seeds in, dropped by stage A, dropped
+ * by stage B, and the HIP-event times stage_ms[4] = stage A, Voronoi + seed graph, consistency, compaction (either may be
+ * NULL). */
+size_t dflow_epic_prefilter_workspace_bytes(int32_t h, int32_t w);
+int dflow_epic_prefilter(int32_t h, int32_t w, const uint8_t *d_bgr, const float *d_sparse_in, const float *d_edges,
+                         double saliency_th, int32_t pref_nn, double pref_th, double k, float *d_sparse_out, uint8_t *d_reason,
+                         float *d_saliency, float *d_estimate, void *d_ws, size_t ws_bytes, void *stream);
+int dflow_epic_prefilter_last_stats(int32_t *counts, float *stage_ms);
+
 /* Variational refinement of a dense flow: the second half of EpicFlow (Revaud et al., CVPR 2015, section 4, after Brox et al.,
  * ECCV 2004): a one-level minimisation of a robust, normalised gradient- (gamma) and colour-constancy (delta) energy with an
  * image-driven smoothness term (alpha), started from d_flow_in.  This build's own definition (DESIGN.md "Variational

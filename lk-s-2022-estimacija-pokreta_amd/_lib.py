@@ -61,6 +61,9 @@ _SIGNATURES = {
     "dflow_epic_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_epic_interpolate": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_epic_last_stats": (C.c_int, [_vp, _vp]),
+    "dflow_epic_prefilter_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_epic_prefilter": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _f64, _i32, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_epic_prefilter_last_stats": (C.c_int, [_vp, _vp]),
     "dflow_var_default_params": (None, [C.POINTER(VarParams)]),
     "dflow_var_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_var_refine": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.POINTER(VarParams), _vp, _vp, _sz, _vp]),

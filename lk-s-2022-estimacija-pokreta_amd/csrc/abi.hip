@@ -283,6 +283,33 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
 
 int dflow_epic_last_stats(int32_t *rounds, float *stage_ms) { return epic_last_stats(rounds, stage_ms); }
 
+size_t dflow_epic_prefilter_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return epic_prefilter_ws_bytes(h, w);
+}
+
+int dflow_epic_prefilter(int32_t h, int32_t w, const uint8_t *d_bgr, const float *d_sparse_in, const float *d_edges,
+                         double saliency_th, int32_t pref_nn, double pref_th, double k, float *d_sparse_out, uint8_t *d_reason,
+                         float *d_saliency, float *d_estimate, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (!isfinite(saliency_th) || saliency_th < 0.0)
+        return dflow_set_error(DFLOW_EINVAL, "%s: saliency_th=%g must be finite and >= 0", __func__, saliency_th);
+    if (pref_nn < 0 || pref_nn > 255) return dflow_set_error(DFLOW_EINVAL, "%s: pref_nn=%d outside [0,255]", __func__, pref_nn);
+    if (!isfinite(pref_th) || pref_th < 0.0)
+        return dflow_set_error(DFLOW_EINVAL, "%s: pref_th=%g must be finite and >= 0", __func__, pref_th);
+    if (!isfinite(k) || !(k > 0.0)) return dflow_set_error(DFLOW_EINVAL, "%s: k=%g must be finite and > 0", __func__, k);
+    if (saliency_th != 0.0 && !d_bgr)
+        return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr is NULL with saliency_th=%g (only saliency_th = 0 runs without the image)",
+                               __func__, saliency_th);
+    CHECK_PTR(d_sparse_in); CHECK_PTR(d_edges); CHECK_PTR(d_sparse_out); CHECK_WS(epic_prefilter_ws_bytes(h, w));
+    return launch_epic_prefilter(h, w, d_bgr, d_sparse_in, d_edges, saliency_th, pref_nn, pref_th, k, d_sparse_out, d_reason,
+                                 d_saliency, d_estimate, d_ws, (hipStream_t)stream);
+}
+
+int dflow_epic_prefilter_last_stats(int32_t *counts, float *stage_ms) { return epic_prefilter_last_stats(counts, stage_ms); }
+
 void dflow_var_default_params(dflow_var_params *p)
 {
     if (!p) return;

@@ -254,6 +254,18 @@ int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, d
                 int32_t *seed_of, uint32_t *dist, int32_t *lists, uint64_t *list_g, void *ws, hipStream_t s);
 int epic_last_stats(int32_t *rounds, float *stage_ms);
 // variational.hip: variational refinement of a dense flow (arguments validated by the caller)
+#define VAR_MAX_RADIUS 15            // ceil(3 * 5): sigma <= 5
+// the taps of a Gaussian of radius r = ceil(3 sigma), t[0 .. 2r], normalised in double and rounded to float32
+struct VarTaps { float t[2 * VAR_MAX_RADIUS + 1]; int r; };
+VarTaps var_taps(float sigma);
+// its separable Gaussian of one (H,W,3) uint8 image into three float planes (var_smooth_kernel)
+int launch_var_smooth(int H, int W, const uint8_t *bgr, float sigma, float *o0, float *o1, float *o2, hipStream_t s);
 size_t var_ws_bytes(int H, int W);
 int launch_var(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *flow_in, const dflow_var_params *p,
                float *flow_out, void *ws, hipStream_t s);
+// epic_prefilter.hip: EpicFlow's match pre-filter (arguments validated by the caller)
+size_t epic_prefilter_ws_bytes(int H, int W);
+int launch_epic_prefilter(int H, int W, const uint8_t *bgr, const float *sparse_in, const float *edges, double saliency_th,
+                          int pref_nn, double pref_th, double k, float *sparse_out, uint8_t *reason, float *saliency,
+                          float *estimate, void *ws, hipStream_t s);
+int epic_prefilter_last_stats(int32_t *counts, float *stage_ms);

@@ -17,56 +17,13 @@
 // A key is (D << 32) | id with D the integer geodesic distance, so u64 atomicMin realises the lexicographic minimum;
 // keys only decrease, so stale reads of another tile's halo cost progress, never correctness.
 #include <math.h>
-#include "dflow_common.h"
+#include "epic.h"
 
 #define VT_W 64
 #define VT_H 16
 #define VT_THREADS 256
-#define EPIC_CHUNK 4                        // Voronoi rounds launched between two reads of their change counters
-#define EPIC_ID_BITS 26                     // seed ids < 8192 * 8192
-#define EPIC_ID_MASK ((1ull << EPIC_ID_BITS) - 1)
-#define KEY_INF 0xFFFFFFFFFFFFFFFFull
-
-enum { CNT_CHANGED = 0, CNT_NSEEDS = EPIC_CHUNK, CNT_EDGES, CNT_WORDS = 16 };
-
-struct EpicWs {
-    uint32_t *cnt;        // CNT_WORDS counters
-    uint64_t *key;        // (H,W) (D << 32) | S
-    uint16_t *cost;       // (H,W) c(p) in [1, 1001]
-    uint32_t *rowbeg;     // (H,W) first edge of a seed's row
-    uint32_t *rowend;     // (H,W) degree, then the cursor, then one past the row's last edge
-    int32_t *seeds;       // compact list of seed ids
-    uint64_t *edges;      // directed seed-graph edges (w << 32) | t
-    float *model;         // (H,W,6) per seed: u = m0 + m1 dx + m2 dy, v = m3 + m4 dx + m5 dy
-};
-
-// every 4-neighbour pair with different seeds gives two directed edges
-static inline size_t epic_max_edges(int H, int W) { return 2 * ((size_t)H * (W - 1) + (size_t)(H - 1) * W); }
-
-static EpicWs epic_ws(void *ws, int H, int W, size_t *bytes = nullptr)
-{
-    const size_t n = (size_t)H * W;
-    WsCarver c(ws);
-    EpicWs w;
-    w.cnt = c.take<uint32_t>(CNT_WORDS);
-    w.key = c.take<uint64_t>(n);
-    w.cost = c.take<uint16_t>(n);
-    w.rowbeg = c.take<uint32_t>(n);
-    w.rowend = c.take<uint32_t>(n);
-    w.seeds = c.take<int32_t>(n);
-    w.edges = c.take<uint64_t>(epic_max_edges(H, W));
-    w.model = c.take<float>(6 * n);
-    if (bytes) *bytes = c.bytes;
-    return w;
-}
 
 size_t epic_ws_bytes(int H, int W) { size_t b; epic_ws(nullptr, H, W, &b); return b; }
-
-__device__ static inline bool is_seed(const float *__restrict__ sparse, int p)
-{
-    const float u = sparse[3 * (size_t)p], v = sparse[3 * (size_t)p + 1], valid = sparse[3 * (size_t)p + 2];
-    return valid > 0.5f && isfinite(u) && isfinite(v);
-}
 
 __global__ void __launch_bounds__(256) epic_init_kernel(int n, const float *__restrict__ sparse, const float *__restrict__ edges,
                                                         EpicWs ws)
@@ -205,24 +162,8 @@ __global__ void __launch_bounds__(256) epic_graph_fill_kernel(int H, int W, Epic
     });
 }
 
-__device__ static inline uint64_t wave_min_u64(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
-__device__ static inline uint64_t wave_max_u64(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t u = __shfl_xor(v, o); v = u > v ? u : v; }
-    return v;
-}
-
-// One wave per seed s.  The frontier holds (G << 26) | id keys in slots j * 64 + lane (j < 4, so nn <= 256), INF when
-// free; settled ids sit in the same layout.  G < 2^34: a settled seed's shortest path has at most nn - 1 edges of weight
-// below 2^26.  A frontier entry ranked below nn - settled others can never be settled among the first nn, so the frontier
-// is capped at that size: a new entry replaces the largest one or is dropped.  Dropping loses nothing: if the entry's
-// true key is smaller, its predecessor on the true path is settled before it and offers it again.
+// One wave per seed s: the bounded Dijkstra of epic.h (frontier of at most nn - settled entries, held 4 per lane in
+// registers, so nn <= 256), the model's sums accumulated as each seed settles.
 __global__ void __launch_bounds__(256) epic_lists_kernel(int H, int W, int nseeds, int nn, double k, int method,
                                                          const float *__restrict__ sparse, EpicWs ws,
                                                          int32_t *__restrict__ lists, uint64_t *__restrict__ list_g)
@@ -230,28 +171,10 @@ __global__ void __launch_bounds__(256) epic_lists_kernel(int H, int W, int nseed
     const int lane = threadIdx.x & 63, wi = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (wi >= nseeds) return;
     const int s = ws.seeds[wi], xs = s % W, ys = s / W;
-    const int nslot = (nn + 63) >> 6;
-    uint64_t fk[4];
-    int lid[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) { fk[j] = KEY_INF; lid[j] = -1; }
-    if (lane == 0) fk[0] = (uint64_t)s;
-    int nf = 1, nl = 0;
     double sw = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0, su = 0, sv = 0, sxu = 0, syu = 0, sxv = 0, syv = 0;
-    while (nf > 0) {
-        uint64_t m = fk[0];
-#pragma unroll
-        for (int j = 1; j < 4; j++) m = fk[j] < m ? fk[j] : m;
-        m = wave_min_u64(m);
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (fk[j] == m) fk[j] = KEY_INF;
-        nf--;
-        const int id = (int)(m & EPIC_ID_MASK);
-        const uint64_t g = m >> EPIC_ID_BITS;
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (j == (nl >> 6) && lane == (nl & 63)) lid[j] = id;
-        if (lists && lane == 0) lists[(size_t)s * nn + nl] = id;
-        if (list_g && lane == 0) list_g[(size_t)s * nn + nl] = g;
+    const int nl = epic_dijkstra<4>(ws, s, nn, lane, [&](int pos, int id, uint64_t g) {
+        if (lists && lane == 0) lists[(size_t)s * nn + pos] = id;
+        if (list_g && lane == 0) list_g[(size_t)s * nn + pos] = g;
         // the model's sums, in list order; every lane holds the same values
         const double w = id == s ? 1.0 : exp(-(k * (double)g) / 2000.0);
         const double dx = (double)(id % W - xs), dy = (double)(id / W - ys);
@@ -259,47 +182,7 @@ __global__ void __launch_bounds__(256) epic_lists_kernel(int H, int W, int nseed
         const double wx = w * dx, wy = w * dy;
         sw += w; sx += wx; sy += wy; sxx += wx * dx; sxy += wx * dy; syy += wy * dy;
         su += w * u; sv += w * v; sxu += wx * u; syu += wy * u; sxv += wx * v; syv += wy * v;
-        if (++nl == nn) break;
-        const int limit = nn - nl;
-        const uint32_t beg = ws.rowbeg[id], end = ws.rowend[id];
-        for (uint32_t base = beg; base < end; base += 64) {
-            const uint64_t mine = base + lane < end ? ws.edges[base + lane] : 0;
-            const int cnt = (int)min(64u, end - base);
-            for (int i = 0; i < cnt; i++) {
-                const uint64_t e = __shfl(mine, i);
-                const uint32_t t = (uint32_t)e;
-                const uint64_t nk = ((g + (e >> 32)) << EPIC_ID_BITS) | t;
-                bool hit = false;
-#pragma unroll
-                for (int j = 0; j < 4; j++) hit |= j < nslot && lid[j] == (int)t;
-                if (__any(hit)) continue;                              // settled already
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    if (fk[j] != KEY_INF && (fk[j] & EPIC_ID_MASK) == t) { hit = true; if (nk < fk[j]) fk[j] = nk; }
-                if (__any(hit)) continue;                              // on the frontier: decreased if shorter
-                if (nf < limit) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint64_t free_lanes = __ballot(fk[j] == KEY_INF);
-                        if (j < nslot && free_lanes) {
-                            if (lane == __ffsll((unsigned long long)free_lanes) - 1) fk[j] = nk;
-                            break;
-                        }
-                    }
-                    nf++;
-                } else {
-                    uint64_t mx = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; j++) if (fk[j] != KEY_INF && fk[j] > mx) mx = fk[j];
-                    mx = wave_max_u64(mx);
-                    if (nk < mx) {
-#pragma unroll
-                        for (int j = 0; j < 4; j++) if (fk[j] == mx) fk[j] = nk;
-                    }
-                }
-            }
-        }
-    }
+    });
     if (lane != 0) return;
     const double mu = su / sw, mv = sv / sw;
     float out[6] = {(float)mu, 0.0f, 0.0f, (float)mv, 0.0f, 0.0f};
@@ -355,20 +238,14 @@ int epic_last_stats(int32_t *rounds, float *stage_ms)
     return DFLOW_OK;
 }
 
-int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, double k, int method, float *flow,
-                int32_t *seed_of, uint32_t *dist, int32_t *lists, uint64_t *list_g, void *wsp, hipStream_t st)
+int epic_build_graph(int H, int W, const float *sparse, const float *edges, const EpicWs &ws, hipStream_t st, int *nseeds,
+                     int *rounds, hipEvent_t after_voronoi)
 {
-    const EpicWs ws = epic_ws(wsp, H, W);
     const int n = H * W, blocks = (n + 255) / 256;
     const dim3 tiles((W + VT_W - 1) / VT_W, (H + VT_H - 1) / VT_H);
     // A round settles at least the next tile crossing of every shortest path, and a shortest path crosses each pair of
     // neighbouring pixels in different tiles at most once.
     const long long max_rounds = (long long)H * (tiles.x - 1) + (long long)W * (tiles.y - 1) + 2;
-    if (!g_ev[0])
-        for (int i = 0; i < 5; i++) DFLOW_HIP(hipEventCreate(&g_ev[i]));
-    g_rounds = 0;
-
-    DFLOW_HIP(hipEventRecord(g_ev[0], st));
     DFLOW_HIP(hipMemsetAsync(ws.cnt, 0, CNT_WORDS * 4, st));
     epic_init_kernel<<<blocks, 256, 0, st>>>(n, sparse, edges, ws);
     uint32_t h_cnt[EPIC_CHUNK + 1];
@@ -380,18 +257,34 @@ int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, d
         DFLOW_HIP(hipStreamSynchronize(st));
         int j = 0;
         while (j < EPIC_CHUNK && h_cnt[CNT_CHANGED + j]) j++;
-        if (j < EPIC_CHUNK) { g_rounds = (int)(round + j + 1); break; }
+        if (j < EPIC_CHUNK) { *rounds = (int)(round + j + 1); break; }
         round += EPIC_CHUNK;
         if (round >= max_rounds)
             return dflow_set_error(DFLOW_EHIP, "epic: the Voronoi relaxation still changed after %lld rounds", round);
     }
-    const int nseeds = (int)h_cnt[CNT_NSEEDS];
-    DFLOW_HIP(hipEventRecord(g_ev[1], st));
-    if (nseeds) {
+    *nseeds = (int)h_cnt[CNT_NSEEDS];
+    if (after_voronoi) DFLOW_HIP(hipEventRecord(after_voronoi, st));
+    if (*nseeds) {
         epic_graph_count_kernel<<<blocks, 256, 0, st>>>(H, W, ws);
-        epic_graph_alloc_kernel<<<(nseeds + 255) / 256, 256, 0, st>>>(nseeds, ws);
+        epic_graph_alloc_kernel<<<(*nseeds + 255) / 256, 256, 0, st>>>(*nseeds, ws);
         epic_graph_fill_kernel<<<blocks, 256, 0, st>>>(H, W, ws);
     }
+    return dflow_check_launch("epic graph kernels");
+}
+
+int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, double k, int method, float *flow,
+                int32_t *seed_of, uint32_t *dist, int32_t *lists, uint64_t *list_g, void *wsp, hipStream_t st)
+{
+    const EpicWs ws = epic_ws(wsp, H, W);
+    const int n = H * W, blocks = (n + 255) / 256;
+    if (!g_ev[0])
+        for (int i = 0; i < 5; i++) DFLOW_HIP(hipEventCreate(&g_ev[i]));
+    g_rounds = 0;
+
+    DFLOW_HIP(hipEventRecord(g_ev[0], st));
+    int nseeds = 0;
+    const int rc = epic_build_graph(H, W, sparse, edges, ws, st, &nseeds, &g_rounds, g_ev[1]);
+    if (rc) return rc;
     DFLOW_HIP(hipEventRecord(g_ev[2], st));
     if (lists) DFLOW_HIP(hipMemsetAsync(lists, 0xFF, (size_t)n * nn * sizeof(int32_t), st));
     if (list_g) DFLOW_HIP(hipMemsetAsync(list_g, 0xFF, (size_t)n * nn * sizeof(uint64_t), st));

@@ -8,7 +8,6 @@
 
 #define VAR_EPS2 1e-6f
 #define VAR_ZETA2 0.01f
-#define VAR_MAX_RADIUS 15            // ceil(3 * 5): sigma <= 5
 #define VAR_BX 32
 #define VAR_BY 8
 #define VAR_THREADS (VAR_BX * VAR_BY)
@@ -35,8 +34,6 @@ static VarWs var_ws(void *ws, int H, int W)
 }
 
 size_t var_ws_bytes(int H, int W) { return var_ws(nullptr, H, W).bytes; }
-
-struct VarTaps { float t[2 * VAR_MAX_RADIUS + 1]; int r; };
 
 __device__ __forceinline__ static int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
@@ -357,7 +354,7 @@ __global__ __launch_bounds__(VAR_THREADS) void var_add_kernel(int H, int W, VarW
     w.v[i] = w.v[i] + dv[i];
 }
 
-static VarTaps var_taps(float sigma)
+VarTaps var_taps(float sigma)
 {
     VarTaps t = {};
     if (sigma == 0.0f) { t.t[0] = 1.0f; return t; }
@@ -367,6 +364,13 @@ static VarTaps var_taps(float sigma)
     for (int i = -t.r; i <= t.r; i++) sum += e[i + t.r] = exp(-(double)(i * i) / (2.0 * s * s));
     for (int i = 0; i <= 2 * t.r; i++) t.t[i] = (float)(e[i] / sum);
     return t;
+}
+
+int launch_var_smooth(int H, int W, const uint8_t *bgr, float sigma, float *o0, float *o1, float *o2, hipStream_t s)
+{
+    const dim3 stiles((W + VAR_ST - 1) / VAR_ST, (H + VAR_ST - 1) / VAR_ST);
+    var_smooth_kernel<<<stiles, VAR_THREADS, 0, s>>>(bgr, H, W, var_taps(sigma), o0, o1, o2);
+    return dflow_check_launch("var_smooth_kernel");
 }
 
 int launch_var(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *flow_in, const dflow_var_params *p,

@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """Drop-in for EpicFlow's interpolation binary, the last call of the reference's spremiZaEpic.py:28:
 
-    python epicflow.py <img1> <img2> <edges.bin> <matches.txt> <out.flo> [-nw] [-nn N] [-k K] [--refine] [--refine-preset NAME]
+    python epicflow.py <img1> <img2> <edges.bin> <matches.txt> <out.flo> [-nw] [-nn N] [-k K]
+                       [--prefilter] [--pref-nn N] [--pref-th T] [--saliency-th T] [--refine] [--refine-preset NAME]
 
 img1 and img2 give H x W (they must have the same size; read as the first CLI reads them).  edges.bin is raw float32
 (H,W), exactly H*W*4 bytes, read as edge strength.  Each line of matches.txt is "x1 y1 x2 y2": a seed at (rint(x1),
 rint(y1)) with flow (x2 - x1, y2 - y1); matches outside the image are dropped and the later of two lines for one pixel
 wins.  The dense flow (pipeline.epic_interpolate on the GPU: locally-weighted affine by default, Nadaraya-Watson with -nw;
--nn neighbours, default 100; kernel coefficient -k, default 0.8) goes to out.flo.  With --refine the interpolated flow
+-nn neighbours, default 100; kernel coefficient -k, default 0.8) goes to out.flo.  With --prefilter the matches first go
+through pipeline.epic_prefilter with img1 (the match pre-filter: seeds in image regions of saliency below --saliency-th,
+default 0.045, and seeds further than --pref-th px, default 5, from the estimate of their --pref-nn nearest seeds, default
+25, are removed; 0 switches a stage off; any of the three options implies --prefilter; the values are EpicFlow's as recalled,
+not checked against the binary; DESIGN.md "Match pre-filter").  With --refine the interpolated flow
 first goes through pipeline.variational_refine with img1 and img2 (--refine-preset sintel|kitti|middlebury implies it and
 selects that preset's values).  That step is this build's own definition of EpicFlow's variational refinement (DESIGN.md
 "Variational refinement"; red-black SOR, not bit-matched to epicflow-static), which is why it has a long option of its own:
 EpicFlow's single-dash refinement options (-iter -alpha -gamma -delta -sigma and the dataset presets) would promise that
-binary's behaviour and stay refused here, as does its match pre-filter, which is not built; variational.py takes those
-names for this build's step.  Malformed input and unsupported options exit with status 2.
+binary's behaviour and stay refused here; variational.py takes those names for this build's step.  For the same reason
+the binary's -prefnn stays refused: --prefilter is this build's definition of the pre-filter.  Malformed input and unsupported options exit with status 2.
 """
 import importlib
 import os
@@ -28,6 +33,9 @@ UNSUPPORTED = ("-prefnn", "-iter", "-alpha", "-gamma", "-delta", "-sigma", "-kit
 
 
 REFINE_PRESETS = ("sintel", "kitti", "middlebury")
+# option -> (keyword of pipeline.epic_prefilter, type, largest value)
+PREFILTER_OPTIONS = {"--pref-nn": ("pref_nn", int, 255), "--pref-th": ("pref_th", float, None),
+                     "--saliency-th": ("saliency_th", float, None)}
 
 
 class UsageError(ValueError):
@@ -91,8 +99,25 @@ def parse_args(argv):
             if i + 1 >= len(argv) or argv[i + 1] not in REFINE_PRESETS:
                 raise UsageError("--refine-preset needs one of %s" % ", ".join(REFINE_PRESETS))
             i += 1
+        elif a == "--prefilter":                                # read by parse_prefilter
+            pass
+        elif a in PREFILTER_OPTIONS:
+            name, kind, top = PREFILTER_OPTIONS[a]
+            if i + 1 >= len(argv):
+                raise UsageError("%s needs a value" % a)
+            try:
+                v = kind(argv[i + 1])
+            except ValueError:
+                raise UsageError("%s: bad value %r" % (a, argv[i + 1]))
+            if not (np.isfinite(v) and v >= 0 and (top is None or v <= top)):
+                raise UsageError("%s %s must be finite, >= 0%s" % (a, argv[i + 1], "" if top is None else " and <= %d" % top))
+            i += 1
+        elif a == "-prefnn":
+            raise UsageError("-prefnn is not supported: it would promise epicflow-static's pre-filter; this build's own is "
+                             "--prefilter [--pref-nn N] [--pref-th T] [--saliency-th T]")
         elif a in UNSUPPORTED:
-            raise UsageError("%s is not supported: the match pre-filter and the variational refinement are not built" % a)
+            raise UsageError("%s is not supported: it would promise epicflow-static's variational refinement; this build's own "
+                             "is --refine" % a)
         elif a.startswith("-") and len(a) > 1:
             raise UsageError("unknown option %s" % a)
         else:
@@ -117,11 +142,23 @@ def parse_refine(argv):
     return "--refine" in argv or preset is not None, preset
 
 
+def parse_prefilter(argv):
+    """None, or the keyword arguments of pipeline.epic_prefilter, of an argument list parse_args accepts: --prefilter, or any
+    of --pref-nn N, --pref-th T, --saliency-th T (which imply it; the last one given counts)."""
+    kw = {}
+    for i, a in enumerate(argv):
+        if a in PREFILTER_OPTIONS:
+            name, kind, _ = PREFILTER_OPTIONS[a]
+            kw[name] = kind(argv[i + 1])
+    return kw if kw or "--prefilter" in argv else None
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     try:
         (im1, im2, edges_bin, matches, out), nn, k, method = parse_args(argv)
         refine, refine_preset = parse_refine(argv)
+        prefilter = parse_prefilter(argv)
         read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
         img1, img2 = read_bgr(im1), read_bgr(im2)
         H, W = img1.shape[:2]
@@ -139,6 +176,8 @@ def main(argv=None):
         return 2
     pipeline = importlib.import_module(PKG + ".pipeline")
     flowio = importlib.import_module(PKG + ".flowio")
+    if prefilter is not None:
+        sparse = pipeline.epic_prefilter(sparse, edges, img1, k=k, **prefilter)
     flow = pipeline.epic_interpolate(sparse, edges, nn=nn, k=k, method=method)
     if refine:
         flow = pipeline.variational_refine(img1, img2, flow, preset=refine_preset)

@@ -332,6 +332,63 @@ def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists
     return (flow, S, D, lst, list_g) if aux else flow
 
 
+# EpicFlow's pre-filter defaults; recalled, not checked against the binary.
+PREFILTER_DEFAULTS = dict(saliency_th=0.045, pref_nn=25, pref_th=5.0)
+
+
+def epic_prefilter(sparse, edges, img1=None, saliency_th=None, pref_nn=25, pref_th=5.0, k=0.8, aux=False):
+    """EpicFlow's match pre-filter (dflow_epic_prefilter, DESIGN.md "Match pre-filter"): a (H,W,3) float32 [U,V,valid] sparse
+    field, a (H,W) float32 edge map and optionally the first image, (H,W,3) uint8 BGR (device tensors or host arrays; host
+    data is uploaded to the current device) -> the (H,W,3) float32 device tensor with every dropped seed set to [0,0,0].
+    Stage A drops seeds whose image saliency is below saliency_th (None: 0.045 with img1, 0 without; it needs the image, so
+    a non-zero saliency_th with img1=None is a ValueError), stage B those whose flow is further than pref_th px from the
+    Nadaraya-Watson estimate of their pref_nn nearest seeds (kernel coefficient k); 0 skips a stage.  The defaults are
+    EpicFlow's as recalled, not checked against the binary.  With aux=True returns (filtered, reason, saliency, estimate):
+    (H,W) uint8 0 no seed / 1 kept / 2 saliency / 3 consistency, (H,W) float32, (H,W,2) float32 [u^,v^].  The input is not
+    modified.  Runs on torch's current stream; the call synchronises that stream."""
+    if saliency_th is None:
+        saliency_th = PREFILTER_DEFAULTS["saliency_th"] if img1 is not None else 0.0
+    if img1 is None and saliency_th != 0:
+        raise ValueError("epic_prefilter: saliency_th=%g needs img1 (without an image only saliency_th = 0 runs)" % saliency_th)
+
+    def upload(a, name, dtype, shape):
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        if a.dtype != dtype or tuple(a.shape) != shape:
+            raise ValueError("epic_prefilter: %s must be %s %s, got %s %s" % (name, dtype, shape, tuple(a.shape), a.dtype))
+        return a.to(dev).contiguous()
+    if not hasattr(sparse, "shape") or len(sparse.shape) != 3 or sparse.shape[2] != 3:
+        raise ValueError("epic_prefilter: sparse must be (H,W,3) [U,V,valid]")
+    dev = sparse.device if isinstance(sparse, torch.Tensor) and sparse.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    H, W = int(sparse.shape[0]), int(sparse.shape[1])
+    sparse = upload(sparse, "sparse", torch.float32, (H, W, 3))
+    edges = upload(edges, "edges", torch.float32, (H, W))
+    if img1 is not None:
+        img1 = upload(img1, "img1", torch.uint8, (H, W, 3))
+    ws, ws_bytes = _lib.workspace("dflow_epic_prefilter_workspace_bytes", H, W, dev)
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    reason = saliency = estimate = None
+    if aux:
+        reason = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        saliency = torch.empty((H, W), dtype=torch.float32, device=dev)
+        estimate = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None else None
+    _lib.call("dflow_epic_prefilter", H, W, ptr(img1), sparse.data_ptr(), edges.data_ptr(), float(saliency_th), int(pref_nn),
+              float(pref_th), float(k), out.data_ptr(), ptr(reason), ptr(saliency), ptr(estimate), ws.data_ptr(), ws_bytes,
+              _lib.stream(dev))
+    return (out, reason, saliency, estimate) if aux else out
+
+
+def epic_prefilter_last_stats():
+    """({"seeds", "dropped_saliency", "dropped_consistency"}, {stage: ms}) of the last epic_prefilter on this thread."""
+    counts, ms = (C.c_int32 * 3)(), (C.c_float * 4)()
+    _lib.call("dflow_epic_prefilter_last_stats", counts, ms)
+    return (dict(zip(("seeds", "dropped_saliency", "dropped_consistency"), (int(v) for v in counts))),
+            dict(zip(("saliency", "graph", "consistency", "compact"), (float(v) for v in ms))))
+
+
 # The variational part of EpicFlow's presets, as its documentation gives them; recalled, not checked against the binary.
 VAR_PRESETS = {
     "sintel": dict(niter_outer=5, alpha=1.0, gamma=0.72, delta=0.0, sigma=1.1),

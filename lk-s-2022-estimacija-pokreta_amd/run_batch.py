@@ -11,7 +11,9 @@ for both directions, a .flo of the forward flow, sparse_field_<pair>.npy and par
 ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_ivice: the third EpicFlow input); with
 --epic also epic_<pair>.flo, the dense flow interpolated from the pair's sparse field and that edge map
 (pipeline.epic_interpolate, EpicFlow's defaults); with --epic-refine (implies --epic) that flow goes through the variational
-refinement with the pair's two images (pipeline.variational_refine, its defaults) before epic_<pair>.flo is written.
+refinement with the pair's two images (pipeline.variational_refine, its defaults) before epic_<pair>.flo is written; with
+--prefilter (implies --epic) the sparse field first goes through the match pre-filter with the pair's first image
+(pipeline.epic_prefilter, its defaults) before it is interpolated; sparse_field_<pair>.npy and parovi_<pair>.txt stay unfiltered.
 """
 import argparse
 import importlib
@@ -38,8 +40,9 @@ def main(argv=None):
     ap.add_argument("--edges", action="store_true", help="also write ivice_NN.bin (Canny edge map of each pair's first image)")
     ap.add_argument("--epic", action="store_true", help="also write epic_NN.flo (edge-aware interpolation of each pair's sparse field)")
     ap.add_argument("--epic-refine", action="store_true", help="--epic, and epic_NN.flo is the variationally refined flow")
+    ap.add_argument("--prefilter", action="store_true", help="--epic, and the sparse field goes through the match pre-filter first")
     a = ap.parse_args(argv)
-    a.epic = a.epic or a.epic_refine
+    a.epic = a.epic or a.epic_refine or a.prefilter
     import torch
     import torch.distributed as dist
     pipeline = importlib.import_module(PKG + ".pipeline")
@@ -130,6 +133,8 @@ def main(argv=None):
             if a.edges:
                 ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
             if a.epic:
+                if a.prefilter:
+                    sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, img1)
                 epic = pipeline.epic_interpolate(sparse_dev, ivice)
                 if a.epic_refine:
                     epic = pipeline.variational_refine(img1, img2, epic)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed [--gpu-epic [--refine]]
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed [--gpu-epic [--prefilter] [--refine]]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
@@ -11,7 +11,10 @@ runs if that binary exists; otherwise one line says the inputs are ready and the
 With the opt-in seventh token --gpu-epic, epic.flo is written by this package's own interpolation (epicflow.py,
 pipeline.epic_interpolate) from the device-side sparse field and edge map, with EpicFlow's defaults, and the binary is not
 run.  ivice.bin is handed over as the reference writes it, (255 - edges) / 255 (DESIGN.md "EpicFlow interpolation").
-With --refine as the eighth token, directly after --gpu-epic, the interpolated flow goes through this package's variational
+With --prefilter directly after --gpu-epic, the matches first go through this package's match pre-filter with img1
+(pipeline.epic_prefilter, its defaults; DESIGN.md "Match pre-filter"): the first thing epicflow-static does.  Only what the
+interpolation reads is filtered: sparse_field.npy and parovi.txt are written unfiltered, as the reference writes them.
+With --refine as the last token, after --gpu-epic [--prefilter], the interpolated flow goes through this package's variational
 refinement with img1 and img2 (pipeline.variational_refine, its defaults; DESIGN.md "Variational refinement") before epic.flo
 is written: the second thing epicflow-static does.
 """
@@ -30,8 +33,10 @@ EPICFLOW = "../discrete_flow/external/EpicFlow_v1.00/epicflow-static"     # spre
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    refine = len(argv) == 8 and argv[6:] == ["--gpu-epic", "--refine"]
-    gpu_epic = refine or (len(argv) == 7 and argv[6] == "--gpu-epic")
+    tail = argv[6:]
+    gpu_epic = tail in (["--gpu-epic"], ["--gpu-epic", "--prefilter"], ["--gpu-epic", "--refine"],
+                        ["--gpu-epic", "--prefilter", "--refine"])
+    prefilter, refine = gpu_epic and "--prefilter" in tail, gpu_epic and "--refine" in tail
     if len(argv) != 6 and not gpu_epic:
         print(__doc__, file=sys.stderr)
         return 2
@@ -61,13 +66,15 @@ def main(argv=None):
         ivice = edge.canny_ivice_tensor(kitti1)
         with open("ivice.bin", "wb") as f:
             f.write(ivice.cpu().numpy().tobytes())
+        read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+        if prefilter:
+            sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, read_bgr(kitti1))
         flow = pipeline.epic_interpolate(sparse_dev, ivice)                # the step epicflow-static would take
         if refine:
-            read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
             flow = pipeline.variational_refine(read_bgr(kitti1), read_bgr(kitti2), flow)
         importlib.import_module(PKG + ".flowio").write_flo("epic.flo", flow.cpu().numpy())
-        print("spremiZaEpic: sparse_field.npy, parovi.txt, ivice.bin and epic.flo written (GPU interpolation%s)"
-              % (" + variational refinement" if refine else ""))
+        print("spremiZaEpic: sparse_field.npy, parovi.txt, ivice.bin and epic.flo written (%sGPU interpolation%s)"
+              % ("match pre-filter + " if prefilter else "", " + variational refinement" if refine else ""))
         return 0
     edge.canny_ivice(kitti1, "ivice.bin")                                  # :19-23
     if not os.path.exists(EPICFLOW):
