@@ -203,6 +203,34 @@ size_t dflow_canny_workspace_bytes(int32_t h, int32_t w);
 int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, double high, uint8_t *d_edges, float *d_ivice,
                       void *d_ws, size_t ws_bytes, void *stream);
 
+/* Soft edge strength without a trained model: a Pb-style oriented half-disc histogram gradient (Martin, Fowlkes, Malik, PAMI
+ * 2004: brightness and colour gradient as the chi^2 distance between the histograms of the two halves of a disc).  This
+ * build's own definition (DESIGN.md "Pb edge strength"), not bit-matched to any binary; it stands in for the reference's
+ * structured edge detector (sed_ivice, edge.py:4-17), whose trained model the reference does not ship.
+ * d_bgr (h,w,3) uint8 BGR, 1 <= h, w <= 8192; 1 <= radius R <= DFLOW_PB_MAX_RADIUS.
+ * 1. Channels, integers in 0..255, per pixel: c0 = the fixed-point BGR2GRAY of the Canny entry, (1868 B + 9617 G + 4899 R +
+ *    8192) >> 14; c1 = (R - G + 255) >> 1; c2 = (2 B - R - G + 510) >> 2.  Bin = c >> 4: 16 bins.
+ * 2. Disc: the offsets (dx,dy) with 0 < dx^2 + dy^2 <= R^2; a pixel outside the frame is read at the clamped coordinate
+ *    (replicate border).
+ * 3. Orientations o = 0..7 have the integer normals (nx,ny) = (1,0), (2,1), (1,1), (1,2), (0,1), (-1,2), (-1,1), (-2,1).  An
+ *    offset is on side A of o when dx nx + dy ny > 0, on side B when it is < 0, on neither side when it is 0.  The disc is
+ *    point-symmetric: both sides hold the same number N_o(R) of offsets.
+ * 4. For channel c and orientation o, with G_b, H_b the integer counts of bin b on side A and side B,
+ *    chi_{c,o} = (sum over b = 0..15 with G_b + H_b > 0 of (G_b - H_b)^2 / (G_b + H_b)) / (2 N_o), in [0,1]: the sum in
+ *    ascending b in float32, every numerator and denominator converted exactly from an integer, one IEEE operation per
+ *    written operation.
+ * 5. m_o = (2 chi_{0,o} + chi_{1,o} + chi_{2,o}) / 4, in that order in float32; e = max over o of m_o.  No non-maximum
+ *    suppression and no gain: a constant image gives exactly 0.0 everywhere.
+ * d_strength (h,w) float32 e (required); d_orient_strength (h,w,8) float32 m_o (optional, NULL to skip; e is the same
+ * either way).  A size or radius outside its range or a NULL required pointer returns DFLOW_EINVAL, a NULL or too small
+ * workspace DFLOW_ENOSPC, both before anything is launched.  The call is asynchronous on `stream`, allocates nothing, reads
+ * nothing back and can be captured into a graph.  The workspace is 2 bytes per pixel; dflow_pb_workspace_bytes returns 0
+ * (and sets dflow_last_error) for sizes outside the range. */
+#define DFLOW_PB_MAX_RADIUS 7
+size_t dflow_pb_workspace_bytes(int32_t h, int32_t w);
+int dflow_pb_edges(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t radius, float *d_strength, float *d_orient_strength,
+                   void *d_ws, size_t ws_bytes, void *stream);
+
 /* Edge-aware interpolation of a sparse flow field: EpicFlow's sparse-to-dense step (Revaud et al., CVPR 2015), with integer
  * geodesics so that the result is unique (DESIGN.md "EpicFlow interpolation").  1 <= h, w <= 8192.
  * d_sparse (h,w,3) float32 [U,V,valid] (what dflow_fb_consistency writes): a seed is a pixel with valid > 0.5 and finite U,

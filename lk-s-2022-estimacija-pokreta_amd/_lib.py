@@ -58,6 +58,8 @@ _SIGNATURES = {
     "dflow_remove_small_segments_host": (C.c_int, [_vp, _i32, _i32, _f32, _i32]),
     "dflow_canny_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_canny_edges": (C.c_int, [_i32, _i32, _vp, _f64, _f64, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_pb_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_pb_edges": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "dflow_epic_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_epic_interpolate": (C.c_int, [_i32, _i32, _vp, _vp, _i32, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_epic_last_stats": (C.c_int, [_vp, _vp]),

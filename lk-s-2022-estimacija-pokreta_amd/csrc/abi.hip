@@ -261,6 +261,22 @@ int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, do
     return launch_canny(h, w, d_bgr, lo, hi, d_edges, d_ivice, d_ws, (hipStream_t)stream);
 }
 
+size_t dflow_pb_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return pb_ws_bytes(h, w);
+}
+
+int dflow_pb_edges(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t radius, float *d_strength, float *d_orient_strength,
+                   void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (radius < 1 || radius > DFLOW_PB_MAX_RADIUS)
+        return dflow_set_error(DFLOW_EINVAL, "%s: radius=%d outside [1,%d]", __func__, radius, DFLOW_PB_MAX_RADIUS);
+    CHECK_PTR(d_bgr); CHECK_PTR(d_strength); CHECK_WS(pb_ws_bytes(h, w));
+    return launch_pb(h, w, d_bgr, radius, d_strength, d_orient_strength, d_ws, (hipStream_t)stream);
+}
+
 size_t dflow_epic_workspace_bytes(int32_t h, int32_t w)
 {
     if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;

@@ -248,6 +248,9 @@ int launch_fb_consistency(const dflow_params *p, const float *fwd, const float *
 // edges.hip: Canny edge map of a (H,W,3) BGR image; thresholds already swapped and floored
 size_t canny_ws_bytes(int H, int W);
 int launch_canny(int H, int W, const uint8_t *bgr, int lo, int hi, uint8_t *edges, float *ivice, void *ws, hipStream_t s);
+// pb_edges.hip: Pb-style soft edge strength of a (H,W,3) BGR image (arguments validated by the caller); orient may be NULL
+size_t pb_ws_bytes(int H, int W);
+int launch_pb(int H, int W, const uint8_t *bgr, int radius, float *strength, float *orient, void *ws, hipStream_t s);
 // epic.hip: edge-aware interpolation of a sparse flow field (arguments validated by the caller)
 size_t epic_ws_bytes(int H, int W);
 int launch_epic(int H, int W, const float *sparse, const float *edges, int nn, double k, int method, float *flow,

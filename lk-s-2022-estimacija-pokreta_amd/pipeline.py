@@ -287,6 +287,28 @@ def canny_edges(bgr, low=100, high=200, ivice=True):
     return edges, iv
 
 
+def pb_edges(bgr, radius=5, per_orientation=False):
+    """Soft edge strength without a trained model (dflow_pb_edges, DESIGN.md "Pb edge strength"): a Pb-style oriented half-disc
+    histogram gradient of a (H,W,3) uint8 BGR image (numpy array or tensor; a host image is uploaded to the current device)
+    with disc radius 1..7 -> the (H,W) float32 device tensor e in [0,1], the edge strength dflow_epic_interpolate and
+    dflow_epic_prefilter are defined on; with per_orientation=True (e, m): m the (H,W,8) float32 responses of the 8
+    orientations, e their maximum.  Runs on torch's current stream and does not wait for it."""
+    if not isinstance(bgr, torch.Tensor):
+        bgr = torch.from_numpy(np.ascontiguousarray(bgr))
+    if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
+        raise ValueError("pb_edges wants a (H,W,3) uint8 BGR image, got %s %s" % (tuple(bgr.shape), bgr.dtype))
+    if not bgr.is_cuda:
+        bgr = bgr.to(torch.device("cuda", torch.cuda.current_device()))
+    bgr = bgr.contiguous()
+    H, W, _ = bgr.shape
+    ws, ws_bytes = _lib.workspace("dflow_pb_workspace_bytes", H, W, bgr.device)
+    e = torch.empty((H, W), dtype=torch.float32, device=bgr.device)
+    m = torch.empty((H, W, 8), dtype=torch.float32, device=bgr.device) if per_orientation else None
+    _lib.call("dflow_pb_edges", H, W, bgr.data_ptr(), int(radius), e.data_ptr(), m.data_ptr() if m is not None else None,
+              ws.data_ptr(), ws_bytes, _lib.stream(bgr.device))
+    return (e, m) if per_orientation else e
+
+
 EPIC_METHODS = {"LA": 0, "NW": 1}     # DFLOW_EPIC_LA, DFLOW_EPIC_NW
 
 

@@ -14,6 +14,9 @@ ivice_<pair>.bin, the Canny edge map of the pair's first image (edge.py canny_iv
 refinement with the pair's two images (pipeline.variational_refine, its defaults) before epic_<pair>.flo is written; with
 --prefilter (implies --epic) the sparse field first goes through the match pre-filter with the pair's first image
 (pipeline.epic_prefilter, its defaults) before it is interpolated; sparse_field_<pair>.npy and parovi_<pair>.txt stay unfiltered.
+--edge-kind pb takes the edges of all of these from the soft detector instead of Canny (pipeline.pb_edges, radius 5; DESIGN.md
+"Pb edge strength"), with spremiZaEpic.py's conventions: ivice_<pair>.bin holds 1 - e, the pre-filter and the interpolation
+receive the strength e itself.  Without it (canny, the default) nothing changes.
 """
 import argparse
 import importlib
@@ -26,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--pairs", type=int, default=1)
     ap.add_argument("--bcd-times", type=int, default=4)
@@ -41,7 +44,13 @@ def main(argv=None):
     ap.add_argument("--epic", action="store_true", help="also write epic_NN.flo (edge-aware interpolation of each pair's sparse field)")
     ap.add_argument("--epic-refine", action="store_true", help="--epic, and epic_NN.flo is the variationally refined flow")
     ap.add_argument("--prefilter", action="store_true", help="--epic, and the sparse field goes through the match pre-filter first")
-    a = ap.parse_args(argv)
+    ap.add_argument("--edge-kind", choices=("canny", "pb"), default="canny",
+                    help="edge source of --edges, --epic, --epic-refine and --prefilter: Canny, or the soft Pb-style strength")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     a.epic = a.epic or a.epic_refine or a.prefilter
     import torch
     import torch.distributed as dist
@@ -129,8 +138,13 @@ def main(argv=None):
             evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
             if a.edges or a.epic:
                 img1, img2 = images[pair] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[:2]
-                _, ivice = pipeline.canny_edges(img1)
-            if a.edges:
+                if a.edge_kind == "pb":
+                    ivice = pipeline.pb_edges(img1)               # e itself for the GPU steps, 1 - e in the file
+                else:
+                    _, ivice = pipeline.canny_edges(img1)
+            if a.edges and a.edge_kind == "pb":
+                importlib.import_module(PKG + ".edge").write_pb_ivice(ivice, os.path.join(a.out, "ivice_%02d.bin" % pair))
+            elif a.edges:
                 ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
             if a.epic:
                 if a.prefilter:

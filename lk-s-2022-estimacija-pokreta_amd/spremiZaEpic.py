@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed [--gpu-epic [--prefilter] [--refine]]
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--gpu-epic [--prefilter] [--refine]]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
 dflow_canny_edges).  Then ../discrete_flow/external/EpicFlow_v1.00/epicflow-static img1 img2 ivice.bin parovi.txt epic.flo
 runs if that binary exists; otherwise one line says the inputs are ready and the binary is absent, and the exit status is 0.
 'sed' edges need a model the reference does not ship: it exits with status 2 and says so.
+'pb' (not in the reference) is the model-free substitute for 'sed': ivice.bin is 1 - e as raw float32, e the soft edge strength
+of dflow_pb_edges on img1 (edge.pb_ivice, radius 5; DESIGN.md "Pb edge strength"): sed_ivice's file convention, so
+epicflow-static reads it as it would read the sed file.  With --gpu-epic [--prefilter] [--refine] the pre-filter and the
+interpolation receive e ITSELF, not 1 - e: edge strength is what the C-ABI defines d_edges to be.
 With the opt-in seventh token --gpu-epic, epic.flo is written by this package's own interpolation (epicflow.py,
 pipeline.epic_interpolate) from the device-side sparse field and edge map, with EpicFlow's defaults, and the binary is not
 run.  ivice.bin is handed over as the reference writes it, (255 - edges) / 255 (DESIGN.md "EpicFlow interpolation").
@@ -31,8 +35,11 @@ PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 EPICFLOW = "../discrete_flow/external/EpicFlow_v1.00/epicflow-static"     # spremiZaEpic.py:28
 
 
-def main(argv=None):
-    argv = sys.argv[1:] if argv is None else list(argv)
+EDGE_KINDS = ("canny", "sed", "pb")
+
+
+def parse(argv):
+    """The command line -> (the six positional tokens, gpu_epic, prefilter, refine), or the exit status 2 after saying why."""
     tail = argv[6:]
     gpu_epic = tail in (["--gpu-epic"], ["--gpu-epic", "--prefilter"], ["--gpu-epic", "--refine"],
                         ["--gpu-epic", "--prefilter", "--refine"])
@@ -40,11 +47,19 @@ def main(argv=None):
     if len(argv) != 6 and not gpu_epic:
         print(__doc__, file=sys.stderr)
         return 2
-    kitti1, kitti2, foward, backward, tresh, kind = argv[:6]
-    con_tresh = int(tresh)                                                 # :14
-    if kind not in ("canny", "sed"):
-        print("spremiZaEpic: edge kind must be 'canny' or 'sed', not %r" % kind, file=sys.stderr)
+    int(argv[4])                                                           # :14
+    if argv[5] not in EDGE_KINDS:
+        print("spremiZaEpic: edge kind must be 'canny' or 'sed', not %r" % argv[5], file=sys.stderr)
         return 2
+    return argv[:6], gpu_epic, prefilter, refine
+
+
+def main(argv=None):
+    parsed = parse(sys.argv[1:] if argv is None else list(argv))
+    if parsed == 2:
+        return 2
+    (kitti1, kitti2, foward, backward, tresh, kind), gpu_epic, prefilter, refine = parsed
+    con_tresh = int(tresh)                                                 # :14
     edge = importlib.import_module(PKG + ".edge")
     if kind == "sed":
         try:
@@ -63,9 +78,13 @@ def main(argv=None):
     np.save("sparse_field.npy", sparse)
     evaluate.parovi(sparse, "parovi.txt")                                  # :17
     if gpu_epic:
-        ivice = edge.canny_ivice_tensor(kitti1)
-        with open("ivice.bin", "wb") as f:
-            f.write(ivice.cpu().numpy().tobytes())
+        if kind == "pb":
+            ivice = edge.pb_strength_tensor(kitti1)                        # e itself for the GPU steps, 1 - e in the file
+            edge.write_pb_ivice(ivice, "ivice.bin")
+        else:
+            ivice = edge.canny_ivice_tensor(kitti1)
+            with open("ivice.bin", "wb") as f:
+                f.write(ivice.cpu().numpy().tobytes())
         read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
         if prefilter:
             sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, read_bgr(kitti1))
@@ -76,7 +95,10 @@ def main(argv=None):
         print("spremiZaEpic: sparse_field.npy, parovi.txt, ivice.bin and epic.flo written (%sGPU interpolation%s)"
               % ("match pre-filter + " if prefilter else "", " + variational refinement" if refine else ""))
         return 0
-    edge.canny_ivice(kitti1, "ivice.bin")                                  # :19-23
+    if kind == "pb":
+        edge.pb_ivice(kitti1, "ivice.bin")
+    else:
+        edge.canny_ivice(kitti1, "ivice.bin")                              # :19-23
     if not os.path.exists(EPICFLOW):
         print("spremiZaEpic: sparse_field.npy, parovi.txt and ivice.bin are ready; %s is absent, EpicFlow not run" % EPICFLOW)
         return 0
