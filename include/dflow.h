@@ -318,6 +318,51 @@ size_t dflow_var_workspace_bytes(int32_t h, int32_t w);
 int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow_in,
                      const dflow_var_params *p, float *d_flow_out, void *d_ws, size_t ws_bytes, void *stream);
 
+/* Flow evaluation: how far a flow field is from the ground truth, after errorImage of the reference's visualization.py:128-156
+ * (mean end-point error, percentage of outliers, colour error picture).  This build's definition (DESIGN.md "Flow
+ * evaluation").  1 <= h, w <= 8192; the planes are walked as h*w pixels in row-major order.
+ * d_gt (h,w,3) float32 [U,V,valid].  d_test, by test_layout: DFLOW_EVAL_UVV (h,w,3) float32 [U,V,valid], what
+ * dflow_fb_consistency writes and the KITTI reader gives; DFLOW_EVAL_DYDX (h,w,2) float32 [dy,dx] (U = dx, V = dy), every pixel
+ * valid: what the dense stages write.  d_test, d_gt and d_err must be 16-byte aligned, d_stats 8-byte, d_err_bgr 4-byte.
+ * Which pixels count: a pixel is COMPARED when gt.valid > 0.5 and test.valid > 0.5 (a NaN valid compares false).  n_gt_valid
+ * and n_test_valid count the two masks on their own (n_test_valid = h*w under DFLOW_EVAL_DYDX).
+ * Per compared pixel, in float32, one correctly rounded IEEE operation per written operation (no fused multiply-add):
+ *     dfu = tU - gU, dfv = tV - gV, err = sqrt(dfu*dfu + dfv*dfv)
+ * the bits numpy gives.  If err is not finite (NaN or Inf) the pixel adds 1 to n_nonfinite and to nothing else.  Otherwise it
+ * adds 1 to n, err (widened to double) to sum_err, and max_err = max(max_err, err); 1 to n_out_abs when err > abs_thresh
+ * (the reference: 3); 1 to n_out_kitti when err > 3 and err > 0.05f * sqrt(gU*gU + gV*gV) in float32: KITTI's 3 px / 5 % rule.
+ * Mean end-point error = sum_err / n; the reference's outlier percentage = n_out_abs * 100 / n.
+ * Optional outputs (NULL to skip):
+ *   d_err (h,w) float32: err at compared pixels, whatever it is (a NaN as the quiet NaN 0x7FC00000, an infinity as +Inf);
+ *     -1 at all others.
+ *   d_err_bgr (h,w,3) uint8: the reference's error picture in the channel order it hands to imwrite.  At a pixel counted in
+ *     n: t = min(err, 3) / 3, idx = min(255, (int)(t * 256)), both float32, and the bytes are (b, g, r) of LUT[idx], LUT being
+ *     matplotlib's 256-entry 'jet' as uint8(value * 255) (csrc/jet_lut.h: jet's segment data interpolated linearly at
+ *     linspace(0,1,256) in float64; the entry matplotlib's cmap(t) picks for a float32 t).  (0,0,0) at every other pixel, the
+ *     non-finite ones included.
+ * Statistics: the counts and max_err are exact and independent of any order.  sum_err is a sum of float32 values in double in
+ * a fixed order (per lane, a fixed tree per block, the blocks' partial sums in block order in a second launch; no floating
+ * atomics): the same inputs give the same 8 bytes on every call.  Without DFLOW_EVAL_FLAG_ACCUMULATE *d_stats is
+ * overwritten (max_err = 0 when n = 0); with it the call's values are added to what *d_stats holds (max_err by max, sum_err
+ * as old + this call's sum), so a batch totals its pairs on the device and reads back once; the caller zeroes it first.
+ * An unknown flag bit or layout, an abs_thresh that is not finite or is negative, a NULL or misaligned d_test, d_gt or
+ * d_stats, a misaligned optional output or a size out of range returns DFLOW_EINVAL, a NULL or too small workspace
+ * DFLOW_ENOSPC, both before anything is launched.  The call is asynchronous on `stream`, allocates nothing, reads nothing
+ * back and can be captured into a graph.  The workspace holds one partial result per block of the first launch, a fixed
+ * function of h*w; dflow_eval_workspace_bytes returns 0 (and sets dflow_last_error) for sizes outside the range. */
+#define DFLOW_EVAL_UVV  0
+#define DFLOW_EVAL_DYDX 1
+#define DFLOW_EVAL_FLAG_ACCUMULATE 1u
+typedef struct dflow_eval_stats {
+    uint64_t n, n_out_abs, n_out_kitti, n_nonfinite, n_gt_valid, n_test_valid;
+    double sum_err;
+    float max_err; uint32_t reserved;
+} dflow_eval_stats;
+size_t dflow_eval_workspace_bytes(int32_t h, int32_t w);
+int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layout, const float *d_gt, float abs_thresh,
+                    uint32_t flags, dflow_eval_stats *d_stats, float *d_err, uint8_t *d_err_bgr,
+                    void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ FLAG_KNN_EXACT = 1      # DFLOW_FLAG_KNN_EXACT
 FLAG_DESCR_F16 = 8      # DFLOW_FLAG_DESCR_F16
 DESC_PITCH_F16 = 72     # DFLOW_DESC_PITCH_F16: binary16 descriptor planes are (H,W,72)
 VAR_FLAG_SOR_UNFUSED = 1    # DFLOW_VAR_FLAG_SOR_UNFUSED
+EVAL_UVV, EVAL_DYDX = 0, 1  # DFLOW_EVAL_UVV, DFLOW_EVAL_DYDX: the test field's layout in dflow_flow_eval
+EVAL_FLAG_ACCUMULATE = 1    # DFLOW_EVAL_FLAG_ACCUMULATE
 
 
 class DflowError(RuntimeError):
@@ -31,6 +33,13 @@ class VarParams(C.Structure):
     _fields_ = [("alpha", C.c_float), ("gamma", C.c_float), ("delta", C.c_float), ("sigma", C.c_float),
                 ("sor_omega", C.c_float), ("niter_outer", C.c_int32), ("niter_inner", C.c_int32),
                 ("niter_solver", C.c_int32), ("flags", C.c_uint32)]
+
+
+class EvalStats(C.Structure):
+    """struct dflow_eval_stats (include/dflow.h): what dflow_flow_eval leaves in device memory."""
+    _fields_ = [("n", C.c_uint64), ("n_out_abs", C.c_uint64), ("n_out_kitti", C.c_uint64), ("n_nonfinite", C.c_uint64),
+                ("n_gt_valid", C.c_uint64), ("n_test_valid", C.c_uint64), ("sum_err", C.c_double), ("max_err", C.c_float),
+                ("reserved", C.c_uint32)]
 
 
 _vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
@@ -69,6 +78,8 @@ _SIGNATURES = {
     "dflow_var_default_params": (None, [C.POINTER(VarParams)]),
     "dflow_var_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_var_refine": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.POINTER(VarParams), _vp, _vp, _sz, _vp]),
+    "dflow_eval_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_flow_eval": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

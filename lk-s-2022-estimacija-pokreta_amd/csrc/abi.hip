@@ -364,6 +364,33 @@ int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t 
     return launch_var(h, w, d_bgr1, d_bgr2, d_flow_in, p, d_flow_out, d_ws, (hipStream_t)stream);
 }
 
+size_t dflow_eval_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return eval_ws_bytes(h, w);
+}
+
+int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layout, const float *d_gt, float abs_thresh,
+                    uint32_t flags, dflow_eval_stats *d_stats, float *d_err, uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes,
+                    void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (test_layout != DFLOW_EVAL_UVV && test_layout != DFLOW_EVAL_DYDX)
+        return dflow_set_error(DFLOW_EINVAL, "%s: unknown test_layout %d", __func__, test_layout);
+    if (!isfinite(abs_thresh) || abs_thresh < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: abs_thresh=%g must be finite and >= 0", __func__, (double)abs_thresh);
+    if (flags & ~DFLOW_EVAL_FLAG_ACCUMULATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    CHECK_PTR(d_test); CHECK_PTR(d_gt); CHECK_PTR(d_stats);
+    // the kernel moves four pixels per lane with 16-byte loads and stores
+    const struct { const char *name; const void *p; uintptr_t align; } ptrs[] = {
+        {"d_test", d_test, 16}, {"d_gt", d_gt, 16}, {"d_stats", d_stats, 8}, {"d_err", d_err, 16}, {"d_err_bgr", d_err_bgr, 4}};
+    for (const auto &q : ptrs)
+        if ((uintptr_t)q.p % q.align)
+            return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", __func__, q.name, (int)q.align);
+    CHECK_WS(eval_ws_bytes(h, w));
+    return launch_flow_eval(h, w, d_test, test_layout, d_gt, abs_thresh, flags, d_stats, d_err, d_err_bgr, d_ws, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -272,3 +272,8 @@ int launch_epic_prefilter(int H, int W, const uint8_t *bgr, const float *sparse_
                           int pref_nn, double pref_th, double k, float *sparse_out, uint8_t *reason, float *saliency,
                           float *estimate, void *ws, hipStream_t s);
 int epic_prefilter_last_stats(int32_t *counts, float *stage_ms);
+// flow_eval.hip: error statistics, error plane and error picture of a flow against the ground truth (arguments validated by
+// the caller); err and bgr may be NULL
+size_t eval_ws_bytes(int H, int W);
+int launch_flow_eval(int H, int W, const float *test, int layout, const float *gt, float abs_thresh, uint32_t flags,
+                     dflow_eval_stats *stats, float *err, uint8_t *bgr, void *ws, hipStream_t s);

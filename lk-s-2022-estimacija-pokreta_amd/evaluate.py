@@ -1,5 +1,6 @@
 """Consumers on the far side of the hot path, host side: the EpicFlow match exporter of
 napravi_parove.py and the error metrics of visualization.py.  Plain numpy on small (H,W,3) fields; not on the hot path.
+error_metrics_gpu is the same measure through the GPU evaluation stage (dflow_flow_eval).
 """
 import numpy as np
 
@@ -42,6 +43,16 @@ def error_metrics(test_uvv, gt_uvv, abs_thresh=3.0):
     mean_epe = float(np.average(err)) if n else float("nan")
     outliers = float((err > abs_thresh).sum() * 100 / n) if n else float("nan")
     return mean_epe, outliers, n
+
+
+def error_metrics_gpu(test_uvv, gt_uvv, abs_thresh=3.0):
+    """error_metrics through dflow_flow_eval (pipeline.flow_eval): the same (mean_epe, outliers, n) from one kernel pass and
+    one 64-byte read-back.  n and the outlier percentage are error_metrics' own; the mean is the double sum of the float32
+    errors over n, where numpy averages in float32 pairwise, so the two means may differ in the last float32 digits.  Pixels
+    whose error is not finite are left out of all three (error_metrics lets them poison the mean)."""
+    from . import pipeline
+    st = pipeline.eval_stats(pipeline.flow_eval(test_uvv, gt_uvv, abs_thresh))
+    return st["mean_epe"], float(st["outliers_pct"]), st["n"]
 
 
 def ucitajFlow(path):

@@ -138,6 +138,25 @@ def write_png16(path, rgb16):
                 + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def write_png8(path, bgr):
+    """(H,W,3) uint8 in B,G,R order (what cv2.imwrite takes) -> 8-bit truecolour PNG (R,G,B on disk, filter type 0 on every
+    line)."""
+    import struct
+    import zlib
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3:
+        raise ValueError("write_png8 wants a (H,W,3) uint8 image, got %s %s" % (bgr.shape, bgr.dtype))
+    h, w, _ = bgr.shape
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)               # a filter byte, then the line
+    rows[:, 1:] = bgr[..., ::-1].reshape(h, 3 * w)
+
+    def chunk(typ, body):
+        return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(typ + body) & 0xFFFFFFFF)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
 def read_kitti_flow_png(path):
     """FlowImage.readFlowFieldFromImage, visualization.py:37-53: (H,W,3) float32 [U,V,valid]."""
     img = read_png16(path).astype(np.float64)

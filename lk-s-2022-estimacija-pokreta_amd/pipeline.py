@@ -467,3 +467,59 @@ def epic_last_stats():
     rounds, ms = C.c_int32(0), (C.c_float * 4)()
     _lib.call("dflow_epic_last_stats", C.byref(rounds), ms)
     return rounds.value, dict(zip(("voronoi", "graph", "lists", "fill"), (float(v) for v in ms)))
+
+
+EVAL_COUNTS = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_test_valid")
+
+
+def flow_eval(test, gt, abs_thresh=3.0, err=False, image=False, stats=None):
+    """errorImage, visualization.py:128-156, on the GPU (dflow_flow_eval, DESIGN.md "Flow evaluation"): the end-point error
+    of `test` against the ground truth `gt`, (H,W,3) float32 [U,V,valid].  test is (H,W,3) float32 [U,V,valid] (what
+    fb_consistency and evaluate.ucitajFlow give) or (H,W,2) float32 [dy,dx] with every pixel valid (what the dense stages
+    write); the last dimension says which.  Device tensors or host arrays; host data is uploaded to the current device.
+    Returns the statistics as a device tensor (struct dflow_eval_stats as 8 int64 words; eval_stats reads it back), then, if
+    asked for, err: (H,W) float32, the error at the compared pixels and -1 elsewhere, and image: (H,W,3) uint8, the reference's
+    colour picture in BGR order.  stats: the tensor of an earlier call (or torch.zeros(8, int64)) to add this field's values
+    to, so that a batch is totalled on the device.  Runs on torch's current stream and does not wait for it."""
+    def tensor(a):
+        return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    test, gt = tensor(test), tensor(gt)
+    if gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[2] != 3:
+        raise ValueError("flow_eval: gt must be (H,W,3) float32 [U,V,valid], got %s %s" % (tuple(gt.shape), gt.dtype))
+    H, W = int(gt.shape[0]), int(gt.shape[1])
+    if test.dtype != torch.float32 or test.dim() != 3 or tuple(test.shape[:2]) != (H, W) or test.shape[2] not in (2, 3):
+        raise ValueError("flow_eval: test must be float32 (%d,%d,3) [U,V,valid] or (%d,%d,2) [dy,dx], got %s %s"
+                         % (H, W, H, W, tuple(test.shape), test.dtype))
+    dev = next((t.device for t in (test, gt) if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    test, gt = test.to(dev).contiguous(), gt.to(dev).contiguous()
+    flags = 0
+    if stats is None:
+        stats = torch.empty(8, dtype=torch.int64, device=dev)
+    else:
+        if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and stats.numel() == 8 and stats.is_contiguous()
+                and stats.device == dev):
+            raise ValueError("flow_eval: stats must be the int64[8] tensor of an earlier call on %s" % dev)
+        flags = _lib.EVAL_FLAG_ACCUMULATE
+    ws, ws_bytes = _lib.workspace("dflow_eval_workspace_bytes", H, W, dev)
+    e = torch.empty((H, W), dtype=torch.float32, device=dev) if err else None
+    img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if image else None
+    _lib.call("dflow_flow_eval", H, W, test.data_ptr(), _lib.EVAL_UVV if test.shape[2] == 3 else _lib.EVAL_DYDX, gt.data_ptr(),
+              float(abs_thresh), flags, stats.data_ptr(), e.data_ptr() if err else None, img.data_ptr() if image else None,
+              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    out = (stats,) + ((e,) if err else ()) + ((img,) if image else ())
+    return out if len(out) > 1 else stats
+
+
+def eval_stats(t):
+    """The one read-back of flow_eval: its statistics tensor -> a dict of struct dflow_eval_stats's fields plus mean_epe
+    = sum_err / n, outliers_pct = n_out_abs * 100 / n (the reference's two numbers) and kitti_fl_pct = n_out_kitti * 100 / n;
+    the three are NaN when n == 0."""
+    s = _lib.EvalStats.from_buffer_copy(t.cpu().numpy().tobytes())
+    d = {k: int(getattr(s, k)) for k in EVAL_COUNTS}
+    d["sum_err"], d["max_err"] = float(s.sum_err), float(s.max_err)
+    n = d["n"]
+    nan = float("nan")
+    d["mean_epe"] = d["sum_err"] / n if n else nan
+    d["outliers_pct"] = d["n_out_abs"] * 100 / n if n else nan
+    d["kitti_fl_pct"] = d["n_out_kitti"] * 100 / n if n else nan
+    return d

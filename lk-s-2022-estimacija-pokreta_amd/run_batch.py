@@ -17,6 +17,10 @@ refinement with the pair's two images (pipeline.variational_refine, its defaults
 --edge-kind pb takes the edges of all of these from the soft detector instead of Canny (pipeline.pb_edges, radius 5; DESIGN.md
 "Pb edge strength"), with spremiZaEpic.py's conventions: ivice_<pair>.bin holds 1 - e, the pre-filter and the interpolation
 receive the strength e itself.  Without it (canny, the default) nothing changes.
+--eval compares every pair's fields with the true flow synth.make_pair returns (pipeline.flow_eval, DESIGN.md "Flow
+evaluation"): the forward flow ("fwd"), the sparse field ("sparse": the pixels that survive the consistency check) and, with
+--epic, the final dense flow ("epic"), each on the device where it lies.  One line per pair is printed, and eval.json in DIR
+holds the per-pair rows and, per kind, the totals accumulated on the device.  Without it output and files are unchanged.
 """
 import argparse
 import importlib
@@ -46,7 +50,18 @@ def parser():
     ap.add_argument("--prefilter", action="store_true", help="--epic, and the sparse field goes through the match pre-filter first")
     ap.add_argument("--edge-kind", choices=("canny", "pb"), default="canny",
                     help="edge source of --edges, --epic, --epic-refine and --prefilter: Canny, or the soft Pb-style strength")
+    ap.add_argument("--eval", action="store_true",
+                    help="compare each pair's forward, sparse and (with --epic) final flow with the true flow; writes eval.json")
     return ap
+
+
+EVAL_ROW = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_test_valid", "sum_err", "max_err", "mean_epe",
+            "outliers_pct", "kitti_fl_pct")
+
+
+def eval_row(st):
+    """pipeline.eval_stats' dict as a JSON object: the fields of EVAL_ROW, a NaN (nothing compared) as null."""
+    return {k: (None if st[k] != st[k] else st[k]) for k in EVAL_ROW}
 
 
 def main(argv=None):
@@ -127,9 +142,11 @@ def main(argv=None):
                   % (len(passes), a.pairs, W, H, a.bcd_times, world, dt * 1e3, dt * 1e3 / len(passes), len(passes) * H * W / dt / 1e6))
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
+        eval_rows, eval_totals = [], {}
         for pair in range(a.pairs):
             fwd, bwd = flows[2 * pair], flows[2 * pair + 1]
             sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
+            sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
             sparse = sparse_dev.cpu().numpy()
             for backward, f in ((0, fwd), (1, bwd)):
                 np.save(os.path.join(a.out, flowio.flow_name(pair, backward, a.bcd_times)), f.cpu().numpy().astype(np.float64))
@@ -154,6 +171,26 @@ def main(argv=None):
                     epic = pipeline.variational_refine(img1, img2, epic)
                 flowio.write_flo(os.path.join(a.out, "epic_%02d.flo" % pair), epic.cpu().numpy())
             print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
+            if a.eval:
+                gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]
+                gt = torch.from_numpy(evaluate.to_uv_valid(gt) if gt.shape[2] == 2 else np.asarray(gt, np.float32)).to(dev)
+                fields = [("fwd", fwd), ("sparse", sparse_raw)] + ([("epic", epic)] if a.epic else [])
+                row, line = {"pair": pair}, []
+                for kind, field in fields:
+                    if kind not in eval_totals:
+                        eval_totals[kind] = torch.zeros(8, dtype=torch.int64, device=dev)
+                    st = pipeline.eval_stats(pipeline.flow_eval(field, gt))        # the pair's own row
+                    pipeline.flow_eval(field, gt, stats=eval_totals[kind])         # and into the kind's total, on the device
+                    row[kind] = eval_row(st)
+                    line.append("%s EPE %.3f px, %.2f%% > 3 px, Fl %.2f%% over %d px"
+                                % (kind, st["mean_epe"], st["outliers_pct"], st["kitti_fl_pct"], st["n"]))
+                eval_rows.append(row)
+                print("pair %d: %s" % (pair, "; ".join(line)))
+        if a.eval:
+            import json
+            totals = {kind: eval_row(pipeline.eval_stats(t)) for kind, t in eval_totals.items()}
+            with open(os.path.join(a.out, "eval.json"), "w") as f:
+                json.dump({"size": [H, W], "bcd_times": a.bcd_times, "abs_thresh": 3.0, "pairs": eval_rows, "totals": totals}, f, indent=1)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
