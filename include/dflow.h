@@ -98,6 +98,11 @@ size_t dflow_workspace_bytes(const dflow_params *p);
 int dflow_daisy(const dflow_params *p, const uint8_t *d_bgr, void *d_descr,
                 void *d_ws, size_t ws_bytes, void *stream);
 
+/* The same for the two images of a pair (daisy i flann.py:406-407) in one set of launches: 7 kernels instead of 14, the image
+ * as a grid dimension.  d_descr1 / d_descr2 are bit for bit what two dflow_daisy calls write; they must be two planes. */
+int dflow_daisy_pair(const dflow_params *p, const uint8_t *d_bgr1, const uint8_t *d_bgr2, void *d_descr1, void *d_descr2,
+                     void *d_ws, size_t ws_bytes, void *stream);
+
 /* napraviCD2 + generisi, daisy i flann.py:144-189: per-cell exact 5-NN proposals, truncated-L1 costs,
  * WTA labels.  Initialises and fills proposals/lcosts/nprop/bestlabels. */
 int dflow_knn_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2,

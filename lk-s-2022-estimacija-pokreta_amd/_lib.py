@@ -51,6 +51,7 @@ _SIGNATURES = {
     "dflow_default_params": (None, [_pp, _i32, _i32, _i32, _i32]),
     "dflow_workspace_bytes": (_sz, [_pp]),
     "dflow_daisy": (C.c_int, [_pp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_daisy_pair": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_knn_proposals": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_knn_proposals_timed": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(_f32), C.POINTER(_f64)]),
     "dflow_knn_screen_stats": (C.c_int, [_pp, _vp, _sz, _vp, C.POINTER(C.c_int64)]),

@@ -78,7 +78,7 @@ void dflow_default_params(dflow_params *p, int32_t pich, int32_t picw, int32_t c
 size_t dflow_workspace_bytes(const dflow_params *p)
 {
     if (dflow_check_params(p) != DFLOW_OK) return 0;
-    size_t m = daisy_ws_bytes(p);
+    size_t m = daisy_pair_ws_bytes(p);
     for (size_t b : {bcd_ws_bytes(p), neighbour_ws_bytes(p), knn_mfma_supported(p) ? knn_mfma_ws_bytes(p) : (size_t)0})
         if (b > m) m = b;
     return m + DFLOW_WS_SLACK;
@@ -93,6 +93,16 @@ int dflow_daisy(const dflow_params *p, const uint8_t *d_bgr, void *d_descr, void
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_bgr); CHECK_PTR(d_descr); CHECK_WS(daisy_ws_bytes(p));
     return launch_daisy(p, d_bgr, d_descr, d_ws, (hipStream_t)stream);
+}
+
+int dflow_daisy_pair(const dflow_params *p, const uint8_t *d_bgr1, const uint8_t *d_bgr2, void *d_descr1, void *d_descr2,
+                     void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = dflow_check_params(p); if (rc) return rc;
+    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_WS(daisy_pair_ws_bytes(p));
+    // the two images run side by side: the outputs must be two planes
+    if (d_descr1 == d_descr2) return dflow_set_error(DFLOW_EINVAL, "%s: d_descr1 and d_descr2 are the same plane", __func__);
+    return launch_daisy_pair(p, d_bgr1, d_bgr2, d_descr1, d_descr2, d_ws, (hipStream_t)stream);
 }
 
 int dflow_knn_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2, uint32_t *d_proposals,

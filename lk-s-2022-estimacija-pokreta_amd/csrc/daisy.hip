@@ -4,7 +4,9 @@
 // definition (DESIGN.md "DAISY"; parity with cv2 unpinned); it is bit-identical to oracle/dflow_oracle.c:
 // every float operation is a single IEEE op in a fixed order (the file is compiled with -ffp-contract=off).
 //
-// Pipeline (all HBM-streaming, 4 orientation layers interleaved as one float4 per pixel), 7 launches per image:
+// Pipeline (all HBM-streaming, 4 orientation layers interleaved as one float4 per pixel), 7 launches, for one image
+// (dflow_daisy) or for the two images of a pair at once (dflow_daisy_pair: the image is the last grid dimension, every
+// image has its own scratch planes; per-pixel arithmetic, tiles and taps are those of the single call):
 //   front_kernel   gray/255 -> 5-tap blur (sigma 0.5) -> central differences -> 4 half-rectified orientation layers,
 //                  one LDS tile per workgroup (the three stencils need a halo of 3)
 //   blur2d_kernel  x5: 7-tap blur (sigma sqrt(1.6^2-0.25)), then 4 cascaded blurs (3/5/7/9 taps) = histogram cubes; both
@@ -35,12 +37,20 @@ __device__ static inline float4 tadd(float4 a, float4 b) { return make_float4(a.
 
 struct LayerW { float wc[4], ws[4]; };
 
+// one pointer per image of a launch; the image index is the (block-uniform) last grid dimension
+template <typename T> struct PerImage {
+    T *p[2];
+    __device__ T *at(unsigned i) const { return i ? p[1] : p[0]; }
+};
+
 // gray -> sm (5-tap separable blur, taps accumulated left to right, multiply then add) -> gradient -> layers.
 // Tile FX x FY outputs; g = gray on the tile + 3, th = horizontally blurred on (FX + 2) x (FY + 6), sm on the tile + 1.
 #define FX 32
 #define FY 8
-__global__ void __launch_bounds__(FX * FY) front_kernel(const uint8_t *__restrict__ bgr, float4 *__restrict__ lay, int H, int W, Taps t, LayerW w)
+__global__ void __launch_bounds__(FX * FY) front_kernel(PerImage<const uint8_t> bgrs, PerImage<float4> lays, int H, int W, Taps t, LayerW w)
 {
+    const uint8_t *__restrict__ bgr = bgrs.at(blockIdx.z);
+    float4 *__restrict__ lay = lays.at(blockIdx.z);
     __shared__ float g[FY + 6][FX + 6], th[FY + 6][FX + 2], sm[FY + 2][FX + 2];
     const int gx0 = blockIdx.x * FX, gy0 = blockIdx.y * FY, tid = threadIdx.y * FX + threadIdx.x;
     for (int i = tid; i < (FY + 6) * (FX + 6); i += FX * FY) {
@@ -82,8 +92,10 @@ __global__ void __launch_bounds__(FX * FY) front_kernel(const uint8_t *__restric
 #define BX 32
 #define BY 16
 #define BR 4
-__global__ void __launch_bounds__(BX * BY / 2) blur2d_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, int H, int W, Taps t)
+__global__ void __launch_bounds__(BX * BY / 2) blur2d_kernel(PerImage<const float4> srcs, PerImage<float4> dsts, int H, int W, Taps t)
 {
+    const float4 *__restrict__ src = srcs.at(blockIdx.z);
+    float4 *__restrict__ dst = dsts.at(blockIdx.z);
     __shared__ float4 s[BY + 2 * BR][BX + 2 * BR], h[BY + 2 * BR][BX];
     const int r = t.n / 2;
     const int gx0 = blockIdx.x * BX, gy0 = blockIdx.y * BY, tid = threadIdx.y * BX + threadIdx.x, nthr = BX * BY / 2;
@@ -113,8 +125,10 @@ __global__ void __launch_bounds__(BX * BY / 2) blur2d_kernel(const float4 *__res
 }
 
 // one thread = one (pixel, grid point): a coalesced float4 store into the 68-float descriptor row
-__global__ void gather_kernel(const float4 *__restrict__ cubes, float4 *__restrict__ descr, int H, int W, GridTab g, int f16)
+__global__ void gather_kernel(PerImage<const float4> cubess, PerImage<float4> descrs, int H, int W, GridTab g, int f16)
 {
+    const float4 *__restrict__ cubes = cubess.at(blockIdx.y);
+    float4 *__restrict__ descr = descrs.at(blockIdx.y);
     size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t total = (size_t)H * W * 17;
     if (gid >= total) return;
@@ -181,27 +195,36 @@ static Taps gaussian_taps(int n, double sigma)
     return t;
 }
 
-// DAISY's part of the workspace, (H,W) planes of float4: the 4 orientation layers (lay), the layers after the first blur
-// (tmp) and the histogram cubes of the 4 rings (cubes, 4 planes)
-struct DaisyWs { float4 *tmp, *lay, *cubes; size_t bytes; };
-static DaisyWs daisy_ws(const dflow_params *p, void *ws)
+// DAISY's part of the workspace, (H,W) planes of float4, one set per image of the call: the 4 orientation layers (lay), the
+// layers after the first blur (tmp) and the histogram cubes of the 4 rings (cubes, 4 planes)
+struct DaisyWs { float4 *tmp[2], *lay[2], *cubes[2]; size_t bytes; };
+static DaisyWs daisy_ws(const dflow_params *p, void *ws, int nimg)
 {
     const size_t N = (size_t)p->pich * p->picw;
     WsCarver c(ws);
-    float4 *tmp = c.take<float4>(N), *lay = c.take<float4>(N), *cubes = c.take<float4>(4 * N);
-    return {tmp, lay, cubes, c.bytes};
+    DaisyWs w = {};
+    for (int i = 0; i < nimg; i++) { w.tmp[i] = c.take<float4>(N); w.lay[i] = c.take<float4>(N); w.cubes[i] = c.take<float4>(4 * N); }
+    w.bytes = c.bytes;
+    return w;
 }
 
-size_t daisy_ws_bytes(const dflow_params *p) { return daisy_ws(p, nullptr).bytes; }
+size_t daisy_ws_bytes(const dflow_params *p) { return daisy_ws(p, nullptr, 1).bytes; }
+size_t daisy_pair_ws_bytes(const dflow_params *p) { return daisy_ws(p, nullptr, 2).bytes; }
 
-int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *ws, hipStream_t s)
+// nimg = 1 or 2 images through the same 7 launches
+static int daisy_launches(const dflow_params *p, int nimg, const uint8_t *const *bgr, void *const *descr, void *ws, hipStream_t s)
 {
     const double pi = 3.14159265358979323846;
     int H = p->pich, W = p->picw;
     size_t N = (size_t)H * W;
-    const DaisyWs w = daisy_ws(p, ws);
-    float4 *const tmp = w.tmp, *const lay = w.lay, *const cubes = w.cubes;
+    const DaisyWs w = daisy_ws(p, ws, nimg);
+    const unsigned Z = (unsigned)nimg;
     dim3 blk(256);
+    PerImage<const uint8_t> in = {{bgr[0], nimg > 1 ? bgr[1] : nullptr}};
+    PerImage<float4> out = {{(float4 *)descr[0], nimg > 1 ? (float4 *)descr[1] : nullptr}};
+    PerImage<float4> lay = {{w.lay[0], w.lay[1]}}, tmp = {{w.tmp[0], w.tmp[1]}};
+    auto cube = [&](int r) { return PerImage<float4>{{w.cubes[0] + (size_t)r * N, nimg > 1 ? w.cubes[1] + (size_t)r * N : nullptr}}; };
+    auto ro = [](const PerImage<float4> &a) { return PerImage<const float4>{{a.p[0], a.p[1]}}; };
 
     Taps t = gaussian_taps(5, 0.5);
     LayerW lw;
@@ -210,21 +233,21 @@ int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *w
         lw.wc[l] = (float)cos((double)angle);
         lw.ws[l] = (float)sin((double)angle);
     }
-    hipLaunchKernelGGL(front_kernel, dim3((W + FX - 1) / FX, (H + FY - 1) / FY), dim3(FX, FY), 0, s, bgr, lay, H, W, t, lw);
-    dim3 bgrd((W + BX - 1) / BX, (H + BY - 1) / BY), bblk(BX, BY / 2);
+    hipLaunchKernelGGL(front_kernel, dim3((W + FX - 1) / FX, (H + FY - 1) / FY, Z), dim3(FX, FY), 0, s, in, lay, H, W, t, lw);
+    dim3 bgrd((W + BX - 1) / BX, (H + BY - 1) / BY, Z), bblk(BX, BY / 2);
     {
         double sg = sqrt(1.6 * 1.6 - 0.25);
         t = gaussian_taps(filter_size((float)sg), (float)sg);
-        hipLaunchKernelGGL(blur2d_kernel, bgrd, bblk, 0, s, (const float4 *)lay, tmp, H, W, t);
+        hipLaunchKernelGGL(blur2d_kernel, bgrd, bblk, 0, s, ro(lay), tmp, H, W, t);
     }
     double sig[4];
     for (int r = 0; r < 4; r++) sig[r] = (r + 1) * (5.0 / 4 / 2);
-    const float4 *prev = tmp;
+    PerImage<const float4> prev = ro(tmp);
     for (int r = 0; r < 4; r++) {
         double sg = r == 0 ? sig[0] : sqrt(sig[r] * sig[r] - sig[r - 1] * sig[r - 1]);
         t = gaussian_taps(filter_size(sg), sg);
-        hipLaunchKernelGGL(blur2d_kernel, bgrd, bblk, 0, s, prev, cubes + (size_t)r * N, H, W, t);
-        prev = cubes + (size_t)r * N;
+        hipLaunchKernelGGL(blur2d_kernel, bgrd, bblk, 0, s, prev, cube(r), H, W, t);
+        prev = ro(cube(r));
     }
     GridTab g;
     double r_step = 5.0 / 4.0, t_step = 2 * pi / 4;
@@ -235,7 +258,20 @@ int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *w
             g.gx[1 + r * 4 + a] = (r + 1) * r_step * cos(a * t_step);
         }
     size_t total = N * 17;
-    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((total + 255) / 256)), blk, 0, s, (const float4 *)cubes,
-                       (float4 *)descr, H, W, g, (p->flags & DFLOW_FLAG_DESCR_F16) ? 1 : 0);
+    hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((total + 255) / 256), Z), blk, 0, s, ro(cube(0)), out, H, W, g,
+                       (p->flags & DFLOW_FLAG_DESCR_F16) ? 1 : 0);
     return dflow_check_launch("daisy kernels");
+}
+
+int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *ws, hipStream_t s)
+{
+    return daisy_launches(p, 1, &bgr, &descr, ws, s);
+}
+
+int launch_daisy_pair(const dflow_params *p, const uint8_t *bgr1, const uint8_t *bgr2, void *descr1, void *descr2, void *ws,
+                      hipStream_t s)
+{
+    const uint8_t *const bgr[2] = {bgr1, bgr2};
+    void *const descr[2] = {descr1, descr2};
+    return daisy_launches(p, 2, bgr, descr, ws, s);
 }

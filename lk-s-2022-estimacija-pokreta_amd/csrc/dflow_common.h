@@ -217,6 +217,10 @@ struct WsCarver {
 // stage launchers (one per .hip file)
 int launch_daisy(const dflow_params *p, const uint8_t *bgr, void *descr, void *ws, hipStream_t s);
 size_t daisy_ws_bytes(const dflow_params *p);
+// both images of a pair through one set of launches (a second set of scratch planes: daisy_pair_ws_bytes)
+int launch_daisy_pair(const dflow_params *p, const uint8_t *bgr1, const uint8_t *bgr2, void *descr1, void *descr2, void *ws,
+                      hipStream_t s);
+size_t daisy_pair_ws_bytes(const dflow_params *p);
 // d1, d2: float32 (H,W,68) or, with DFLOW_FLAG_DESCR_F16, binary16 (H,W,72)
 int launch_knn(const dflow_params *p, const void *d1, const void *d2, uint32_t *proposals, float *lcosts,
                int32_t *nprop, int32_t *bestlabels, hipStream_t s);

@@ -141,17 +141,23 @@ __global__ void __launch_bounds__(KNN_THREADS, 4) knn_exact_kernel(KnnArgs a, co
 
 // Fix-up for the MFMA path.  Work item = (query cell, first query index, 64 queries, candidate cell).  Items come
 // from the overflow list, or -- if the prep kernel flagged out-of-range descriptors or the list itself overflowed --
-// every item of the pass is enumerated.  A workgroup of KNN_FIX_WAVES waves takes one item at a time (grid-stride): all
+// every item of the pass is enumerated.  A team of KNN_FIX_WAVES waves takes one item at a time (grid-stride): all
 // waves hold the same 64 queries (lane = query); the candidate cell streams through LDS in chunks of KNN_FIX_CHUNK rows that
-// all threads fetch together (one 16-byte piece per thread, the next chunk's loads in flight while this one is evaluated);
-// wave w evaluates candidates w, w + 16 of every chunk (broadcast LDS reads), the partial top-5 lists meet in LDS and wave
-// 0 merges them by (distance, index), so the result is that of one sequential scan.  A single overflowed list used to
-// cost the latency of one wave walking a whole cell through the scalar cache (1.3 ms at 64x27 cells; 0.34 ms with the
-// rows dealt to 16 waves: about 2 us per candidate, all of it load latency).
-#define KNN_FIX_WAVES 16
-#define KNN_FIX_CHUNK 64              // candidates per LDS chunk (four per wave)
-#define KNN_FIX_BLOCKS 256            // one per CU: a launch that finds no item costs 4 096 wave starts (1 024 blocks: 16 384, which
-                                  // delayed the stream by a millisecond when other kernels held the CUs)
+// all threads fetch together (16-byte pieces, the next chunk's loads in flight while this one is evaluated);
+// wave w evaluates candidates w, w + KNN_FIX_WAVES, ... of every chunk (broadcast LDS reads), the partial top-5 lists meet in
+// LDS and wave 0 merges them by (distance, index), so the result is that of one sequential scan.
+// The launch is unconditional (no counter is read back on the host) and on almost every frame it finds no item, so what it
+// costs a stream is the placement of its workgroups while other streams' kernels hold the CUs.  A team of 16 waves with 75 KB
+// of LDS needed a whole drained CU (all of its registers): with three front-end streams the empty launch took 0.79 ms on
+// average (up to 7.5 ms) behind knn_screen_kernel, against 5 us alone.  A team of 4 waves with 26 KB and 128 VGPRs fits where
+// one knn_screen_kernel workgroup has left: median 6 to 7 us, mean 0.07 to 0.09 ms in the same trace, for 64 teams and for 256
+// alike (knn_fix_kernel).  The price is paid per item, with a quarter of the waves: a list takes 1.07 us instead of
+// 0.58 at the bench's cell size, a whole pass 165 ms instead of 88.
+#define KNN_FIX_WAVES 4
+#define KNN_FIX_CHUNK 28              // candidates per LDS chunk (seven per wave): 28 float32 rows are two 16-byte pieces per thread,
+                                  // which keeps the float32 kernel within 128 VGPRs (4 waves per SIMD) without scratch; the binary16
+                                  // kernel (rows widened on the way into LDS) keeps the 236 bytes of scratch per lane it had with 16 waves
+#define KNN_FIX_BLOCKS 256            // one per CU, as before (64 teams: no cheaper when empty, four times slower per item)
 // sorted insertion into an ascending top 5: the entry goes in front of the first slot it beats, and every later entry shifts
 // down unconditionally (a displaced entry must stay in front of an equal one that followed it).  top5_insert: beats = a
 // smaller distance (a sequential scan, where equal distances arrive in index order); top5_merge: a smaller distance, or an
@@ -168,7 +174,7 @@ __device__ static inline void top5_insert(Top5 &t, float cd, int cidx) { top5_pl
 __device__ static inline void top5_merge(Top5 &t, float cd, int cidx) { top5_place<true>(t, cd, cidx); }
 
 template <typename T>
-__global__ void __launch_bounds__(64 * KNN_FIX_WAVES) knn_fix_kernel(KnnArgs a, const T *__restrict__ gd1, const T *__restrict__ gd2,
+__global__ void __launch_bounds__(64 * KNN_FIX_WAVES, 4) knn_fix_kernel(KnnArgs a, const T *__restrict__ gd1, const T *__restrict__ gd2,
                                                         uint32_t *__restrict__ gproposals, float *__restrict__ glcosts,
                                                         const int *__restrict__ ovf_count, const int4 *__restrict__ ovf_list,
                                                         int ovf_cap, const int *__restrict__ flags, int qwaves)

@@ -158,8 +158,9 @@ __device__ static inline _Float16 km_f16_up(double v) { return (_Float16)(float)
 // summation order (= its L1 cost), so that the all-zero queries' answer can be found once per cell
 struct KmCellTop { uint32_t idx[5]; float cost[5]; };
 
-// which = 0: image 1 (queries), one thread per pixel, rows in pixel order.  which = 1: image 2 (candidates), one thread
-// per (cell = blockIdx.y, tile position), rows in position order (above).  The rotation y_j = sum_i V[j][i] x_i runs as two
+// One launch prepares both images (both need the basis and nothing else).  Blocks [0, qblocks): image 1 (queries, which = 0),
+// one thread per pixel, rows in pixel order.  The blocks after them: image 2 (candidates, which = 1), cblocks blocks per cell,
+// cell by cell, one thread per tile position, rows in position order (above).  The rotation y_j = sum_i V[j][i] x_i runs as two
 // float32 fmaf chains (even / odd dimensions: one chain of packed fmas) that are added at the end; the components of V arrive
 // through the scalar cache (vt is wave-uniform), 8 components per iteration = one 16-byte store.  Its rounding is part of E:
 // for ANY order of the 68 additions |y^_j - y_j| <= gamma_68 sum_i |V_ji x_i| <= 68 * 2^-24 (1 + 5e-6) |x|, over the 40
@@ -167,10 +168,15 @@ struct KmCellTop { uint32_t idx[5]; float cost[5]; };
 #define KM_RHO 2.65e-5
 typedef float km_f2p __attribute__((ext_vector_type(2)));
 template <typename T>
-__global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d, const float *__restrict__ vt, _Float16 *__restrict__ h,
+__global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d1, const T *__restrict__ d2, const float *__restrict__ vt,
+                                                       _Float16 *__restrict__ h1, _Float16 *__restrict__ h2,
                                                        float2 *__restrict__ qs, float2 *__restrict__ z0, uint8_t *__restrict__ zflag,
-                                                       int *__restrict__ cell_bad, Geom g, int which)
+                                                       int *__restrict__ cell_bad, Geom g, int qblocks, int cblocks)
 {
+    const int which = (int)blockIdx.x >= qblocks ? 1 : 0;             // block-uniform
+    const T *__restrict__ d = which ? d2 : d1;
+    _Float16 *__restrict__ h = which ? h2 : h1;
+    const int cell = which ? ((int)blockIdx.x - qblocks) / cblocks : 0;
     int pix;
     size_t orow;
     if (which == 0) {
@@ -178,9 +184,9 @@ __global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d, 
         if (pix >= g.H * g.W) return;
         orow = (size_t)pix;
     } else {
-        const int ci = blockIdx.y % g.ncx, cj = blockIdx.y / g.ncx;
+        const int ci = cell % g.ncx, cj = cell / g.ncx;
         const int cx0 = g.x0(ci), cy0 = g.y0(cj), ccw = g.x1(ci) - cx0, cnpts = ccw * (g.y1(cj) - cy0);
-        const int pos = blockIdx.x * blockDim.x + threadIdx.x;
+        const int pos = (((int)blockIdx.x - qblocks) % cblocks) * blockDim.x + threadIdx.x;
         if (pos >= km_pad(cnpts)) return;
         orow = km_cell_base(g, ci, cj) + pos;
         const int idx = (pos & 31) * km_ntiles(cnpts) + (pos >> 5);
@@ -267,7 +273,7 @@ __global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d, 
         last[KM_SLOT_S - 40] = km_f16_up(scs * KM_SSCALE);
         last[KM_SLOT_ONE - 40] = (_Float16)1.0f; last[KM_SLOT_ONE + 1 - 40] = (_Float16)1.0f;
         zflag[orow] = zero ? 1 : 0;
-        if (bad) cell_bad[blockIdx.y] = 1;
+        if (bad) cell_bad[cell] = 1;
     }
     o[KM_K / 8 - 1] = last;
 }
@@ -1126,11 +1132,11 @@ int launch_knn_mfma(const dflow_params *p, const void *d1, const void *d2, uint3
     int rc = launch_knn_pca(p, d2, k.vt, k.ctr + 1, k.pca_ws, s);
     if (rc) return rc;
     KM_MARK(1);
-    const dim3 cgrid((km_pad(max_cell_points(g)) + 255) / 256, g.ncx * g.ncy);
+    const int cblocks = (km_pad(max_cell_points(g)) + 255) / 256;          // blocks per candidate cell
     with_descr_type(p, [&](auto d) {
         using T = typename decltype(d)::T;
-        hipLaunchKernelGGL(knn_prep_kernel<T>, dim3(nb), dim3(256), 0, s, (const T *)d1, (const float *)k.vt, k.h1, k.qs, (float2 *)nullptr, (uint8_t *)nullptr, (int *)nullptr, g, 0);
-        hipLaunchKernelGGL(knn_prep_kernel<T>, cgrid, dim3(256), 0, s, (const T *)d2, (const float *)k.vt, k.h2, (float2 *)nullptr, k.z0, k.zflag, k.cell_bad, g, 1);
+        hipLaunchKernelGGL(knn_prep_kernel<T>, dim3(nb + cblocks * g.ncx * g.ncy), dim3(256), 0, s, (const T *)d1, (const T *)d2, (const float *)k.vt,
+                           k.h1, k.h2, k.qs, k.z0, k.zflag, k.cell_bad, g, nb, cblocks);
     });
     hipLaunchKernelGGL(knn_cell_post_kernel, dim3(g.ncx * g.ncy), dim3(256), 0, s, k.h2, (const float2 *)k.z0, (const uint8_t *)k.zflag, k.ztop, g);
     rc = dflow_check_launch("knn_cell_post_kernel");

@@ -50,7 +50,8 @@ class DiscreteFlow:
         self.bestlabels = torch.empty((H, W), dtype=torch.int32, device=dev)        # :95
         self.flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        self._img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        self._img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)          # staging of host images
+        self._img2 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
         self._bcd_ready = False     # compat matrices in the workspace are valid for the current proposals
 
     # ------------------------------------------------------------------ helpers
@@ -76,19 +77,22 @@ class DiscreteFlow:
         return C.byref(self.p)
 
     # ------------------------------------------------------------------ reference-named stages
-    def izracunajDaisy(self, picture, out=None):
-        """daisy i flann.py:69-77.  picture: (H,W,3) uint8 BGR (numpy or device tensor) -> (H,W,68) f32 tensor (with
-        DFLOW_FLAG_DESCR_F16: (H,W,72) binary16, see descriptors_f32)."""
+    def _device_image(self, picture, staging):
+        """picture: (H,W,3) uint8 BGR, numpy (copied into the device tensor `staging`) or a contiguous device tensor."""
         H, W = self.p.pich, self.p.picw
         if isinstance(picture, np.ndarray):
             if picture.shape != (H, W, 3) or picture.dtype != np.uint8:
                 raise ValueError("picture must be uint8 (%d,%d,3)" % (H, W))
-            self._img.copy_(torch.from_numpy(np.ascontiguousarray(picture)))
-            img = self._img
-        else:
-            if tuple(picture.shape) != (H, W, 3) or picture.dtype != torch.uint8 or not picture.is_contiguous():
-                raise ValueError("picture must be a contiguous uint8 (%d,%d,3) tensor" % (H, W))
-            img = picture
+            staging.copy_(torch.from_numpy(np.ascontiguousarray(picture)))
+            return staging
+        if tuple(picture.shape) != (H, W, 3) or picture.dtype != torch.uint8 or not picture.is_contiguous():
+            raise ValueError("picture must be a contiguous uint8 (%d,%d,3) tensor" % (H, W))
+        return picture
+
+    def izracunajDaisy(self, picture, out=None):
+        """daisy i flann.py:69-77.  picture: (H,W,3) uint8 BGR (numpy or device tensor) -> (H,W,68) f32 tensor (with
+        DFLOW_FLAG_DESCR_F16: (H,W,72) binary16, see descriptors_f32)."""
+        img = self._device_image(picture, self._img)
         if out is None:
             out = self._new_descr()
         self._bcd_ready = False
@@ -96,9 +100,12 @@ class DiscreteFlow:
         return out
 
     def load_pair(self, pic3, pic4):
-        """daisy i flann.py:406-407."""
-        self.izracunajDaisy(pic3, out=self.descrs1)
-        self.izracunajDaisy(pic4, out=self.descrs2)
+        """daisy i flann.py:406-407: the descriptors of both images, in one set of launches (dflow_daisy_pair; the planes
+        are bit for bit those of two izracunajDaisy calls)."""
+        img1, img2 = self._device_image(pic3, self._img), self._device_image(pic4, self._img2)
+        self._bcd_ready = False
+        _lib.call("dflow_daisy_pair", self._pp(), img1.data_ptr(), img2.data_ptr(), self.descrs1.data_ptr(), self.descrs2.data_ptr(),
+                  self.ws.data_ptr(), self.ws_bytes, self._stream())
 
     def set_descriptors(self, descrs1, descrs2):
         """(H,W,68) arrays -> the descriptor planes (rounded to binary16 if the pass stores them that way)."""
