@@ -368,6 +368,65 @@ int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layo
                     uint32_t flags, dflow_eval_stats *d_stats, float *d_err, uint8_t *d_err_bgr,
                     void *d_ws, size_t ws_bytes, void *stream);
 
+/* Looking at a flow without a ground truth: its colour picture, and the second image warped back onto the first with the
+ * photometric error that results.  This build's definitions (DESIGN.md "Flow pictures and the warp check"); no counterpart
+ * in the reference.  Common to both entry points: 1 <= h, w <= 8192, the planes are walked as h*w pixels in row-major order;
+ * d_flow by `layout` is DFLOW_EVAL_UVV (h,w,3) float32 [U,V,valid] or DFLOW_EVAL_DYDX (h,w,2) float32 [dy,dx] (U = dx, V = dy,
+ * valid = 1), as for dflow_flow_eval.  A pixel is KNOWN when valid > 0.5 and |U| <= 1e9 and |V| <= 1e9 (float32 compares, so
+ * a NaN or an infinity anywhere makes it unknown); every other pixel is UNKNOWN.  d_flow and d_err must be 16-byte aligned,
+ * d_stats 8-byte, the uint8 planes the kernels move four pixels at a time (d_bgr of the colour picture, d_bgr1, d_warped,
+ * d_err_bgr) and d_maxrad 4-byte; d_bgr2 is read byte by byte.  A size, layout, flag or parameter outside its range, a NULL
+ * required pointer or a misaligned pointer returns DFLOW_EINVAL, a NULL or too small workspace DFLOW_ENOSPC, both before
+ * anything is launched.  Both calls are asynchronous on `stream`, allocate nothing, read nothing back and can be captured
+ * into a graph; their workspace holds one partial result per block of the first launch, a fixed function of h*w, and the
+ * *_workspace_bytes functions return 0 (and set dflow_last_error) for sizes outside the range.
+ *
+ * dflow_flow_color: the Middlebury colour coding (Baker et al., "A Database and Evaluation Methodology for Optical Flow",
+ * the colorcode of its flow tools), written from the published algorithm as recalled and not checked against that tool.
+ * The wheel has 55 entries (r,g,b), csrc/flow_wheel.h, in the order RY 15, YG 6, GC 4, CB 11, BM 13, MR 6; with i counting
+ * within a segment of length n and integer divisions: RY (255, 255*i/n, 0), YG (255 - 255*i/n, 255, 0), GC (0, 255, 255*i/n),
+ * CB (0, 255 - 255*i/n, 255), BM (255*i/n, 0, 255), MR (255, 0, 255 - 255*i/n).
+ * Radius: max_flow > 0: maxrad = max_flow.  max_flow == 0: maxrad = the maximum over the known pixels of sqrtf(U*U + V*V) in
+ * float32, and 1 when that is 0 or no pixel is known; it is found by a first launch and read from the workspace by the one
+ * that colours.  Any other max_flow (negative, NaN, Inf) is DFLOW_EINVAL.  d_maxrad (device float, NULL to skip) receives it.
+ * Per known pixel, in double, one correctly rounded IEEE operation per written operation, no fused multiply-add:
+ *     fx = U / maxrad, fy = V / maxrad, rad = sqrt(fx*fx + fy*fy)
+ *     a = atan2(-fy, -fx) / pi, fk = (a + 1) / 2 * 54, k0 = min(54, (int)floor(fk)), k1 = (k0 + 1) % 55, f = fk - k0
+ *     per channel: c0 = wheel[k0] / 255, c1 = wheel[k1] / 255, col = c0 + f * (c1 - c0)
+ *                  col = 1 - rad * (1 - col) when rad <= 1, col * 0.75 otherwise;  byte = (int)(255 * col)
+ * Everything but atan2 is determined to the bit; a channel whose two wheel entries are equal is exact whatever f is.
+ * d_bgr (h,w,3) uint8 in (b, g, r) order, as d_err_bgr; (0,0,0) at unknown pixels. */
+size_t dflow_flow_color_workspace_bytes(int32_t h, int32_t w);
+int dflow_flow_color(int32_t h, int32_t w, const float *d_flow, int32_t layout, float max_flow, uint8_t *d_bgr,
+                     float *d_maxrad, void *d_ws, size_t ws_bytes, void *stream);
+
+/* dflow_warp_eval: d_bgr1, d_bgr2 (h,w,3) uint8 BGR, the two frames; the flow takes pixel (x,y) of the first to
+ * (x + U, y + V) in the second.  Per known pixel, in float32, one IEEE operation per written operation:
+ *     xs = x + U, ys = y + V;  the pixel is INSIDE when 0 <= xs <= w-1 and 0 <= ys <= h-1
+ *     x0 = floorf(xs), ax = xs - x0, x1 = min(x0 + 1, w-1), and likewise y0, ay, y1
+ *     per channel: top = (1-ax)*I2[y0][x0] + ax*I2[y0][x1], bot the same on row y1, wv = (1-ay)*top + ay*bot
+ *     err = ((|wv_b - I1_b| + |wv_g - I1_g|) + |wv_r - I1_r|) / 3
+ * (the bilinear operation order of the variational refinement's warp).  Statistics: n counts the inside pixels, n_outside
+ * the known pixels that are not inside, n_unknown the unknown ones (the three add up to h*w), n_above the inside pixels
+ * with err > err_thresh; sum_err adds err widened to double in the fixed order of dflow_flow_eval (the same inputs give the
+ * same 8 bytes on every call), max_err is the largest err (0 when n = 0).  Mean photometric error = sum_err / n.  Without
+ * DFLOW_WARP_FLAG_ACCUMULATE *d_stats is overwritten; with it the call's values are added to what it holds (max_err by
+ * max, sum_err as old + this call's sum); the caller zeroes it first.
+ * Optional outputs (NULL to skip): d_warped (h,w,3) uint8 (int)floorf(wv + 0.5f), (0,0,0) where the pixel is not inside;
+ * d_err (h,w) float32 err, -1 where the pixel is not inside; d_err_bgr (h,w,3) uint8: the jet table of dflow_flow_eval at
+ * idx = min(255, (int)(t * 256)), t = min(err, err_max) / err_max, black where the pixel is not inside.
+ * err_thresh finite and >= 0, err_max finite and > 0. */
+#define DFLOW_WARP_FLAG_ACCUMULATE 1u
+typedef struct dflow_photo_stats {
+    uint64_t n, n_outside, n_unknown, n_above;
+    double sum_err;
+    float max_err; uint32_t reserved;
+} dflow_photo_stats;
+size_t dflow_warp_eval_workspace_bytes(int32_t h, int32_t w);
+int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow, int32_t layout,
+                    float err_thresh, float err_max, uint32_t flags, dflow_photo_stats *d_stats, uint8_t *d_warped,
+                    float *d_err, uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

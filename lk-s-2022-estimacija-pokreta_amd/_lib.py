@@ -14,6 +14,7 @@ DESC_PITCH_F16 = 72     # DFLOW_DESC_PITCH_F16: binary16 descriptor planes are (
 VAR_FLAG_SOR_UNFUSED = 1    # DFLOW_VAR_FLAG_SOR_UNFUSED
 EVAL_UVV, EVAL_DYDX = 0, 1  # DFLOW_EVAL_UVV, DFLOW_EVAL_DYDX: the test field's layout in dflow_flow_eval
 EVAL_FLAG_ACCUMULATE = 1    # DFLOW_EVAL_FLAG_ACCUMULATE
+WARP_FLAG_ACCUMULATE = 1    # DFLOW_WARP_FLAG_ACCUMULATE
 
 
 class DflowError(RuntimeError):
@@ -40,6 +41,12 @@ class EvalStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_out_abs", C.c_uint64), ("n_out_kitti", C.c_uint64), ("n_nonfinite", C.c_uint64),
                 ("n_gt_valid", C.c_uint64), ("n_test_valid", C.c_uint64), ("sum_err", C.c_double), ("max_err", C.c_float),
                 ("reserved", C.c_uint32)]
+
+
+class PhotoStats(C.Structure):
+    """struct dflow_photo_stats (include/dflow.h): what dflow_warp_eval leaves in device memory."""
+    _fields_ = [("n", C.c_uint64), ("n_outside", C.c_uint64), ("n_unknown", C.c_uint64), ("n_above", C.c_uint64),
+                ("sum_err", C.c_double), ("max_err", C.c_float), ("reserved", C.c_uint32)]
 
 
 _vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
@@ -81,6 +88,10 @@ _SIGNATURES = {
     "dflow_var_refine": (C.c_int, [_i32, _i32, _vp, _vp, _vp, C.POINTER(VarParams), _vp, _vp, _sz, _vp]),
     "dflow_eval_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_flow_eval": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_flow_color_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_flow_color": (C.c_int, [_i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_warp_eval_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_warp_eval": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <initializer_list>
 #include "dflow_common.h"
 
 static thread_local char g_err[512] = "";
@@ -58,6 +59,15 @@ int dflow_check_params(const dflow_params *p)
     if (!(p->sigma > 0.0f) || p->sigma > 8.0f) return dflow_set_error(DFLOW_EINVAL, "sigma=%g outside (0,8]", (double)p->sigma);
     if (p->max_attempts < p->ngauss) return dflow_set_error(DFLOW_EINVAL, "max_attempts < ngauss");
     if (p->flags & ~(DFLOW_FLAG_KNN_EXACT | DFLOW_FLAG_DESCR_F16)) return dflow_set_error(DFLOW_EINVAL, "unknown flags 0x%x", (unsigned)p->flags);
+    return DFLOW_OK;
+}
+
+// a pointer the kernels move several elements of at a time; NULL (an optional output left out) passes
+struct AlignedPtr { const char *name; const void *p; uintptr_t align; };
+static int check_aligned(const char *fn, std::initializer_list<AlignedPtr> ptrs)
+{
+    for (const AlignedPtr &q : ptrs)
+        if ((uintptr_t)q.p % q.align) return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", fn, q.name, (int)q.align);
     return DFLOW_OK;
 }
 
@@ -399,6 +409,53 @@ int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layo
             return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", __func__, q.name, (int)q.align);
     CHECK_WS(eval_ws_bytes(h, w));
     return launch_flow_eval(h, w, d_test, test_layout, d_gt, abs_thresh, flags, d_stats, d_err, d_err_bgr, d_ws, (hipStream_t)stream);
+}
+
+size_t dflow_flow_color_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return flow_color_ws_bytes(h, w);
+}
+
+int dflow_flow_color(int32_t h, int32_t w, const float *d_flow, int32_t layout, float max_flow, uint8_t *d_bgr, float *d_maxrad,
+                     void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (!isfinite(max_flow) || max_flow < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: max_flow=%g must be finite and >= 0 (0: the field's own maximum)", __func__, (double)max_flow);
+    CHECK_PTR(d_flow); CHECK_PTR(d_bgr);
+    // the kernels move four pixels per lane: 16-byte loads of the flow, 12-byte stores of the picture
+    rc = check_aligned(__func__, {{"d_flow", d_flow, 16}, {"d_bgr", d_bgr, 4}, {"d_maxrad", d_maxrad, 4}}); if (rc) return rc;
+    CHECK_WS(flow_color_ws_bytes(h, w));
+    return launch_flow_color(h, w, d_flow, layout, max_flow, d_bgr, d_maxrad, d_ws, (hipStream_t)stream);
+}
+
+size_t dflow_warp_eval_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return warp_eval_ws_bytes(h, w);
+}
+
+int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow, int32_t layout,
+                    float err_thresh, float err_max, uint32_t flags, dflow_photo_stats *d_stats, uint8_t *d_warped, float *d_err,
+                    uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (!isfinite(err_thresh) || err_thresh < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: err_thresh=%g must be finite and >= 0", __func__, (double)err_thresh);
+    if (!isfinite(err_max) || !(err_max > 0.0f))
+        return dflow_set_error(DFLOW_EINVAL, "%s: err_max=%g must be finite and > 0", __func__, (double)err_max);
+    if (flags & ~DFLOW_WARP_FLAG_ACCUMULATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_flow); CHECK_PTR(d_stats);
+    // the kernel moves four pixels per lane: 16-byte loads and stores of the float planes, 12-byte ones of the uint8 planes
+    rc = check_aligned(__func__, {{"d_bgr1", d_bgr1, 4}, {"d_flow", d_flow, 16}, {"d_stats", d_stats, 8}, {"d_warped", d_warped, 4},
+                                  {"d_err", d_err, 16}, {"d_err_bgr", d_err_bgr, 4}});
+    if (rc) return rc;
+    CHECK_WS(warp_eval_ws_bytes(h, w));
+    return launch_warp_eval(h, w, d_bgr1, d_bgr2, d_flow, layout, err_thresh, err_max, flags, d_stats, d_warped, d_err, d_err_bgr,
+                            d_ws, (hipStream_t)stream);
 }
 
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)

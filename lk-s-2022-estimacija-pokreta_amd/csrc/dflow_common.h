@@ -281,3 +281,12 @@ int epic_prefilter_last_stats(int32_t *counts, float *stage_ms);
 size_t eval_ws_bytes(int H, int W);
 int launch_flow_eval(int H, int W, const float *test, int layout, const float *gt, float abs_thresh, uint32_t flags,
                      dflow_eval_stats *stats, float *err, uint8_t *bgr, void *ws, hipStream_t s);
+// flow_picture.hip: the colour-wheel picture of a flow, and the warp of the second image onto the first with its photometric
+// error (arguments validated by the caller); maxrad, warped, err and err_bgr may be NULL
+size_t flow_color_ws_bytes(int H, int W);
+int launch_flow_color(int H, int W, const float *flow, int layout, float max_flow, uint8_t *bgr, float *maxrad, void *ws,
+                      hipStream_t s);
+size_t warp_eval_ws_bytes(int H, int W);
+int launch_warp_eval(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *flow, int layout, float err_thresh,
+                     float err_max, uint32_t flags, dflow_photo_stats *stats, uint8_t *warped, float *err, uint8_t *err_bgr,
+                     void *ws, hipStream_t s);

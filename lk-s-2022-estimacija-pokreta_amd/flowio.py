@@ -57,8 +57,9 @@ def read_flo(path):
 # visualization.py:37-53 reads the KITTI ground truth with cv2.imread(path, -1): 16-bit RGB PNG, U = (R-32768)/64,
 # V = (G-32768)/64, valid = B > 0.  cv2 is not a dependency of this build (and PIL cannot read 16-bit RGB), so the PNG
 # container is decoded here: zlib + the five PNG scanline filters, non-interlaced truecolour, 8 or 16 bit.
-def read_png16(path):
-    """Returns (H,W,3) uint16 in R,G,B order (8-bit files are returned as their 8-bit values)."""
+def _png_lines(path, accepts, what):
+    """The unfiltered scanlines of a non-interlaced PNG as (h, w * bytes per pixel) uint8, with (w, h, depth, colour type);
+    accepts: the (colour type, depth) pairs the caller takes, what: their description for the error message."""
     import struct
     import zlib
     data = open(path, "rb").read()
@@ -78,9 +79,9 @@ def read_png16(path):
     if hdr is None:
         raise ValueError("%s: no IHDR chunk" % path)
     w, h, depth, ctype, _, _, interlace = hdr
-    if ctype != 2 or depth not in (8, 16) or interlace != 0:
-        raise ValueError("%s: only non-interlaced 8/16-bit RGB PNGs are supported (colour type %d, depth %d)" % (path, ctype, depth))
-    bpp = 3 * depth // 8
+    if (ctype, depth) not in accepts or interlace != 0:
+        raise ValueError("%s: only non-interlaced %s PNGs are supported (colour type %d, depth %d)" % (path, what, ctype, depth))
+    bpp = (3 if ctype == 2 else 1) * depth // 8
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
     stride = w * bpp
     if raw.size != h * (stride + 1):
@@ -115,10 +116,25 @@ def read_png16(path):
             raise ValueError("%s: bad filter type %d" % (path, ft))
         out[y] = cur
         prev = cur
+    return out, w, h, depth, ctype
+
+
+def read_png16(path):
+    """Returns (H,W,3) uint16 in R,G,B order (8-bit files are returned as their 8-bit values)."""
+    out, w, h, depth, _ = _png_lines(path, ((2, 8), (2, 16)), "8/16-bit RGB")
     if depth == 16:
         px = out.reshape(h, w, 3, 2).astype(np.uint16)
         return (px[..., 0] << 8) | px[..., 1]
     return out.reshape(h, w, 3).astype(np.uint16)
+
+
+def read_png8(path):
+    """An 8-bit RGB or grey PNG -> (H,W,3) uint8 in B,G,R order (what cv2.imread gives and write_png8 takes); a grey file
+    gives three equal channels.  Palette, alpha, 16-bit and interlaced files are refused."""
+    out, w, h, _, ctype = _png_lines(path, ((2, 8), (0, 8)), "8-bit RGB or grey")
+    if ctype == 0:
+        return np.ascontiguousarray(np.repeat(out.reshape(h, w, 1), 3, axis=2))
+    return np.ascontiguousarray(out.reshape(h, w, 3)[..., ::-1])
 
 
 def write_png16(path, rgb16):

@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Looking at a flow without a ground truth (DESIGN.md "Flow pictures and the warp check"); no counterpart in the reference.
+
+    python flowpicture.py <flow> <picture> [--max-flow M]
+    python flowpicture.py <flow> --warp <img1> <img2> [--warped P] [--error-picture P] [--err-thresh T] [--err-max E]
+
+The first form writes the Middlebury colour-wheel picture of the flow (pipeline.flow_color): hue = direction, saturation =
+length over M, by default over the largest flow of the field; black where the flow is unknown.
+The second form warps <img2> back onto <img1> by the flow (pipeline.warp_eval) and prints the mean photometric error (grey
+levels, the mean absolute difference of the three channels), the share of pixels above T (default 10), and how many pixels
+were compared and how many targets lie outside the frame or are unknown; --warped writes the warped second image,
+--error-picture the jet picture of min(err, E) / E (E default 30).  T and E are this build's defaults.  Both forms may be
+combined.
+Flows are read with evaluate.ucitajFlow ('.png' KITTI, '.npy' the hot path's fields, '.flo' Middlebury), images as '.npy'
+((H,W,3) uint8 BGR), '.ppm' (binary P6) or '.png' (8-bit RGB or grey, flowio.read_png8); pictures are written with
+visualization.write_picture ('.png' and '.ppm' always, anything else through PIL if it can be imported).
+"""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("flow")
+    ap.add_argument("picture", nargs="?", default=None, help="where the colour picture of the flow goes")
+    ap.add_argument("--max-flow", type=float, default=None, help="flow length at which the colours saturate (default: the field's maximum)")
+    ap.add_argument("--warp", nargs=2, metavar=("IMG1", "IMG2"), default=None, help="the two frames: run the warp check")
+    ap.add_argument("--warped", default=None, help="with --warp: where the warped second image goes")
+    ap.add_argument("--error-picture", default=None, help="with --warp: where the colour picture of the photometric error goes")
+    ap.add_argument("--err-thresh", type=float, default=10.0)
+    ap.add_argument("--err-max", type=float, default=30.0)
+    return ap
+
+
+def read_image(path):
+    """An image file -> (H,W,3) uint8 BGR."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        img = np.load(path)
+    elif ext == ".png":
+        img = importlib.import_module(PKG + ".flowio").read_png8(path)
+    elif ext == ".ppm":
+        data = open(path, "rb").read()
+        tok, pos = [], 0
+        while len(tok) < 4:                                 # P6, width, height, maxval; '#' starts a comment
+            while data[pos:pos + 1].isspace():
+                pos += 1
+            if data[pos:pos + 1] == b"#":
+                pos = data.index(b"\n", pos)
+                continue
+            end = pos
+            while not data[end:end + 1].isspace():
+                end += 1
+            tok.append(data[pos:end])
+            pos = end
+        w, h = int(tok[1]), int(tok[2])
+        if tok[0] != b"P6" or int(tok[3]) != 255 or len(data) - (pos + 1) < 3 * w * h:
+            raise ValueError("%s: only binary P6 files with maxval 255 are supported" % path)
+        img = np.frombuffer(data, np.uint8, 3 * w * h, pos + 1).reshape(h, w, 3)[..., ::-1]
+    else:
+        raise ValueError("%s: images are read as .npy, .ppm or .png" % path)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("%s: not a (H,W,3) uint8 image (%s %s)" % (path, img.shape, img.dtype))
+    return np.ascontiguousarray(img)
+
+
+def main(argv=None):
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.picture is None and a.warp is None:
+        ap.error("nothing to do: give a picture path, --warp, or both")
+    if a.warp is None and (a.warped or a.error_picture):
+        ap.error("--warped and --error-picture need --warp")
+    evaluate = importlib.import_module(PKG + ".evaluate")
+    pipeline = importlib.import_module(PKG + ".pipeline")
+    write_picture = importlib.import_module(PKG + ".visualization").write_picture
+    flow = evaluate.ucitajFlow(a.flow)
+    if a.picture is not None:
+        write_picture(a.picture, pipeline.flow_color(flow, a.max_flow).cpu().numpy())
+    if a.warp is not None:
+        img1, img2 = (read_image(p) for p in a.warp)
+        if img1.shape != img2.shape or img1.shape[:2] != flow.shape[:2]:
+            print("flowpicture: the flow is %dx%d, the images %dx%d and %dx%d"
+                  % (flow.shape[1], flow.shape[0], img1.shape[1], img1.shape[0], img2.shape[1], img2.shape[0]), file=sys.stderr)
+            return 2
+        out = pipeline.warp_eval(img1, img2, flow, a.err_thresh, a.err_max, warped=a.warped is not None,
+                                 image=a.error_picture is not None)
+        out = out if isinstance(out, tuple) else (out,)
+        st = pipeline.photo_stats(out[0])
+        print("mean photometric error %.4f, %.2f%% above %g, over %d px; %d targets outside the frame, %d unknown"
+              % (st["mean_err"], st["above_pct"], a.err_thresh, st["n"], st["n_outside"], st["n_unknown"]))
+        rest = list(out[1:])
+        if a.warped is not None:
+            write_picture(a.warped, rest.pop(0).cpu().numpy())
+        if a.error_picture is not None:
+            write_picture(a.error_picture, rest.pop(0).cpu().numpy())
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

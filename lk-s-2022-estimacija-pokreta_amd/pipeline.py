@@ -530,3 +530,87 @@ def eval_stats(t):
     d["outliers_pct"] = d["n_out_abs"] * 100 / n if n else nan
     d["kitti_fl_pct"] = d["n_out_kitti"] * 100 / n if n else nan
     return d
+
+
+def _flow_tensor(flow, what):
+    """A flow for flow_color / warp_eval: a float32 (H,W,3) [U,V,valid] or (H,W,2) [dy,dx] tensor or array, as it is."""
+    t = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow))
+    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] not in (2, 3):
+        raise ValueError("%s: flow must be float32 (H,W,3) [U,V,valid] or (H,W,2) [dy,dx], got %s %s" % (what, tuple(t.shape), t.dtype))
+    return t
+
+
+def flow_color(flow, max_flow=None, return_radius=False):
+    """The Middlebury colour-wheel picture of a flow on the GPU (dflow_flow_color, DESIGN.md "Flow pictures and the warp
+    check"): hue = direction, saturation = length over the radius.  flow is (H,W,3) float32 [U,V,valid] or (H,W,2) float32
+    [dy,dx]; the last dimension says which.  Device tensor or host array; host data is uploaded to the current device.
+    max_flow: the radius at which the colours saturate; None or 0: the largest flow of the field (found on the device,
+    nothing is read back).  Returns the (H,W,3) uint8 picture in BGR order, black where the flow is unknown (not valid, not
+    finite, or beyond 1e9), and with return_radius=True also the radius used as a one-element float32 device tensor.  Runs on
+    torch's current stream and does not wait for it."""
+    flow = _flow_tensor(flow, "flow_color")
+    H, W = int(flow.shape[0]), int(flow.shape[1])
+    dev = flow.device if flow.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    flow = flow.to(dev).contiguous()
+    ws, ws_bytes = _lib.workspace("dflow_flow_color_workspace_bytes", H, W, dev)
+    img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    radius = torch.empty(1, dtype=torch.float32, device=dev) if return_radius else None
+    _lib.call("dflow_flow_color", H, W, flow.data_ptr(), _lib.EVAL_UVV if flow.shape[2] == 3 else _lib.EVAL_DYDX,
+              0.0 if max_flow is None else float(max_flow), img.data_ptr(), radius.data_ptr() if return_radius else None,
+              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    return (img, radius) if return_radius else img
+
+
+PHOTO_COUNTS = ("n", "n_outside", "n_unknown", "n_above")
+
+
+def warp_eval(img1, img2, flow, err_thresh=10.0, err_max=30.0, warped=False, err=False, image=False, stats=None):
+    """A quality check that needs no ground truth (dflow_warp_eval, DESIGN.md "Flow pictures and the warp check"): img2
+    sampled bilinearly at (x + U, y + V) and compared with img1, the mean absolute difference of the three channels per pixel.
+    img1, img2: (H,W,3) uint8 BGR; flow: (H,W,3) float32 [U,V,valid] or (H,W,2) float32 [dy,dx].  Device tensors or host
+    arrays; host data is uploaded to the current device.  err_thresh (grey levels; the share of pixels above it is reported)
+    and err_max (where the error picture saturates) default to 10 and 30: this build's choices, no reference sets them.
+    Returns the statistics as a device tensor (struct dflow_photo_stats as 6 int64 words; photo_stats reads it back), then,
+    if asked for, warped: (H,W,3) uint8, the warped second image; err: (H,W) float32; image: (H,W,3) uint8, the jet picture
+    of min(err, err_max) / err_max in BGR order.  All three are 0 / -1 / black where the flow is unknown or leaves the frame.
+    stats: the tensor of an earlier call (or torch.zeros(6, int64)) to add this pair's values to, so that a batch is
+    totalled on the device.  Runs on torch's current stream and does not wait for it."""
+    flow = _flow_tensor(flow, "warp_eval")
+    H, W = int(flow.shape[0]), int(flow.shape[1])
+    imgs = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in (img1, img2)]
+    for a in imgs:
+        if a.dtype != torch.uint8 or tuple(a.shape) != (H, W, 3):
+            raise ValueError("warp_eval: the images must be (%d,%d,3) uint8 BGR, got %s %s" % (H, W, tuple(a.shape), a.dtype))
+    dev = next((t.device for t in [flow] + imgs if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    flow, img1, img2 = (t.to(dev).contiguous() for t in [flow] + imgs)
+    flags = 0
+    if stats is None:
+        stats = torch.empty(6, dtype=torch.int64, device=dev)
+    else:
+        if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and stats.numel() == 6 and stats.is_contiguous()
+                and stats.device == dev):
+            raise ValueError("warp_eval: stats must be the int64[6] tensor of an earlier call on %s" % dev)
+        flags = _lib.WARP_FLAG_ACCUMULATE
+    ws, ws_bytes = _lib.workspace("dflow_warp_eval_workspace_bytes", H, W, dev)
+    wp = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if warped else None
+    e = torch.empty((H, W), dtype=torch.float32, device=dev) if err else None
+    pic = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if image else None
+    _lib.call("dflow_warp_eval", H, W, img1.data_ptr(), img2.data_ptr(), flow.data_ptr(),
+              _lib.EVAL_UVV if flow.shape[2] == 3 else _lib.EVAL_DYDX, float(err_thresh), float(err_max), flags, stats.data_ptr(),
+              wp.data_ptr() if warped else None, e.data_ptr() if err else None, pic.data_ptr() if image else None,
+              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    out = (stats,) + tuple(t for t in (wp, e, pic) if t is not None)
+    return out if len(out) > 1 else stats
+
+
+def photo_stats(t):
+    """The one read-back of warp_eval: its statistics tensor -> a dict of struct dflow_photo_stats's fields plus mean_err =
+    sum_err / n and above_pct = n_above * 100 / n; the two are NaN when n == 0 (no pixel's target is inside the frame)."""
+    s = _lib.PhotoStats.from_buffer_copy(t.cpu().numpy().tobytes())
+    d = {k: int(getattr(s, k)) for k in PHOTO_COUNTS}
+    d["sum_err"], d["max_err"] = float(s.sum_err), float(s.max_err)
+    n = d["n"]
+    nan = float("nan")
+    d["mean_err"] = d["sum_err"] / n if n else nan
+    d["above_pct"] = d["n_above"] * 100 / n if n else nan
+    return d

@@ -21,6 +21,11 @@ receive the strength e itself.  Without it (canny, the default) nothing changes.
 evaluation"): the forward flow ("fwd"), the sparse field ("sparse": the pixels that survive the consistency check) and, with
 --epic, the final dense flow ("epic"), each on the device where it lies.  One line per pair is printed, and eval.json in DIR
 holds the per-pair rows and, per kind, the totals accumulated on the device.  Without it output and files are unchanged.
+--pictures writes flowcolor_<pair>.png, the colour-wheel picture of the forward flow (pipeline.flow_color, DESIGN.md "Flow
+pictures and the warp check"), and with --epic flowcolor_epic_<pair>.png of the final dense flow.  --photo warps each pair's
+second image back onto the first by the forward flow ("fwd") and, with --epic, by the final dense flow ("epic")
+(pipeline.warp_eval, its default thresholds): no ground truth is involved.  One line per pair is printed, and photo.json in
+DIR holds the per-pair rows and, per kind, the totals accumulated on the device.  Without them output and files are unchanged.
 """
 import argparse
 import importlib
@@ -52,6 +57,10 @@ def parser():
                     help="edge source of --edges, --epic, --epic-refine and --prefilter: Canny, or the soft Pb-style strength")
     ap.add_argument("--eval", action="store_true",
                     help="compare each pair's forward, sparse and (with --epic) final flow with the true flow; writes eval.json")
+    ap.add_argument("--pictures", action="store_true",
+                    help="also write flowcolor_NN.png (colour-wheel picture of the forward flow) and, with --epic, flowcolor_epic_NN.png")
+    ap.add_argument("--photo", action="store_true",
+                    help="warp each pair's second image by the forward and (with --epic) final flow; prints the photometric error, writes photo.json")
     return ap
 
 
@@ -62,6 +71,14 @@ EVAL_ROW = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_tes
 def eval_row(st):
     """pipeline.eval_stats' dict as a JSON object: the fields of EVAL_ROW, a NaN (nothing compared) as null."""
     return {k: (None if st[k] != st[k] else st[k]) for k in EVAL_ROW}
+
+
+PHOTO_ROW = ("n", "n_outside", "n_unknown", "n_above", "sum_err", "max_err", "mean_err", "above_pct")
+
+
+def photo_row(st):
+    """pipeline.photo_stats' dict as a JSON object: the fields of PHOTO_ROW, a NaN (no target inside the frame) as null."""
+    return {k: (None if st[k] != st[k] else st[k]) for k in PHOTO_ROW}
 
 
 def main(argv=None):
@@ -143,6 +160,7 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
         eval_rows, eval_totals = [], {}
+        photo_rows, photo_totals = [], {}
         for pair in range(a.pairs):
             fwd, bwd = flows[2 * pair], flows[2 * pair + 1]
             sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
@@ -153,8 +171,9 @@ def main(argv=None):
             flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
             np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
             evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
-            if a.edges or a.epic:
+            if a.edges or a.epic or a.photo:
                 img1, img2 = images[pair] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[:2]
+            if a.edges or a.epic:
                 if a.edge_kind == "pb":
                     ivice = pipeline.pb_edges(img1)               # e itself for the GPU steps, 1 - e in the file
                 else:
@@ -186,6 +205,27 @@ def main(argv=None):
                                 % (kind, st["mean_epe"], st["outliers_pct"], st["kitti_fl_pct"], st["n"]))
                 eval_rows.append(row)
                 print("pair %d: %s" % (pair, "; ".join(line)))
+            if a.pictures:
+                for name, field in [("flowcolor", fwd)] + ([("flowcolor_epic", epic)] if a.epic else []):
+                    flowio.write_png8(os.path.join(a.out, "%s_%02d.png" % (name, pair)), pipeline.flow_color(field).cpu().numpy())
+            if a.photo:
+                row, line = {"pair": pair}, []
+                for kind, field in [("fwd", fwd)] + ([("epic", epic)] if a.epic else []):
+                    if kind not in photo_totals:
+                        photo_totals[kind] = torch.zeros(6, dtype=torch.int64, device=dev)
+                    st = pipeline.photo_stats(pipeline.warp_eval(img1, img2, field))      # the pair's own row
+                    pipeline.warp_eval(img1, img2, field, stats=photo_totals[kind])       # and into the kind's total, on the device
+                    row[kind] = photo_row(st)
+                    line.append("%s photometric error %.3f, %.2f%% > 10, over %d px (%d targets outside)"
+                                % (kind, st["mean_err"], st["above_pct"], st["n"], st["n_outside"]))
+                photo_rows.append(row)
+                print("pair %d: %s" % (pair, "; ".join(line)))
+        if a.photo:
+            import json
+            totals = {kind: photo_row(pipeline.photo_stats(t)) for kind, t in photo_totals.items()}
+            with open(os.path.join(a.out, "photo.json"), "w") as f:
+                json.dump({"size": [H, W], "bcd_times": a.bcd_times, "err_thresh": 10.0, "err_max": 30.0, "pairs": photo_rows,
+                           "totals": totals}, f, indent=1)
         if a.eval:
             import json
             totals = {kind: eval_row(pipeline.eval_stats(t)) for kind, t in eval_totals.items()}
