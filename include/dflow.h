@@ -177,6 +177,52 @@ int dflow_bcd_phase_batch(const dflow_params *p, int32_t npass, const int32_t *c
 int dflow_bcd_sweep_batch(const dflow_params *p, int32_t npass, const int32_t *const *d_nprop, int32_t *const *d_bestlabels,
                           void *const *d_ws, size_t ws_bytes, void *stream);
 
+/* How well the optimiser is doing: the energy of a labelling and the labels that differ from an earlier one (DESIGN.md "BCD
+ * statistics and the stop rule").  No counterpart in the reference, which runs a fixed number of sweeps.
+ * With l_p = d_bestlabels[p] and f_p the (dy, dx) of d_proposals[p][l_p], unpacked as everywhere else:
+ *   smooth_sum     sum over the 4-adjacent pairs (p, right of p) and (p, below p) of min(tpsi, |f_p - f_q|_1); pixels of the
+ *                  last column have no right pair, those of the last row no lower pair
+ *   n_pairs_trunc  pairs with |f_p - f_q|_1 >= tpsi
+ *   data_sum       sum over p of d_lcosts[p][l_p], each float32 widened to double, NOT multiplied by lamda
+ *   n_data_trunc   pixels with d_lcosts[p][l_p] >= tphi (a float32 compare)
+ *   n_changed      pixels with d_bestlabels[p] != d_prev_labels[p]; 0 when d_prev_labels is NULL
+ *   n_bad_label    pixels with l_p < 0 or l_p >= d_nprop[p] (or >= label_pitch, which no slot lies beyond).  Such a pixel adds
+ *                  1 to n_bad_label, 1 to n_changed (when d_prev_labels is given) and nothing else: it has no data cost, and
+ *                  the pairs it is in are skipped
+ * The image energy is E = lamda * data_sum + smooth_sum; the caller forms it on the host in double.  This is the energy
+ * sum lamda lcost + sum_{4-adjacent} min(tpsi, |f_p - f_q|_1) of the whole labelling.  It is NOT the per-chain energy a phase
+ * of the reference algorithm minimises (the side terms of a chain look along it at its own old labels, and its pair cost
+ * forbids incompatible pairs where a compatible one exists), so E can rise in a phase and in a sweep.
+ * d_prev_out (NULL to skip) receives a copy of d_bestlabels, bad labels included; it may be d_prev_labels itself, which then
+ * holds the labels to compare the next sweep against.
+ * Only pich, picw, maxnprop, label_pitch, tpsi and tphi of *p are read and checked: 1 <= pich, picw <= 8192 (a labelling needs
+ * no cell grid), 1 <= maxnprop <= label_pitch <= DFLOW_MAX_LABELS, label_pitch a multiple of 16, 1 <= tpsi <= 8, tphi finite
+ * and >= 0.
+ * All integer fields are exact and independent of any order.  data_sum is a sum in double in the fixed order of
+ * dflow_flow_eval (per lane, a fixed tree per block, the blocks' partial sums in block order in a second launch; no floating
+ * atomics): the same inputs give the same 8 bytes on every call.
+ * dflow_bcd_stats_batch does the same for npass passes of identical parameters in one pair of launches per 8 passes, the
+ * pass as a grid dimension: the arrays are HOST arrays of npass device pointers (as for dflow_bcd_sweep_batch); d_prev[i] is
+ * both d_prev_labels and d_prev_out of pass i, the array or any entry may be NULL; d_stats[i] receives, byte for byte, what
+ * the single call writes for pass i.  Its workspace is npass times dflow_bcd_stats_workspace_bytes.
+ * A bad parameter, a NULL required pointer (every one but d_prev_labels, d_prev_out, d_prev and its entries), a d_stats or
+ * d_ws that is not 8-byte aligned (both hold doubles) or an npass outside [1, 1024] returns DFLOW_EINVAL, a NULL or too small
+ * workspace DFLOW_ENOSPC, both before anything is launched.  The calls are asynchronous on `stream`, allocate nothing, read nothing back and can be captured into a graph.
+ * The workspace is the calls' own (one partial result per block of the first launch, at most 32 KiB per pass): the records
+ * dflow_bcd_prepare left in the passes' workspaces are neither read nor written, so statistics may be taken between sweeps.
+ * dflow_bcd_stats_workspace_bytes returns 0 (and sets dflow_last_error) for parameters outside the range. */
+struct dflow_bcd_stats {        /* no typedef: the entry point has the name, so write `struct dflow_bcd_stats` */
+    uint64_t smooth_sum, n_pairs_trunc, n_data_trunc, n_changed, n_bad_label;
+    double data_sum;
+};
+size_t dflow_bcd_stats_workspace_bytes(const dflow_params *p);
+int dflow_bcd_stats(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
+                    const int32_t *d_bestlabels, const int32_t *d_prev_labels, int32_t *d_prev_out,
+                    struct dflow_bcd_stats *d_stats, void *d_ws, size_t ws_bytes, void *stream);
+int dflow_bcd_stats_batch(const dflow_params *p, int32_t npass, const uint32_t *const *d_proposals, const float *const *d_lcosts,
+                          const int32_t *const *d_nprop, const int32_t *const *d_bestlabels, int32_t *const *d_prev,
+                          struct dflow_bcd_stats *d_stats, void *d_ws, size_t ws_bytes, void *stream);
+
 /* vratiKonacniFlow, python bcd.py:90-95 / daisy i flann.py:192-197. */
 int dflow_labels_to_flow(const dflow_params *p, const uint32_t *d_proposals, const int32_t *d_bestlabels,
                          float *d_flow, void *stream);

@@ -49,6 +49,12 @@ class PhotoStats(C.Structure):
                 ("sum_err", C.c_double), ("max_err", C.c_float), ("reserved", C.c_uint32)]
 
 
+class BcdStats(C.Structure):
+    """struct dflow_bcd_stats (include/dflow.h): what dflow_bcd_stats leaves in device memory, 48 bytes."""
+    _fields_ = [("smooth_sum", C.c_uint64), ("n_pairs_trunc", C.c_uint64), ("n_data_trunc", C.c_uint64), ("n_changed", C.c_uint64),
+                ("n_bad_label", C.c_uint64), ("data_sum", C.c_double)]
+
+
 _vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
 _pp = C.POINTER(Params)
 # every C-ABI function: name -> (return type, argument types)
@@ -69,6 +75,9 @@ _SIGNATURES = {
     "dflow_bcd_sweep": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_bcd_phase_batch": (C.c_int, [_pp, _i32, _vp, _vp, _i32, _vp, _sz, _vp]),
     "dflow_bcd_sweep_batch": (C.c_int, [_pp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_bcd_stats_workspace_bytes": (_sz, [_pp]),
+    "dflow_bcd_stats": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_bcd_stats_batch": (C.c_int, [_pp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_labels_to_flow": (C.c_int, [_pp, _vp, _vp, _vp, _vp]),
     "dflow_fb_consistency": (C.c_int, [_pp, _vp, _vp, _f32, _vp, _vp]),
     "dflow_pack_compat": (C.c_int, [_pp, _vp, _vp, _vp, _vp]),

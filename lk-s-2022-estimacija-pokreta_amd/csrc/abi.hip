@@ -232,6 +232,55 @@ int dflow_bcd_sweep_batch(const dflow_params *p, int32_t npass, const int32_t *c
     return DFLOW_OK;
 }
 
+// the fields of *p a labelling's statistics depend on; no cell grid, so frames below 8 x 8 pass
+static int bcd_stats_check_params(const char *fn, const dflow_params *p)
+{
+    if (!p) return dflow_set_error(DFLOW_EINVAL, "%s: params is NULL", fn);
+    if (p->pich < 1 || p->picw < 1 || p->pich > 8192 || p->picw > 8192)
+        return dflow_set_error(DFLOW_EINVAL, "%s: image size %dx%d outside [1,8192]", fn, p->picw, p->pich);
+    if (p->label_pitch < 16 || p->label_pitch % 16 != 0 || p->label_pitch > DFLOW_MAX_LABELS)
+        return dflow_set_error(DFLOW_EINVAL, "%s: label_pitch=%d must be a multiple of 16 in [16,%d]", fn, p->label_pitch, DFLOW_MAX_LABELS);
+    if (p->maxnprop < 1 || p->maxnprop > p->label_pitch)
+        return dflow_set_error(DFLOW_EINVAL, "%s: maxnprop=%d outside [1,label_pitch=%d]", fn, p->maxnprop, p->label_pitch);
+    if (p->tpsi < 1 || p->tpsi > 8) return dflow_set_error(DFLOW_EINVAL, "%s: tpsi=%d outside [1,8]", fn, p->tpsi);
+    if (!isfinite(p->tphi) || p->tphi < 0.0f) return dflow_set_error(DFLOW_EINVAL, "%s: tphi=%g must be finite and >= 0", fn, (double)p->tphi);
+    return DFLOW_OK;
+}
+
+size_t dflow_bcd_stats_workspace_bytes(const dflow_params *p)
+{
+    if (bcd_stats_check_params(__func__, p) != DFLOW_OK) return 0;
+    return bcd_stats_ws_bytes(p->pich, p->picw);
+}
+
+int dflow_bcd_stats_batch(const dflow_params *p, int32_t npass, const uint32_t *const *d_proposals, const float *const *d_lcosts,
+                          const int32_t *const *d_nprop, const int32_t *const *d_bestlabels, int32_t *const *d_prev,
+                          struct dflow_bcd_stats *d_stats, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
+    if (npass < 1 || npass > 1024) return dflow_set_error(DFLOW_EINVAL, "%s: npass=%d outside [1,1024]", __func__, npass);
+    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
+    for (int i = 0; i < npass; i++)
+        if (!d_proposals[i] || !d_lcosts[i] || !d_nprop[i] || !d_bestlabels[i])
+            return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
+    rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
+    CHECK_WS((size_t)npass * bcd_stats_ws_bytes(p->pich, p->picw));
+    return launch_bcd_stats_batch(p, npass, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_prev, d_prev, d_stats, d_ws,
+                                  (hipStream_t)stream);
+}
+
+int dflow_bcd_stats(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
+                    const int32_t *d_bestlabels, const int32_t *d_prev_labels, int32_t *d_prev_out, struct dflow_bcd_stats *d_stats,
+                    void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
+    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
+    rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
+    CHECK_WS(bcd_stats_ws_bytes(p->pich, p->picw));
+    return launch_bcd_stats_batch(p, 1, &d_proposals, &d_lcosts, &d_nprop, &d_bestlabels, &d_prev_labels, &d_prev_out, d_stats,
+                                  d_ws, (hipStream_t)stream);
+}
+
 int dflow_labels_to_flow(const dflow_params *p, const uint32_t *d_proposals, const int32_t *d_bestlabels, float *d_flow,
                          void *stream)
 {

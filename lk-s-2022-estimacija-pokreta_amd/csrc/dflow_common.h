@@ -243,6 +243,12 @@ int launch_bcd_phase_batch(const dflow_params *p, int npass, const int32_t *cons
 size_t bcd_ws_bytes(const dflow_params *p);
 int launch_bcd_prepare(const dflow_params *p, const uint32_t *proposals, const float *lcosts, const int32_t *nprop, void *ws,
                        hipStream_t s);
+// bcd_stats.hip: energy and label-change statistics of npass labellings (arguments validated by the caller); prev, prev_out
+// and their entries may be NULL; ws holds npass regions of bcd_stats_ws_bytes
+size_t bcd_stats_ws_bytes(int H, int W);
+int launch_bcd_stats_batch(const dflow_params *p, int npass, const uint32_t *const *proposals, const float *const *lcosts,
+                           const int32_t *const *nprop, const int32_t *const *labels, const int32_t *const *prev,
+                           int32_t *const *prev_out, struct dflow_bcd_stats *stats, void *ws, hipStream_t s);
 int launch_labels_to_flow(const dflow_params *p, const uint32_t *proposals, const int32_t *bestlabels, float *flow,
                           hipStream_t s);
 int launch_pack_compat(const dflow_params *p, const uint32_t *proposals, const int32_t *nprop, uint8_t *packed, hipStream_t s);

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import bcdstats
 from . import flowio
 
 DEFAULT_CELLS = {  # (pich, picw) -> (cellh, cellw)
@@ -167,10 +168,38 @@ class DiscreteFlow:
         _lib.call("dflow_bcd_phase", self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), phase,
                   self.ws.data_ptr(), self.ws_bytes, self._stream())
 
-    def ceoBCD(self, bcd_times, on_sweep=None):
-        """python bcd.py:261-284.  on_sweep(w) is called after sweep w (the reference saves .npy there)."""
+    def bcd_stats(self, prev=None, prev_out=None):
+        """dflow_bcd_stats of the current labelling (DESIGN.md "BCD statistics and the stop rule"): its data and smoothness
+        sums, and with prev, an (H,W) int32 device tensor of earlier labels, the number of labels that differ from it.
+        prev_out, an (H,W) int32 device tensor (it may be prev itself), receives a copy of the labels.  Returns struct
+        dflow_bcd_stats as a device tensor of 6 int64 words (bcd_stats_dict reads it back).  Runs on torch's current stream
+        and does not wait for it; its small workspace is its own, the BCD records in self.ws stay valid."""
+        H, W = self.p.pich, self.p.picw
+        for name, t in (("prev", prev), ("prev_out", prev_out)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == (H, W)
+                                      and t.is_contiguous() and t.device == self.device):
+                raise ValueError("bcd_stats: %s must be a contiguous int32 (%d,%d) tensor on %s" % (name, H, W, self.device))
+        ws, ws_bytes = _bcd_stats_ws(self, 1)
+        out = torch.empty(6, dtype=torch.int64, device=self.device)
+        _lib.call("dflow_bcd_stats", self._pp(), self.proposals.data_ptr(), self.lcosts.data_ptr(), self.nprop.data_ptr(),
+                  self.bestlabels.data_ptr(), prev.data_ptr() if prev is not None else None,
+                  prev_out.data_ptr() if prev_out is not None else None, out.data_ptr(), ws.data_ptr(), ws_bytes, self._stream())
+        return out
+
+    def ceoBCD(self, bcd_times, on_sweep=None, stop=None):
+        """python bcd.py:261-284.  on_sweep(w) is called after sweep w (the reference saves .npy there).
+        stop=None: bcd_times sweeps and nothing else, returns None.  stop a dict with "changed_frac" and / or "rel_energy"
+        (bcdstats.check_stop; an empty dict: statistics only): dflow_bcd_stats runs before the first sweep and after every
+        sweep, and after every sweep its 48 bytes are read back -- the ONE synchronisation per sweep that a stop rule costs.
+        The pass ends after the sweep with n_changed / (H*W) <= changed_frac, or with (E_prev - E) / E_prev <= rel_energy (a
+        rise of E included: the labels kept are those of the sweep just done, nothing is rolled back), or after bcd_times
+        sweeps.  Returns the history, a list of dicts (bcd_stats_dict plus "sweep"): entry 0 is the labelling before the
+        first sweep (n_changed 0), entry w the one after sweep w."""
+        stop = bcdstats.check_stop(stop)
         if not self._bcd_ready:
             self.pakovanje()
+        if stop is not None:
+            return ceoBCD_batch([self], bcd_times, on_sweep=on_sweep, stop=stop)[0]
         for w in range(1, bcd_times + 1):
             _lib.call("dflow_bcd_sweep", self._pp(), self.proposals.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(),
                       self.ws.data_ptr(), self.ws_bytes, self._stream())
@@ -233,13 +262,36 @@ class DiscreteFlow:
         self._bcd_ready = False
 
 
-def ceoBCD_batch(passes, bcd_times, on_sweep=None):
+def _bcd_stats_ws(df, npass):
+    """The workspace of dflow_bcd_stats(_batch) for npass passes like df: kept on df, grown when a larger batch asks."""
+    per_pass = int(_lib.lib().dflow_bcd_stats_workspace_bytes(C.byref(df.p)))
+    _lib.check(0 if per_pass else -1, "dflow_bcd_stats_workspace_bytes")
+    need = per_pass * npass
+    ws = getattr(df, "_stats_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = df._stats_ws = torch.empty(need, dtype=torch.uint8, device=df.device)
+    return ws, need
+
+
+def bcd_stats_dict(t, lamda, npix):
+    """The one read-back of DiscreteFlow.bcd_stats: its statistics tensor -> a dict of struct dflow_bcd_stats's fields plus
+    energy = lamda * data_sum + smooth_sum, formed here in double, and changed_frac = n_changed / npix, npix the pixel count
+    H*W of the pass (the 48 bytes do not carry it)."""
+    return bcdstats.stats_dict(t.cpu().numpy().tobytes(), lamda, int(npix))
+
+
+def ceoBCD_batch(passes, bcd_times, on_sweep=None, stop=None):
     """ceoBCD (python bcd.py:261-284) for several independent passes at once (forward and backward runs of a pair, several
     pairs: README.md:40 of the reference): the chains of all passes share the four launches of a sweep.  `passes` are
-    DiscreteFlow objects of identical geometry and constants on one device; results equal separate ceoBCD calls."""
+    DiscreteFlow objects of identical geometry and constants on one device; results equal separate ceoBCD calls.
+    stop as for DiscreteFlow.ceoBCD: None runs bcd_times sweeps with no other launch and returns None.  With a dict, one
+    dflow_bcd_stats_batch follows every sweep (and one precedes the first), the 48 bytes per pass are read back together --
+    one synchronisation per sweep -- and a pass whose rule fires leaves the later launches; on_sweep(w) is called while any
+    pass still runs.  Returns one history per pass (see ceoBCD)."""
     passes = list(passes)
+    stop = bcdstats.check_stop(stop)
     if not passes:
-        return
+        return None if stop is None else []
     first = passes[0]
     for df in passes:
         if bytes(df.p) != bytes(first.p) and (df.p.pich, df.p.picw, df.p.cellh, df.p.cellw, df.p.tpsi, df.p.lamda, df.p.label_pitch, df.p.maxnprop) != \
@@ -249,15 +301,62 @@ def ceoBCD_batch(passes, bcd_times, on_sweep=None):
             raise ValueError("batched passes must live on one device")
         if not df._bcd_ready:
             df.pakovanje()
-    n = len(passes)
-    arr = C.c_void_p * n
-    nprop = arr(*[df.nprop.data_ptr() for df in passes])
-    best = arr(*[df.bestlabels.data_ptr() for df in passes])
-    ws = arr(*[df.ws.data_ptr() for df in passes])
+
+    def ptrs(dfs, get):
+        return (C.c_void_p * len(dfs))(*[get(df).data_ptr() for df in dfs])
+
+    if stop is None:
+        n = len(passes)
+        nprop, best, ws = ptrs(passes, lambda d: d.nprop), ptrs(passes, lambda d: d.bestlabels), ptrs(passes, lambda d: d.ws)
+        for w in range(1, bcd_times + 1):
+            _lib.call("dflow_bcd_sweep_batch", first._pp(), n, nprop, best, ws, first.ws_bytes, first._stream())
+            if on_sweep is not None:
+                on_sweep(w)
+        return None
+
+    if any(df.p.tphi != first.p.tphi for df in passes):
+        raise ValueError("batched passes must share geometry and constants")
+    npix = first.p.pich * first.p.picw
+    lamda = first.p.lamda
+    prevs = [torch.empty_like(df.bestlabels) for df in passes]
+    histories = [[] for _ in passes]
+
+    def stats(active):
+        """dflow_bcd_stats_batch of the passes `active` (indices) against prevs, which then hold their labels; one read-back."""
+        dfs = [passes[i] for i in active]
+        pv = (C.c_void_p * len(dfs))(*[prevs[i].data_ptr() for i in active])
+        sws, sws_bytes = _bcd_stats_ws(first, len(dfs))
+        out = torch.empty((len(dfs), 6), dtype=torch.int64, device=first.device)
+        _lib.call("dflow_bcd_stats_batch", first._pp(), len(dfs), ptrs(dfs, lambda d: d.proposals), ptrs(dfs, lambda d: d.lcosts),
+                  ptrs(dfs, lambda d: d.nprop), ptrs(dfs, lambda d: d.bestlabels), pv, out.data_ptr(), sws.data_ptr(), sws_bytes,
+                  first._stream())
+        raw = out.cpu().numpy().tobytes()               # the synchronisation
+        return [bcdstats.stats_dict(raw[k * bcdstats.STATS_BYTES:(k + 1) * bcdstats.STATS_BYTES], lamda, npix) for k in range(len(dfs))]
+
+    active = list(range(len(passes)))
+    # entry 0, the labelling the sweeps start from: compared with itself (n_changed 0); its energy is the E_prev of sweep 1
+    for i in active:
+        prevs[i].copy_(passes[i].bestlabels)
+    for i, d in zip(active, stats(active)):
+        d["sweep"] = 0
+        histories[i].append(d)
     for w in range(1, bcd_times + 1):
-        _lib.call("dflow_bcd_sweep_batch", first._pp(), n, nprop, best, ws, first.ws_bytes, first._stream())
+        if not active:
+            break
+        dfs = [passes[i] for i in active]
+        _lib.call("dflow_bcd_sweep_batch", first._pp(), len(dfs), ptrs(dfs, lambda d: d.nprop), ptrs(dfs, lambda d: d.bestlabels),
+                  ptrs(dfs, lambda d: d.ws), first.ws_bytes, first._stream())
+        still = []
+        for i, d in zip(active, stats(active)):
+            d["sweep"] = w
+            e_prev = histories[i][-1]["energy"]
+            histories[i].append(d)
+            if not bcdstats.should_stop(stop, d, e_prev):
+                still.append(i)
+        active = still
         if on_sweep is not None:
             on_sweep(w)
+    return histories
 
 
 def fb_consistency(fwd, bwd, tresh, p=None):

@@ -6,6 +6,13 @@
 Loads the files the first CLI wrote (ucitajSvePodatkeDoBCD, python bcd.py:67-81; always the "posle 00"
 labels), runs bcd_times BCD sweeps on the GPU and, after every sweep, writes the reference's two .npy files
 (python bcd.py:282-283) plus a Middlebury .flo of the same flow.  packedksets.npy is neither needed nor read.
+
+--stats prints one line per sweep (sweep, changed labels, data sum, smoothness sum, image energy E = lamda * data + smooth;
+sweep 0 is the labelling that was loaded) and writes "Daisy output slike <idx> backward=<b> bcd_stats.json" (DESIGN.md "BCD
+statistics and the stop rule").  --stop-changed F ends the run after the sweep that changed at most the fraction F of the
+labels, --stop-energy R after the sweep that lowered E by at most the fraction R (a rise of E included); bcd_times stays the
+upper bound, and the files of the sweeps not run are not written.  Each of the three costs one read-back of 48 bytes per
+sweep; without them the run issues exactly the launches it always did.
 """
 import argparse
 import importlib
@@ -18,11 +25,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("picindex"); ap.add_argument("backward", choices=("0", "1")); ap.add_argument("bcd_times", type=int)
     ap.add_argument("--cell"); ap.add_argument("--device", default="cuda:0")
-    a = ap.parse_args(argv)
+    importlib.import_module(PKG + ".bcdstats").add_cli_options(ap, "--stats")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    bcdstats = importlib.import_module(PKG + ".bcdstats")
+    stop = bcdstats.stop_from_args(a)
     pipeline = importlib.import_module(PKG + ".pipeline")
     flowio = importlib.import_module(PKG + ".flowio")
     idx = a.picindex if len(a.picindex) > 1 else "0" + a.picindex
@@ -42,7 +56,12 @@ def main(argv=None):
         flowio.write_flo(flowio.flow_name(idx, a.backward, w)[:-4] + ".flo", flow)
         print("uradjen bcd broj", w)
 
-    df.ceoBCD(a.bcd_times, on_sweep=save)
+    history = df.ceoBCD(a.bcd_times, on_sweep=save, stop=stop)
+    if history is not None:
+        for h in history:
+            print(bcdstats.format_row(h))
+        bcdstats.write_history_json(flowio.stage_name(idx, a.backward, "bcd_stats")[:-4] + ".json",
+                                    [("backward=%s" % a.backward, history)], df.p.lamda, a.bcd_times, stop, (pich, picw))
 
 
 if __name__ == "__main__":

@@ -26,6 +26,11 @@ pictures and the warp check"), and with --epic flowcolor_epic_<pair>.png of the 
 second image back onto the first by the forward flow ("fwd") and, with --epic, by the final dense flow ("epic")
 (pipeline.warp_eval, its default thresholds): no ground truth is involved.  One line per pair is printed, and photo.json in
 DIR holds the per-pair rows and, per kind, the totals accumulated on the device.  Without them output and files are unchanged.
+--bcd-stats records, for every pass, the labels changed, the data and smoothness sums and the image energy E after every BCD
+sweep (pipeline.ceoBCD_batch with a stop rule, DESIGN.md "BCD statistics and the stop rule") and writes them to bcd_stats.json
+in DIR.  --stop-changed F ends a pass after the sweep that changed at most the fraction F of its labels, --stop-energy R
+after the sweep that lowered E by at most the fraction R; --bcd-times stays the upper bound and names the flow files.  Each
+of the three costs one read-back of 48 bytes per pass and sweep; without them the launches are unchanged.
 """
 import argparse
 import importlib
@@ -61,6 +66,7 @@ def parser():
                     help="also write flowcolor_NN.png (colour-wheel picture of the forward flow) and, with --epic, flowcolor_epic_NN.png")
     ap.add_argument("--photo", action="store_true",
                     help="warp each pair's second image by the forward and (with --epic) final flow; prints the photometric error, writes photo.json")
+    importlib.import_module(PKG + ".bcdstats").add_cli_options(ap, "--bcd-stats")
     return ap
 
 
@@ -91,6 +97,9 @@ def main(argv=None):
     synth = importlib.import_module(PKG + ".synth")
     flowio = importlib.import_module(PKG + ".flowio")
     evaluate = importlib.import_module(PKG + ".evaluate")
+    bcdstats = importlib.import_module(PKG + ".bcdstats")
+    stop = bcdstats.stop_from_args(a)
+    histories = {}                                  # pass index -> per-sweep history (this rank's passes)
     H, W = (int(v) for v in a.size.lower().split("x"))
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -138,7 +147,10 @@ def main(argv=None):
                     done.append(e)
             for e in done:
                 main.wait_event(e)
-            pipeline.ceoBCD_batch(dfs[:len(part)], a.bcd_times)
+            hist = pipeline.ceoBCD_batch(dfs[:len(part)], a.bcd_times, stop=stop)
+            if hist is not None:
+                for desc, h in zip(part, hist):
+                    histories[passes.index(desc)] = h
             flows += [df.vratiKonacniFlow().clone() for df in dfs[:len(part)]]
         return flows
 
@@ -157,8 +169,18 @@ def main(argv=None):
         if rank == 0:
             print("%d passes (%d pairs, forward + backward) of %dx%d, bcd_times=%d on %d GPU(s): %.1f ms = %.2f ms per pass = %.1f Mpix/s"
                   % (len(passes), a.pairs, W, H, a.bcd_times, world, dt * 1e3, dt * 1e3 / len(passes), len(passes) * H * W / dt / 1e6))
+    if stop is not None and world > 1:
+        gathered = [None] * world
+        dist.all_gather_object(gathered, histories)
+        histories = {k: v for g in gathered for k, v in g.items()}
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
+        if stop is not None:
+            named = [("pair %d backward=%d" % passes[i], histories[i]) for i in sorted(histories)]
+            bcdstats.write_history_json(os.path.join(a.out, "bcd_stats.json"), named, dfs[0].p.lamda, a.bcd_times, stop, (H, W))
+            for name, h in named:
+                print("%s: %d sweeps, E %.3f -> %.3f, last sweep changed %d labels"
+                      % (name, len(h) - 1, h[0]["energy"], h[-1]["energy"], h[-1]["n_changed"]))
         eval_rows, eval_totals = [], {}
         photo_rows, photo_totals = [], {}
         for pair in range(a.pairs):
