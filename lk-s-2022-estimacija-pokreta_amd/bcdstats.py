@@ -21,6 +21,11 @@ def stats_dict(buf, lamda, npix):
     return d
 
 
+def stats_dicts(buf, lamda, npix):
+    """The read-back of dflow_bcd_stats_batch, one struct dflow_bcd_stats per pass -> one stats_dict per pass."""
+    return [stats_dict(buf[at:at + STATS_BYTES], lamda, npix) for at in range(0, len(buf), STATS_BYTES)]
+
+
 def check_stop(stop):
     """The stop rule of ceoBCD / ceoBCD_batch: None (fixed sweep count, no statistics), or a dict with changed_frac and / or
     rel_energy (an empty dict: statistics per sweep, no rule).  Returns a plain dict of floats; raises ValueError otherwise."""

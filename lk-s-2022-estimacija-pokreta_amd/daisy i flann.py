@@ -31,11 +31,6 @@ PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
 PACKEDKSETS_DEFAULT_LIMIT = 256 << 20
 
 
-def read_bgr(path):
-    from PIL import Image
-    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[..., ::-1])
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("picindex"); ap.add_argument("backward", choices=("0", "1")); ap.add_argument("dopython", choices=("0", "1"))
@@ -57,8 +52,8 @@ def main(argv=None):
     else:
         other = "1" if a.backward == "0" else "0"                           # :19-22
         base = "../data_scene_flow/training/image_2/0001" + idx + "_1"
-        pic1 = read_bgr(a.image1 or base + a.backward + ".png")
-        pic2 = read_bgr(a.image2 or base + other + ".png")
+        pic1 = flowio.read_bgr(a.image1 or base + a.backward + ".png")
+        pic2 = flowio.read_bgr(a.image2 or base + other + ".png")
         if not (a.image1 or a.image2):                                      # :34-35,52-53 KITTI crop
             pic1, pic2 = pic1[:375, :1241], pic2[:375, :1241]
     pich, picw = pic1.shape[:2]

@@ -30,14 +30,14 @@ def canny_ivice(fileslike, binfile, low=CANNY_LOW, high=CANNY_HIGH):
 
 def canny_ivice_tensor(fileslike, low=CANNY_LOW, high=CANNY_HIGH):
     """The (H,W) float32 ivice map of canny_ivice as a device tensor, without writing it."""
-    read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+    read_bgr = importlib.import_module(PKG + ".flowio").read_bgr
     pipeline = importlib.import_module(PKG + ".pipeline")
     return pipeline.canny_edges(read_bgr(fileslike), low, high, ivice=True)[1]
 
 
 def pb_strength_tensor(fileslike, radius=PB_RADIUS):
     """The (H,W) float32 edge strength e of the image file (dflow_pb_edges) as a device tensor."""
-    read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+    read_bgr = importlib.import_module(PKG + ".flowio").read_bgr
     pipeline = importlib.import_module(PKG + ".pipeline")
     return pipeline.pb_edges(read_bgr(fileslike), radius)
 

@@ -159,7 +159,7 @@ def main(argv=None):
         (im1, im2, edges_bin, matches, out), nn, k, method = parse_args(argv)
         refine, refine_preset = parse_refine(argv)
         prefilter = parse_prefilter(argv)
-        read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+        read_bgr = importlib.import_module(PKG + ".flowio").read_bgr
         img1, img2 = read_bgr(im1), read_bgr(im2)
         H, W = img1.shape[:2]
         if img2.shape[:2] != (H, W):

@@ -1,6 +1,9 @@
 """On-disk contract of the hot path: the reference's .npy names/dtypes/[dy,dx] order,
 plus Middlebury .flo ([u=dx, v=dy] float32) as parsed by visualization.py:9-29.
+Also the image files of the command-line tools: read_bgr, read_image and write_picture.
 """
+import os
+
 import numpy as np
 
 FLO_MAGIC = np.float32(202021.25)
@@ -195,3 +198,56 @@ def write_kitti_flow_png(path, uvv):
     img[..., 1] = np.where(valid, uvv[..., 1].astype(np.float64) * 64.0 + 32768, 0).astype(np.uint16)
     img[..., 2] = valid
     write_png16(path, img)
+
+
+# ------------------------------------------------------------------------------------------------ images and pictures
+def read_bgr(path):
+    """Any image file PIL opens -> (H,W,3) uint8 BGR (what cv2.imread gives)."""
+    from PIL import Image
+    return np.ascontiguousarray(np.asarray(Image.open(path).convert("RGB"))[..., ::-1])
+
+
+def read_image(path):
+    """An image file -> (H,W,3) uint8 BGR, without an imaging library: '.npy', '.png' (read_png8) or '.ppm' (binary P6)."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        img = np.load(path)
+    elif ext == ".png":
+        img = read_png8(path)
+    elif ext == ".ppm":
+        data = open(path, "rb").read()
+        tok, pos = [], 0
+        while len(tok) < 4:                                 # P6, width, height, maxval; '#' starts a comment
+            while data[pos:pos + 1].isspace():
+                pos += 1
+            if data[pos:pos + 1] == b"#":
+                pos = data.index(b"\n", pos)
+                continue
+            end = pos
+            while not data[end:end + 1].isspace():
+                end += 1
+            tok.append(data[pos:end])
+            pos = end
+        w, h = int(tok[1]), int(tok[2])
+        if tok[0] != b"P6" or int(tok[3]) != 255 or len(data) - (pos + 1) < 3 * w * h:
+            raise ValueError("%s: only binary P6 files with maxval 255 are supported" % path)
+        img = np.frombuffer(data, np.uint8, 3 * w * h, pos + 1).reshape(h, w, 3)[..., ::-1]
+    else:
+        raise ValueError("%s: images are read as .npy, .ppm or .png" % path)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("%s: not a (H,W,3) uint8 image (%s %s)" % (path, img.shape, img.dtype))
+    return np.ascontiguousarray(img)
+
+
+def write_picture(path, bgr):
+    """A (H,W,3) uint8 BGR picture -> path, by its extension: '.png' (write_png8) and '.ppm' (binary P6) without an imaging
+    library, anything else through PIL."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".png":
+        write_png8(path, bgr)
+    elif ext == ".ppm":
+        with open(path, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (bgr.shape[1], bgr.shape[0]) + np.ascontiguousarray(bgr[..., ::-1]).tobytes())
+    else:
+        from PIL import Image
+        Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(path)

@@ -11,16 +11,14 @@ levels, the mean absolute difference of the three channels), the share of pixels
 were compared and how many targets lie outside the frame or are unknown; --warped writes the warped second image,
 --error-picture the jet picture of min(err, E) / E (E default 30).  T and E are this build's defaults.  Both forms may be
 combined.
-Flows are read with evaluate.ucitajFlow ('.png' KITTI, '.npy' the hot path's fields, '.flo' Middlebury), images as '.npy'
-((H,W,3) uint8 BGR), '.ppm' (binary P6) or '.png' (8-bit RGB or grey, flowio.read_png8); pictures are written with
-visualization.write_picture ('.png' and '.ppm' always, anything else through PIL if it can be imported).
+Flows are read with evaluate.ucitajFlow ('.png' KITTI, '.npy' the hot path's fields, '.flo' Middlebury), images with
+flowio.read_image as '.npy' ((H,W,3) uint8 BGR), '.ppm' (binary P6) or '.png' (8-bit RGB or grey); pictures are written with
+flowio.write_picture ('.png' and '.ppm' always, anything else through PIL if it can be imported).
 """
 import argparse
 import importlib
 import os
 import sys
-
-import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
@@ -39,38 +37,6 @@ def parser():
     return ap
 
 
-def read_image(path):
-    """An image file -> (H,W,3) uint8 BGR."""
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".npy":
-        img = np.load(path)
-    elif ext == ".png":
-        img = importlib.import_module(PKG + ".flowio").read_png8(path)
-    elif ext == ".ppm":
-        data = open(path, "rb").read()
-        tok, pos = [], 0
-        while len(tok) < 4:                                 # P6, width, height, maxval; '#' starts a comment
-            while data[pos:pos + 1].isspace():
-                pos += 1
-            if data[pos:pos + 1] == b"#":
-                pos = data.index(b"\n", pos)
-                continue
-            end = pos
-            while not data[end:end + 1].isspace():
-                end += 1
-            tok.append(data[pos:end])
-            pos = end
-        w, h = int(tok[1]), int(tok[2])
-        if tok[0] != b"P6" or int(tok[3]) != 255 or len(data) - (pos + 1) < 3 * w * h:
-            raise ValueError("%s: only binary P6 files with maxval 255 are supported" % path)
-        img = np.frombuffer(data, np.uint8, 3 * w * h, pos + 1).reshape(h, w, 3)[..., ::-1]
-    else:
-        raise ValueError("%s: images are read as .npy, .ppm or .png" % path)
-    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-        raise ValueError("%s: not a (H,W,3) uint8 image (%s %s)" % (path, img.shape, img.dtype))
-    return np.ascontiguousarray(img)
-
-
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
@@ -80,7 +46,8 @@ def main(argv=None):
         ap.error("--warped and --error-picture need --warp")
     evaluate = importlib.import_module(PKG + ".evaluate")
     pipeline = importlib.import_module(PKG + ".pipeline")
-    write_picture = importlib.import_module(PKG + ".visualization").write_picture
+    flowio = importlib.import_module(PKG + ".flowio")
+    read_image, write_picture = flowio.read_image, flowio.write_picture
     flow = evaluate.ucitajFlow(a.flow)
     if a.picture is not None:
         write_picture(a.picture, pipeline.flow_color(flow, a.max_flow).cpu().numpy())

@@ -54,6 +54,7 @@ class DiscreteFlow:
         self._img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)          # staging of host images
         self._img2 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
         self._bcd_ready = False     # compat matrices in the workspace are valid for the current proposals
+        self._stats_ws = None       # workspace of dflow_bcd_stats(_batch), made by _bcd_stats_ws when first asked for
 
     # ------------------------------------------------------------------ helpers
     @property
@@ -77,18 +78,30 @@ class DiscreteFlow:
                                   % ("binary16 (H,W,72)" if self._descr_f16 else "float32 (H,W,68)"))
         return C.byref(self.p)
 
+    def _state_args(self):
+        """The tail of the front-end calls: the six state pointers, then workspace, its size and the stream."""
+        return (self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(), self.lcosts.data_ptr(),
+                self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes, self._stream())
+
+    def _bcd_stats_ws(self, npass):
+        """The workspace of dflow_bcd_stats(_batch) for npass passes like this one: kept here, grown when a larger batch asks."""
+        per_pass = int(_lib.lib().dflow_bcd_stats_workspace_bytes(C.byref(self.p)))
+        _lib.check(0 if per_pass else -1, "dflow_bcd_stats_workspace_bytes")
+        need = per_pass * npass
+        if self._stats_ws is None or self._stats_ws.numel() < need:
+            self._stats_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._stats_ws, need
+
     # ------------------------------------------------------------------ reference-named stages
     def _device_image(self, picture, staging):
         """picture: (H,W,3) uint8 BGR, numpy (copied into the device tensor `staging`) or a contiguous device tensor."""
-        H, W = self.p.pich, self.p.picw
+        t = _check(picture, "DiscreteFlow", "picture", torch.uint8, (self.p.pich, self.p.picw, 3))
         if isinstance(picture, np.ndarray):
-            if picture.shape != (H, W, 3) or picture.dtype != np.uint8:
-                raise ValueError("picture must be uint8 (%d,%d,3)" % (H, W))
-            staging.copy_(torch.from_numpy(np.ascontiguousarray(picture)))
+            staging.copy_(t)
             return staging
-        if tuple(picture.shape) != (H, W, 3) or picture.dtype != torch.uint8 or not picture.is_contiguous():
-            raise ValueError("picture must be a contiguous uint8 (%d,%d,3) tensor" % (H, W))
-        return picture
+        if not t.is_contiguous():
+            raise ValueError("DiscreteFlow: picture must be a contiguous tensor")
+        return t
 
     def izracunajDaisy(self, picture, out=None):
         """daisy i flann.py:69-77.  picture: (H,W,3) uint8 BGR (numpy or device tensor) -> (H,W,68) f32 tensor (with
@@ -120,9 +133,7 @@ class DiscreteFlow:
     def generisi(self):
         """napraviCD2 + generisi, daisy i flann.py:144-189."""
         self._bcd_ready = False
-        _lib.call("dflow_knn_proposals", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
-                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                  self._stream())
+        _lib.call("dflow_knn_proposals", self._pp(), *self._state_args())
 
     KNN_KERNELS = ("basis", "prep", "knn_screen_kernel", "knn_resolve_kernel", "knn_fix_kernel", "knn_finalize_kernel")
 
@@ -131,9 +142,7 @@ class DiscreteFlow:
         self._bcd_ready = False
         ms = (C.c_float * 6)()
         issued = C.c_double()
-        _lib.call("dflow_knn_proposals_timed", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
-                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                  self._stream(), ms, C.byref(issued))
+        _lib.call("dflow_knn_proposals_timed", self._pp(), *self._state_args(), ms, C.byref(issued))
         return dict(zip(self.KNN_KERNELS, (float(v) for v in ms))), float(issued.value)
 
     KNN_STATS = ("lists_exact", "flags", "lists", "entries", "events", "max_entries_per_lane", "zero_queries", "bad_queries",
@@ -151,9 +160,7 @@ class DiscreteFlow:
     def nasumicni(self):
         """daisy i flann.py:205-233."""
         self._bcd_ready = False
-        _lib.call("dflow_neighbour_proposals", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), self.proposals.data_ptr(),
-                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                  self._stream())
+        _lib.call("dflow_neighbour_proposals", self._pp(), *self._state_args())
 
     def pakovanje(self):
         """daisy i flann.py:256-309: compat bit matrices, built into the workspace for the chain kernel."""
@@ -179,11 +186,10 @@ class DiscreteFlow:
             if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == (H, W)
                                       and t.is_contiguous() and t.device == self.device):
                 raise ValueError("bcd_stats: %s must be a contiguous int32 (%d,%d) tensor on %s" % (name, H, W, self.device))
-        ws, ws_bytes = _bcd_stats_ws(self, 1)
+        ws, ws_bytes = self._bcd_stats_ws(1)
         out = torch.empty(6, dtype=torch.int64, device=self.device)
         _lib.call("dflow_bcd_stats", self._pp(), self.proposals.data_ptr(), self.lcosts.data_ptr(), self.nprop.data_ptr(),
-                  self.bestlabels.data_ptr(), prev.data_ptr() if prev is not None else None,
-                  prev_out.data_ptr() if prev_out is not None else None, out.data_ptr(), ws.data_ptr(), ws_bytes, self._stream())
+                  self.bestlabels.data_ptr(), _ptr(prev), _ptr(prev_out), out.data_ptr(), ws.data_ptr(), ws_bytes, self._stream())
         return out
 
     def ceoBCD(self, bcd_times, on_sweep=None, stop=None):
@@ -262,17 +268,6 @@ class DiscreteFlow:
         self._bcd_ready = False
 
 
-def _bcd_stats_ws(df, npass):
-    """The workspace of dflow_bcd_stats(_batch) for npass passes like df: kept on df, grown when a larger batch asks."""
-    per_pass = int(_lib.lib().dflow_bcd_stats_workspace_bytes(C.byref(df.p)))
-    _lib.check(0 if per_pass else -1, "dflow_bcd_stats_workspace_bytes")
-    need = per_pass * npass
-    ws = getattr(df, "_stats_ws", None)
-    if ws is None or ws.numel() < need:
-        ws = df._stats_ws = torch.empty(need, dtype=torch.uint8, device=df.device)
-    return ws, need
-
-
 def bcd_stats_dict(t, lamda, npix):
     """The one read-back of DiscreteFlow.bcd_stats: its statistics tensor -> a dict of struct dflow_bcd_stats's fields plus
     energy = lamda * data_sum + smooth_sum, formed here in double, and changed_frac = n_changed / npix, npix the pixel count
@@ -293,70 +288,61 @@ def ceoBCD_batch(passes, bcd_times, on_sweep=None, stop=None):
     if not passes:
         return None if stop is None else []
     first = passes[0]
+
+    def constants(p):
+        return (p.pich, p.picw, p.cellh, p.cellw, p.tpsi, p.lamda, p.label_pitch, p.maxnprop)
     for df in passes:
-        if bytes(df.p) != bytes(first.p) and (df.p.pich, df.p.picw, df.p.cellh, df.p.cellw, df.p.tpsi, df.p.lamda, df.p.label_pitch, df.p.maxnprop) != \
-                (first.p.pich, first.p.picw, first.p.cellh, first.p.cellw, first.p.tpsi, first.p.lamda, first.p.label_pitch, first.p.maxnprop):
+        if constants(df.p) != constants(first.p):
             raise ValueError("batched passes must share geometry and constants")
         if df.device != first.device:
             raise ValueError("batched passes must live on one device")
         if not df._bcd_ready:
             df.pakovanje()
 
-    def ptrs(dfs, get):
-        return (C.c_void_p * len(dfs))(*[get(df).data_ptr() for df in dfs])
+    def ptrs(active, get):
+        return (C.c_void_p * len(active))(*[get(passes[i]).data_ptr() for i in active])
 
-    if stop is None:
-        n = len(passes)
-        nprop, best, ws = ptrs(passes, lambda d: d.nprop), ptrs(passes, lambda d: d.bestlabels), ptrs(passes, lambda d: d.ws)
-        for w in range(1, bcd_times + 1):
-            _lib.call("dflow_bcd_sweep_batch", first._pp(), n, nprop, best, ws, first.ws_bytes, first._stream())
-            if on_sweep is not None:
-                on_sweep(w)
-        return None
+    def sweep_args(active):
+        return len(active), ptrs(active, lambda d: d.nprop), ptrs(active, lambda d: d.bestlabels), ptrs(active, lambda d: d.ws)
 
-    if any(df.p.tphi != first.p.tphi for df in passes):
-        raise ValueError("batched passes must share geometry and constants")
-    npix = first.p.pich * first.p.picw
-    lamda = first.p.lamda
-    prevs = [torch.empty_like(df.bestlabels) for df in passes]
-    histories = [[] for _ in passes]
-
-    def stats(active):
-        """dflow_bcd_stats_batch of the passes `active` (indices) against prevs, which then hold their labels; one read-back."""
-        dfs = [passes[i] for i in active]
-        pv = (C.c_void_p * len(dfs))(*[prevs[i].data_ptr() for i in active])
-        sws, sws_bytes = _bcd_stats_ws(first, len(dfs))
-        out = torch.empty((len(dfs), 6), dtype=torch.int64, device=first.device)
-        _lib.call("dflow_bcd_stats_batch", first._pp(), len(dfs), ptrs(dfs, lambda d: d.proposals), ptrs(dfs, lambda d: d.lcosts),
-                  ptrs(dfs, lambda d: d.nprop), ptrs(dfs, lambda d: d.bestlabels), pv, out.data_ptr(), sws.data_ptr(), sws_bytes,
+    def stats(active, w):
+        """dflow_bcd_stats_batch of the passes `active` (indices) against prevs, which then hold their labels; one read-back.
+        Appends entry w to their histories and returns the indices of those that sweep w does not stop."""
+        sws, sws_bytes = first._bcd_stats_ws(len(active))
+        out = torch.empty((len(active), 6), dtype=torch.int64, device=first.device)
+        _lib.call("dflow_bcd_stats_batch", first._pp(), len(active), ptrs(active, lambda d: d.proposals), ptrs(active, lambda d: d.lcosts),
+                  ptrs(active, lambda d: d.nprop), ptrs(active, lambda d: d.bestlabels),
+                  (C.c_void_p * len(active))(*[prevs[i].data_ptr() for i in active]), out.data_ptr(), sws.data_ptr(), sws_bytes,
                   first._stream())
         raw = out.cpu().numpy().tobytes()               # the synchronisation
-        return [bcdstats.stats_dict(raw[k * bcdstats.STATS_BYTES:(k + 1) * bcdstats.STATS_BYTES], lamda, npix) for k in range(len(dfs))]
+        still = []
+        for i, d in zip(active, bcdstats.stats_dicts(raw, first.p.lamda, first.p.pich * first.p.picw)):
+            d["sweep"] = w
+            if w == 0 or not bcdstats.should_stop(stop, d, histories[i][-1]["energy"]):
+                still.append(i)
+            histories[i].append(d)
+        return still
 
     active = list(range(len(passes)))
-    # entry 0, the labelling the sweeps start from: compared with itself (n_changed 0); its energy is the E_prev of sweep 1
-    for i in active:
-        prevs[i].copy_(passes[i].bestlabels)
-    for i, d in zip(active, stats(active)):
-        d["sweep"] = 0
-        histories[i].append(d)
+    if stop is not None:
+        if any(df.p.tphi != first.p.tphi for df in passes):
+            raise ValueError("batched passes must share geometry and constants")
+        histories = [[] for _ in passes]
+        # entry 0, the labelling the sweeps start from: compared with itself (n_changed 0); its energy is the E_prev of sweep 1
+        prevs = [df.bestlabels.clone() for df in passes]
+        stats(active, 0)
+    args = sweep_args(active)
     for w in range(1, bcd_times + 1):
         if not active:
             break
-        dfs = [passes[i] for i in active]
-        _lib.call("dflow_bcd_sweep_batch", first._pp(), len(dfs), ptrs(dfs, lambda d: d.nprop), ptrs(dfs, lambda d: d.bestlabels),
-                  ptrs(dfs, lambda d: d.ws), first.ws_bytes, first._stream())
-        still = []
-        for i, d in zip(active, stats(active)):
-            d["sweep"] = w
-            e_prev = histories[i][-1]["energy"]
-            histories[i].append(d)
-            if not bcdstats.should_stop(stop, d, e_prev):
-                still.append(i)
-        active = still
+        _lib.call("dflow_bcd_sweep_batch", first._pp(), *args, first.ws_bytes, first._stream())
+        if stop is not None:
+            still = stats(active, w)
+            if len(still) != len(active):
+                active, args = still, sweep_args(still)
         if on_sweep is not None:
             on_sweep(w)
-    return histories
+    return None if stop is None else histories
 
 
 def fb_consistency(fwd, bwd, tresh, p=None):
@@ -372,24 +358,77 @@ def fb_consistency(fwd, bwd, tresh, p=None):
     return out
 
 
+# ---------------------------------------------------------------------- image-plane stages: what every wrapper below shares
+def _check(a, fn, name, dtype, shape):
+    """The input gate: an array or tensor -> the tensor, as it is (no copy of a tensor, no device touched), if it has `dtype`
+    and fits `shape`: one entry per dimension, None for any size, a tuple for a choice of sizes.  ValueError otherwise."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != dtype or t.dim() != len(shape) or any(
+            want is not None and got not in (want if isinstance(want, tuple) else (want,)) for got, want in zip(t.shape, shape)):
+        text = ",".join("HWC"[i] if want is None else "|".join(map(str, want)) if isinstance(want, tuple) else str(want)
+                        for i, want in enumerate(shape))
+        raise ValueError("%s: %s must be %s (%s), got %s %s" % (fn, name, str(dtype)[6:], text, tuple(t.shape), t.dtype))
+    return t
+
+
+def _device_of(*tensors):
+    """The device of the first CUDA tensor among the arguments, else the current CUDA device."""
+    for t in tensors:
+        if t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _on(dev, *tensors):
+    return [t.to(dev).contiguous() for t in tensors]
+
+
+def _out(cond, shape, dtype, dev):
+    return torch.empty(shape, dtype=dtype, device=dev) if cond else None
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _layout(flow):
+    return _lib.EVAL_UVV if flow.shape[2] == 3 else _lib.EVAL_DYDX
+
+
+def _stats_arg(stats, nwords, dev, fn):
+    """The stats= argument of flow_eval / warp_eval -> (tensor, accumulate): a new tensor to overwrite, or the caller's."""
+    if stats is None:
+        return torch.empty(nwords, dtype=torch.int64, device=dev), False
+    if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and stats.numel() == nwords and stats.is_contiguous()
+            and stats.device == dev):
+        raise ValueError("%s: stats must be the int64[%d] tensor of an earlier call on %s" % (fn, nwords, dev))
+    return stats, True
+
+
+def _struct_dict(cls, t):
+    """The read-back of a statistics tensor: struct `cls` of _lib -> a dict of its fields, ints and floats, without `reserved`."""
+    s = cls.from_buffer_copy(t.cpu().numpy().tobytes())
+    return {name: getattr(s, name) for name, _ in cls._fields_ if name != "reserved"}
+
+
+def _pct(x, n):
+    return x * 100 / n if n else float("nan")
+
+
 def canny_edges(bgr, low=100, high=200, ivice=True):
     """canny_ivice, edge.py:19-35 (cv2.cvtColor BGR2GRAY -> cv2.GaussianBlur((3,3), 0) -> cv2.Canny(low, high)) on a (H,W,3)
     uint8 BGR image (numpy array or tensor; a host image is uploaded to the current device) -> (edges, ivice): device
     tensors (H,W) uint8 0/255 and (H,W) float32 (255 - edges) / 255, or None with ivice=False.  Runs on torch's current
     stream and does not wait for it."""
-    if not isinstance(bgr, torch.Tensor):
-        bgr = torch.from_numpy(np.ascontiguousarray(bgr))
-    if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
-        raise ValueError("canny_edges wants a (H,W,3) uint8 BGR image, got %s %s" % (tuple(bgr.shape), bgr.dtype))
-    if not bgr.is_cuda:
-        bgr = bgr.to(torch.device("cuda", torch.cuda.current_device()))
-    bgr = bgr.contiguous()
+    bgr = _check(bgr, "canny_edges", "bgr", torch.uint8, (None, None, 3))
+    dev = _device_of(bgr)
+    bgr, = _on(dev, bgr)
     H, W, _ = bgr.shape
-    ws, ws_bytes = _lib.workspace("dflow_canny_workspace_bytes", H, W, bgr.device)
-    edges = torch.empty((H, W), dtype=torch.uint8, device=bgr.device)
-    iv = torch.empty((H, W), dtype=torch.float32, device=bgr.device) if ivice else None
-    _lib.call("dflow_canny_edges", H, W, bgr.data_ptr(), float(low), float(high), edges.data_ptr(),
-              iv.data_ptr() if iv is not None else None, ws.data_ptr(), ws_bytes, _lib.stream(bgr.device))
+    ws, ws_bytes = _lib.workspace("dflow_canny_workspace_bytes", H, W, dev)
+    edges = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    iv = _out(ivice, (H, W), torch.float32, dev)
+    _lib.call("dflow_canny_edges", H, W, bgr.data_ptr(), float(low), float(high), edges.data_ptr(), _ptr(iv), ws.data_ptr(), ws_bytes,
+              _lib.stream(dev))
     return edges, iv
 
 
@@ -399,19 +438,14 @@ def pb_edges(bgr, radius=5, per_orientation=False):
     with disc radius 1..7 -> the (H,W) float32 device tensor e in [0,1], the edge strength dflow_epic_interpolate and
     dflow_epic_prefilter are defined on; with per_orientation=True (e, m): m the (H,W,8) float32 responses of the 8
     orientations, e their maximum.  Runs on torch's current stream and does not wait for it."""
-    if not isinstance(bgr, torch.Tensor):
-        bgr = torch.from_numpy(np.ascontiguousarray(bgr))
-    if bgr.dtype != torch.uint8 or bgr.dim() != 3 or bgr.shape[2] != 3:
-        raise ValueError("pb_edges wants a (H,W,3) uint8 BGR image, got %s %s" % (tuple(bgr.shape), bgr.dtype))
-    if not bgr.is_cuda:
-        bgr = bgr.to(torch.device("cuda", torch.cuda.current_device()))
-    bgr = bgr.contiguous()
+    bgr = _check(bgr, "pb_edges", "bgr", torch.uint8, (None, None, 3))
+    dev = _device_of(bgr)
+    bgr, = _on(dev, bgr)
     H, W, _ = bgr.shape
-    ws, ws_bytes = _lib.workspace("dflow_pb_workspace_bytes", H, W, bgr.device)
-    e = torch.empty((H, W), dtype=torch.float32, device=bgr.device)
-    m = torch.empty((H, W, 8), dtype=torch.float32, device=bgr.device) if per_orientation else None
-    _lib.call("dflow_pb_edges", H, W, bgr.data_ptr(), int(radius), e.data_ptr(), m.data_ptr() if m is not None else None,
-              ws.data_ptr(), ws_bytes, _lib.stream(bgr.device))
+    ws, ws_bytes = _lib.workspace("dflow_pb_workspace_bytes", H, W, dev)
+    e = torch.empty((H, W), dtype=torch.float32, device=dev)
+    m = _out(per_orientation, (H, W, 8), torch.float32, dev)
+    _lib.call("dflow_pb_edges", H, W, bgr.data_ptr(), int(radius), e.data_ptr(), _ptr(m), ws.data_ptr(), ws_bytes, _lib.stream(dev))
     return (e, m) if per_orientation else e
 
 
@@ -428,35 +462,18 @@ def epic_interpolate(sparse, edges, nn=100, k=0.8, method="LA", aux=False, lists
     that stream (the Voronoi loop reads a counter back)."""
     if method not in EPIC_METHODS:
         raise ValueError("epic_interpolate: method must be 'LA' or 'NW', not %r" % (method,))
-    dev = sparse.device if isinstance(sparse, torch.Tensor) and sparse.is_cuda else torch.device("cuda", torch.cuda.current_device())
-
-    def upload(a, name, shape):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(a))
-        if a.dtype != torch.float32 or tuple(a.shape) != shape:
-            raise ValueError("epic_interpolate: %s must be float32 %s, got %s %s" % (name, shape, tuple(a.shape), a.dtype))
-        return a.to(dev).contiguous()
-    if not isinstance(sparse, torch.Tensor):
-        sparse = torch.from_numpy(np.ascontiguousarray(sparse))
-    if sparse.dim() != 3 or sparse.shape[2] != 3:
-        raise ValueError("epic_interpolate: sparse must be (H,W,3) [U,V,valid], got %s" % (tuple(sparse.shape),))
-    H, W = int(sparse.shape[0]), int(sparse.shape[1])
-    sparse = upload(sparse, "sparse", (H, W, 3))
-    edges = upload(edges, "edges", (H, W))
+    sparse = _check(sparse, "epic_interpolate", "sparse", torch.float32, (None, None, 3))
+    H, W, _ = sparse.shape
+    edges = _check(edges, "epic_interpolate", "edges", torch.float32, (H, W))
+    dev = _device_of(sparse)
+    sparse, edges = _on(dev, sparse, edges)
     ws, ws_bytes = _lib.workspace("dflow_epic_workspace_bytes", H, W, dev)
     flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
-    S = D = lst = list_g = None
-    if aux:
-        S = torch.empty((H, W), dtype=torch.int32, device=dev)
-        D = torch.empty((H, W), dtype=torch.int32, device=dev)
-        if lists:
-            lst = torch.empty((H * W, int(nn)), dtype=torch.int32, device=dev)
-            list_g = torch.empty((H * W, int(nn)), dtype=torch.int64, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
+    S, D = _out(aux, (H, W), torch.int32, dev), _out(aux, (H, W), torch.int32, dev)
+    lst = _out(aux and lists, (H * W, int(nn)), torch.int32, dev)
+    list_g = _out(aux and lists, (H * W, int(nn)), torch.int64, dev)
     _lib.call("dflow_epic_interpolate", H, W, sparse.data_ptr(), edges.data_ptr(), int(nn), float(k), EPIC_METHODS[method],
-              flow.data_ptr(), ptr(S), ptr(D), ptr(lst), ptr(list_g), ws.data_ptr(), ws_bytes, _lib.stream(dev))
+              flow.data_ptr(), _ptr(S), _ptr(D), _ptr(lst), _ptr(list_g), ws.data_ptr(), ws_bytes, _lib.stream(dev))
     return (flow, S, D, lst, list_g) if aux else flow
 
 
@@ -478,33 +495,20 @@ def epic_prefilter(sparse, edges, img1=None, saliency_th=None, pref_nn=25, pref_
         saliency_th = PREFILTER_DEFAULTS["saliency_th"] if img1 is not None else 0.0
     if img1 is None and saliency_th != 0:
         raise ValueError("epic_prefilter: saliency_th=%g needs img1 (without an image only saliency_th = 0 runs)" % saliency_th)
-
-    def upload(a, name, dtype, shape):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(a))
-        if a.dtype != dtype or tuple(a.shape) != shape:
-            raise ValueError("epic_prefilter: %s must be %s %s, got %s %s" % (name, dtype, shape, tuple(a.shape), a.dtype))
-        return a.to(dev).contiguous()
-    if not hasattr(sparse, "shape") or len(sparse.shape) != 3 or sparse.shape[2] != 3:
-        raise ValueError("epic_prefilter: sparse must be (H,W,3) [U,V,valid]")
-    dev = sparse.device if isinstance(sparse, torch.Tensor) and sparse.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    H, W = int(sparse.shape[0]), int(sparse.shape[1])
-    sparse = upload(sparse, "sparse", torch.float32, (H, W, 3))
-    edges = upload(edges, "edges", torch.float32, (H, W))
+    sparse = _check(sparse, "epic_prefilter", "sparse", torch.float32, (None, None, 3))
+    H, W, _ = sparse.shape
+    edges = _check(edges, "epic_prefilter", "edges", torch.float32, (H, W))
     if img1 is not None:
-        img1 = upload(img1, "img1", torch.uint8, (H, W, 3))
+        img1 = _check(img1, "epic_prefilter", "img1", torch.uint8, (H, W, 3))
+    dev = _device_of(sparse)
+    sparse, edges = _on(dev, sparse, edges)
+    if img1 is not None:
+        img1, = _on(dev, img1)
     ws, ws_bytes = _lib.workspace("dflow_epic_prefilter_workspace_bytes", H, W, dev)
     out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-    reason = saliency = estimate = None
-    if aux:
-        reason = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        saliency = torch.empty((H, W), dtype=torch.float32, device=dev)
-        estimate = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
-
-    def ptr(t):
-        return t.data_ptr() if t is not None else None
-    _lib.call("dflow_epic_prefilter", H, W, ptr(img1), sparse.data_ptr(), edges.data_ptr(), float(saliency_th), int(pref_nn),
-              float(pref_th), float(k), out.data_ptr(), ptr(reason), ptr(saliency), ptr(estimate), ws.data_ptr(), ws_bytes,
+    reason, saliency, estimate = _out(aux, (H, W), torch.uint8, dev), _out(aux, (H, W), torch.float32, dev), _out(aux, (H, W, 2), torch.float32, dev)
+    _lib.call("dflow_epic_prefilter", H, W, _ptr(img1), sparse.data_ptr(), edges.data_ptr(), float(saliency_th), int(pref_nn),
+              float(pref_th), float(k), out.data_ptr(), _ptr(reason), _ptr(saliency), _ptr(estimate), ws.data_ptr(), ws_bytes,
               _lib.stream(dev))
     return (out, reason, saliency, estimate) if aux else out
 
@@ -546,21 +550,12 @@ def variational_refine(img1, img2, flow, preset=None, **params):
     -> the refined (H,W,2) float32 [dy,dx] device tensor.  preset and params as in var_params (alpha, gamma, delta, sigma,
     sor_omega, niter_outer, niter_inner, niter_solver, flags).  Runs on torch's current stream and does not wait for it."""
     p = var_params(preset, **params)
-
-    def tensor(a, name, dtype, last):
-        if not isinstance(a, torch.Tensor):
-            a = torch.from_numpy(np.ascontiguousarray(a))
-        if a.dtype != dtype or a.dim() != 3 or a.shape[2] != last:
-            raise ValueError("variational_refine: %s must be (H,W,%d) %s, got %s %s" % (name, last, dtype, tuple(a.shape), a.dtype))
-        return a
-    flow = tensor(flow, "flow", torch.float32, 2)
-    img1, img2 = tensor(img1, "img1", torch.uint8, 3), tensor(img2, "img2", torch.uint8, 3)
-    H, W = int(flow.shape[0]), int(flow.shape[1])
-    if tuple(img1.shape[:2]) != (H, W) or tuple(img2.shape[:2]) != (H, W):
-        raise ValueError("variational_refine: images %s, %s and flow %s differ in size"
-                         % (tuple(img1.shape[:2]), tuple(img2.shape[:2]), (H, W)))
-    dev = flow.device if flow.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    flow, img1, img2 = (t.to(dev).contiguous() for t in (flow, img1, img2))
+    flow = _check(flow, "variational_refine", "flow", torch.float32, (None, None, 2))
+    H, W, _ = flow.shape
+    img1 = _check(img1, "variational_refine", "img1", torch.uint8, (H, W, 3))
+    img2 = _check(img2, "variational_refine", "img2", torch.uint8, (H, W, 3))
+    dev = _device_of(flow)
+    flow, img1, img2 = _on(dev, flow, img1, img2)
     ws, ws_bytes = _lib.workspace("dflow_var_workspace_bytes", H, W, dev)
     out = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
     _lib.call("dflow_var_refine", H, W, img1.data_ptr(), img2.data_ptr(), flow.data_ptr(), C.byref(p), out.data_ptr(),
@@ -575,9 +570,6 @@ def epic_last_stats():
     return rounds.value, dict(zip(("voronoi", "graph", "lists", "fill"), (float(v) for v in ms)))
 
 
-EVAL_COUNTS = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_test_valid")
-
-
 def flow_eval(test, gt, abs_thresh=3.0, err=False, image=False, stats=None):
     """errorImage, visualization.py:128-156, on the GPU (dflow_flow_eval, DESIGN.md "Flow evaluation"): the end-point error
     of `test` against the ground truth `gt`, (H,W,3) float32 [U,V,valid].  test is (H,W,3) float32 [U,V,valid] (what
@@ -587,32 +579,18 @@ def flow_eval(test, gt, abs_thresh=3.0, err=False, image=False, stats=None):
     asked for, err: (H,W) float32, the error at the compared pixels and -1 elsewhere, and image: (H,W,3) uint8, the reference's
     colour picture in BGR order.  stats: the tensor of an earlier call (or torch.zeros(8, int64)) to add this field's values
     to, so that a batch is totalled on the device.  Runs on torch's current stream and does not wait for it."""
-    def tensor(a):
-        return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
-    test, gt = tensor(test), tensor(gt)
-    if gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[2] != 3:
-        raise ValueError("flow_eval: gt must be (H,W,3) float32 [U,V,valid], got %s %s" % (tuple(gt.shape), gt.dtype))
-    H, W = int(gt.shape[0]), int(gt.shape[1])
-    if test.dtype != torch.float32 or test.dim() != 3 or tuple(test.shape[:2]) != (H, W) or test.shape[2] not in (2, 3):
-        raise ValueError("flow_eval: test must be float32 (%d,%d,3) [U,V,valid] or (%d,%d,2) [dy,dx], got %s %s"
-                         % (H, W, H, W, tuple(test.shape), test.dtype))
-    dev = next((t.device for t in (test, gt) if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
-    test, gt = test.to(dev).contiguous(), gt.to(dev).contiguous()
-    flags = 0
-    if stats is None:
-        stats = torch.empty(8, dtype=torch.int64, device=dev)
-    else:
-        if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and stats.numel() == 8 and stats.is_contiguous()
-                and stats.device == dev):
-            raise ValueError("flow_eval: stats must be the int64[8] tensor of an earlier call on %s" % dev)
-        flags = _lib.EVAL_FLAG_ACCUMULATE
+    gt = _check(gt, "flow_eval", "gt", torch.float32, (None, None, 3))
+    H, W, _ = gt.shape
+    test = _check(test, "flow_eval", "test", torch.float32, (H, W, (2, 3)))
+    dev = _device_of(test, gt)
+    test, gt = _on(dev, test, gt)
+    stats, accumulate = _stats_arg(stats, 8, dev, "flow_eval")
     ws, ws_bytes = _lib.workspace("dflow_eval_workspace_bytes", H, W, dev)
-    e = torch.empty((H, W), dtype=torch.float32, device=dev) if err else None
-    img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if image else None
-    _lib.call("dflow_flow_eval", H, W, test.data_ptr(), _lib.EVAL_UVV if test.shape[2] == 3 else _lib.EVAL_DYDX, gt.data_ptr(),
-              float(abs_thresh), flags, stats.data_ptr(), e.data_ptr() if err else None, img.data_ptr() if image else None,
-              ws.data_ptr(), ws_bytes, _lib.stream(dev))
-    out = (stats,) + ((e,) if err else ()) + ((img,) if image else ())
+    e, img = _out(err, (H, W), torch.float32, dev), _out(image, (H, W, 3), torch.uint8, dev)
+    _lib.call("dflow_flow_eval", H, W, test.data_ptr(), _layout(test), gt.data_ptr(), float(abs_thresh),
+              _lib.EVAL_FLAG_ACCUMULATE if accumulate else 0, stats.data_ptr(), _ptr(e), _ptr(img), ws.data_ptr(), ws_bytes,
+              _lib.stream(dev))
+    out = (stats,) + tuple(t for t in (e, img) if t is not None)
     return out if len(out) > 1 else stats
 
 
@@ -620,23 +598,10 @@ def eval_stats(t):
     """The one read-back of flow_eval: its statistics tensor -> a dict of struct dflow_eval_stats's fields plus mean_epe
     = sum_err / n, outliers_pct = n_out_abs * 100 / n (the reference's two numbers) and kitti_fl_pct = n_out_kitti * 100 / n;
     the three are NaN when n == 0."""
-    s = _lib.EvalStats.from_buffer_copy(t.cpu().numpy().tobytes())
-    d = {k: int(getattr(s, k)) for k in EVAL_COUNTS}
-    d["sum_err"], d["max_err"] = float(s.sum_err), float(s.max_err)
-    n = d["n"]
-    nan = float("nan")
-    d["mean_epe"] = d["sum_err"] / n if n else nan
-    d["outliers_pct"] = d["n_out_abs"] * 100 / n if n else nan
-    d["kitti_fl_pct"] = d["n_out_kitti"] * 100 / n if n else nan
+    d = _struct_dict(_lib.EvalStats, t)
+    d["mean_epe"] = d["sum_err"] / d["n"] if d["n"] else float("nan")
+    d["outliers_pct"], d["kitti_fl_pct"] = _pct(d["n_out_abs"], d["n"]), _pct(d["n_out_kitti"], d["n"])
     return d
-
-
-def _flow_tensor(flow, what):
-    """A flow for flow_color / warp_eval: a float32 (H,W,3) [U,V,valid] or (H,W,2) [dy,dx] tensor or array, as it is."""
-    t = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow))
-    if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] not in (2, 3):
-        raise ValueError("%s: flow must be float32 (H,W,3) [U,V,valid] or (H,W,2) [dy,dx], got %s %s" % (what, tuple(t.shape), t.dtype))
-    return t
 
 
 def flow_color(flow, max_flow=None, return_radius=False):
@@ -647,20 +612,16 @@ def flow_color(flow, max_flow=None, return_radius=False):
     nothing is read back).  Returns the (H,W,3) uint8 picture in BGR order, black where the flow is unknown (not valid, not
     finite, or beyond 1e9), and with return_radius=True also the radius used as a one-element float32 device tensor.  Runs on
     torch's current stream and does not wait for it."""
-    flow = _flow_tensor(flow, "flow_color")
-    H, W = int(flow.shape[0]), int(flow.shape[1])
-    dev = flow.device if flow.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    flow = flow.to(dev).contiguous()
+    flow = _check(flow, "flow_color", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    dev = _device_of(flow)
+    flow, = _on(dev, flow)
     ws, ws_bytes = _lib.workspace("dflow_flow_color_workspace_bytes", H, W, dev)
     img = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-    radius = torch.empty(1, dtype=torch.float32, device=dev) if return_radius else None
-    _lib.call("dflow_flow_color", H, W, flow.data_ptr(), _lib.EVAL_UVV if flow.shape[2] == 3 else _lib.EVAL_DYDX,
-              0.0 if max_flow is None else float(max_flow), img.data_ptr(), radius.data_ptr() if return_radius else None,
-              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    radius = _out(return_radius, 1, torch.float32, dev)
+    _lib.call("dflow_flow_color", H, W, flow.data_ptr(), _layout(flow), 0.0 if max_flow is None else float(max_flow), img.data_ptr(),
+              _ptr(radius), ws.data_ptr(), ws_bytes, _lib.stream(dev))
     return (img, radius) if return_radius else img
-
-
-PHOTO_COUNTS = ("n", "n_outside", "n_unknown", "n_above")
 
 
 def warp_eval(img1, img2, flow, err_thresh=10.0, err_max=30.0, warped=False, err=False, image=False, stats=None):
@@ -674,29 +635,17 @@ def warp_eval(img1, img2, flow, err_thresh=10.0, err_max=30.0, warped=False, err
     of min(err, err_max) / err_max in BGR order.  All three are 0 / -1 / black where the flow is unknown or leaves the frame.
     stats: the tensor of an earlier call (or torch.zeros(6, int64)) to add this pair's values to, so that a batch is
     totalled on the device.  Runs on torch's current stream and does not wait for it."""
-    flow = _flow_tensor(flow, "warp_eval")
-    H, W = int(flow.shape[0]), int(flow.shape[1])
-    imgs = [a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)) for a in (img1, img2)]
-    for a in imgs:
-        if a.dtype != torch.uint8 or tuple(a.shape) != (H, W, 3):
-            raise ValueError("warp_eval: the images must be (%d,%d,3) uint8 BGR, got %s %s" % (H, W, tuple(a.shape), a.dtype))
-    dev = next((t.device for t in [flow] + imgs if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
-    flow, img1, img2 = (t.to(dev).contiguous() for t in [flow] + imgs)
-    flags = 0
-    if stats is None:
-        stats = torch.empty(6, dtype=torch.int64, device=dev)
-    else:
-        if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and stats.numel() == 6 and stats.is_contiguous()
-                and stats.device == dev):
-            raise ValueError("warp_eval: stats must be the int64[6] tensor of an earlier call on %s" % dev)
-        flags = _lib.WARP_FLAG_ACCUMULATE
+    flow = _check(flow, "warp_eval", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    img1 = _check(img1, "warp_eval", "img1: the images", torch.uint8, (H, W, 3))
+    img2 = _check(img2, "warp_eval", "img2: the images", torch.uint8, (H, W, 3))
+    dev = _device_of(flow, img1, img2)
+    flow, img1, img2 = _on(dev, flow, img1, img2)
+    stats, accumulate = _stats_arg(stats, 6, dev, "warp_eval")
     ws, ws_bytes = _lib.workspace("dflow_warp_eval_workspace_bytes", H, W, dev)
-    wp = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if warped else None
-    e = torch.empty((H, W), dtype=torch.float32, device=dev) if err else None
-    pic = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if image else None
-    _lib.call("dflow_warp_eval", H, W, img1.data_ptr(), img2.data_ptr(), flow.data_ptr(),
-              _lib.EVAL_UVV if flow.shape[2] == 3 else _lib.EVAL_DYDX, float(err_thresh), float(err_max), flags, stats.data_ptr(),
-              wp.data_ptr() if warped else None, e.data_ptr() if err else None, pic.data_ptr() if image else None,
+    wp, e, pic = _out(warped, (H, W, 3), torch.uint8, dev), _out(err, (H, W), torch.float32, dev), _out(image, (H, W, 3), torch.uint8, dev)
+    _lib.call("dflow_warp_eval", H, W, img1.data_ptr(), img2.data_ptr(), flow.data_ptr(), _layout(flow), float(err_thresh),
+              float(err_max), _lib.WARP_FLAG_ACCUMULATE if accumulate else 0, stats.data_ptr(), _ptr(wp), _ptr(e), _ptr(pic),
               ws.data_ptr(), ws_bytes, _lib.stream(dev))
     out = (stats,) + tuple(t for t in (wp, e, pic) if t is not None)
     return out if len(out) > 1 else stats
@@ -705,11 +654,7 @@ def warp_eval(img1, img2, flow, err_thresh=10.0, err_max=30.0, warped=False, err
 def photo_stats(t):
     """The one read-back of warp_eval: its statistics tensor -> a dict of struct dflow_photo_stats's fields plus mean_err =
     sum_err / n and above_pct = n_above * 100 / n; the two are NaN when n == 0 (no pixel's target is inside the frame)."""
-    s = _lib.PhotoStats.from_buffer_copy(t.cpu().numpy().tobytes())
-    d = {k: int(getattr(s, k)) for k in PHOTO_COUNTS}
-    d["sum_err"], d["max_err"] = float(s.sum_err), float(s.max_err)
-    n = d["n"]
-    nan = float("nan")
-    d["mean_err"] = d["sum_err"] / n if n else nan
-    d["above_pct"] = d["n_above"] * 100 / n if n else nan
+    d = _struct_dict(_lib.PhotoStats, t)
+    d["mean_err"] = d["sum_err"] / d["n"] if d["n"] else float("nan")
+    d["above_pct"] = _pct(d["n_above"], d["n"])
     return d

@@ -66,194 +66,236 @@ def parser():
                     help="also write flowcolor_NN.png (colour-wheel picture of the forward flow) and, with --epic, flowcolor_epic_NN.png")
     ap.add_argument("--photo", action="store_true",
                     help="warp each pair's second image by the forward and (with --epic) final flow; prints the photometric error, writes photo.json")
-    importlib.import_module(PKG + ".bcdstats").add_cli_options(ap, "--bcd-stats")
+    mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     return ap
 
 
 EVAL_ROW = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_test_valid", "sum_err", "max_err", "mean_epe",
             "outliers_pct", "kitti_fl_pct")
-
-
-def eval_row(st):
-    """pipeline.eval_stats' dict as a JSON object: the fields of EVAL_ROW, a NaN (nothing compared) as null."""
-    return {k: (None if st[k] != st[k] else st[k]) for k in EVAL_ROW}
-
-
 PHOTO_ROW = ("n", "n_outside", "n_unknown", "n_above", "sum_err", "max_err", "mean_err", "above_pct")
 
 
-def photo_row(st):
-    """pipeline.photo_stats' dict as a JSON object: the fields of PHOTO_ROW, a NaN (no target inside the frame) as null."""
-    return {k: (None if st[k] != st[k] else st[k]) for k in PHOTO_ROW}
+def mod(name):
+    return importlib.import_module(PKG + "." + name)
+
+
+def stats_row(st, fields):
+    """A dict of pipeline.eval_stats or photo_stats as a JSON object: the given fields, a NaN (nothing compared) as null."""
+    return {k: (None if st[k] != st[k] else st[k]) for k in fields}
+
+
+# what --eval and --photo differ in: the words of the statistics struct, pipeline's reader of it, the fields of a JSON row, the
+# printed line and the fields it shows
+EVAL = (8, "eval_stats", EVAL_ROW, "%s EPE %.3f px, %.2f%% > 3 px, Fl %.2f%% over %d px", ("mean_epe", "outliers_pct", "kitti_fl_pct", "n"))
+PHOTO = (6, "photo_stats", PHOTO_ROW, "%s photometric error %.3f, %.2f%% > 10, over %d px (%d targets outside)",
+         ("mean_err", "above_pct", "n", "n_outside"))
+
+
+def tally(spec, pair, fields, run, rows, totals, dev):
+    """--eval or --photo of one pair.  Per (kind, field): run(field) for the pair's own statistics, then run(field, stats=...)
+    adds the field to the device total of its kind (created when the kind is first met).  Appends the pair's row to rows and
+    prints its line."""
+    import torch
+    nwords, reader, row_fields, fmt, shown = spec
+    read = getattr(mod("pipeline"), reader)
+    row, line = {"pair": pair}, []
+    for kind, field in fields:
+        if kind not in totals:
+            totals[kind] = torch.zeros(nwords, dtype=torch.int64, device=dev)
+        st = read(run(field))                   # the pair's own row
+        run(field, stats=totals[kind])          # and into the kind's total, on the device
+        row[kind] = stats_row(st, row_fields)
+        line.append(fmt % ((kind,) + tuple(st[k] for k in shown)))
+    rows.append(row)
+    print("pair %d: %s" % (pair, "; ".join(line)))
+
+
+def write_tally(path, header, spec, rows, totals):
+    """eval.json / photo.json: the header, the per-pair rows and, per kind, the totals read back from the device."""
+    import json
+    read = getattr(mod("pipeline"), spec[1])
+    with open(path, "w") as f:
+        json.dump(dict(header, pairs=rows, totals={kind: stats_row(read(t), spec[2]) for kind, t in totals.items()}), f, indent=1)
+
+
+def setup(a):
+    """The device and process group of this rank, the images of its passes on the device and its DiscreteFlow objects."""
+    import torch
+    import torch.distributed as dist
+    pipeline, sharding, synth = mod("pipeline"), mod("sharding"), mod("synth")
+    s = argparse.Namespace(a=a, stop=mod("bcdstats").stop_from_args(a), histories={})   # histories: pass index -> per-sweep history
+    s.H, s.W = (int(v) for v in a.size.lower().split("x"))
+    s.rank, s.world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    s.dev = torch.device("cuda", local)
+    if s.world > 1:
+        dist.init_process_group("nccl", device_id=s.dev)
+    s.passes = [(pair, backward) for pair in range(a.pairs) for backward in (0, 1)]
+    # this rank's pairs are generated and uploaded BEFORE the passes run: the compute functions are GPU work only
+    mine = sharding.assign_passes(len(s.passes), s.world, s.rank)
+    s.images = {}
+    for pair in sorted({s.passes[i][0] for i in mine}):
+        img1, img2, _ = synth.make_pair(s.H, s.W, seed=synth.pair_seed(pair, 0))
+        s.images[pair] = (torch.from_numpy(img1).to(s.dev), torch.from_numpy(img2).to(s.dev))
+    # the passes of a rank (forward and backward runs, several pairs) are independent: their front ends run one after the
+    # other, their BCD sweeps as batched launches (dflow_bcd_sweep_batch), `group` passes at a time
+    s.group = max(1, min(a.group, len(mine)))
+    flags = mod("_lib").FLAG_DESCR_F16 if a.fp16_descriptors else 0
+    ch, cw = (int(v) for v in a.cell.lower().split("x")) if a.cell else (None, None)
+    s.dfs = [pipeline.DiscreteFlow(s.H, s.W, ch, cw, device=s.dev, seed=s.rank, flags=flags) for _ in range(s.group)]
+    s.front = [torch.cuda.Stream(device=s.dev) for _ in range(min(3, s.group))]     # front ends of a group's passes side by side
+    return s
+
+
+def compute_many(s, descs):
+    """The flows of this rank's passes `descs`, group by group; with a stop rule their histories go to s.histories."""
+    import torch
+    flows = []
+    main = torch.cuda.current_stream(s.dev)
+    for g0 in range(0, len(descs), s.group):
+        part = descs[g0:g0 + s.group]
+        start = torch.cuda.Event()
+        start.record(main)                                   # the previous group's read-out is done
+        done = []
+        for j, (df, (pair, backward)) in enumerate(zip(s.dfs, part)):
+            img1, img2 = s.images[pair]
+            if backward:
+                img1, img2 = img2, img1
+            st = s.front[j % len(s.front)]
+            with torch.cuda.stream(st):
+                st.wait_event(start)
+                df.load_pair(img1, img2)
+                df.generisi()
+                df.nasumicni()
+                df.pakovanje()
+                e = torch.cuda.Event()
+                e.record(st)
+                done.append(e)
+        for e in done:
+            main.wait_event(e)
+        hist = mod("pipeline").ceoBCD_batch(s.dfs[:len(part)], s.a.bcd_times, stop=s.stop)
+        if hist is not None:
+            for desc, h in zip(part, hist):
+                s.histories[s.passes.index(desc)] = h
+        flows += [df.vratiKonacniFlow().clone() for df in s.dfs[:len(part)]]
+    return flows
+
+
+def run_passes(s):
+    """Every pass on its rank and the flows gathered on rank 0 (with --time twice, the second run timed); the histories of
+    a stop rule are gathered into s.histories."""
+    import torch
+    import torch.distributed as dist
+    a, H, W = s.a, s.H, s.W
+
+    def run():
+        return mod("sharding").run_passes(s.passes, None, s.world, s.rank, s.dfs[0].flow, compute_many=lambda descs: compute_many(s, descs))
+
+    def settle():
+        torch.cuda.synchronize()
+        if s.world > 1:
+            dist.barrier()
+    flows = run()
+    if a.time:
+        import time
+        settle()
+        t0 = time.perf_counter()
+        flows = run()
+        settle()
+        dt = time.perf_counter() - t0
+        if s.rank == 0:
+            n = len(s.passes)
+            print("%d passes (%d pairs, forward + backward) of %dx%d, bcd_times=%d on %d GPU(s): %.1f ms = %.2f ms per pass = %.1f Mpix/s"
+                  % (n, a.pairs, W, H, a.bcd_times, s.world, dt * 1e3, dt * 1e3 / n, n * H * W / dt / 1e6))
+    if s.stop is not None and s.world > 1:
+        gathered = [None] * s.world
+        dist.all_gather_object(gathered, s.histories)
+        s.histories = {k: v for g in gathered for k, v in g.items()}
+    return flows
+
+
+def write_pair(s, pair, fwd, bwd):
+    """The flow, sparse-field, edge and Epic files of one pair and its printed line; returns the sparse field on the device,
+    the final dense flow (None without --epic) and the pair's images (None unless a stage asked for them)."""
+    a = s.a
+    pipeline, synth, flowio = mod("pipeline"), mod("synth"), mod("flowio")
+    sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
+    sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
+    sparse = sparse_dev.cpu().numpy()
+    for backward, f in ((0, fwd), (1, bwd)):
+        np.save(os.path.join(a.out, flowio.flow_name(pair, backward, a.bcd_times)), f.cpu().numpy().astype(np.float64))
+    flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
+    np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
+    mod("evaluate").parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
+    img1 = img2 = epic = None
+    if a.edges or a.epic or a.photo:
+        img1, img2 = s.images[pair] if pair in s.images else synth.make_pair(s.H, s.W, seed=synth.pair_seed(pair, 0))[:2]
+    if a.edges or a.epic:
+        if a.edge_kind == "pb":
+            ivice = pipeline.pb_edges(img1)               # e itself for the GPU steps, 1 - e in the file
+        else:
+            _, ivice = pipeline.canny_edges(img1)
+    if a.edges and a.edge_kind == "pb":
+        mod("edge").write_pb_ivice(ivice, os.path.join(a.out, "ivice_%02d.bin" % pair))
+    elif a.edges:
+        ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
+    if a.epic:
+        if a.prefilter:
+            sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, img1)
+        epic = pipeline.epic_interpolate(sparse_dev, ivice)
+        if a.epic_refine:
+            epic = pipeline.variational_refine(img1, img2, epic)
+        flowio.write_flo(os.path.join(a.out, "epic_%02d.flo" % pair), epic.cpu().numpy())
+    print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
+    return sparse_raw, epic, img1, img2
+
+
+def write_out(s, flows):
+    """Rank 0: every file of DIR and every printed line after the passes."""
+    import torch
+    a, H, W = s.a, s.H, s.W
+    pipeline, synth, flowio, evaluate, bcdstats = mod("pipeline"), mod("synth"), mod("flowio"), mod("evaluate"), mod("bcdstats")
+    os.makedirs(a.out, exist_ok=True)
+    if s.stop is not None:
+        named = [("pair %d backward=%d" % s.passes[i], s.histories[i]) for i in sorted(s.histories)]
+        bcdstats.write_history_json(os.path.join(a.out, "bcd_stats.json"), named, s.dfs[0].p.lamda, a.bcd_times, s.stop, (H, W))
+        for name, h in named:
+            print("%s: %d sweeps, E %.3f -> %.3f, last sweep changed %d labels"
+                  % (name, len(h) - 1, h[0]["energy"], h[-1]["energy"], h[-1]["n_changed"]))
+    eval_rows, eval_totals = [], {}
+    photo_rows, photo_totals = [], {}
+    for pair in range(a.pairs):
+        fwd = flows[2 * pair]
+        sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, flows[2 * pair + 1])
+        dense = [("epic", epic)] if a.epic else []
+        if a.eval:
+            gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]
+            gt = torch.from_numpy(evaluate.to_uv_valid(gt) if gt.shape[2] == 2 else np.asarray(gt, np.float32)).to(s.dev)
+            tally(EVAL, pair, [("fwd", fwd), ("sparse", sparse_raw)] + dense, lambda field, **kw: pipeline.flow_eval(field, gt, **kw),
+                  eval_rows, eval_totals, s.dev)
+        if a.pictures:
+            for name, field in [("flowcolor", fwd)] + [("flowcolor_" + kind, f) for kind, f in dense]:
+                flowio.write_png8(os.path.join(a.out, "%s_%02d.png" % (name, pair)), pipeline.flow_color(field).cpu().numpy())
+        if a.photo:
+            tally(PHOTO, pair, [("fwd", fwd)] + dense, lambda field, **kw: pipeline.warp_eval(img1, img2, field, **kw),
+                  photo_rows, photo_totals, s.dev)
+    head = {"size": [H, W], "bcd_times": a.bcd_times}
+    if a.photo:
+        write_tally(os.path.join(a.out, "photo.json"), dict(head, err_thresh=10.0, err_max=30.0), PHOTO, photo_rows, photo_totals)
+    if a.eval:
+        write_tally(os.path.join(a.out, "eval.json"), dict(head, abs_thresh=3.0), EVAL, eval_rows, eval_totals)
 
 
 def main(argv=None):
     a = parser().parse_args(argv)
     a.epic = a.epic or a.epic_refine or a.prefilter
-    import torch
-    import torch.distributed as dist
-    pipeline = importlib.import_module(PKG + ".pipeline")
-    sharding = importlib.import_module(PKG + ".sharding")
-    synth = importlib.import_module(PKG + ".synth")
-    flowio = importlib.import_module(PKG + ".flowio")
-    evaluate = importlib.import_module(PKG + ".evaluate")
-    bcdstats = importlib.import_module(PKG + ".bcdstats")
-    stop = bcdstats.stop_from_args(a)
-    histories = {}                                  # pass index -> per-sweep history (this rank's passes)
-    H, W = (int(v) for v in a.size.lower().split("x"))
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    if world > 1:
-        dist.init_process_group("nccl", device_id=dev)
-    passes = [(pair, backward) for pair in range(a.pairs) for backward in (0, 1)]
-    # this rank's pairs are generated and uploaded BEFORE the passes run: the compute functions are GPU work only
-    mine = sharding.assign_passes(len(passes), world, rank)
-    images = {}
-    for pair in sorted({passes[i][0] for i in mine}):
-        img1, img2, _ = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))
-        images[pair] = (torch.from_numpy(img1).to(dev), torch.from_numpy(img2).to(dev))
-    # the passes of a rank (forward and backward runs, several pairs) are independent: their front ends run one after the
-    # other, their BCD sweeps as batched launches (dflow_bcd_sweep_batch), `group` passes at a time
-    group = max(1, min(a.group, len(mine)))
-    flags = importlib.import_module(PKG + "._lib").FLAG_DESCR_F16 if a.fp16_descriptors else 0
-    ch, cw = (int(v) for v in a.cell.lower().split("x")) if a.cell else (None, None)
-    dfs = [pipeline.DiscreteFlow(H, W, ch, cw, device=dev, seed=rank, flags=flags) for _ in range(group)]
-
-    front = [torch.cuda.Stream(device=dev) for _ in range(min(3, group))]     # front ends of a group's passes side by side
-
-    def compute_many(descs):
-        flows = []
-        main = torch.cuda.current_stream(dev)
-        for g0 in range(0, len(descs), group):
-            part = descs[g0:g0 + group]
-            start = torch.cuda.Event()
-            start.record(main)                                   # the previous group's read-out is done
-            done = []
-            for j, (df, (pair, backward)) in enumerate(zip(dfs, part)):
-                img1, img2 = images[pair]
-                if backward:
-                    img1, img2 = img2, img1
-                st = front[j % len(front)]
-                with torch.cuda.stream(st):
-                    st.wait_event(start)
-                    df.load_pair(img1, img2)
-                    df.generisi()
-                    df.nasumicni()
-                    df.pakovanje()
-                    e = torch.cuda.Event()
-                    e.record(st)
-                    done.append(e)
-            for e in done:
-                main.wait_event(e)
-            hist = pipeline.ceoBCD_batch(dfs[:len(part)], a.bcd_times, stop=stop)
-            if hist is not None:
-                for desc, h in zip(part, hist):
-                    histories[passes.index(desc)] = h
-            flows += [df.vratiKonacniFlow().clone() for df in dfs[:len(part)]]
-        return flows
-
-    flows = sharding.run_passes(passes, None, world, rank, dfs[0].flow, compute_many=compute_many)
-    if a.time:
-        import time
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t0 = time.perf_counter()
-        flows = sharding.run_passes(passes, None, world, rank, dfs[0].flow, compute_many=compute_many)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        dt = time.perf_counter() - t0
-        if rank == 0:
-            print("%d passes (%d pairs, forward + backward) of %dx%d, bcd_times=%d on %d GPU(s): %.1f ms = %.2f ms per pass = %.1f Mpix/s"
-                  % (len(passes), a.pairs, W, H, a.bcd_times, world, dt * 1e3, dt * 1e3 / len(passes), len(passes) * H * W / dt / 1e6))
-    if stop is not None and world > 1:
-        gathered = [None] * world
-        dist.all_gather_object(gathered, histories)
-        histories = {k: v for g in gathered for k, v in g.items()}
-    if rank == 0:
-        os.makedirs(a.out, exist_ok=True)
-        if stop is not None:
-            named = [("pair %d backward=%d" % passes[i], histories[i]) for i in sorted(histories)]
-            bcdstats.write_history_json(os.path.join(a.out, "bcd_stats.json"), named, dfs[0].p.lamda, a.bcd_times, stop, (H, W))
-            for name, h in named:
-                print("%s: %d sweeps, E %.3f -> %.3f, last sweep changed %d labels"
-                      % (name, len(h) - 1, h[0]["energy"], h[-1]["energy"], h[-1]["n_changed"]))
-        eval_rows, eval_totals = [], {}
-        photo_rows, photo_totals = [], {}
-        for pair in range(a.pairs):
-            fwd, bwd = flows[2 * pair], flows[2 * pair + 1]
-            sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
-            sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
-            sparse = sparse_dev.cpu().numpy()
-            for backward, f in ((0, fwd), (1, bwd)):
-                np.save(os.path.join(a.out, flowio.flow_name(pair, backward, a.bcd_times)), f.cpu().numpy().astype(np.float64))
-            flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
-            np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
-            evaluate.parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
-            if a.edges or a.epic or a.photo:
-                img1, img2 = images[pair] if pair in images else synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[:2]
-            if a.edges or a.epic:
-                if a.edge_kind == "pb":
-                    ivice = pipeline.pb_edges(img1)               # e itself for the GPU steps, 1 - e in the file
-                else:
-                    _, ivice = pipeline.canny_edges(img1)
-            if a.edges and a.edge_kind == "pb":
-                importlib.import_module(PKG + ".edge").write_pb_ivice(ivice, os.path.join(a.out, "ivice_%02d.bin" % pair))
-            elif a.edges:
-                ivice.cpu().numpy().tofile(os.path.join(a.out, "ivice_%02d.bin" % pair))
-            if a.epic:
-                if a.prefilter:
-                    sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, img1)
-                epic = pipeline.epic_interpolate(sparse_dev, ivice)
-                if a.epic_refine:
-                    epic = pipeline.variational_refine(img1, img2, epic)
-                flowio.write_flo(os.path.join(a.out, "epic_%02d.flo" % pair), epic.cpu().numpy())
-            print("pair %d: %.1f%% of the forward flow survives the consistency check" % (pair, 100.0 * sparse[..., 2].mean()))
-            if a.eval:
-                gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]
-                gt = torch.from_numpy(evaluate.to_uv_valid(gt) if gt.shape[2] == 2 else np.asarray(gt, np.float32)).to(dev)
-                fields = [("fwd", fwd), ("sparse", sparse_raw)] + ([("epic", epic)] if a.epic else [])
-                row, line = {"pair": pair}, []
-                for kind, field in fields:
-                    if kind not in eval_totals:
-                        eval_totals[kind] = torch.zeros(8, dtype=torch.int64, device=dev)
-                    st = pipeline.eval_stats(pipeline.flow_eval(field, gt))        # the pair's own row
-                    pipeline.flow_eval(field, gt, stats=eval_totals[kind])         # and into the kind's total, on the device
-                    row[kind] = eval_row(st)
-                    line.append("%s EPE %.3f px, %.2f%% > 3 px, Fl %.2f%% over %d px"
-                                % (kind, st["mean_epe"], st["outliers_pct"], st["kitti_fl_pct"], st["n"]))
-                eval_rows.append(row)
-                print("pair %d: %s" % (pair, "; ".join(line)))
-            if a.pictures:
-                for name, field in [("flowcolor", fwd)] + ([("flowcolor_epic", epic)] if a.epic else []):
-                    flowio.write_png8(os.path.join(a.out, "%s_%02d.png" % (name, pair)), pipeline.flow_color(field).cpu().numpy())
-            if a.photo:
-                row, line = {"pair": pair}, []
-                for kind, field in [("fwd", fwd)] + ([("epic", epic)] if a.epic else []):
-                    if kind not in photo_totals:
-                        photo_totals[kind] = torch.zeros(6, dtype=torch.int64, device=dev)
-                    st = pipeline.photo_stats(pipeline.warp_eval(img1, img2, field))      # the pair's own row
-                    pipeline.warp_eval(img1, img2, field, stats=photo_totals[kind])       # and into the kind's total, on the device
-                    row[kind] = photo_row(st)
-                    line.append("%s photometric error %.3f, %.2f%% > 10, over %d px (%d targets outside)"
-                                % (kind, st["mean_err"], st["above_pct"], st["n"], st["n_outside"]))
-                photo_rows.append(row)
-                print("pair %d: %s" % (pair, "; ".join(line)))
-        if a.photo:
-            import json
-            totals = {kind: photo_row(pipeline.photo_stats(t)) for kind, t in photo_totals.items()}
-            with open(os.path.join(a.out, "photo.json"), "w") as f:
-                json.dump({"size": [H, W], "bcd_times": a.bcd_times, "err_thresh": 10.0, "err_max": 30.0, "pairs": photo_rows,
-                           "totals": totals}, f, indent=1)
-        if a.eval:
-            import json
-            totals = {kind: eval_row(pipeline.eval_stats(t)) for kind, t in eval_totals.items()}
-            with open(os.path.join(a.out, "eval.json"), "w") as f:
-                json.dump({"size": [H, W], "bcd_times": a.bcd_times, "abs_thresh": 3.0, "pairs": eval_rows, "totals": totals}, f, indent=1)
-    if world > 1:
+    s = setup(a)
+    flows = run_passes(s)
+    if s.rank == 0:
+        write_out(s, flows)
+    if s.world > 1:
+        import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
 

@@ -85,7 +85,7 @@ def main(argv=None):
             ivice = edge.canny_ivice_tensor(kitti1)
             with open("ivice.bin", "wb") as f:
                 f.write(ivice.cpu().numpy().tobytes())
-        read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+        read_bgr = importlib.import_module(PKG + ".flowio").read_bgr
         if prefilter:
             sparse_dev = pipeline.epic_prefilter(sparse_dev, ivice, read_bgr(kitti1))
         flow = pipeline.epic_interpolate(sparse_dev, ivice)                # the step epicflow-static would take

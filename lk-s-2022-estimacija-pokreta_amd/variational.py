@@ -79,7 +79,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     try:
         (im1, im2, flo_in, flo_out), preset, params = parse_args(argv)
-        read_bgr = importlib.import_module(PKG + ".daisy i flann").read_bgr
+        read_bgr = importlib.import_module(PKG + ".flowio").read_bgr
         flowio = importlib.import_module(PKG + ".flowio")
         img1, img2 = read_bgr(im1), read_bgr(im2)
         try:

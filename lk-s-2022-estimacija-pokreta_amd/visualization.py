@@ -14,7 +14,7 @@ them in double and rounds once, so the two lines may differ in the last digits. 
 lines are 'nan' and the exit status is 0 (the reference divides by zero there).  Pixels whose error is not finite are left
 out of both numbers, and a warning on stderr says how many.
 With a third argument the colour error picture (jet over min(err, 3) / 3, black where nothing is compared; :133-143,:156) is
-written there: '.png' through flowio.write_png8, '.ppm' as a binary P6 file, both without any imaging library; any other
+written there with flowio.write_picture: '.png' and '.ppm' (a binary P6 file) without any imaging library; any other
 extension goes through PIL if it can be imported, and otherwise the command exits with status 2 and names those two.
 The reference's trailing cv2.waitKey / imshow window is not reproduced.
 """
@@ -45,19 +45,6 @@ def parse(argv):
     return argv[0], argv[1], errimg
 
 
-def write_picture(path, bgr):
-    """The (H,W,3) uint8 BGR error picture -> path, by its extension."""
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".png":
-        importlib.import_module(PKG + ".flowio").write_png8(path, bgr)
-    elif ext == ".ppm":
-        with open(path, "wb") as f:
-            f.write(b"P6\n%d %d\n255\n" % (bgr.shape[1], bgr.shape[0]) + np.ascontiguousarray(bgr[..., ::-1]).tobytes())
-    else:
-        from PIL import Image
-        Image.fromarray(np.ascontiguousarray(bgr[..., ::-1])).save(path)
-
-
 def main(argv=None):
     parsed = parse(sys.argv[1:] if argv is None else list(argv))
     if parsed == 2:
@@ -82,7 +69,7 @@ def main(argv=None):
     with open("procenat_outliera.txt", "a+", encoding="utf-8") as f:      # :151-152
         f.write((str(st["n_out_abs"] * 100 / n) if n else "nan") + "\n")
     if errimg is not None:
-        write_picture(errimg, out[1].cpu().numpy())                       # :155-156
+        importlib.import_module(PKG + ".flowio").write_picture(errimg, out[1].cpu().numpy())    # :155-156
     return 0
 
 

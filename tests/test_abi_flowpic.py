@@ -86,3 +86,36 @@ def test_python_layer_refuses_bad_arguments_without_a_gpu():
         pipeline.warp_eval(np.zeros((4, 5, 3), np.uint8), np.zeros((4, 4, 3), np.uint8), np.zeros((4, 4, 2), np.float32))
     with pytest.raises(ValueError, match="images must be"):
         pipeline.warp_eval(np.zeros((4, 4, 3), np.float32), np.zeros((4, 4, 3), np.uint8), np.zeros((4, 4, 2), np.float32))
+
+
+def test_every_image_plane_wrapper_checks_its_arrays_before_any_cuda_use(L, monkeypatch):
+    """Wrong dtype, wrong rank and wrong last dimension of every array argument of the eight image-plane wrappers: a ValueError
+    that names the wrapper and the argument, raised before torch.cuda is asked for anything."""
+    import numpy as np
+    import torch
+    pipeline = pkg("pipeline")
+
+    def touched(*args, **kw):
+        raise AssertionError("torch.cuda was used before the arguments were checked")
+    for name in ("current_device", "current_stream", "is_available"):
+        monkeypatch.setattr(torch.cuda, name, touched)
+    H, W = 4, 5
+    u8, f32 = (lambda *shape: np.zeros(shape, np.uint8)), (lambda *shape: np.zeros(shape, np.float32))
+    wrappers = {"canny_edges": dict(bgr=u8(H, W, 3)),
+                "pb_edges": dict(bgr=u8(H, W, 3)),
+                "epic_interpolate": dict(sparse=f32(H, W, 3), edges=f32(H, W)),
+                "epic_prefilter": dict(sparse=f32(H, W, 3), edges=f32(H, W), img1=u8(H, W, 3)),
+                "variational_refine": dict(img1=u8(H, W, 3), img2=u8(H, W, 3), flow=f32(H, W, 2)),
+                "flow_eval": dict(test=f32(H, W, 3), gt=f32(H, W, 3)),
+                "flow_color": dict(flow=f32(H, W, 2)),
+                "warp_eval": dict(img1=u8(H, W, 3), img2=u8(H, W, 3), flow=f32(H, W, 3))}
+    cases = 0
+    for fn, good in wrappers.items():
+        for arg, a in good.items():
+            for what, bad in (("dtype", a.astype(np.float64 if a.dtype == np.float32 else np.float32)), ("rank", a[0]),
+                              ("last dimension", np.concatenate([a, a], axis=-1))):
+                with pytest.raises(ValueError) as ei:
+                    getattr(pipeline, fn)(**dict(good, **{arg: bad}))
+                assert fn in str(ei.value) and arg in str(ei.value), (fn, arg, what, str(ei.value))
+                cases += 1
+    assert cases == 3 * 16

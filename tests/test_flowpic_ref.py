@@ -204,15 +204,15 @@ def test_flowpicture_arguments_and_images(tmp_path, capsys):
     bgr = np.random.default_rng(6).integers(0, 256, (4, 6, 3)).astype(np.uint8)
     paths = [os.path.join(tmp_path, "i" + ext) for ext in (".npy", ".ppm", ".png")]
     np.save(paths[0], bgr)
-    pkg("visualization").write_picture(paths[1], bgr)
-    pkg("visualization").write_picture(paths[2], bgr)
+    pkg("flowio").write_picture(paths[1], bgr)
+    pkg("flowio").write_picture(paths[2], bgr)
     for p in paths:
-        assert np.array_equal(fp.read_image(p), bgr), p
+        assert np.array_equal(pkg("flowio").read_image(p), bgr), p
     with open(paths[1], "wb") as f:
         f.write(b"P6\n# a comment\n6 4\n255\n" + bgr[..., ::-1].tobytes())
-    assert np.array_equal(fp.read_image(paths[1]), bgr)
+    assert np.array_equal(pkg("flowio").read_image(paths[1]), bgr)
     with pytest.raises(ValueError):
-        fp.read_image(os.path.join(tmp_path, "i.jpg"))
+        pkg("flowio").read_image(os.path.join(tmp_path, "i.jpg"))
 
 
 def test_run_batch_flags():

@@ -259,7 +259,7 @@ def test_epicflow_cli_prefilter(torch_, golden, tmp_path):
     edges.tofile(os.path.join(tmp_path, "e.bin"))
     ef, flowio, pipeline = pkg("epicflow"), pkg("flowio"), pkg("pipeline")
     sp = ef.read_matches(os.path.join(tmp_path, "m.txt"), H, W)
-    img = pkg("daisy i flann").read_bgr(os.path.join(tmp_path, "a.png"))
+    img = flowio.read_bgr(os.path.join(tmp_path, "a.png"))
     th = median_saliency(img)
     pos = [os.path.join(tmp_path, n) for n in ("a.png", "b.png", "e.bin", "m.txt", "o.flo")]
     for extra, kw in ((["--prefilter"], {}), (["--pref-th", "1.5", "--saliency-th", repr(th), "--pref-nn", "12", "-k", "2.5"],

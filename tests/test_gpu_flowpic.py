@@ -213,7 +213,7 @@ def test_captured_into_a_graph_on_a_side_stream(torch_):
 
 # ------------------------------------------------------------------------------------------------ command lines
 def test_flowpicture_command(torch_, tmp_path, monkeypatch, capsys):
-    fp, flowio, pipeline, vis = pkg("flowpicture"), pkg("flowio"), pkg("pipeline"), pkg("visualization")
+    fp, flowio, pipeline = pkg("flowpicture"), pkg("flowio"), pkg("pipeline")
     H, W = 33, 65
     img1, img2, flow, _ = R.warp_case(H, W, 4.0)
     field = R.dydx(flow).astype(np.float64)
@@ -222,12 +222,12 @@ def test_flowpicture_command(torch_, tmp_path, monkeypatch, capsys):
     np.save("f.npy", field)                                   # [dy,dx], as the hot path saves it
     flowio.write_flo("f.flo", field)
     np.save("a.npy", img1)
-    vis.write_picture("b.ppm", img2)
+    flowio.write_picture("b.ppm", img2)
     read = pkg("evaluate").ucitajFlow("f.npy")
     assert fp.main(["f.npy", "c.png"]) == 0 and fp.main(["f.flo", "c8.ppm", "--max-flow", "8"]) == 0
     assert capsys.readouterr().out == ""
     assert np.array_equal(flowio.read_png8("c.png"), pipeline.flow_color(read).cpu().numpy())
-    assert np.array_equal(fp.read_image("c8.ppm"), pipeline.flow_color(read, 8.0).cpu().numpy())
+    assert np.array_equal(flowio.read_image("c8.ppm"), pipeline.flow_color(read, 8.0).cpu().numpy())
     assert fp.main(["f.npy", "--warp", "a.npy", "b.ppm", "--warped", "w.png", "--error-picture", "e.png"]) == 0
     stats, wp, pic = pipeline.warp_eval(img1, img2, read, warped=True, image=True)
     st = pipeline.photo_stats(stats)
