@@ -24,6 +24,8 @@
  *   bestlabels int32   (H,W)                                              daisy i flann.py:95
  *   flow       float32 (H,W,2)   [dy,dx]                                  python bcd.py:90-95 (float64; values are small integers)
  *   sparse     float32 (H,W,3)   [U=dx, V=dy, valid]                      postprocessing.py:7-17,123-135
+ *   prior      float32 (H,W,2)   [dy,dx] (DFLOW_EVAL_DYDX) or (H,W,3) [U,V,valid] (DFLOW_EVAL_UVV): a flow somebody already has,
+ *                                read by dflow_prior_proposals and dflow_flow_advance (no counterpart in the reference)
  */
 #ifndef DFLOW_H
 #define DFLOW_H
@@ -472,6 +474,65 @@ size_t dflow_warp_eval_workspace_bytes(int32_t h, int32_t w);
 int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow, int32_t layout,
                     float err_thresh, float err_max, uint32_t flags, dflow_photo_stats *d_stats, uint8_t *d_warped,
                     float *d_err, uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Starting a pass from a flow somebody already has (the previous pair's flow, the inverse of the other direction's, a coarse
+ * estimate, a sparse ground truth): dflow_prior_proposals appends the prior's vectors to the pixels' label sets and may start
+ * the labelling on them; dflow_flow_advance makes such a prior out of a flow.  This build's definitions (DESIGN.md "Prior
+ * proposals"); no counterpart in the reference, whose label sets hold kNN matches within +-window cells and copies of
+ * neighbouring winners only.  A prior label competes on its DAISY cost like every other; the label space is integer.
+ *
+ * A VECTOR of a flow plane is USABLE (both entry points): under DFLOW_EVAL_UVV (H,W,3) [U,V,valid] the pixel needs valid > 0.5
+ * (a NaN compares false) and dy = V, dx = U; under DFLOW_EVAL_DYDX (H,W,2) [dy,dx] every pixel is valid.  (dy,dx) = rintf of the
+ * two components (ties to even); the vector is unusable if a component is not finite or a rounded component lies outside
+ * [-32767, 32767] (32767.4 is usable, 32767.5 and 32767.6 are not, nor is -32768).
+ *
+ * dflow_prior_proposals.  Runs after dflow_neighbour_proposals (the neighbour kernel does not bound nprop itself, so never
+ * between it and dflow_knn_proposals); needs no workspace and leaves the caller's alone, but the records of dflow_bcd_prepare
+ * describe the old label sets: prepare again before the next sweep.  d_descr1 / d_descr2 as for the kNN stage (binary16 with
+ * DFLOW_FLAG_DESCR_F16).  Every pixel (y,x) is handled on its own.  Its candidates are k = 0..4 with the source offsets (oy,ox)
+ * = (0,0), (-s,0), (0,-s), (0,+s), (+s,0), s = stride; with s = 0 only k = 0 exists.  They are taken in that order, with
+ * n = nprop[y,x] as it stands at that moment:
+ *   1. the source (y+oy, x+ox) lies outside the frame: SKIPPED;
+ *   2. the prior's vector at the source is not usable: SKIPPED;
+ *   3. the target (y+dy, x+dx) lies outside the frame: SKIPPED;
+ *   4. the packed label equals proposals[y,x,j] for some j < n (both halves equal: not the component-wise `in` of nasumicni;
+ *      a label appended for an earlier candidate of this pixel counts): FOUND, slot = the smallest such j;
+ *   5. otherwise, if n < maxnprop: APPENDED, slot = n, proposals[y,x,n] = the label, lcosts[y,x,n] = l1 < tphi ? l1 : tphi with
+ *      l1 = sum_k |descr1[y,x][k] - descr2[target][k]| in numpy's float32 pairwise order, the kNN stage's cost (8 running sums,
+ *      the tree, then the 4-element tail; not the neighbour stage's |sum(a-b)|), nprop[y,x] = n + 1; a NaN l1 gives tphi, so the
+ *      costs of used slots stay in [0, tphi] (DFLOW_DP_SENTINEL);
+ *   6. otherwise the row is FULL and nothing happens for this candidate;
+ *   7. if k = 0 was found or appended and DFLOW_PRIOR_SEED_LABELS is set: bestlabels[y,x] = slot.
+ * Slots at or above nprop keep what they hold (the fills).  d_counts (NULL to skip) receives int32 {appended, found, full,
+ * skipped} over all (pixel, candidate), which add up to H*W*(s ? 5 : 1); the call zeroes them itself, on the stream (integer
+ * atomics: exact in any order).  The results do not depend on any order and a second identical call changes nothing.
+ * DFLOW_EINVAL before anything is launched: whatever dflow_check_params refuses, a layout other than the two, a stride outside
+ * [0, 8192], an unknown flag bit, a NULL pointer (d_counts excepted), d_descr1, d_descr2 or d_proposals not 16-byte aligned,
+ * another pointer not 4-byte aligned, d_prior equal to one of the other pointers.  Asynchronous on `stream`, allocates nothing,
+ * reads nothing back, can be captured into a graph. */
+#define DFLOW_PRIOR_SEED_LABELS 1u
+int dflow_prior_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2,
+                          const float *d_prior, int32_t layout, int32_t stride, uint32_t flags,
+                          uint32_t *d_proposals, float *d_lcosts, int32_t *d_nprop, int32_t *d_bestlabels,
+                          int32_t *d_counts /* NULL or int32[4] */, void *stream);
+
+/* dflow_flow_advance carries every vector to the pixel it points at: the flow of t -> t+1 becomes a prior for t+1 -> t+2
+ * (constant velocity), and with DFLOW_ADVANCE_NEGATE a prior for the backward pass (the inverse flow).  1 <= h, w <= 8192.
+ * A source with raster index i = y*w + x TAKES PART if its vector is usable (above) and its target (y+dy, x+dx) lies inside the
+ * frame.  Each target takes the claimant with the smallest i; its output is [dx, dy, 1], the integers as floats, with NEGATE
+ * [(float)(-dx), (float)(-dy), 1] (the integer is negated, so 0 stays +0.0).  A target nobody claims gets [0,0,0].  d_out is
+ * (h,w,3) float32 [U,V,valid]; d_counts (NULL to skip) receives int32 {claimed targets, claimants that lost, sources that did
+ * not take part}, which add up to h*w.  The workspace holds a uint32 winner per pixel, set to 0xFFFFFFFF, written with
+ * atomicMin and resolved by a second launch: the result does not depend on the order of arrival.
+ * A size, layout or flag outside its range, a NULL d_flow or d_out, a pointer that is not 4-byte aligned or d_out == d_flow
+ * returns DFLOW_EINVAL, a NULL or too small workspace DFLOW_ENOSPC, both before anything is launched.  Asynchronous on
+ * `stream`, allocates nothing, reads nothing back, can be captured into a graph; dflow_flow_advance_workspace_bytes returns 0
+ * (and sets dflow_last_error) for sizes outside the range. */
+#define DFLOW_ADVANCE_NEGATE 1u
+size_t dflow_flow_advance_workspace_bytes(int32_t h, int32_t w);
+int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout, uint32_t flags,
+                       float *d_out /* (H,W,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[3] */,
+                       void *d_ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ VAR_FLAG_SOR_UNFUSED = 1    # DFLOW_VAR_FLAG_SOR_UNFUSED
 EVAL_UVV, EVAL_DYDX = 0, 1  # DFLOW_EVAL_UVV, DFLOW_EVAL_DYDX: the test field's layout in dflow_flow_eval
 EVAL_FLAG_ACCUMULATE = 1    # DFLOW_EVAL_FLAG_ACCUMULATE
 WARP_FLAG_ACCUMULATE = 1    # DFLOW_WARP_FLAG_ACCUMULATE
+PRIOR_SEED_LABELS = 1       # DFLOW_PRIOR_SEED_LABELS
+ADVANCE_NEGATE = 1          # DFLOW_ADVANCE_NEGATE
 
 
 class DflowError(RuntimeError):
@@ -101,6 +103,9 @@ _SIGNATURES = {
     "dflow_flow_color": (C.c_int, [_i32, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "dflow_warp_eval_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_warp_eval": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _f32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_prior_proposals": (C.c_int, [_pp, _vp, _vp, _vp, _i32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_flow_advance_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_flow_advance": (C.c_int, [_i32, _i32, _vp, _i32, C.c_uint32, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

@@ -507,6 +507,50 @@ int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *
                             d_ws, (hipStream_t)stream);
 }
 
+int dflow_prior_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2, const float *d_prior, int32_t layout,
+                          int32_t stride, uint32_t flags, uint32_t *d_proposals, float *d_lcosts, int32_t *d_nprop,
+                          int32_t *d_bestlabels, int32_t *d_counts, void *stream)
+{
+    int rc = dflow_check_params(p); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (stride < 0 || stride > 8192) return dflow_set_error(DFLOW_EINVAL, "%s: stride=%d outside [0,8192]", __func__, stride);
+    if (flags & ~DFLOW_PRIOR_SEED_LABELS) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_prior); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop);
+    CHECK_PTR(d_bestlabels);
+    // the kernel reads the label rows and the descriptors' tails 16 bytes at a time
+    rc = check_aligned(__func__, {{"d_descr1", d_descr1, 16}, {"d_descr2", d_descr2, 16}, {"d_prior", d_prior, 4},
+                                  {"d_proposals", d_proposals, 16}, {"d_lcosts", d_lcosts, 4}, {"d_nprop", d_nprop, 4},
+                                  {"d_bestlabels", d_bestlabels, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the prior is read while the state is written
+    for (const void *q : {d_descr1, d_descr2, (const void *)d_proposals, (const void *)d_lcosts, (const void *)d_nprop,
+                          (const void *)d_bestlabels, (const void *)d_counts})
+        if (q == (const void *)d_prior) return dflow_set_error(DFLOW_EINVAL, "%s: d_prior is one of the state pointers", __func__);
+    return launch_prior(p, d_descr1, d_descr2, d_prior, layout, stride, flags, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_counts,
+                        (hipStream_t)stream);
+}
+
+size_t dflow_flow_advance_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return flow_advance_ws_bytes(h, w);
+}
+
+int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout, uint32_t flags, float *d_out, int32_t *d_counts,
+                       void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (flags & ~DFLOW_ADVANCE_NEGATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    CHECK_PTR(d_flow); CHECK_PTR(d_out);
+    rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}, {"d_ws", d_ws, 4}});
+    if (rc) return rc;
+    // a target's winner is read from d_flow after other targets have been written
+    if (d_out == d_flow) return dflow_set_error(DFLOW_EINVAL, "%s: d_out and d_flow are the same plane", __func__);
+    CHECK_WS(flow_advance_ws_bytes(h, w));
+    return launch_flow_advance(h, w, d_flow, layout, flags, d_out, d_counts, d_ws, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

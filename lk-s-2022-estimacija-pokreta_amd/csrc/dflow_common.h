@@ -296,3 +296,10 @@ size_t warp_eval_ws_bytes(int H, int W);
 int launch_warp_eval(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *flow, int layout, float err_thresh,
                      float err_max, uint32_t flags, dflow_photo_stats *stats, uint8_t *warped, float *err, uint8_t *err_bgr,
                      void *ws, hipStream_t s);
+// prior.hip: labels from a prior flow appended to the state, and a flow carried to the pixels it points at (arguments
+// validated by the caller); counts may be NULL
+int launch_prior(const dflow_params *p, const void *d1, const void *d2, const float *prior, int layout, int stride, uint32_t flags,
+                 uint32_t *proposals, float *lcosts, int32_t *nprop, int32_t *bestlabels, int32_t *counts, hipStream_t s);
+size_t flow_advance_ws_bytes(int H, int W);
+int launch_flow_advance(int H, int W, const float *flow, int layout, uint32_t flags, float *out, int32_t *counts, void *ws,
+                        hipStream_t s);

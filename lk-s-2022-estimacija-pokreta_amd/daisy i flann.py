@@ -16,6 +16,17 @@ All computation runs in libdflow.so on the GPU; there is no CPU fallback.
 Options for inputs the reference cannot handle: --image1/--image2 PATH, --cell HxW, --synthetic HxW
 (synthetic pair with seed 1000*idx+backward), --seed N (neighbour-sampler key), --device cuda:N,
 --fp16-descriptors (BASELINE configs[4]: DAISY values rounded to binary16).
+
+Starting from a flow somebody already has (DESIGN.md "Prior proposals"): --prior FILE, a .npy of shape (H,W,2) [dy,dx] or
+(H,W,3) [U,V,valid], or a Middlebury .flo.  Its vectors are appended to the pixels' label sets after nasumicni, so
+proposals_nakon_gausa, lcosts_nakon_gausa and nprop hold them; "posle 00" stays the kNN winner, and the labelling that starts on
+the prior goes to "Daisy output slike <idx> backward=<b> labels_prior.npy", which `python bcd.py --labels` takes.  maxnprop stays
+150 here, so the prior fills free slots only (maxnprop - nprop per pixel); one printed line gives how many candidates were
+appended, found, met a full row or were skipped.  --prior-stride N (default 2; 0: the pixel's own vector only) also offers the
+vectors of the four pixels N away; --prior-advance carries every vector to the pixel it points at first (the previous pair's
+flow as a constant-velocity prior), --prior-inverse does the same and negates it (the other direction's flow as a prior);
+--no-prior-seed leaves the starting labels alone (labels_prior then equals "posle 00").
+Seed only a prior you believe: started on a wrong but smooth flow the sweeps stay on it (the control run).
 """
 import argparse
 import importlib
@@ -39,7 +50,17 @@ def main(argv=None):
     ap.add_argument("--packedksets", action="store_true", help="write the reference's compat-matrix file(s) whatever their size")
     ap.add_argument("--no-packedksets", action="store_true", help="never write them")
     ap.add_argument("--fp16-descriptors", action="store_true", help="round the DAISY values to binary16 (DFLOW_FLAG_DESCR_F16)")
+    ap.add_argument("--prior", metavar="FILE", help=".npy (H,W,2) [dy,dx] or (H,W,3) [U,V,valid], or .flo: a flow to start from; "
+                    "maxnprop stays 150, so it fills free label slots only")
+    ap.add_argument("--prior-stride", type=int, default=2, metavar="N", help="also offer the prior of the four pixels N away (0: own pixel only)")
+    ap.add_argument("--prior-advance", action="store_true", help="carry the prior's vectors to the pixels they point at first")
+    ap.add_argument("--prior-inverse", action="store_true", help="the same, negated: the other direction's flow as a prior")
+    ap.add_argument("--no-prior-seed", action="store_true", help="append the prior's labels but do not start the labelling on them")
     a = ap.parse_args(argv)
+    if a.prior is None and (a.prior_advance or a.prior_inverse or a.no_prior_seed or a.prior_stride != 2):
+        ap.error("--prior-stride, --prior-advance, --prior-inverse and --no-prior-seed need --prior FILE")
+    if a.prior_advance and a.prior_inverse:
+        ap.error("--prior-advance and --prior-inverse exclude each other")
     pipeline = importlib.import_module(PKG + ".pipeline")
     flowio = importlib.import_module(PKG + ".flowio")
     synth = importlib.import_module(PKG + ".synth")
@@ -68,6 +89,14 @@ def main(argv=None):
     np.save(flowio.labels_name(idx, a.backward, 0), st0["bestlabels"])
     flowio.write_flo(flowio.flow_name(idx, a.backward, 0)[:-4] + ".flo", flow0)
     df.nasumicni()                                                          # :418
+    if a.prior is not None:
+        prior = flowio.read_flo(a.prior)[..., ::-1] if a.prior.lower().endswith(".flo") else np.load(a.prior)
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if a.prior_advance or a.prior_inverse:
+            prior = pipeline.flow_advance(prior, negate=a.prior_inverse)
+        counts = df.prior_proposals(prior, stride=a.prior_stride, seed_labels=not a.no_prior_seed, counts=True).cpu().tolist()
+        np.save(flowio.stage_name(idx, a.backward, "labels_prior"), df.bestlabels.cpu().numpy().astype(np.int64))
+        print("daisy i flann: prior %s: appended %d, found %d, full %d, skipped %d" % ((os.path.basename(a.prior),) + tuple(counts)))
     st = df.host_state()
     np.save(flowio.stage_name(idx, a.backward, "proposals_nakon_gausa"), st["proposals"])   # sacuvajPodatke1 :249-253
     np.save(flowio.stage_name(idx, a.backward, "lcosts_nakon_gausa"), st["lcosts"])

@@ -219,11 +219,35 @@ class DiscreteFlow:
                   out.data_ptr(), self._stream())
         return out
 
-    def run(self, pic3, pic4, bcd_times):
-        """daisy i flann.py main (:406-422, without the file writes) followed by ceoBCD; returns the flow tensor."""
+    def prior_proposals(self, prior, stride=2, seed_labels=True, counts=False):
+        """dflow_prior_proposals (DESIGN.md "Prior proposals"): appends the vectors of a flow somebody already has to the
+        pixels' label sets, the pixel's own and, with stride > 0, those of the four pixels stride away, and with seed_labels
+        starts the labelling on the pixel's own.  prior: (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; the last
+        dimension says which.  Device tensor or host array; host data is uploaded to the pass's device.  Call it after
+        nasumicni() (or set_host_state) and before the sweeps.  A prior only fills slots that are free (maxnprop - nprop per
+        pixel).  Seed only a prior you believe: started on a wrong but smooth flow the sweeps stay on it.
+        With counts=True returns the int32[4] device tensor {appended, found, full, skipped}, else None.  Runs on
+        torch's current stream and does not wait for it."""
+        prior = _check(prior, "prior_proposals", "prior", torch.float32, (self.p.pich, self.p.picw, (2, 3)))
+        stride = int(stride)
+        if not 0 <= stride <= 8192:
+            raise ValueError("prior_proposals: stride must be in [0, 8192], got %d" % stride)
+        prior, = _on(self.device, prior)
+        cnt = _out(counts, 4, torch.int32, self.device)
+        self._bcd_ready = False
+        _lib.call("dflow_prior_proposals", self._pp(), self.descrs1.data_ptr(), self.descrs2.data_ptr(), prior.data_ptr(),
+                  _layout(prior), stride, _lib.PRIOR_SEED_LABELS if seed_labels else 0, self.proposals.data_ptr(),
+                  self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), _ptr(cnt), self._stream())
+        return cnt
+
+    def run(self, pic3, pic4, bcd_times, prior=None, prior_stride=2):
+        """daisy i flann.py main (:406-422, without the file writes) followed by ceoBCD; returns the flow tensor.  prior: a
+        flow to start from (prior_proposals, with seeded labels); None: the reference's pass."""
         self.load_pair(pic3, pic4)
         self.generisi()
         self.nasumicni()
+        if prior is not None:
+            self.prior_proposals(prior, stride=prior_stride)
         self.ceoBCD(bcd_times)
         return self.vratiKonacniFlow()
 
@@ -658,3 +682,23 @@ def photo_stats(t):
     d["mean_err"] = d["sum_err"] / d["n"] if d["n"] else float("nan")
     d["above_pct"] = _pct(d["n_above"], d["n"])
     return d
+
+
+def flow_advance(flow, negate=False, counts=False):
+    """Carries every vector of a flow to the pixel it points at (dflow_flow_advance, DESIGN.md "Prior proposals"): the flow of
+    t -> t+1 becomes a prior for t+1 -> t+2 (constant velocity), and with negate=True a prior for the backward pass (the inverse
+    flow).  flow is (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; the last dimension says which.  Device tensor or
+    host array; host data is uploaded to the current device.  Vectors are rounded to integers; where several land on one pixel
+    the one from the smallest raster index stays; a pixel nothing lands on is invalid.  Returns the (H,W,3) float32 [U,V,valid]
+    device tensor, what DiscreteFlow.prior_proposals takes, and with counts=True also the int32[3] device tensor {claimed
+    targets, claimants that lost, sources that did not take part}.  Runs on torch's current stream and does not wait for it."""
+    flow = _check(flow, "flow_advance", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    dev = _device_of(flow)
+    flow, = _on(dev, flow)
+    ws, ws_bytes = _lib.workspace("dflow_flow_advance_workspace_bytes", H, W, dev)
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    cnt = _out(counts, 3, torch.int32, dev)
+    _lib.call("dflow_flow_advance", H, W, flow.data_ptr(), _layout(flow), _lib.ADVANCE_NEGATE if negate else 0, out.data_ptr(),
+              _ptr(cnt), ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    return (out, cnt) if counts else out

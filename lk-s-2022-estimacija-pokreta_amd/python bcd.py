@@ -13,6 +13,9 @@ statistics and the stop rule").  --stop-changed F ends the run after the sweep t
 labels, --stop-energy R after the sweep that lowered E by at most the fraction R (a rise of E included); bcd_times stays the
 upper bound, and the files of the sweeps not run are not written.  Each of the three costs one read-back of 48 bytes per
 sweep; without them the run issues exactly the launches it always did.
+
+--labels FILE starts from the labels in that .npy instead of "posle 00": the labels_prior file `daisy i flann.py --prior` writes,
+or any (H,W) integer labelling with 0 <= label < nprop.
 """
 import argparse
 import importlib
@@ -29,6 +32,7 @@ def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("picindex"); ap.add_argument("backward", choices=("0", "1")); ap.add_argument("bcd_times", type=int)
     ap.add_argument("--cell"); ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--labels", metavar="FILE", help="start from these labels (an (H,W) integer .npy) instead of \"posle 00\"")
     importlib.import_module(PKG + ".bcdstats").add_cli_options(ap, "--stats")
     return ap
 
@@ -43,8 +47,11 @@ def main(argv=None):
     proposals = np.load(flowio.stage_name(idx, a.backward, "proposals_nakon_gausa"))
     lcosts = np.load(flowio.stage_name(idx, a.backward, "lcosts_nakon_gausa"))
     nprop = np.load(flowio.stage_name(idx, a.backward, "nprop"))
-    bestlabels = np.load(flowio.labels_name(idx, a.backward, 0))
+    bestlabels = np.load(a.labels if a.labels is not None else flowio.labels_name(idx, a.backward, 0))
     pich, picw = nprop.shape
+    if a.labels is not None and not (bestlabels.shape == nprop.shape and np.issubdtype(bestlabels.dtype, np.integer)
+                                     and (bestlabels >= 0).all() and (bestlabels < nprop).all()):
+        raise SystemExit("python bcd: --labels %s is not an (%d,%d) integer labelling with 0 <= label < nprop" % (a.labels, pich, picw))
     cellh, cellw = (int(v) for v in a.cell.lower().split("x")) if a.cell else pipeline.default_cells(pich, picw)
     df = pipeline.DiscreteFlow(pich, picw, cellh, cellw, device=a.device)
     df.set_host_state(proposals, lcosts, nprop, bestlabels)
