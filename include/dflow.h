@@ -476,10 +476,11 @@ int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *
                     float *d_err, uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes, void *stream);
 
 /* Starting a pass from a flow somebody already has (the previous pair's flow, the inverse of the other direction's, a coarse
- * estimate, a sparse ground truth): dflow_prior_proposals appends the prior's vectors to the pixels' label sets and may start
- * the labelling on them; dflow_flow_advance makes such a prior out of a flow.  This build's definitions (DESIGN.md "Prior
- * proposals"); no counterpart in the reference, whose label sets hold kNN matches within +-window cells and copies of
- * neighbouring winners only.  A prior label competes on its DAISY cost like every other; the label space is integer.
+ * estimate (dflow_flow_upsample, below, makes one from a half-size level), a sparse ground truth): dflow_prior_proposals appends
+ * the prior's vectors to the pixels' label sets and may start the labelling on them; dflow_flow_advance makes such a prior out
+ * of a flow.  This build's definitions (DESIGN.md "Prior proposals"); no counterpart in the reference, whose label sets hold kNN
+ * matches within +-window cells and copies of neighbouring winners only.  A prior label competes on its DAISY cost like every
+ * other; the label space is integer.
  *
  * A VECTOR of a flow plane is USABLE (both entry points): under DFLOW_EVAL_UVV (H,W,3) [U,V,valid] the pixel needs valid > 0.5
  * (a NaN compares false) and dy = V, dx = U; under DFLOW_EVAL_DYDX (H,W,2) [dy,dx] every pixel is valid.  (dy,dx) = rintf of the
@@ -533,6 +534,38 @@ size_t dflow_flow_advance_workspace_bytes(int32_t h, int32_t w);
 int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout, uint32_t flags,
                        float *d_out /* (H,W,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[3] */,
                        void *d_ws, size_t ws_bytes, void *stream);
+
+/* Coarse to fine (DESIGN.md "Coarse to fine"): the two image-plane steps that connect two levels of a pyramid.  A level of
+ * size (h,w) has the coarser level (hc,wc) = ((h+1)/2, (w+1)/2) above it; coarse pixel j sits at fine position 2j.  This build's
+ * definitions; the reference runs one level and has no counterpart.  Both: 1 <= h, w <= 8192, asynchronous on `stream`, allocate
+ * nothing, need no workspace, read nothing back, can be captured into a graph; every refusal happens before anything is launched.
+ *
+ * dflow_pyr_down makes the next coarser level of one image, or of the two images of a pair in one launch (d_in2 and d_out2 both
+ * NULL or both given).  d_in* (h,w,3) uint8 BGR, d_out* (hc,wc,3) uint8.  With k = [1,4,6,4,1], i, j = -2..2 and the border
+ * replicated:
+ *     out[y][x][c] = (sum_i sum_j k_i k_j in[clamp(2y+i, 0, h-1)][clamp(2x+j, 0, w-1)][c] + 128) >> 8
+ * in integers, with the one rounding at the end (the kernel forms the sum separably, which changes nothing).  A constant image
+ * stays constant; 255 stays 255.  The planes of a pair equal those of two single calls.
+ * DFLOW_EINVAL: a size outside the range, a NULL d_in1 or d_out1, only one of d_in2 / d_out2 given, a pointer that is not 4-byte
+ * aligned, an output that is an input, d_out1 == d_out2.
+ *
+ * dflow_flow_upsample turns the flow of the coarser level into a prior for level (h,w): d_coarse (hc,wc,.) float32 in
+ * DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout, d_out (h,w,3) float32 [U,V,valid], what dflow_prior_proposals reads under
+ * DFLOW_EVAL_UVV.  A coarse vector is GOOD when it is valid (valid > 0.5 under UVV, always under DYDX) and both components are
+ * finite.  For fine pixel (y,x): y0 = y>>1, y1 = min((y+1)>>1, hc-1), x0 = x>>1, x1 = min((x+1)>>1, wc-1).  In float32, one IEEE
+ * operation per written operation:
+ *   BILINEAR  the four corners (y0|y1, x0|x1) are all good, U = ((U00 + U01) + (U10 + U11)) * 0.5f, V likewise, and both are
+ *             finite: [U, V, 1].  Twice the mean of the corners: a + b or 2a where corners coincide;
+ *   NEAREST   otherwise, corner (y0,x0) is good and 2*U00, 2*V00 are finite: [2*U00, 2*V00, 1];
+ *   INVALID   otherwise: [0, 0, 0].
+ * d_counts (NULL to skip) receives int32 {bilinear, nearest, invalid}, which add up to h*w; the call zeroes them itself, on the
+ * stream (integer atomics: exact in any order).
+ * DFLOW_EINVAL: a size or layout outside its range, a NULL d_coarse or d_out, a pointer that is not 4-byte aligned, d_out ==
+ * d_coarse, d_counts equal to either. */
+int dflow_pyr_down(int32_t h, int32_t w, const uint8_t *d_in1, const uint8_t *d_in2 /* NULL: one image */,
+                   uint8_t *d_out1, uint8_t *d_out2 /* NULL with d_in2 */, void *stream);
+int dflow_flow_upsample(int32_t h, int32_t w, const float *d_coarse, int32_t layout,
+                        float *d_out /* (h,w,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[3] */, void *stream);
 
 #ifdef __cplusplus
 }

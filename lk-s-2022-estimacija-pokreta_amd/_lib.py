@@ -106,6 +106,8 @@ _SIGNATURES = {
     "dflow_prior_proposals": (C.c_int, [_pp, _vp, _vp, _vp, _i32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dflow_flow_advance_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_flow_advance": (C.c_int, [_i32, _i32, _vp, _i32, C.c_uint32, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_pyr_down": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_flow_upsample": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

@@ -91,9 +91,10 @@ def history_json(passes, lamda, bcd_times, stop, size):
             "passes": [{"pass": name, "sweeps_run": len(h) - 1, "history": history_rows(h)} for name, h in passes]}
 
 
-def write_history_json(path, passes, lamda, bcd_times, stop, size):
+def write_history_json(path, passes, lamda, bcd_times, stop, size, extra=None):
+    """extra: further header entries (run_batch.py --pyramid adds "pyramid")."""
     with open(path, "w") as f:
-        json.dump(history_json(passes, lamda, bcd_times, stop, size), f, indent=1)
+        json.dump(dict(history_json(passes, lamda, bcd_times, stop, size), **(extra or {})), f, indent=1)
 
 
 def format_row(h):

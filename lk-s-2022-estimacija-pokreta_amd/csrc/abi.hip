@@ -551,6 +551,37 @@ int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout
     return launch_flow_advance(h, w, d_flow, layout, flags, d_out, d_counts, d_ws, (hipStream_t)stream);
 }
 
+int dflow_pyr_down(int32_t h, int32_t w, const uint8_t *d_in1, const uint8_t *d_in2, uint8_t *d_out1, uint8_t *d_out2, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    CHECK_PTR(d_in1); CHECK_PTR(d_out1);
+    if ((d_in2 == NULL) != (d_out2 == NULL))
+        return dflow_set_error(DFLOW_EINVAL, "%s: d_in2 and d_out2 must both be NULL or both be given", __func__);
+    // the kernel reads and writes the aligned dwords of the planes
+    rc = check_aligned(__func__, {{"d_in1", d_in1, 4}, {"d_in2", d_in2, 4}, {"d_out1", d_out1, 4}, {"d_out2", d_out2, 4}});
+    if (rc) return rc;
+    // a tile's input is read while other tiles' output is written, and the two images run side by side
+    for (const uint8_t *in : {d_in1, d_in2})
+        for (const uint8_t *out : {(const uint8_t *)d_out1, (const uint8_t *)d_out2})
+            if (in && in == out) return dflow_set_error(DFLOW_EINVAL, "%s: an output is the same plane as an input", __func__);
+    if (d_out1 == d_out2) return dflow_set_error(DFLOW_EINVAL, "%s: d_out1 and d_out2 are the same plane", __func__);
+    return launch_pyr_down(h, w, d_in1, d_in2, d_out1, d_out2, (hipStream_t)stream);
+}
+
+int dflow_flow_upsample(int32_t h, int32_t w, const float *d_coarse, int32_t layout, float *d_out, int32_t *d_counts, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    CHECK_PTR(d_coarse); CHECK_PTR(d_out);
+    rc = check_aligned(__func__, {{"d_coarse", d_coarse, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a fine pixel's corners are read after other fine pixels have been written
+    if (d_out == d_coarse) return dflow_set_error(DFLOW_EINVAL, "%s: d_out and d_coarse are the same plane", __func__);
+    if ((const void *)d_counts == (const void *)d_coarse || (const void *)d_counts == (const void *)d_out)
+        return dflow_set_error(DFLOW_EINVAL, "%s: d_counts is the same plane as d_coarse or d_out", __func__);
+    return launch_flow_upsample(h, w, d_coarse, layout, d_out, d_counts, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -61,6 +61,22 @@ __host__ __device__ static inline uint32_t pack_flow(int dy, int dx)
 __host__ __device__ static inline int flow_dy(uint32_t f) { return (int)(int16_t)(f & 0xFFFFu); }
 __host__ __device__ static inline int flow_dx(uint32_t f) { return (int)(int16_t)(f >> 16); }
 
+// The vector (fy, fx) of pixel `src` of a flow plane in either layout: DFLOW_EVAL_UVV (H,W,3) [U,V,valid], false when the pixel
+// is not valid (a NaN compares false); DFLOW_EVAL_DYDX (H,W,2) [dy,dx], every pixel valid.  prior.hip and pyramid.hip read
+// their flows through it.
+__device__ static inline bool flow_vector(const float *__restrict__ f, int layout, size_t src, float &fy, float &fx)
+{
+    if (layout == DFLOW_EVAL_UVV) {
+        const float *q = f + src * 3;
+        if (!(q[2] > 0.5f)) return false;
+        fx = q[0]; fy = q[1];
+    } else {
+        const float *q = f + src * 2;
+        fy = q[0]; fx = q[1];
+    }
+    return true;
+}
+
 // |dy-dy'| + |dx-dx'| of two packed labels (purepsi, daisy i flann.py:114-115): flip the sign bits so that the
 // int16 halves order like uint16, then one v_sad_u16.
 __device__ static inline uint32_t flow_bias(uint32_t f) { return f ^ 0x80008000u; }
@@ -303,3 +319,7 @@ int launch_prior(const dflow_params *p, const void *d1, const void *d2, const fl
 size_t flow_advance_ws_bytes(int H, int W);
 int launch_flow_advance(int H, int W, const float *flow, int layout, uint32_t flags, float *out, int32_t *counts, void *ws,
                         hipStream_t s);
+// pyramid.hip: one level of an image pyramid (in2 / out2 both NULL: one image) and a coarse flow doubled onto the next finer
+// grid (arguments validated by the caller); counts may be NULL
+int launch_pyr_down(int H, int W, const uint8_t *in1, const uint8_t *in2, uint8_t *out1, uint8_t *out2, hipStream_t s);
+int launch_flow_upsample(int H, int W, const float *coarse, int layout, float *out, int32_t *counts, hipStream_t s);

@@ -39,14 +39,7 @@ __device__ static inline int row_min16(int v)
 __device__ static inline bool prior_vector(const float *__restrict__ f, int layout, size_t src, int &dy, int &dx)
 {
     float fy, fx;
-    if (layout == DFLOW_EVAL_UVV) {
-        const float *q = f + src * 3;
-        if (!(q[2] > 0.5f)) return false;
-        fx = q[0]; fy = q[1];
-    } else {
-        const float *q = f + src * 2;
-        fy = q[0]; fx = q[1];
-    }
+    if (!flow_vector(f, layout, src, fy, fx)) return false;
     const float ry = rintf(fy), rx = rintf(fx);                             // ties to even
     if (!(fabsf(ry) <= 32767.0f) || !(fabsf(rx) <= 32767.0f)) return false; // NaN and infinities fail the compare
     dy = (int)ry; dx = (int)rx;

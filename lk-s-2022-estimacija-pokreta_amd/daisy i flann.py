@@ -27,6 +27,12 @@ vectors of the four pixels N away; --prior-advance carries every vector to the p
 flow as a constant-velocity prior), --prior-inverse does the same and negates it (the other direction's flow as a prior);
 --no-prior-seed leaves the starting labels alone (labels_prior then equals "posle 00").
 Seed only a prior you believe: started on a wrong but smooth flow the sweeps stay on it (the control run).
+
+Coarse to fine (DESIGN.md "Coarse to fine"): --pyramid L runs L - 1 coarser levels of the pair to completion in this process
+(pipeline.PyramidFlow: half the size per level, the same cells in pixels, --coarse-bcd-times N sweeps each, default 4) and uses
+the upsampled flow of level 1 where --prior FILE would stand: the files are those of --prior, labels_prior included, and
+--prior-stride and --no-prior-seed apply.  --fine-window W (0..2) narrows the kNN search of the full-size level to +-W cells.
+--pyramid together with --prior is refused.
 """
 import argparse
 import importlib
@@ -56,9 +62,20 @@ def main(argv=None):
     ap.add_argument("--prior-advance", action="store_true", help="carry the prior's vectors to the pixels they point at first")
     ap.add_argument("--prior-inverse", action="store_true", help="the same, negated: the other direction's flow as a prior")
     ap.add_argument("--no-prior-seed", action="store_true", help="append the prior's labels but do not start the labelling on them")
+    ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine: L levels, the coarser ones produce the prior")
+    ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="BCD sweeps of every coarse level of --pyramid (default 4)")
+    ap.add_argument("--fine-window", type=int, default=None, metavar="W", help="with --pyramid: the kNN window of the full-size level")
     a = ap.parse_args(argv)
-    if a.prior is None and (a.prior_advance or a.prior_inverse or a.no_prior_seed or a.prior_stride != 2):
-        ap.error("--prior-stride, --prior-advance, --prior-inverse and --no-prior-seed need --prior FILE")
+    if a.pyramid < 1:
+        ap.error("--pyramid L needs L >= 1")
+    if a.pyramid > 1 and a.prior is not None:
+        ap.error("--pyramid produces the prior itself: it excludes --prior FILE")
+    if a.pyramid == 1 and (a.fine_window is not None or a.coarse_bcd_times is not None):
+        ap.error("--coarse-bcd-times and --fine-window need --pyramid L with L > 1")
+    if a.prior is None and (a.prior_advance or a.prior_inverse):
+        ap.error("--prior-advance and --prior-inverse need --prior FILE")
+    if a.prior is None and a.pyramid == 1 and (a.no_prior_seed or a.prior_stride != 2):
+        ap.error("--prior-stride and --no-prior-seed need --prior FILE or --pyramid L")
     if a.prior_advance and a.prior_inverse:
         ap.error("--prior-advance and --prior-inverse exclude each other")
     pipeline = importlib.import_module(PKG + ".pipeline")
@@ -80,7 +97,15 @@ def main(argv=None):
     pich, picw = pic1.shape[:2]
     cellh, cellw = (int(v) for v in a.cell.lower().split("x")) if a.cell else pipeline.default_cells(pich, picw)
     flags = importlib.import_module(PKG + "._lib").FLAG_DESCR_F16 if a.fp16_descriptors else 0
-    df = pipeline.DiscreteFlow(pich, picw, cellh, cellw, device=a.device, seed=a.seed, flags=flags)
+    prior = None
+    if a.pyramid > 1:
+        pf = pipeline.PyramidFlow(pich, picw, a.pyramid, cellh, cellw, device=a.device, seed=a.seed, fine_window=a.fine_window, flags=flags)
+        df = pf.levels[0]
+        prior = pf.coarse_prior(pf.image_pyramid(np.ascontiguousarray(pic1), np.ascontiguousarray(pic2)),
+                                4 if a.coarse_bcd_times is None else a.coarse_bcd_times,
+                                a.prior_stride, not a.no_prior_seed)
+    else:
+        df = pipeline.DiscreteFlow(pich, picw, cellh, cellw, device=a.device, seed=a.seed, flags=flags)
     df.load_pair(np.ascontiguousarray(pic1), np.ascontiguousarray(pic2))    # :406-407
     df.generisi()                                                           # :409-412
     flow0 = df.vratiKonacniFlow().cpu().numpy().astype(np.float64)
@@ -94,9 +119,11 @@ def main(argv=None):
         prior = np.ascontiguousarray(prior, dtype=np.float32)
         if a.prior_advance or a.prior_inverse:
             prior = pipeline.flow_advance(prior, negate=a.prior_inverse)
+    if prior is not None:
         counts = df.prior_proposals(prior, stride=a.prior_stride, seed_labels=not a.no_prior_seed, counts=True).cpu().tolist()
         np.save(flowio.stage_name(idx, a.backward, "labels_prior"), df.bestlabels.cpu().numpy().astype(np.int64))
-        print("daisy i flann: prior %s: appended %d, found %d, full %d, skipped %d" % ((os.path.basename(a.prior),) + tuple(counts)))
+        source = os.path.basename(a.prior) if a.prior else "of %d pyramid levels" % a.pyramid
+        print("daisy i flann: prior %s: appended %d, found %d, full %d, skipped %d" % ((source,) + tuple(counts)))
     st = df.host_state()
     np.save(flowio.stage_name(idx, a.backward, "proposals_nakon_gausa"), st["proposals"])   # sacuvajPodatke1 :249-253
     np.save(flowio.stage_name(idx, a.backward, "lcosts_nakon_gausa"), st["lcosts"])

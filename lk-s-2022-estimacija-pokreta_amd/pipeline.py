@@ -702,3 +702,138 @@ def flow_advance(flow, negate=False, counts=False):
     _lib.call("dflow_flow_advance", H, W, flow.data_ptr(), _layout(flow), _lib.ADVANCE_NEGATE if negate else 0, out.data_ptr(),
               _ptr(cnt), ws.data_ptr(), ws_bytes, _lib.stream(dev))
     return (out, cnt) if counts else out
+
+
+def pyr_down(img1, img2=None):
+    """One level of an image pyramid (dflow_pyr_down, DESIGN.md "Coarse to fine"): a (H,W,3) uint8 BGR image, or the two images
+    of a pair in one launch, smoothed with the 5x5 binomial kernel [1,4,6,4,1] x [1,4,6,4,1] / 256 (replicated border, integer
+    arithmetic, one rounding) and sampled at the even pixels -> ((H+1)//2, (W+1)//2, 3) uint8 device tensor(s).  Device tensors or
+    host arrays; host data is uploaded to the current device.  Returns the level of img1, or with img2 the pair of levels.  Runs
+    on torch's current stream and does not wait for it."""
+    img1 = _check(img1, "pyr_down", "img1", torch.uint8, (None, None, 3))
+    H, W, _ = img1.shape
+    imgs = [img1] if img2 is None else [img1, _check(img2, "pyr_down", "img2", torch.uint8, (H, W, 3))]
+    dev = _device_of(*imgs)
+    imgs = _on(dev, *imgs)
+    outs = [torch.empty(((H + 1) // 2, (W + 1) // 2, 3), dtype=torch.uint8, device=dev) for _ in imgs]
+    _lib.call("dflow_pyr_down", H, W, imgs[0].data_ptr(), _ptr(imgs[1] if img2 is not None else None), outs[0].data_ptr(),
+              _ptr(outs[1] if img2 is not None else None), _lib.stream(dev))
+    return outs[0] if img2 is None else tuple(outs)
+
+
+def flow_upsample(flow, size, counts=False):
+    """The flow of a pyramid level as a prior for the next finer one (dflow_flow_upsample, DESIGN.md "Coarse to fine"): flow is
+    ((H+1)//2, (W+1)//2, 2) float32 [dy,dx] or (.., 3) float32 [U,V,valid] for size = (H, W); the last dimension says which.
+    Device tensor or host array; host data is uploaded to the current device.  Coarse pixel j sits at fine position 2j; a fine
+    pixel gets twice the mean of its four coarse corners where all four are valid and finite, else twice its corner (y>>1, x>>1),
+    else it is invalid.  Returns the (H,W,3) float32 [U,V,valid] device tensor, what DiscreteFlow.prior_proposals takes, and with
+    counts=True also the int32[3] device tensor {bilinear, nearest, invalid}.  Runs on torch's current stream and does not wait
+    for it."""
+    H, W = (int(v) for v in size)
+    if H < 1 or W < 1:
+        raise ValueError("flow_upsample: size must be (H, W) >= 1, got %r" % (size,))
+    flow = _check(flow, "flow_upsample", "flow", torch.float32, ((H + 1) // 2, (W + 1) // 2, (2, 3)))
+    dev = _device_of(flow)
+    flow, = _on(dev, flow)
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    cnt = _out(counts, 3, torch.int32, dev)
+    _lib.call("dflow_flow_upsample", H, W, flow.data_ptr(), _layout(flow), out.data_ptr(), _ptr(cnt), _lib.stream(dev))
+    return (out, cnt) if counts else out
+
+
+def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
+    """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
+    cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels
+    as level 0, clipped to its image, so a cell covers twice the scene per level and the reach of the +-window-cell search
+    doubles with it.  All coarse levels keep `window` as given (the library's default without it); level 0 takes fine_window
+    when that is not None.  ValueError, naming the level, for a level the library would refuse (an image below 8 px, a cell
+    with fewer than knn points, a window outside [0,2], ...).  Needs the library, not a device."""
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError("PyramidFlow: levels must be >= 1, got %d" % levels)
+    if cellh is None or cellw is None:
+        cellh, cellw = default_cells(pich, picw)
+    out, H, W = [], int(pich), int(picw)
+    for level in range(levels):
+        over = dict(overrides)
+        if level == 0 and fine_window is not None:
+            over["window"] = int(fine_window)
+        geom = dict(pich=H, picw=W, cellh=min(int(cellh), H), cellw=min(int(cellw), W))
+        p = _lib.default_params(geom["pich"], geom["picw"], geom["cellh"], geom["cellw"], **over)
+        if not _lib.lib().dflow_workspace_bytes(C.byref(p)):
+            raise ValueError("PyramidFlow: level %d (%dx%d, cells %dx%d) is refused: %s"
+                             % (level, W, H, geom["cellw"], geom["cellh"], _lib.lib().dflow_last_error().decode()))
+        out.append(dict(geom, **over))
+        H, W = (H + 1) // 2, (W + 1) // 2
+    return out
+
+
+class PyramidFlow:
+    """Coarse-to-fine passes (DESIGN.md "Coarse to fine"): one DiscreteFlow per level (self.levels, level 0 the finest, geometry
+    by pyramid_levels' rule); the coarsest level runs as DiscreteFlow.run does, every finer one starts from the upsampled flow of
+    the next coarser level, level l from level l + 1 (flow_upsample -> prior_proposals).  A vector beyond level 0's search window can enter its label sets
+    this way, and with a believed prior level 0 may search fewer cells (fine_window 1 or 0)."""
+
+    def __init__(self, pich, picw, levels=2, cellh=None, cellw=None, device="cuda:0", seed=0, fine_window=None, **overrides):
+        geoms = pyramid_levels(pich, picw, levels, cellh, cellw, fine_window, **overrides)
+        self.levels = [DiscreteFlow(device=device, seed=seed, **g) for g in geoms]
+        self.device = self.levels[0].device
+        self.counts = []
+
+    def size(self, level):
+        p = self.levels[level].p
+        return p.pich, p.picw
+
+    def image_pyramid(self, pic3, pic4):
+        """[(img1, img2)] per level as device tensors: one dflow_pyr_down launch per coarse level, for both images."""
+        df = self.levels[0]
+        pyr = [(df._device_image(pic3, df._img), df._device_image(pic4, df._img2))]
+        for _ in self.levels[1:]:
+            pyr.append(pyr_down(*pyr[-1]))
+        return pyr
+
+    def run_level(self, level, imgs, bcd_times, prior=None, prior_stride=2, seed_labels=True, counts=False):
+        """One level's pass on its images; prior None: DiscreteFlow.run.  Returns (the level's flow tensor, the int32[4] counts of
+        its prior step as a device tensor, or None without a prior or with counts=False)."""
+        df = self.levels[level]
+        if prior is None:
+            return df.run(imgs[0], imgs[1], bcd_times), None
+        df.load_pair(*imgs)
+        df.generisi()
+        df.nasumicni()
+        cnt = df.prior_proposals(prior, stride=prior_stride, seed_labels=seed_labels, counts=counts)
+        df.ceoBCD(bcd_times)
+        return df.vratiKonacniFlow(), cnt
+
+    def coarse_prior(self, pyramid, bcd_times, prior_stride=2, seed_labels=True, counts=False):
+        """Levels len - 1 .. 1 run to completion on `pyramid` (image_pyramid); returns the upsampled flow of level 1, the prior of
+        level 0 ((H,W,3) [U,V,valid]), or None with one level.  With counts=True self.counts is started anew and receives one
+        entry (level, int32[3] of flow_upsample, int32[4] of prior_proposals) per coarse level that had a prior, and last the
+        entry (0, int32[3] of the upsampling for level 0): the caller that runs level 0's prior step adds its counts."""
+        prior, ups = None, None
+        self.counts = []
+        for level in range(len(self.levels) - 1, 0, -1):
+            flow, cnt = self.run_level(level, pyramid[level], bcd_times, prior, prior_stride, seed_labels, counts)
+            if counts and prior is not None:
+                self.counts.append((level, ups, cnt))
+            prior = flow_upsample(flow, self.size(level - 1), counts=counts)
+            if counts:
+                prior, ups = prior
+        if counts and prior is not None:
+            self.counts.append((0, ups))
+        return prior
+
+    def run(self, pic3, pic4, bcd_times, coarse_bcd_times=None, prior_stride=2, seed_labels=True, counts=False):
+        """The whole run; returns level 0's flow tensor.  coarse_bcd_times: the sweeps of the coarse levels (None: bcd_times).
+        prior_stride and seed_labels as in DiscreteFlow.prior_proposals, for every level that has a prior.  With counts=True
+        self.counts holds, per level that had a prior, (level, int32[3] of flow_upsample, int32[4] of prior_proposals) as device
+        tensors.  Everything runs on torch's current stream; nothing is read back.  With one level these are exactly the
+        calls of DiscreteFlow.run."""
+        if len(self.levels) == 1:
+            return self.levels[0].run(pic3, pic4, bcd_times)
+        pyramid = self.image_pyramid(pic3, pic4)
+        prior = self.coarse_prior(pyramid, bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride, seed_labels, counts)
+        flow, cnt = self.run_level(0, pyramid[0], bcd_times, prior, prior_stride, seed_labels, counts)
+        if counts:
+            self.counts[-1] += (cnt,)
+        return flow

@@ -14,7 +14,7 @@ labels, --stop-energy R after the sweep that lowered E by at most the fraction R
 upper bound, and the files of the sweeps not run are not written.  Each of the three costs one read-back of 48 bytes per
 sweep; without them the run issues exactly the launches it always did.
 
---labels FILE starts from the labels in that .npy instead of "posle 00": the labels_prior file `daisy i flann.py --prior` writes,
+--labels FILE starts from the labels in that .npy instead of "posle 00": the labels_prior file `daisy i flann.py --prior` (or --pyramid) writes,
 or any (H,W) integer labelling with 0 <= label < nprop.
 """
 import argparse

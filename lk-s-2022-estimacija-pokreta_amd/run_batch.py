@@ -31,6 +31,12 @@ sweep (pipeline.ceoBCD_batch with a stop rule, DESIGN.md "BCD statistics and the
 in DIR.  --stop-changed F ends a pass after the sweep that changed at most the fraction F of its labels, --stop-energy R
 after the sweep that lowered E by at most the fraction R; --bcd-times stays the upper bound and names the flow files.  Each
 of the three costs one read-back of 48 bytes per pass and sweep; without them the launches are unchanged.
+--pyramid L runs every pass coarse to fine (pipeline.PyramidFlow, DESIGN.md "Coarse to fine"): inside a group the levels run
+from the coarsest to the finest for all its passes, each level with its own front ends side by side and its sweeps as batched
+launches, and a level's flow is upsampled into the prior of the next.  --coarse-bcd-times N sets the sweeps of the coarse
+levels (default: --bcd-times), --fine-window W the kNN window of the full-size level.  The files are those of a run without
+it (--bcd-stats describes the full-size level); the headers of eval.json, photo.json and bcd_stats.json gain "pyramid": L.
+Without it the launches are unchanged.
 """
 import argparse
 import importlib
@@ -67,6 +73,9 @@ def parser():
     ap.add_argument("--photo", action="store_true",
                     help="warp each pair's second image by the forward and (with --epic) final flow; prints the photometric error, writes photo.json")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
+    ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
+    ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="with --pyramid: sweeps of the coarse levels (default: --bcd-times)")
+    ap.add_argument("--fine-window", type=int, default=None, metavar="W", help="with --pyramid: kNN window (0..2) of the full-size level")
     return ap
 
 
@@ -143,14 +152,72 @@ def setup(a):
     s.group = max(1, min(a.group, len(mine)))
     flags = mod("_lib").FLAG_DESCR_F16 if a.fp16_descriptors else 0
     ch, cw = (int(v) for v in a.cell.lower().split("x")) if a.cell else (None, None)
-    s.dfs = [pipeline.DiscreteFlow(s.H, s.W, ch, cw, device=s.dev, seed=s.rank, flags=flags) for _ in range(s.group)]
+    if a.pyramid > 1:
+        s.pfs = [pipeline.PyramidFlow(s.H, s.W, a.pyramid, ch, cw, device=s.dev, seed=s.rank, fine_window=a.fine_window, flags=flags)
+                 for _ in range(s.group)]
+        s.dfs = [pf.levels[0] for pf in s.pfs]
+    else:
+        s.dfs = [pipeline.DiscreteFlow(s.H, s.W, ch, cw, device=s.dev, seed=s.rank, flags=flags) for _ in range(s.group)]
     s.front = [torch.cuda.Stream(device=s.dev) for _ in range(min(3, s.group))]     # front ends of a group's passes side by side
     return s
+
+
+def compute_many_pyramid(s, descs):
+    """compute_many with --pyramid L: per group, level L-1 .. 0 for all its passes.  A level's front ends (at the coarsest level
+    after the image pyramid, at the others with the prior step) run on the front streams, its sweeps as one batch on the main
+    stream, where its flows are then upsampled into the next level's priors."""
+    import torch
+    pipeline = mod("pipeline")
+    flows = []
+    main = torch.cuda.current_stream(s.dev)
+    nlev = s.a.pyramid
+    coarse_times = s.a.bcd_times if s.a.coarse_bcd_times is None else s.a.coarse_bcd_times
+    for g0 in range(0, len(descs), s.group):
+        part = descs[g0:g0 + s.group]
+        pfs = s.pfs[:len(part)]
+        pyramids, priors = [None] * len(part), [None] * len(part)
+        for level in range(nlev - 1, -1, -1):
+            start = torch.cuda.Event()
+            start.record(main)                               # the previous group's read-out, or the next coarser level, is done
+            done = []
+            for j, (pf, (pair, backward)) in enumerate(zip(pfs, part)):
+                img1, img2 = s.images[pair]
+                if backward:
+                    img1, img2 = img2, img1
+                st = s.front[j % len(s.front)]
+                with torch.cuda.stream(st):
+                    st.wait_event(start)
+                    if pyramids[j] is None:
+                        pyramids[j] = pf.image_pyramid(img1, img2)
+                    df = pf.levels[level]
+                    df.load_pair(*pyramids[j][level])
+                    df.generisi()
+                    df.nasumicni()
+                    if priors[j] is not None:
+                        priors[j].record_stream(st)          # made on the main stream
+                        df.prior_proposals(priors[j])
+                    df.pakovanje()
+                    e = torch.cuda.Event()
+                    e.record(st)
+                    done.append(e)
+            for e in done:
+                main.wait_event(e)
+            dfs = [pf.levels[level] for pf in pfs]
+            hist = pipeline.ceoBCD_batch(dfs, s.a.bcd_times if level == 0 else coarse_times, stop=s.stop if level == 0 else None)
+            if level > 0:
+                priors = [pipeline.flow_upsample(df.vratiKonacniFlow(), pf.size(level - 1)) for df, pf in zip(dfs, pfs)]
+        if hist is not None:
+            for desc, h in zip(part, hist):
+                s.histories[s.passes.index(desc)] = h
+        flows += [df.vratiKonacniFlow().clone() for df in dfs]
+    return flows
 
 
 def compute_many(s, descs):
     """The flows of this rank's passes `descs`, group by group; with a stop rule their histories go to s.histories."""
     import torch
+    if s.a.pyramid > 1:
+        return compute_many_pyramid(s, descs)
     flows = []
     main = torch.cuda.current_stream(s.dev)
     for g0 in range(0, len(descs), s.group):
@@ -259,7 +326,8 @@ def write_out(s, flows):
     os.makedirs(a.out, exist_ok=True)
     if s.stop is not None:
         named = [("pair %d backward=%d" % s.passes[i], s.histories[i]) for i in sorted(s.histories)]
-        bcdstats.write_history_json(os.path.join(a.out, "bcd_stats.json"), named, s.dfs[0].p.lamda, a.bcd_times, s.stop, (H, W))
+        bcdstats.write_history_json(os.path.join(a.out, "bcd_stats.json"), named, s.dfs[0].p.lamda, a.bcd_times, s.stop, (H, W),
+                                    extra={"pyramid": a.pyramid} if a.pyramid > 1 else None)
         for name, h in named:
             print("%s: %d sweeps, E %.3f -> %.3f, last sweep changed %d labels"
                   % (name, len(h) - 1, h[0]["energy"], h[-1]["energy"], h[-1]["n_changed"]))
@@ -281,6 +349,8 @@ def write_out(s, flows):
             tally(PHOTO, pair, [("fwd", fwd)] + dense, lambda field, **kw: pipeline.warp_eval(img1, img2, field, **kw),
                   photo_rows, photo_totals, s.dev)
     head = {"size": [H, W], "bcd_times": a.bcd_times}
+    if a.pyramid > 1:
+        head["pyramid"] = a.pyramid
     if a.photo:
         write_tally(os.path.join(a.out, "photo.json"), dict(head, err_thresh=10.0, err_max=30.0), PHOTO, photo_rows, photo_totals)
     if a.eval:
@@ -290,6 +360,8 @@ def write_out(s, flows):
 def main(argv=None):
     a = parser().parse_args(argv)
     a.epic = a.epic or a.epic_refine or a.prefilter
+    if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
+        raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)
     flows = run_passes(s)
     if s.rank == 0:
