@@ -567,6 +567,41 @@ int dflow_pyr_down(int32_t h, int32_t w, const uint8_t *d_in1, const uint8_t *d_
 int dflow_flow_upsample(int32_t h, int32_t w, const float *d_coarse, int32_t layout,
                         float *d_out /* (h,w,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[3] */, void *stream);
 
+/* The forward/backward check in image coordinates (DESIGN.md "Forward/backward check in image coordinates"): the vector at p
+ * against the other direction's vector at p + f(p).  This build's definition: dflow_fb_consistency, above, restates the
+ * reference's check, which adds U to the row and V to the column, and stays what it is; the reference has no
+ * counterpart to this one.  1 <= h, w <= 8192.  d_fwd and d_bwd are (h,w,.) float32, each in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX
+ * layout.  A vector is GOOD as in dflow_flow_upsample: valid under its layout (valid > 0.5 under UVV, always under DYDX) and
+ * both components finite.  Float32, one IEEE operation per written operation.  For pixel (y,x) of the forward output, with
+ * (V,U) = (dy,dx) of d_fwd there, the class is the first that applies:
+ *   FWD_INVALID  the forward vector is not good;
+ *   OUTSIDE      nearest (no flag): (ry,rx) = rintf of (V,U), ties to even; a rounded component outside [-32767, 32767], or a
+ *                target (ty,tx) = (y+ry, x+rx) outside the frame.  DFLOW_FBC_BILINEAR: py = (float)y + V, px = (float)x + U, and
+ *                not (py >= 0 && py <= (float)(h-1) && px >= 0 && px <= (float)(w-1));
+ *   BWD_INVALID  nearest: the vector of d_bwd at (ty,tx) is not good; else (bv,bu) is that vector.  Bilinear: y0 = (int)floorf(py),
+ *                ay = py - (float)y0, y1 = ay > 0 ? y0+1 : y0, and x0, ax, x1 likewise (a corner of weight zero is not looked
+ *                at); one of the corners (y0|y1, x0|x1) is not good; else t = U00 + ax*(U01 - U00), b = U10 + ax*(U11 - U10),
+ *                bu = t + ay*(b - t), and bv likewise;
+ *   ABOVE        du = U + bu, dv = V + bv, err = sqrtf(du*du + dv*dv), and not err <= thresh (a NaN or infinite err is above);
+ *   CONSISTENT   otherwise.
+ * d_out_fwd (h,w,3) float32 receives [U, V, 1], the forward vector's own bits, for CONSISTENT and [0,0,0] for every other class;
+ * d_err_fwd (NULL to skip) (h,w) float32 receives err for ABOVE and CONSISTENT and -1 otherwise; d_counts (NULL to skip) receives
+ * int32 {consistent, above, bwd_invalid, outside, fwd_invalid}, which add up to h*w; the call zeroes them itself, on the stream
+ * (integer atomics: exact in any order).  With d_out_bwd the same is done with the roles of d_fwd and d_bwd swapped, in the same
+ * launch, into d_out_bwd, d_err_bwd and d_counts[5..9]; outputs and counts equal those of two single calls.  On integer-valued
+ * fields (every BCD output) bilinear equals nearest bit for bit.
+ * DFLOW_EINVAL before anything is launched: a size, layout or flag outside its range, thresh not finite or negative, a NULL
+ * d_fwd, d_bwd or d_out_fwd, d_err_bwd without d_out_bwd, a pointer that is not 4-byte aligned, an output equal to an input or to
+ * another output.  Asynchronous on `stream`, allocates nothing, needs no workspace, reads nothing back, can be captured into a
+ * graph. */
+#define DFLOW_FBC_BILINEAR 1u
+int dflow_flow_consistency(int32_t h, int32_t w,
+        const float *d_fwd, int32_t layout_fwd, const float *d_bwd, int32_t layout_bwd,
+        float thresh, uint32_t flags,
+        float *d_out_fwd /* (h,w,3) [U,V,valid] */, float *d_out_bwd /* NULL: forward only */,
+        float *d_err_fwd /* NULL or (h,w) */, float *d_err_bwd /* NULL or (h,w); needs d_out_bwd */,
+        int32_t *d_counts /* NULL, or int32[5], int32[10] with d_out_bwd */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

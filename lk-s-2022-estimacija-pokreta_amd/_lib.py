@@ -17,6 +17,7 @@ EVAL_FLAG_ACCUMULATE = 1    # DFLOW_EVAL_FLAG_ACCUMULATE
 WARP_FLAG_ACCUMULATE = 1    # DFLOW_WARP_FLAG_ACCUMULATE
 PRIOR_SEED_LABELS = 1       # DFLOW_PRIOR_SEED_LABELS
 ADVANCE_NEGATE = 1          # DFLOW_ADVANCE_NEGATE
+FBC_BILINEAR = 1            # DFLOW_FBC_BILINEAR
 
 
 class DflowError(RuntimeError):
@@ -108,6 +109,7 @@ _SIGNATURES = {
     "dflow_flow_advance": (C.c_int, [_i32, _i32, _vp, _i32, C.c_uint32, _vp, _vp, _vp, _sz, _vp]),
     "dflow_pyr_down": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dflow_flow_upsample": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "dflow_flow_consistency": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

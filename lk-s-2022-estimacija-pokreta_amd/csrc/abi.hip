@@ -582,6 +582,34 @@ int dflow_flow_upsample(int32_t h, int32_t w, const float *d_coarse, int32_t lay
     return launch_flow_upsample(h, w, d_coarse, layout, d_out, d_counts, (hipStream_t)stream);
 }
 
+int dflow_flow_consistency(int32_t h, int32_t w, const float *d_fwd, int32_t layout_fwd, const float *d_bwd, int32_t layout_bwd,
+                           float thresh, uint32_t flags, float *d_out_fwd, float *d_out_bwd, float *d_err_fwd, float *d_err_bwd,
+                           int32_t *d_counts, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    for (int layout : {layout_fwd, layout_bwd})
+        if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (flags & ~DFLOW_FBC_BILINEAR) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    if (!isfinite(thresh) || thresh < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: thresh=%g must be finite and >= 0", __func__, (double)thresh);
+    CHECK_PTR(d_fwd); CHECK_PTR(d_bwd); CHECK_PTR(d_out_fwd);
+    if (d_err_bwd && !d_out_bwd) return dflow_set_error(DFLOW_EINVAL, "%s: d_err_bwd needs d_out_bwd", __func__);
+    rc = check_aligned(__func__, {{"d_fwd", d_fwd, 4}, {"d_bwd", d_bwd, 4}, {"d_out_fwd", d_out_fwd, 4}, {"d_out_bwd", d_out_bwd, 4},
+                                  {"d_err_fwd", d_err_fwd, 4}, {"d_err_bwd", d_err_bwd, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a pixel's target is read after other pixels have been written, and the two directions run side by side
+    const void *outs[] = {d_out_fwd, d_out_bwd, d_err_fwd, d_err_bwd, d_counts};
+    for (size_t i = 0; i < 5; i++) {
+        if (!outs[i]) continue;
+        if (outs[i] == (const void *)d_fwd || outs[i] == (const void *)d_bwd)
+            return dflow_set_error(DFLOW_EINVAL, "%s: an output is the same plane as an input", __func__);
+        for (size_t j = 0; j < i; j++)
+            if (outs[i] == outs[j]) return dflow_set_error(DFLOW_EINVAL, "%s: two outputs are the same plane", __func__);
+    }
+    return launch_flow_consistency(h, w, d_fwd, layout_fwd, d_bwd, layout_bwd, thresh, flags, d_out_fwd, d_out_bwd, d_err_fwd, d_err_bwd,
+                                   d_counts, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -323,3 +323,8 @@ int launch_flow_advance(int H, int W, const float *flow, int layout, uint32_t fl
 // grid (arguments validated by the caller); counts may be NULL
 int launch_pyr_down(int H, int W, const uint8_t *in1, const uint8_t *in2, uint8_t *out1, uint8_t *out2, hipStream_t s);
 int launch_flow_upsample(int H, int W, const float *coarse, int layout, float *out, int32_t *counts, hipStream_t s);
+// consistency.hip: the forward/backward check in image coordinates, one direction or (out_bwd given) both in one launch
+// (arguments validated by the caller); err_* and counts may be NULL
+int launch_flow_consistency(int H, int W, const float *fwd, int layout_fwd, const float *bwd, int layout_bwd, float thresh,
+                            uint32_t flags, float *out_fwd, float *out_bwd, float *err_fwd, float *err_bwd, int32_t *counts,
+                            hipStream_t s);

@@ -32,7 +32,10 @@ Coarse to fine (DESIGN.md "Coarse to fine"): --pyramid L runs L - 1 coarser leve
 (pipeline.PyramidFlow: half the size per level, the same cells in pixels, --coarse-bcd-times N sweeps each, default 4) and uses
 the upsampled flow of level 1 where --prior FILE would stand: the files are those of --prior, labels_prior included, and
 --prior-stride and --no-prior-seed apply.  --fine-window W (0..2) narrows the kNN search of the full-size level to +-W cells.
---pyramid together with --prior is refused.
+--pyramid together with --prior is refused.  --gate T (pixels of the level it is applied at; needs --pyramid L > 1): every coarse
+level runs in both directions and its two flows go through the forward/backward check in image coordinates
+(pipeline.flow_consistency, DESIGN.md "Forward/backward check in image coordinates") before they are upsampled, so a coarse vector
+that fails the check is no prior for the next level.
 """
 import argparse
 import importlib
@@ -65,7 +68,11 @@ def main(argv=None):
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine: L levels, the coarser ones produce the prior")
     ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="BCD sweeps of every coarse level of --pyramid (default 4)")
     ap.add_argument("--fine-window", type=int, default=None, metavar="W", help="with --pyramid: the kNN window of the full-size level")
+    ap.add_argument("--gate", type=float, default=None, metavar="T", help="with --pyramid: coarse levels run both ways, vectors failing the "
+                    "forward/backward check by more than T px are no prior")
     a = ap.parse_args(argv)
+    if a.gate is not None and (a.pyramid <= 1 or not (np.isfinite(a.gate) and a.gate >= 0)):
+        ap.error("--gate T needs --pyramid L with L > 1 and a finite T >= 0")
     if a.pyramid < 1:
         ap.error("--pyramid L needs L >= 1")
     if a.pyramid > 1 and a.prior is not None:
@@ -103,7 +110,9 @@ def main(argv=None):
         df = pf.levels[0]
         prior = pf.coarse_prior(pf.image_pyramid(np.ascontiguousarray(pic1), np.ascontiguousarray(pic2)),
                                 4 if a.coarse_bcd_times is None else a.coarse_bcd_times,
-                                a.prior_stride, not a.no_prior_seed)
+                                a.prior_stride, not a.no_prior_seed, **(dict(gate=a.gate, pair=True) if a.gate is not None else {}))
+        if a.gate is not None:
+            prior = prior[0]                                                # the direction of this run
     else:
         df = pipeline.DiscreteFlow(pich, picw, cellh, cellw, device=a.device, seed=a.seed, flags=flags)
     df.load_pair(np.ascontiguousarray(pic1), np.ascontiguousarray(pic2))    # :406-407

@@ -741,6 +741,37 @@ def flow_upsample(flow, size, counts=False):
     return (out, cnt) if counts else out
 
 
+def flow_consistency(fwd, bwd, thresh, bilinear=False, both=False, err=False, counts=False):
+    """The forward/backward check in image coordinates (dflow_flow_consistency, DESIGN.md "Forward/backward check in image
+    coordinates"): the forward vector at p is kept if the backward vector at p + f(p) undoes it to within thresh pixels
+    (|f(p) + b(p + f(p))| <= thresh).  Not fb_consistency, which restates the reference's check with its transposed lookup.  fwd
+    and bwd are (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid], each on its own; the last dimension says which.  Device
+    tensors or host arrays; host data is uploaded to the current device.  The backward vector is looked up at the rounded
+    target, or with bilinear=True interpolated from the four pixels around the exact one (the same result on integer flows).  A
+    vector that is invalid or not finite, whose target leaves the frame or meets an invalid vector, or whose error is above
+    thresh becomes [0,0,0].  Returns the (H,W,3) float32 [U,V,valid] device tensor of the forward field, or a tuple in the order
+    (out_fwd[, out_bwd][, err_fwd[, err_bwd]][, counts]): both=True checks the backward field against the forward one in the same
+    launch; err=True adds the (H,W) float32 error planes (-1 where no error was formed); counts=True adds the int32 device
+    tensor {consistent, above, bwd_invalid, outside, fwd_invalid}, (5,) or with both (2,5), row 0 the forward field's.  Runs on
+    torch's current stream and does not wait for it."""
+    fwd = _check(fwd, "flow_consistency", "fwd", torch.float32, (None, None, (2, 3)))
+    H, W, _ = fwd.shape
+    bwd = _check(bwd, "flow_consistency", "bwd", torch.float32, (H, W, (2, 3)))
+    thresh = float(thresh)
+    if not (np.isfinite(thresh) and thresh >= 0):
+        raise ValueError("flow_consistency: thresh must be finite and >= 0, got %r" % thresh)
+    dev = _device_of(fwd, bwd)
+    fwd, bwd = _on(dev, fwd, bwd)
+    outs = [torch.empty((H, W, 3), dtype=torch.float32, device=dev), _out(both, (H, W, 3), torch.float32, dev)]
+    errs = [_out(err, (H, W), torch.float32, dev), _out(err and both, (H, W), torch.float32, dev)]
+    cnt = _out(counts, (2, 5) if both else (5,), torch.int32, dev)
+    _lib.call("dflow_flow_consistency", H, W, fwd.data_ptr(), _layout(fwd), bwd.data_ptr(), _layout(bwd), thresh,
+              _lib.FBC_BILINEAR if bilinear else 0, outs[0].data_ptr(), _ptr(outs[1]), _ptr(errs[0]), _ptr(errs[1]), _ptr(cnt),
+              _lib.stream(dev))
+    ret = tuple(t for t in outs + errs + [cnt] if t is not None)
+    return ret if len(ret) > 1 else ret[0]
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels
@@ -779,6 +810,7 @@ class PyramidFlow:
         self.levels = [DiscreteFlow(device=device, seed=seed, **g) for g in geoms]
         self.device = self.levels[0].device
         self.counts = []
+        self.gate_counts = []
 
     def size(self, level):
         p = self.levels[level].p
@@ -805,11 +837,19 @@ class PyramidFlow:
         df.ceoBCD(bcd_times)
         return df.vratiKonacniFlow(), cnt
 
-    def coarse_prior(self, pyramid, bcd_times, prior_stride=2, seed_labels=True, counts=False):
+    def coarse_prior(self, pyramid, bcd_times, prior_stride=2, seed_labels=True, counts=False, gate=None, gate_bilinear=False,
+                     pair=False):
         """Levels len - 1 .. 1 run to completion on `pyramid` (image_pyramid); returns the upsampled flow of level 1, the prior of
         level 0 ((H,W,3) [U,V,valid]), or None with one level.  With counts=True self.counts is started anew and receives one
         entry (level, int32[3] of flow_upsample, int32[4] of prior_proposals) per coarse level that had a prior, and last the
-        entry (0, int32[3] of the upsampling for level 0): the caller that runs level 0's prior step adds its counts."""
+        entry (0, int32[3] of the upsampling for level 0): the caller that runs level 0's prior step adds its counts.
+        pair=True: every coarse level runs forward and then backward (the images swapped) and the pair of priors is returned;
+        the entries of self.counts then hold pairs (forward, backward) in place of the tensors.  gate=T (needs pair): the two
+        flows of a coarse level go through flow_consistency(.., T, both=True) before they are upsampled, T in pixels of that
+        level; a gated-out vector is invalid, so the finer level's prior step skips what the upsampling cannot fill from its
+        neighbours.  With counts=True self.gate_counts holds (level, int32[2,5] of flow_consistency) per coarse level."""
+        if pair or gate is not None:
+            return self._coarse_prior_pair(pyramid, bcd_times, prior_stride, seed_labels, counts, gate, gate_bilinear, pair)
         prior, ups = None, None
         self.counts = []
         for level in range(len(self.levels) - 1, 0, -1):
@@ -822,6 +862,59 @@ class PyramidFlow:
         if counts and prior is not None:
             self.counts.append((0, ups))
         return prior
+
+    def _run_level_pair(self, level, imgs, bcd_times, priors, prior_stride, seed_labels, counts):
+        """run_level forward, then backward with the images swapped, on the level's one DiscreteFlow; vratiKonacniFlow returns
+        the object's buffer, so each flow is cloned before the object is used again.  Returns ([flows], [prior counts])."""
+        flows, cnts = [], []
+        for prior, (a, b) in zip(priors, ((imgs[0], imgs[1]), (imgs[1], imgs[0]))):
+            flow, cnt = self.run_level(level, (a, b), bcd_times, prior, prior_stride, seed_labels, counts)
+            flows.append(flow.clone())
+            cnts.append(cnt)
+        return flows, cnts
+
+    def _coarse_prior_pair(self, pyramid, bcd_times, prior_stride, seed_labels, counts, gate, gate_bilinear, pair):
+        if not pair:
+            raise ValueError("PyramidFlow.coarse_prior: gate needs pair=True (the check needs both directions)")
+        priors, ups = (None, None), None
+        self.counts, self.gate_counts = [], []
+        for level in range(len(self.levels) - 1, 0, -1):
+            flows, cnts = self._run_level_pair(level, pyramid[level], bcd_times, priors, prior_stride, seed_labels, counts)
+            if counts and priors[0] is not None:
+                self.counts.append((level, ups, tuple(cnts)))
+            if gate is not None:
+                res = flow_consistency(flows[0], flows[1], gate, bilinear=gate_bilinear, both=True, counts=counts)
+                flows = res[:2]
+                if counts:
+                    self.gate_counts.append((level, res[2]))
+            res = [flow_upsample(f, self.size(level - 1), counts=counts) for f in flows]
+            priors, ups = (tuple(r[0] for r in res), tuple(r[1] for r in res)) if counts else (tuple(res), None)
+        if counts and priors[0] is not None:
+            self.counts.append((0, ups))
+        return priors
+
+    def run_pair(self, pic3, pic4, bcd_times, coarse_bcd_times=None, gate=None, gate_bilinear=False, prior_stride=2, seed_labels=True,
+                 counts=False):
+        """Both directions of a pair: returns (forward flow, backward flow) of level 0, as tensors of their own.  The image
+        pyramid is built once; every level runs forward (pic3 -> pic4) and then backward (pic4 -> pic3).  gate=None: the flows
+        of run(pic3, pic4, ..) and run(pic4, pic3, ..).  gate=T: the two flows of every coarse level go through
+        flow_consistency(.., T, both=True[, bilinear=gate_bilinear]) before they are upsampled, so a coarse vector that fails the
+        forward/backward check is no prior (coarse_prior; T in pixels of the level it is applied at).  The other arguments and
+        self.counts as in run and coarse_prior(pair=True)."""
+        if gate is not None:
+            gate = float(gate)
+            if not (np.isfinite(gate) and gate >= 0):
+                raise ValueError("PyramidFlow.run_pair: gate must be None or finite and >= 0, got %r" % gate)
+        pyramid = self.image_pyramid(pic3, pic4)
+        priors = (None, None)
+        self.counts, self.gate_counts = [], []
+        if len(self.levels) > 1:
+            priors = self.coarse_prior(pyramid, bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride, seed_labels,
+                                       counts, gate, gate_bilinear, pair=True)
+        flows, cnts = self._run_level_pair(0, pyramid[0], bcd_times, priors, prior_stride, seed_labels, counts)
+        if counts and priors[0] is not None:
+            self.counts[-1] += (tuple(cnts),)
+        return tuple(flows)
 
     def run(self, pic3, pic4, bcd_times, coarse_bcd_times=None, prior_stride=2, seed_labels=True, counts=False):
         """The whole run; returns level 0's flow tensor.  coarse_bcd_times: the sweeps of the coarse levels (None: bcd_times).

@@ -37,6 +37,11 @@ launches, and a level's flow is upsampled into the prior of the next.  --coarse-
 levels (default: --bcd-times), --fine-window W the kNN window of the full-size level.  The files are those of a run without
 it (--bcd-stats describes the full-size level); the headers of eval.json, photo.json and bcd_stats.json gain "pyramid": L.
 Without it the launches are unchanged.
+--check natural replaces the consistency check of every pair by the one in image coordinates (pipeline.flow_consistency, nearest
+lookup, DESIGN.md "Forward/backward check in image coordinates": the forward vector at p against the backward vector at
+p + f(p)); --thresh is its threshold.  The printed "survives" line, sparse_field_<pair>.npy, parovi_<pair>.txt, --prefilter,
+--epic and --eval's "sparse" row follow the choice, and the header of eval.json gains "check": "natural".  The default,
+reference, is the reference's check with its transposed lookup (pipeline.fb_consistency): nothing changes.
 """
 import argparse
 import importlib
@@ -55,6 +60,8 @@ def parser():
     ap.add_argument("--bcd-times", type=int, default=4)
     ap.add_argument("--size", default="436x1024")
     ap.add_argument("--thresh", type=float, default=10.0)     # README.md:65 of the reference
+    ap.add_argument("--check", choices=("reference", "natural"), default="reference",
+                    help="the forward/backward check: the reference's (transposed lookup), or the one in image coordinates")
     ap.add_argument("--out", default=".")
     ap.add_argument("--group", type=int, default=4, help="passes of a rank whose BCD sweeps share their launches")
     ap.add_argument("--cell", default=None, help="cell size HxW (default: the geometry's usual cells)")
@@ -287,7 +294,7 @@ def write_pair(s, pair, fwd, bwd):
     the final dense flow (None without --epic) and the pair's images (None unless a stage asked for them)."""
     a = s.a
     pipeline, synth, flowio = mod("pipeline"), mod("synth"), mod("flowio")
-    sparse_dev = pipeline.fb_consistency(fwd, bwd, a.thresh)
+    sparse_dev = pipeline.flow_consistency(fwd, bwd, a.thresh) if a.check == "natural" else pipeline.fb_consistency(fwd, bwd, a.thresh)
     sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
     sparse = sparse_dev.cpu().numpy()
     for backward, f in ((0, fwd), (1, bwd)):
@@ -354,6 +361,8 @@ def write_out(s, flows):
     if a.photo:
         write_tally(os.path.join(a.out, "photo.json"), dict(head, err_thresh=10.0, err_max=30.0), PHOTO, photo_rows, photo_totals)
     if a.eval:
+        if a.check != "reference":
+            head["check"] = a.check
         write_tally(os.path.join(a.out, "eval.json"), dict(head, abs_thresh=3.0), EVAL, eval_rows, eval_totals)
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--gpu-epic [--prefilter] [--refine]]
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--natural-check] [--gpu-epic [--prefilter] [--refine]]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
@@ -21,6 +21,10 @@ interpolation reads is filtered: sparse_field.npy and parovi.txt are written unf
 With --refine as the last token, after --gpu-epic [--prefilter], the interpolated flow goes through this package's variational
 refinement with img1 and img2 (pipeline.variational_refine, its defaults; DESIGN.md "Variational refinement") before epic.flo
 is written: the second thing epicflow-static does.
+With --natural-check directly after the six positional tokens (before --gpu-epic, if that follows), sparse_field.npy, parovi.txt
+and everything after them come from the forward/backward check in image coordinates (pipeline.flow_consistency, nearest lookup,
+threshold con_tresh; DESIGN.md "Forward/backward check in image coordinates") in place of the reference's postProcessing, whose
+lookup is transposed.
 """
 import importlib
 import os
@@ -54,8 +58,15 @@ def parse(argv):
     return argv[:6], gpu_epic, prefilter, refine
 
 
+def take_natural(argv):
+    """The optional seventh token --natural-check: (the command line without it, whether it was there)."""
+    natural = argv[6:7] == ["--natural-check"]
+    return (argv[:6] + argv[7:] if natural else argv), natural
+
+
 def main(argv=None):
-    parsed = parse(sys.argv[1:] if argv is None else list(argv))
+    argv, natural = take_natural(sys.argv[1:] if argv is None else list(argv))
+    parsed = parse(argv)
     if parsed == 2:
         return 2
     (kitti1, kitti2, foward, backward, tresh, kind), gpu_epic, prefilter, refine = parsed
@@ -73,7 +84,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     fwd = torch.from_numpy(np.load(foward).astype(np.float32)).to(dev)
     bwd = torch.from_numpy(np.load(backward).astype(np.float32)).to(dev)
-    sparse_dev = pipeline.fb_consistency(fwd, bwd, con_tresh)
+    sparse_dev = pipeline.flow_consistency(fwd, bwd, con_tresh) if natural else pipeline.fb_consistency(fwd, bwd, con_tresh)
     sparse = sparse_dev.cpu().numpy()                                      # postProcessing, :15
     np.save("sparse_field.npy", sparse)
     evaluate.parovi(sparse, "parovi.txt")                                  # :17
