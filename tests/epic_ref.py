@@ -166,6 +166,80 @@ def fit(sparse, s, lst, k, method):
     return model, lmin
 
 
+def list_arrays(lists, seeds, nn):
+    """{s: [(id, G)]} -> (ids, G): (len(seeds), nn) int64 arrays in the order of `seeds`, -1 pads after a short list."""
+    ids = np.full((len(seeds), nn), -1, np.int64)
+    G = np.full((len(seeds), nn), -1, np.int64)
+    for i, s in enumerate(seeds):
+        l = lists[s][:nn]
+        ids[i, :len(l)] = [t for t, _ in l]
+        G[i, :len(l)] = [g for _, g in l]
+    return ids, G
+
+
+def fit_prefixes(sparse, seeds, ids, G, k, nns):
+    """fit() of every seed of `seeds` on the first nn entries of its list, for every nn of nns, in one pass over the list
+    positions: the sums grow entry by entry in list order, so the operations and their order are those of fit(), one seed
+    per array element.  ids, G as list_arrays() gives them.  {nn: {"NW": (n,6), "LA": (n,6), "lmin": (n,)}} in float64; lmin
+    is NaN where the list is shorter than 3."""
+    sp = np.asarray(sparse, np.float32)
+    W = sp.shape[1]
+    flat = sp.reshape(-1, 3).astype(np.float64)
+    seeds = np.asarray(seeds, np.int64)
+    n = len(seeds)
+    xs, ys = seeds % W, seeds // W
+    sw, sx, sy, sxx, sxy, syy, su, sv, sxu, syu, sxv, syv = (np.zeros(n) for _ in range(12))
+    count = np.zeros(n, np.int64)
+    out = {}
+    for j in range(max(nns)):
+        live = ids[:, j] >= 0
+        t = np.where(live, ids[:, j], 0)
+        with np.errstate(over="ignore"):
+            w = np.exp(-(k * G[:, j].astype(np.float64)) / 2000.0)
+        w = np.where(live, np.where(t == seeds, 1.0, w), 0.0)
+        dx, dy = (t % W - xs).astype(np.float64), (t // W - ys).astype(np.float64)
+        u, v = np.where(live, flat[t, 0], 0.0), np.where(live, flat[t, 1], 0.0)
+        wx, wy = w * dx, w * dy
+        sw += w; sx += wx; sy += wy; sxx += wx * dx; sxy += wx * dy; syy += wy * dy
+        su += w * u; sv += w * v; sxu += wx * u; syu += wy * u; sxv += wx * v; syv += wy * v
+        count += live
+        if j + 1 not in nns:
+            continue
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            mu, mv = su / sw, sv / sw
+            zero = np.zeros(n)
+            nw = np.stack([mu, zero, zero, mv, zero, zero], axis=1)
+            mx, my = sx / sw, sy / sw
+            cxx, cxy, cyy = sxx / sw - mx * mx, sxy / sw - mx * my, syy / sw - my * my
+            h = 0.5 * (cxx - cyy)
+            lmin = np.where(count >= 3, 0.5 * (cxx + cyy) - np.sqrt(h * h + cxy * cxy), np.nan)
+            det = cxx * cyy - cxy * cxy
+            cxu, cyu = sxu / sw - mx * mu, syu / sw - my * mu
+            cxv, cyv = sxv / sw - mx * mv, syv / sw - my * mv
+            bu, cu = (cyy * cxu - cxy * cyu) / det, (cxx * cyu - cxy * cxu) / det
+            bv, cv = (cyy * cxv - cxy * cyv) / det, (cxx * cyv - cxy * cxv) / det
+            affine = np.stack([mu - bu * mx - cu * my, bu, cu, mv - bv * mx - cv * my, bv, cv], axis=1)
+            la = np.where((lmin >= TAU)[:, None], affine, nw)
+        out[j + 1] = {"NW": nw, "LA": la, "lmin": lmin}
+    return out
+
+
+def fill_plane(S, seeds, models, dt=np.float64):
+    """fill() for models given as an (n,6) array in the order of `seeds`, evaluated in dt: float64 as fill() does, or
+    float32 on the models rounded to float32, in the written order (m0 + m1 dx) + m2 dy: the float32 yardstick."""
+    H, W = S.shape
+    index = np.full(H * W + 1, len(seeds), np.int64)      # S = -1 reads the zero model appended below
+    index[np.asarray(seeds, np.int64)] = np.arange(len(seeds))
+    Sf = S.ravel()
+    m = np.concatenate([np.asarray(models, np.float64), np.zeros((1, 6))]).astype(dt)[index[Sf]]
+    ys, xs = np.divmod(np.arange(H * W), W)
+    dx, dy = np.where(Sf >= 0, xs - Sf % W, 0).astype(dt), np.where(Sf >= 0, ys - Sf // W, 0).astype(dt)
+    flow = np.zeros((H * W, 2), dt)
+    flow[:, 1] = (m[:, 0] + m[:, 1] * dx) + m[:, 2] * dy
+    flow[:, 0] = (m[:, 3] + m[:, 4] * dx) + m[:, 5] * dy
+    return flow.reshape(H, W, 2)
+
+
 def interpolate(sparse, edges, nn=100, k=0.8, method="LA"):
     """The whole step: dict with flow (H,W,2) float64 [dy,dx], S, D, lists {s: [(id, G)]}, lmin {s: lambda_min}."""
     sp = np.asarray(sparse, np.float32)
