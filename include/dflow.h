@@ -602,6 +602,41 @@ int dflow_flow_consistency(int32_t h, int32_t w,
         float *d_err_fwd /* NULL or (h,w) */, float *d_err_bwd /* NULL or (h,w); needs d_out_bwd */,
         int32_t *d_counts /* NULL, or int32[5], int32[10] with d_out_bwd */, void *stream);
 
+/* The small-segment filter of a sparse flow field (DESIGN.md "Small-segment filter"): the second post-processing step of Menze,
+ * Heipke and Geiger, on the device.  This build's definition: dflow_remove_small_segments_host, above, restates the reference's
+ * removeSmallSegments, a sequential flood fill whose result depends on its scan order, and stays what it is; the two agree only
+ * on a field where nothing is removed and no non-member touches a member it could absorb (DESIGN.md names the differences).
+ * 1 <= h, w <= 8192.  d_flow is (h,w,.) float32 in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout.
+ *   MEMBER   a pixel whose vector is GOOD as in dflow_flow_consistency: valid under its layout (valid > 0.5 under UVV, always
+ *            under DYDX) and both components finite.
+ *   JOINED   two 4-adjacent members p and q with fabsf(Up - Uq) + fabsf(Vp - Vq) <= thresh, in float32, one IEEE operation per
+ *            written operation.  The test is symmetric in p and q; a difference that overflows does not join.
+ *   SEGMENT  a connected component of the members under "joined".  Its id is the smallest raster index y*w + x among its
+ *            pixels, its size its pixel count.
+ *   REMOVED  a segment with size < min_size; with DFLOW_SEG_KEEP_SINGLETONS segments of size 1 are kept whatever min_size is
+ *            (the reference's `1 < count`).  min_size 0 or 1 removes nothing.
+ * d_out (h,w,3) float32 receives [U, V, 1], the pixel's own U and V bits, at a member of a segment that is kept and [0,0,0] at
+ * every other pixel.  d_segment (NULL to skip) (h,w) int32 receives the id, -1 at a pixel that is no member; d_size (NULL to skip)
+ * (h,w) int32 the size of the pixel's segment, 0 at a pixel that is no member: both describe the segments of the input, so a
+ * removed segment keeps its id and size there.  d_counts (NULL to skip) receives int32 {segments, segments removed, members,
+ * pixels removed}; the call zeroes them itself, on the stream.  Everything is an integer or a copy of input bits: the result
+ * depends on no order, two calls give the same bytes, and a second call on the first one's output changes nothing (removing
+ * segments joins no others).  Under DFLOW_EVAL_UVV d_out may be d_flow itself; any other overlap of d_flow, d_out, d_segment,
+ * d_size, d_counts and the workspace, and d_out == d_flow under DFLOW_EVAL_DYDX, is refused.
+ * DFLOW_EINVAL before anything is launched: a size, layout or flag bit outside its range, thresh not finite or below 0, min_size
+ * below 0, a NULL d_flow or d_out, a pointer that is not 4-byte aligned, a forbidden overlap.  DFLOW_ENOSPC: a NULL or too small
+ * workspace (a label and a size per pixel, 8 bytes per pixel plus alignment).  Four launches whatever the field holds; no
+ * workgroup waits for another.  Asynchronous on `stream`, allocates nothing, reads nothing back, can be captured into a graph;
+ * dflow_segment_filter_workspace_bytes returns 0 (and sets dflow_last_error) for sizes outside the range. */
+#define DFLOW_SEG_KEEP_SINGLETONS 1u
+size_t dflow_segment_filter_workspace_bytes(int32_t h, int32_t w);
+int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        float thresh, int32_t min_size, uint32_t flags,
+        float *d_out      /* (h,w,3) [U,V,valid] */,
+        int32_t *d_segment /* NULL or (h,w) */, int32_t *d_size /* NULL or (h,w) */,
+        int32_t *d_counts  /* NULL or int32[4] */,
+        void *d_ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ WARP_FLAG_ACCUMULATE = 1    # DFLOW_WARP_FLAG_ACCUMULATE
 PRIOR_SEED_LABELS = 1       # DFLOW_PRIOR_SEED_LABELS
 ADVANCE_NEGATE = 1          # DFLOW_ADVANCE_NEGATE
 FBC_BILINEAR = 1            # DFLOW_FBC_BILINEAR
+SEG_KEEP_SINGLETONS = 1     # DFLOW_SEG_KEEP_SINGLETONS
 
 
 class DflowError(RuntimeError):
@@ -110,6 +111,8 @@ _SIGNATURES = {
     "dflow_pyr_down": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "dflow_flow_upsample": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "dflow_flow_consistency": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_segment_filter_workspace_bytes": (_sz, [_i32, _i32]),
+    "dflow_segment_filter": (C.c_int, [_i32, _i32, _vp, _i32, _f32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

@@ -610,6 +610,45 @@ int dflow_flow_consistency(int32_t h, int32_t w, const float *d_fwd, int32_t lay
                                    d_counts, (hipStream_t)stream);
 }
 
+size_t dflow_segment_filter_workspace_bytes(int32_t h, int32_t w)
+{
+    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
+    return segment_filter_ws_bytes(h, w);
+}
+
+int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layout, float thresh, int32_t min_size, uint32_t flags,
+                         float *d_out, int32_t *d_segment, int32_t *d_size, int32_t *d_counts, void *d_ws, size_t ws_bytes, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (flags & ~DFLOW_SEG_KEEP_SINGLETONS) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    if (!isfinite(thresh) || thresh < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: thresh=%g must be finite and >= 0", __func__, (double)thresh);
+    if (min_size < 0) return dflow_set_error(DFLOW_EINVAL, "%s: min_size=%d must be >= 0", __func__, min_size);
+    CHECK_PTR(d_flow); CHECK_PTR(d_out);
+    rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_segment", d_segment, 4}, {"d_size", d_size, 4},
+                                  {"d_counts", d_counts, 4}, {"d_ws", d_ws, 4}});
+    if (rc) return rc;
+    // Every plane is read or written by lanes other than the pixel's own, but for d_out: seg_write_kernel reads a pixel of d_flow
+    // and writes the same pixel of d_out, so under UVV (equal pitch) the two may be one plane.  Nothing else may share a byte.
+    const size_t n = (size_t)h * (size_t)w, need = segment_filter_ws_bytes(h, w);
+    const struct { const char *name; const void *p; size_t bytes; } planes[] = {
+        {"d_flow", d_flow, n * (layout == DFLOW_EVAL_UVV ? 3 : 2) * sizeof(float)}, {"d_out", d_out, n * 3 * sizeof(float)},
+        {"d_segment", d_segment, n * sizeof(int32_t)}, {"d_size", d_size, n * sizeof(int32_t)},
+        {"d_counts", d_counts, 4 * sizeof(int32_t)}, {"d_ws", d_ws, ws_bytes < need ? ws_bytes : need}};
+    for (size_t i = 0; i < 6; i++)
+        for (size_t j = 0; j < i; j++) {
+            if (!planes[i].p || !planes[j].p) continue;
+            if (i == 1 && j == 0 && d_out == d_flow && layout == DFLOW_EVAL_UVV) continue;
+            const uintptr_t a = (uintptr_t)planes[i].p, b = (uintptr_t)planes[j].p;
+            if (a < b + planes[j].bytes && b < a + planes[i].bytes)
+                return dflow_set_error(DFLOW_EINVAL, "%s: %s and %s overlap", __func__, planes[j].name, planes[i].name);
+        }
+    CHECK_WS(need);
+    return launch_segment_filter(h, w, d_flow, layout, thresh, min_size, flags, d_out, d_segment, d_size, d_counts, d_ws,
+                                 (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

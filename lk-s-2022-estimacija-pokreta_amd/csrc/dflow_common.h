@@ -328,3 +328,8 @@ int launch_flow_upsample(int H, int W, const float *coarse, int layout, float *o
 int launch_flow_consistency(int H, int W, const float *fwd, int layout_fwd, const float *bwd, int layout_bwd, float thresh,
                             uint32_t flags, float *out_fwd, float *out_bwd, float *err_fwd, float *err_bwd, int32_t *counts,
                             hipStream_t s);
+// segments.hip: the small-segment filter of a sparse flow field, four launches whatever the field holds (arguments validated by
+// the caller); segment, size and counts may be NULL
+size_t segment_filter_ws_bytes(int H, int W);
+int launch_segment_filter(int H, int W, const float *flow, int layout, float thresh, int min_size, uint32_t flags, float *out,
+                          int32_t *segment, int32_t *size, int32_t *counts, void *ws, hipStream_t s);

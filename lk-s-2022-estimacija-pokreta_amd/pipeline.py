@@ -772,6 +772,36 @@ def flow_consistency(fwd, bwd, thresh, bilinear=False, both=False, err=False, co
     return ret if len(ret) > 1 else ret[0]
 
 
+def segment_filter(flow, thresh, min_size, keep_singletons=False, segments=False, sizes=False, counts=False):
+    """The small-segment filter of a sparse flow field (dflow_segment_filter, DESIGN.md "Small-segment filter"): the good vectors
+    (valid and finite) fall into segments, the connected components under "4-adjacent and |dU| + |dV| <= thresh", and every
+    segment of fewer than min_size pixels is removed.  Not compat.remove_small_segments, which restates the reference's
+    sequential flood fill on the host.  flow is (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; the last dimension says
+    which.  Device tensor or host array; host data is uploaded to the current device.  keep_singletons=True keeps segments of
+    one pixel whatever min_size is.  Returns the (H,W,3) float32 [U,V,valid] device tensor, removed and invalid pixels [0,0,0],
+    or a tuple in the order (out[, segment][, size][, counts]): segments=True adds the (H,W) int32 plane of segment ids (the
+    smallest raster index of the segment, -1 where there is no vector), sizes=True the (H,W) int32 plane of segment sizes (0
+    there), both of the input's segments; counts=True the int32[4] device tensor {segments, segments removed, members, pixels
+    removed}.  Runs on torch's current stream and does not wait for it."""
+    flow = _check(flow, "segment_filter", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    thresh = float(thresh)
+    if not (np.isfinite(thresh) and thresh >= 0):
+        raise ValueError("segment_filter: thresh must be finite and >= 0, got %r" % thresh)
+    if not (isinstance(min_size, (int, np.integer)) and 0 <= min_size < 2 ** 31):
+        raise ValueError("segment_filter: min_size must be an int in [0, 2^31), got %r" % (min_size,))
+    dev = _device_of(flow)
+    flow, = _on(dev, flow)
+    ws, ws_bytes = _lib.workspace("dflow_segment_filter_workspace_bytes", H, W, dev)
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    extra = [_out(segments, (H, W), torch.int32, dev), _out(sizes, (H, W), torch.int32, dev), _out(counts, 4, torch.int32, dev)]
+    _lib.call("dflow_segment_filter", H, W, flow.data_ptr(), _layout(flow), thresh, int(min_size),
+              _lib.SEG_KEEP_SINGLETONS if keep_singletons else 0, out.data_ptr(), _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
+              ws.data_ptr(), ws_bytes, _lib.stream(dev))
+    ret = tuple(t for t in [out] + extra if t is not None)
+    return ret if len(ret) > 1 else ret[0]
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels

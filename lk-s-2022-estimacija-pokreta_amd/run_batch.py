@@ -42,6 +42,12 @@ lookup, DESIGN.md "Forward/backward check in image coordinates": the forward vec
 p + f(p)); --thresh is its threshold.  The printed "survives" line, sparse_field_<pair>.npy, parovi_<pair>.txt, --prefilter,
 --epic and --eval's "sparse" row follow the choice, and the header of eval.json gains "check": "natural".  The default,
 reference, is the reference's check with its transposed lookup (pipeline.fb_consistency): nothing changes.
+--segments MIN T sends every pair's checked field through the small-segment filter (pipeline.segment_filter, DESIGN.md
+"Small-segment filter"): segments of fewer than MIN pixels, grown over neighbours whose vectors differ by at most T in
+|dU| + |dV|, are removed, after the check and before everything that reads the sparse field: the "survives" line,
+sparse_field_<pair>.npy, parovi_<pair>.txt, --prefilter, --epic and --eval's "sparse" row.  One line per pair gives the four
+counts, and the header of eval.json gains "segments": [MIN, T].  Both values must be given.  Without it nothing is launched
+that was not launched before.
 """
 import argparse
 import importlib
@@ -62,6 +68,8 @@ def parser():
     ap.add_argument("--thresh", type=float, default=10.0)     # README.md:65 of the reference
     ap.add_argument("--check", choices=("reference", "natural"), default="reference",
                     help="the forward/backward check: the reference's (transposed lookup), or the one in image coordinates")
+    ap.add_argument("--segments", nargs=2, default=None, metavar=("MIN", "T"),
+                    help="after the check: remove segments of fewer than MIN pixels, joined where |dU| + |dV| <= T")
     ap.add_argument("--out", default=".")
     ap.add_argument("--group", type=int, default=4, help="passes of a rank whose BCD sweeps share their launches")
     ap.add_argument("--cell", default=None, help="cell size HxW (default: the geometry's usual cells)")
@@ -93,6 +101,17 @@ PHOTO_ROW = ("n", "n_outside", "n_unknown", "n_above", "sum_err", "max_err", "me
 
 def mod(name):
     return importlib.import_module(PKG + "." + name)
+
+
+def segments_arg(tokens):
+    """--segments MIN T -> (MIN, T); exits with status 2 unless MIN is an integer >= 0 and T finite and >= 0."""
+    try:
+        min_size, thresh = int(tokens[0]), float(tokens[1])
+        if min_size < 0 or min_size >= 2 ** 31 or not (np.isfinite(thresh) and thresh >= 0):
+            raise ValueError
+    except ValueError:
+        parser().error("--segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (tokens,))
+    return min_size, thresh
 
 
 def stats_row(st, fields):
@@ -295,6 +314,9 @@ def write_pair(s, pair, fwd, bwd):
     a = s.a
     pipeline, synth, flowio = mod("pipeline"), mod("synth"), mod("flowio")
     sparse_dev = pipeline.flow_consistency(fwd, bwd, a.thresh) if a.check == "natural" else pipeline.fb_consistency(fwd, bwd, a.thresh)
+    if a.segments is not None:
+        sparse_dev, seg_counts = pipeline.segment_filter(sparse_dev, a.segments[1], a.segments[0], counts=True)
+        print("pair %d: %d segments, %d removed; %d consistent pixels, %d removed" % ((pair,) + tuple(seg_counts.cpu().tolist())))
     sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
     sparse = sparse_dev.cpu().numpy()
     for backward, f in ((0, fwd), (1, bwd)):
@@ -363,12 +385,16 @@ def write_out(s, flows):
     if a.eval:
         if a.check != "reference":
             head["check"] = a.check
+        if a.segments is not None:
+            head["segments"] = [a.segments[0], a.segments[1]]
         write_tally(os.path.join(a.out, "eval.json"), dict(head, abs_thresh=3.0), EVAL, eval_rows, eval_totals)
 
 
 def main(argv=None):
     a = parser().parse_args(argv)
     a.epic = a.epic or a.epic_refine or a.prefilter
+    if a.segments is not None:
+        a.segments = segments_arg(a.segments)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)

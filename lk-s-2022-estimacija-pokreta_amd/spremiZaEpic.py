@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--natural-check] [--gpu-epic [--prefilter] [--refine]]
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--natural-check] [--segments MIN T] [--gpu-epic [--prefilter] [--refine]]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
@@ -25,6 +25,12 @@ With --natural-check directly after the six positional tokens (before --gpu-epic
 and everything after them come from the forward/backward check in image coordinates (pipeline.flow_consistency, nearest lookup,
 threshold con_tresh; DESIGN.md "Forward/backward check in image coordinates") in place of the reference's postProcessing, whose
 lookup is transposed.
+With the three tokens --segments MIN T directly after --natural-check if that is there, else after the six positional tokens, and
+before --gpu-epic, the checked field goes through the small-segment filter (pipeline.segment_filter; DESIGN.md "Small-segment
+filter"): segments of fewer than MIN pixels, grown over neighbours whose vectors differ by at most T in |dU| + |dV|, are removed.
+This is part of postProcessing, where the reference has the call commented out (postprocessing.py:132): unlike --prefilter,
+sparse_field.npy, parovi.txt and everything after them come from the filtered field.  Both values must be given: MIN an integer
+>= 0, T finite and >= 0.
 """
 import importlib
 import os
@@ -64,8 +70,27 @@ def take_natural(argv):
     return (argv[:6] + argv[7:] if natural else argv), natural
 
 
+def take_segments(argv):
+    """The optional tokens --segments MIN T after the six positional ones (--natural-check already taken): (the command line
+    without them, (MIN, T) or None), or the exit status 2 after saying why."""
+    if argv[6:7] != ["--segments"]:
+        return argv, None
+    try:
+        min_size, thresh = int(argv[7]), float(argv[8])
+        if min_size < 0 or min_size >= 2 ** 31 or not (np.isfinite(thresh) and thresh >= 0):
+            raise ValueError
+    except (IndexError, ValueError):
+        print("spremiZaEpic: --segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (argv[7:9],), file=sys.stderr)
+        return 2
+    return argv[:6] + argv[9:], (min_size, thresh)
+
+
 def main(argv=None):
     argv, natural = take_natural(sys.argv[1:] if argv is None else list(argv))
+    taken = take_segments(argv)
+    if taken == 2:
+        return 2
+    argv, segments = taken
     parsed = parse(argv)
     if parsed == 2:
         return 2
@@ -85,6 +110,8 @@ def main(argv=None):
     fwd = torch.from_numpy(np.load(foward).astype(np.float32)).to(dev)
     bwd = torch.from_numpy(np.load(backward).astype(np.float32)).to(dev)
     sparse_dev = pipeline.flow_consistency(fwd, bwd, con_tresh) if natural else pipeline.fb_consistency(fwd, bwd, con_tresh)
+    if segments is not None:
+        sparse_dev = pipeline.segment_filter(sparse_dev, segments[1], segments[0])
     sparse = sparse_dev.cpu().numpy()                                      # postProcessing, :15
     np.save("sparse_field.npy", sparse)
     evaluate.parovi(sparse, "parovi.txt")                                  # :17
