@@ -9,14 +9,13 @@
 //                           flow (and whether it has one) goes into an LDS image of (BS_TH + 1) x (BS_TW + 1) entries, the
 //                           extra column and row being the right and lower neighbours of the tile's last pixels, so the
 //                           two pairs of a pixel, (p, right of p) and (p, below p), are formed from LDS.  A lane keeps its
-//                           own counts and its double sum of data costs; they are reduced across the wave by shuffles in
-//                           a fixed tree, across the block's waves through LDS in wave order, and written as the block's
-//                           partial.
+//                           own counts and its double sum of data costs; block_reduce (plane_ops.h) adds them in a fixed
+//                           order and thread 0 writes the block's partial.
 //   bcd_stats_final_kernel  one block per pass: thread t adds the partials t, t + 256, ... in that order, then a fixed
 //                           LDS tree; thread 0 writes the pass's dflow_bcd_stats.
 // The grid is a function of the geometry alone, so the order of every double addition is fixed: the same inputs give the
 // same bits of data_sum on every call, from the single and from the batch entry point.
-#include "dflow_common.h"
+#include "plane_ops.h"
 
 #define BS_TW 32
 #define BS_TH 8
@@ -52,28 +51,6 @@ __device__ __forceinline__ static void bs_merge(BsPartial &a, const BsPartial &b
 {
     a.data = a.data + b.data;
     a.smooth += b.smooth; a.pairs_trunc += b.pairs_trunc; a.data_trunc += b.data_trunc; a.changed += b.changed; a.bad += b.bad;
-}
-
-// the block's total in thread 0: a shuffle tree per wave (64 lanes: offsets 32 .. 1), then the waves in order
-__device__ static BsPartial bs_block_reduce(BsPartial a)
-{
-    __shared__ BsPartial wave_part[BS_WAVES];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        BsPartial b;
-        b.data = __shfl_down(a.data, off, 64);
-        b.smooth = __shfl_down(a.smooth, off, 64); b.pairs_trunc = __shfl_down(a.pairs_trunc, off, 64);
-        b.data_trunc = __shfl_down(a.data_trunc, off, 64); b.changed = __shfl_down(a.changed, off, 64);
-        b.bad = __shfl_down(a.bad, off, 64);
-        bs_merge(a, b);
-    }
-    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < BS_WAVES; k++) bs_merge(a, wave_part[k]);
-    }
-    return a;
 }
 
 // prev and prev_out may be one buffer: a pixel's old label is read and its new one written by the same thread, and no other
@@ -137,7 +114,7 @@ __global__ void __launch_bounds__(BS_THREADS) bcd_stats_main_kernel(BsArgs a)
         }
         __syncthreads();                                     // the image is rewritten by the next tile
     }
-    acc = bs_block_reduce(acc);
+    acc = block_reduce<BS_WAVES>(acc, bs_merge);
     if (tid == 0) ps.partials[blockIdx.x] = acc;
 }
 

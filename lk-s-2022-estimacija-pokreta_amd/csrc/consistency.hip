@@ -3,12 +3,11 @@
 // check (post.hip, dflow_fb_consistency) adds U to the row and V to the column and stays what it is.
 //
 // consistency_kernel: one pixel per lane, blockIdx.z the direction (0: d_fwd checked against d_bwd, 1: the roles swapped).  The
-// lane's own vector and the one (nearest) or up to four (bilinear) vectors at its target through flow_vector (dflow_common.h),
-// 12 bytes out, 4 more with an error plane; the five counts as ballots -> per-block LDS counters -> five integer atomics per
-// block, as upsample_kernel (pyramid.hip) does.  One IEEE float32 operation per written operation (-ffp-contract=off; hipcc's
-// sqrtf is correctly rounded).
+// lane's own vector and the one (nearest) or up to four (bilinear) vectors at its target through flow_good (dflow_common.h),
+// 12 bytes out, 4 more with an error plane; the five counts through block_count_class (plane_ops.h).  One IEEE float32
+// operation per written operation (-ffp-contract=off; hipcc's sqrtf is correctly rounded).
 #include <math.h>
-#include "dflow_common.h"
+#include "plane_ops.h"
 
 #define FBC_THREADS 256
 #define FBC_CLASSES 5                                 // CONSISTENT, ABOVE, BWD_INVALID, OUTSIDE, FWD_INVALID
@@ -24,19 +23,8 @@ struct FbcArgs {
     int32_t *counts;                                  // NULL, or FBC_CLASSES per direction
 };
 
-// a vector that can be checked: valid under its layout and both components finite
-__device__ static inline bool fbc_good(const float *__restrict__ f, int layout, size_t src, float &u, float &v)
-{
-    return flow_vector(f, layout, src, v, u) && isfinite(u) && isfinite(v);
-}
-
-struct FbcOut { float u, v, valid; };
-
 __global__ void __launch_bounds__(FBC_THREADS) consistency_kernel(FbcArgs a)
 {
-    __shared__ int s_cnt[FBC_CLASSES];
-    if (threadIdx.x < FBC_CLASSES) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
     const int dir = blockIdx.z;
     const float *__restrict__ src = a.src[dir];
     const float *__restrict__ other = a.other[dir];
@@ -48,7 +36,7 @@ __global__ void __launch_bounds__(FBC_THREADS) consistency_kernel(FbcArgs a)
         const int y = (int)(i / (uint32_t)w), x = (int)(i % (uint32_t)w);
         float U = 0.0f, V = 0.0f, bu = 0.0f, bv = 0.0f;
         kind = 4;                                                                       // FWD_INVALID
-        if (fbc_good(src, ls, (size_t)i, U, V)) {
+        if (flow_good(src, ls, (size_t)i, U, V)) {
             kind = 3;                                                                   // OUTSIDE
             if (a.flags & DFLOW_FBC_BILINEAR) {
                 const float py = (float)y + V, px = (float)x + U;
@@ -58,10 +46,10 @@ __global__ void __launch_bounds__(FBC_THREADS) consistency_kernel(FbcArgs a)
                     const float ay = py - (float)y0, ax = px - (float)x0;
                     const int y1 = ay > 0.0f ? y0 + 1 : y0, x1 = ax > 0.0f ? x0 + 1 : x0;
                     float u00, v00, u01, v01, u10, v10, u11, v11;
-                    const bool g00 = fbc_good(other, lo, (size_t)y0 * w + x0, u00, v00);
-                    const bool g01 = fbc_good(other, lo, (size_t)y0 * w + x1, u01, v01);
-                    const bool g10 = fbc_good(other, lo, (size_t)y1 * w + x0, u10, v10);
-                    const bool g11 = fbc_good(other, lo, (size_t)y1 * w + x1, u11, v11);
+                    const bool g00 = flow_good(other, lo, (size_t)y0 * w + x0, u00, v00);
+                    const bool g01 = flow_good(other, lo, (size_t)y0 * w + x1, u01, v01);
+                    const bool g10 = flow_good(other, lo, (size_t)y1 * w + x0, u10, v10);
+                    const bool g11 = flow_good(other, lo, (size_t)y1 * w + x1, u11, v11);
                     kind = 2;                                                           // BWD_INVALID
                     if (g00 && g01 && g10 && g11) {
                         const float tu = u00 + ax * (u01 - u00), bu_ = u10 + ax * (u11 - u10);
@@ -76,30 +64,22 @@ __global__ void __launch_bounds__(FBC_THREADS) consistency_kernel(FbcArgs a)
                 if (fabsf(ry) <= 32767.0f && fabsf(rx) <= 32767.0f) {
                     const int ty = y + (int)ry, tx = x + (int)rx;
                     if (ty >= 0 && ty < h && tx >= 0 && tx < w) {
-                        kind = fbc_good(other, lo, (size_t)ty * w + tx, bu, bv) ? 1 : 2;
+                        kind = flow_good(other, lo, (size_t)ty * w + tx, bu, bv) ? 1 : 2;
                     }
                 }
             }
         }
-        FbcOut o = {0.0f, 0.0f, 0.0f};
+        FlowOut o = {0.0f, 0.0f, 0.0f};
         float err = -1.0f;
         if (kind == 1) {                                                                // ABOVE unless err <= thresh (a NaN is above)
             const float du = U + bu, dv = V + bv;
             err = sqrtf(du * du + dv * dv);
             if (err <= a.thresh) { o.u = U; o.v = V; o.valid = 1.0f; kind = 0; }
         }
-        reinterpret_cast<FbcOut *>(a.out[dir])[i] = o;
+        reinterpret_cast<FlowOut *>(a.out[dir])[i] = o;
         if (a.err[dir]) a.err[dir][i] = err;
     }
-    if (a.counts) {
-#pragma unroll
-        for (int k = 0; k < FBC_CLASSES; k++) {
-            const int c = __popcll(__ballot(kind == k));
-            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-        }
-        __syncthreads();
-        if (threadIdx.x < FBC_CLASSES && s_cnt[threadIdx.x]) atomicAdd(&a.counts[dir * FBC_CLASSES + threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    block_count_class<FBC_CLASSES>(kind, a.counts, dir * FBC_CLASSES);
 }
 
 int launch_flow_consistency(int H, int W, const float *fwd, int layout_fwd, const float *bwd, int layout_bwd, float thresh,

@@ -22,8 +22,6 @@ struct Taps { int n; float k[MAX_TAPS]; };
 
 struct GridTab { double gy[17], gx[17]; };
 
-__device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ static inline float gray_of(const uint8_t *__restrict__ bgr, int W, int y, int x)
 {
     return (float)gray_u8(bgr, W, y, x) / 255.0f;

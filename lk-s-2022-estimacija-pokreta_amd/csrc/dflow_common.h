@@ -77,6 +77,16 @@ __device__ static inline bool flow_vector(const float *__restrict__ f, int layou
     return true;
 }
 
+// A good vector (u, v) = (fx, fy): valid under its layout and both components finite.  What pyramid.hip doubles, consistency.hip
+// checks and segments.hip takes as a member; FlowOut is the [U,V,valid] pixel the three write.
+__device__ static inline bool flow_good(const float *__restrict__ f, int layout, size_t src, float &u, float &v)
+{
+    return flow_vector(f, layout, src, v, u) && isfinite(u) && isfinite(v);
+}
+struct FlowOut { float u, v, valid; };
+
+__device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // |dy-dy'| + |dx-dx'| of two packed labels (purepsi, daisy i flann.py:114-115): flip the sign bits so that the
 // int16 halves order like uint16, then one v_sad_u16.
 __device__ static inline uint32_t flow_bias(uint32_t f) { return f ^ 0x80008000u; }

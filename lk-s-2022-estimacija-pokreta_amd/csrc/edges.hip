@@ -6,16 +6,17 @@
 //   canny_front_kernel  per 64x16 tile, all in LDS: gray on the tile + 3 -> 3x3 [1,2,1] blur at BORDER_REFLECT_101 on the
 //                       tile + 2 (centres clamped: the blurred image is read with BORDER_REPLICATE) -> Sobel on the tile + 1,
 //                       L1 magnitude, 0 outside the image -> non-maximum suppression -> one class byte per pixel (none /
-//                       weak / strong); then union-find of the candidates inside the tile (LDS atomics): every candidate's
-//                       label = the global index of its tile-local root
+//                       weak / strong); then union-find of the candidates inside the tile (uf_union of union_find.h on LDS):
+//                       every candidate's label = the global index of its tile-local root
 //   canny_merge_kernel  union-find across tile borders: each candidate on a tile's perimeter links with its 8-neighbours
-//                       in other tiles (agent-scope atomic loads and atomicMin; parents always point to smaller indices)
+//                       in other tiles (agent-scope uf_union, union_find.h: parents always point to smaller indices)
 //   canny_roots_kernel  every candidate finds its root (and stores it: path compression); strong candidates flag theirs
 //   canny_output_kernel edge = candidate whose root is flagged: 255 / 0, and optionally (255 - e) / 255 as float32.
 // The edge set (the candidates 8-connected through candidates to a strong one) does not depend on the order in which the
 // unions happen, so the atomics cannot change the result.
 #include <math.h>
 #include "dflow_common.h"
+#include "union_find.h"
 
 #define CT_W 64
 #define CT_H 16
@@ -45,36 +46,12 @@ static CannyWs canny_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 
 size_t canny_ws_bytes(int H, int W) { size_t b; canny_ws(nullptr, H, W, &b); return b; }
 
-__device__ static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // BORDER_REFLECT_101 for the blur's taps (v in [-1, n]): -1 -> 1, n -> n - 2; a length-1 axis maps everything to 0
 __device__ static inline int reflect101(int v, int n)
 {
     if (n == 1) return 0;
     v = v < 0 ? -v : v;
     return v >= n ? 2 * n - 2 - v : v;
-}
-
-// ---- union-find: parents only ever point to smaller indices, so find terminates; a link is an atomicMin on a root that
-// is retried from the value it returned when another thread got there first.
-template <int SCOPE> __device__ static inline int uf_find(int *par, int x)
-{
-    int p;
-    while ((p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, SCOPE)) != x) x = p;
-    return x;
-}
-
-template <int SCOPE> __device__ static inline void uf_union(int *par, int a, int b)
-{
-    for (;;) {
-        a = uf_find<SCOPE>(par, a);
-        b = uf_find<SCOPE>(par, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }       // link the larger root b below a
-        const int old = __hip_atomic_fetch_min(&par[b], a, __ATOMIC_RELAXED, SCOPE);
-        if (old == b) return;
-        b = old;                                            // b was no longer a root: its new parent must still join a
-    }
 }
 
 __global__ void __launch_bounds__(CT_THREADS) canny_front_kernel(const uint8_t *__restrict__ bgr, int H, int W, int lo, int hi,

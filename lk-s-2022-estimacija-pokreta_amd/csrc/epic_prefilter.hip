@@ -47,16 +47,14 @@ static PfWs pf_ws(void *ws, int H, int W)
 
 size_t epic_prefilter_ws_bytes(int H, int W) { return pf_ws(nullptr, H, W).bytes; }
 
-__device__ __forceinline__ static int pf_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // J = sum over the channels of (fx fx, fx fy, fy fy), fx = 0.5 (f[x + 1] - f[x - 1]), replicate border
 __global__ void __launch_bounds__(PF_THREADS) pf_tensor_kernel(int H, int W, PfWs w)
 {
     const int p = blockIdx.x * PF_THREADS + threadIdx.x;
     if (p >= H * W) return;
     const int y = p / W, x = p % W;
-    const size_t l = (size_t)y * W + pf_clamp(x - 1, W - 1), r = (size_t)y * W + pf_clamp(x + 1, W - 1);
-    const size_t t = (size_t)pf_clamp(y - 1, H - 1) * W + x, b = (size_t)pf_clamp(y + 1, H - 1) * W + x;
+    const size_t l = (size_t)y * W + clampi(x - 1, 0, W - 1), r = (size_t)y * W + clampi(x + 1, 0, W - 1);
+    const size_t t = (size_t)clampi(y - 1, 0, H - 1) * W + x, b = (size_t)clampi(y + 1, 0, H - 1) * W + x;
     float jxx = 0.0f, jxy = 0.0f, jyy = 0.0f;
     for (int c = 0; c < 3; c++) {
         const float *f = w.chan[c];
@@ -96,7 +94,7 @@ __global__ void __launch_bounds__(PF_THREADS) pf_saliency_kernel(int H, int W, V
         const float *__restrict__ plane = w.tensor[c];
         for (int i = threadIdx.x; i < n * n; i += PF_THREADS) {
             const int ly = i / n, lx = i - ly * n;
-            in[ly][lx] = plane[(size_t)pf_clamp(y0 + ly - r, H - 1) * W + pf_clamp(x0 + lx - r, W - 1)];
+            in[ly][lx] = plane[(size_t)clampi(y0 + ly - r, 0, H - 1) * W + clampi(x0 + lx - r, 0, W - 1)];
         }
         __syncthreads();
         for (int i = threadIdx.x; i < n * PF_ST; i += PF_THREADS) {

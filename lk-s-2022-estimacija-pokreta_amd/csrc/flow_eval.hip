@@ -5,22 +5,18 @@
 // Two launches on the caller's stream, nothing read back, no atomics:
 //   eval_main_kernel<LAYOUT>  the planes as flat arrays of h*w pixels, four pixels per lane and step: three (DYDX: two)
 //                             16-byte loads of the test field, three of the ground truth, one 16-byte store of err, one
-//                             12-byte store of the picture.  The last group of a field whose h*w is no multiple of 4 goes
-//                             pixel by pixel.  Grid-stride over at most EVAL_MAX_BLOCKS blocks; every lane keeps its own
-//                             counts, maximum and double sum, which are reduced across the wave by shuffles in a fixed tree,
-//                             across the block's waves through LDS in wave order, and written as the block's partial.
+//                             12-byte store of the picture (flow_load4, bgr_pack4: plane_ops.h).  The last group of a field
+//                             whose h*w is no multiple of 4 goes pixel by pixel.  Grid-stride over at most PLANE_MAX_BLOCKS
+//                             blocks; every lane keeps its own counts, maximum and double sum, which block_reduce
+//                             (plane_ops.h) adds in a fixed order, and thread 0 writes the block's partial.
 //   eval_final_kernel         one block: thread t adds the partials t, t + 256, ... in that order, the same block
 //                             reduction, and thread 0 writes or (DFLOW_EVAL_FLAG_ACCUMULATE) adds to *d_stats.
 // The grid is a function of h*w alone, so the order of every double addition is fixed: the same inputs give the same
 // bits of sum_err on every call.
-#include "dflow_common.h"
-#include "jet_lut.h"
+#include "plane_ops.h"
 
-#define EVAL_THREADS 256
+#define EVAL_THREADS PLANE_THREADS    // plane_blocks counts blocks of this size
 #define EVAL_WAVES (EVAL_THREADS / 64)
-#define EVAL_MAX_BLOCKS 1024          // 4 blocks of 256 threads on each of the 256 CUs
-
-__constant__ uint32_t eval_jet_lut[256] = {JET_LUT_VALUES};
 
 // what a lane, a wave or a block has seen; a block of a 8192 x 8192 field sees at most 2^26 pixels: 32-bit counts
 struct EvalPartial {
@@ -36,29 +32,6 @@ __device__ __forceinline__ static void eval_merge(EvalPartial &a, const EvalPart
     a.n += b.n; a.n_out_abs += b.n_out_abs; a.n_out_kitti += b.n_out_kitti;
     a.n_nonfinite += b.n_nonfinite; a.n_gt_valid += b.n_gt_valid; a.n_test_valid += b.n_test_valid;
     a.max_err = fmaxf(a.max_err, b.max_err);
-}
-
-// the block's total in thread 0: a shuffle tree per wave (64 lanes: offsets 32 .. 1), then the waves in order
-__device__ static EvalPartial eval_block_reduce(EvalPartial a)
-{
-    __shared__ EvalPartial wave_part[EVAL_WAVES];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        EvalPartial b;
-        b.sum = __shfl_down(a.sum, off, 64);
-        b.n = __shfl_down(a.n, off, 64); b.n_out_abs = __shfl_down(a.n_out_abs, off, 64);
-        b.n_out_kitti = __shfl_down(a.n_out_kitti, off, 64); b.n_nonfinite = __shfl_down(a.n_nonfinite, off, 64);
-        b.n_gt_valid = __shfl_down(a.n_gt_valid, off, 64); b.n_test_valid = __shfl_down(a.n_test_valid, off, 64);
-        b.max_err = __shfl_down(a.max_err, off, 64);
-        eval_merge(a, b);
-    }
-    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < EVAL_WAVES; k++) eval_merge(a, wave_part[k]);
-    }
-    return a;
 }
 
 // one pixel: counts it into `acc` and returns its err (-1 when it is not compared) and its picture entry (b | g << 8 | r << 16)
@@ -87,8 +60,6 @@ __device__ __forceinline__ static void eval_pixel(float tU, float tV, float tval
     }
 }
 
-struct EvalBgr4 { uint32_t a, b, c; };      // four (b, g, r) pixels: 12 bytes
-
 template <int LAYOUT>
 __global__ void __launch_bounds__(EVAL_THREADS) eval_main_kernel(const float *__restrict__ test, const float *__restrict__ gt,
                                                                  unsigned npix, float abs_thresh, float *__restrict__ err,
@@ -97,7 +68,7 @@ __global__ void __launch_bounds__(EVAL_THREADS) eval_main_kernel(const float *__
     __shared__ uint32_t lut_s[256];
     const uint32_t *lut = nullptr;
     if (bgr) {                                          // uniform
-        lut_s[threadIdx.x] = eval_jet_lut[threadIdx.x];
+        lut_s[threadIdx.x] = plane_jet_lut[threadIdx.x];
         __syncthreads();
         lut = lut_s;
     }
@@ -107,49 +78,27 @@ __global__ void __launch_bounds__(EVAL_THREADS) eval_main_kernel(const float *__
         float e[4];
         uint32_t c[4];
         if (g < nfull) {
-            const float4 *gp = reinterpret_cast<const float4 *>(gt) + (size_t)g * 3;
-            const float4 g0 = gp[0], g1 = gp[1], g2 = gp[2];
-            const float G[12] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
-            if constexpr (LAYOUT == DFLOW_EVAL_UVV) {
-                const float4 *tp = reinterpret_cast<const float4 *>(test) + (size_t)g * 3;
-                const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-                const float T[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+            float tU[4], tV[4], tvalid[4], gU[4], gV[4], gvalid[4];
+            flow_load4<DFLOW_EVAL_UVV>(gt, g, gU, gV, gvalid);
+            flow_load4<LAYOUT>(test, g, tU, tV, tvalid);
 #pragma unroll
-                for (int k = 0; k < 4; k++)
-                    eval_pixel(T[3 * k], T[3 * k + 1], T[3 * k + 2], G[3 * k], G[3 * k + 1], G[3 * k + 2], abs_thresh, lut, acc, e[k], c[k]);
-            } else {
-                const float4 *tp = reinterpret_cast<const float4 *>(test) + (size_t)g * 2;
-                const float4 t0 = tp[0], t1 = tp[1];
-                const float T[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};       // [dy,dx]: U = dx, V = dy
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    eval_pixel(T[2 * k + 1], T[2 * k], 1.0f, G[3 * k], G[3 * k + 1], G[3 * k + 2], abs_thresh, lut, acc, e[k], c[k]);
-            }
+            for (int k = 0; k < 4; k++) eval_pixel(tU[k], tV[k], tvalid[k], gU[k], gV[k], gvalid[k], abs_thresh, lut, acc, e[k], c[k]);
             if (err) reinterpret_cast<float4 *>(err)[g] = make_float4(e[0], e[1], e[2], e[3]);
-            if (bgr) {
-                EvalBgr4 v;
-                v.a = c[0] | (c[1] << 24);
-                v.b = (c[1] >> 8) | (c[2] << 16);
-                v.c = (c[2] >> 16) | (c[3] << 8);
-                reinterpret_cast<EvalBgr4 *>(bgr)[g] = v;
-            }
+            if (bgr) reinterpret_cast<Bgr4 *>(bgr)[g] = bgr_pack4(c);
         } else {
             // the 1..3 pixels after the last whole group
             for (unsigned p = g * 4u; p < npix; p++) {
-                const float *gq = gt + (size_t)p * 3;
-                float tU, tV, tvalid = 1.0f, e1;
+                float tU, tV, tvalid, gU, gV, gvalid, e1;
                 uint32_t c1;
-                if constexpr (LAYOUT == DFLOW_EVAL_UVV) { tU = test[(size_t)p * 3]; tV = test[(size_t)p * 3 + 1]; tvalid = test[(size_t)p * 3 + 2]; }
-                else { tU = test[(size_t)p * 2 + 1]; tV = test[(size_t)p * 2]; }
-                eval_pixel(tU, tV, tvalid, gq[0], gq[1], gq[2], abs_thresh, lut, acc, e1, c1);
+                flow_load1<LAYOUT>(test, p, tU, tV, tvalid);
+                flow_load1<DFLOW_EVAL_UVV>(gt, p, gU, gV, gvalid);
+                eval_pixel(tU, tV, tvalid, gU, gV, gvalid, abs_thresh, lut, acc, e1, c1);
                 if (err) err[p] = e1;
-                if (bgr) {
-                    bgr[(size_t)p * 3] = (uint8_t)c1; bgr[(size_t)p * 3 + 1] = (uint8_t)(c1 >> 8); bgr[(size_t)p * 3 + 2] = (uint8_t)(c1 >> 16);
-                }
+                if (bgr) bgr_store1(bgr, p, c1);
             }
         }
     }
-    acc = eval_block_reduce(acc);
+    acc = block_reduce<EVAL_WAVES>(acc, eval_merge);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
@@ -159,7 +108,7 @@ __global__ void __launch_bounds__(EVAL_THREADS) eval_final_kernel(const EvalPart
     EvalPartial acc = {};
     // counts of the whole field: up to 2^26, and 32 bits hold them
     for (int b = threadIdx.x; b < nblocks; b += EVAL_THREADS) eval_merge(acc, partials[b]);
-    acc = eval_block_reduce(acc);
+    acc = block_reduce<EVAL_WAVES>(acc, eval_merge);
     if (threadIdx.x != 0) return;
     dflow_eval_stats s = {};
     if (accumulate) s = *stats;
@@ -171,13 +120,6 @@ __global__ void __launch_bounds__(EVAL_THREADS) eval_final_kernel(const EvalPart
     *stats = s;
 }
 
-static int eval_blocks(int H, int W)
-{
-    const size_t ngroups = ((size_t)H * W + 3) / 4;
-    const size_t b = (ngroups + EVAL_THREADS - 1) / EVAL_THREADS;
-    return (int)(b < EVAL_MAX_BLOCKS ? b : EVAL_MAX_BLOCKS);
-}
-
 struct EvalWs {
     EvalPartial *partials;   // one per block of the main kernel
 };
@@ -186,7 +128,7 @@ static EvalWs eval_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 {
     WsCarver c(ws);
     EvalWs w;
-    w.partials = c.take<EvalPartial>((size_t)eval_blocks(H, W));
+    w.partials = c.take<EvalPartial>((size_t)plane_blocks(H, W));
     if (bytes) *bytes = c.bytes;
     return w;
 }
@@ -197,7 +139,7 @@ int launch_flow_eval(int H, int W, const float *test, int layout, const float *g
                      dflow_eval_stats *stats, float *err, uint8_t *bgr, void *ws, hipStream_t s)
 {
     const EvalWs w = eval_ws(ws, H, W);
-    const int nblocks = eval_blocks(H, W);
+    const int nblocks = plane_blocks(H, W);
     const unsigned npix = (unsigned)H * (unsigned)W;
     if (layout == DFLOW_EVAL_UVV)
         eval_main_kernel<DFLOW_EVAL_UVV><<<nblocks, EVAL_THREADS, 0, s>>>(test, gt, npix, abs_thresh, err, bgr, w.partials);

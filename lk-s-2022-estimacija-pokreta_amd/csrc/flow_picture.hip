@@ -2,41 +2,23 @@
 //   dflow_flow_color  the Middlebury colour-wheel picture of a flow field, in double, one IEEE operation per written operation
 //   dflow_warp_eval   the second image warped back onto the first (bilinear, the operation order of var_warp_kernel,
 //                     variational.hip), the photometric error per pixel and its statistics, in float32
-// Built like flow_eval.hip (-ffp-contract=off; hipcc's sqrt and / are correctly rounded): the planes as flat arrays of h*w
-// pixels, four pixels per lane and step with 16-byte loads of the flow and 12- / 16-byte stores, the last group of a field
-// whose h*w is no multiple of 4 pixel by pixel, grid-stride over at most PIC_MAX_BLOCKS blocks, every block's partial result
-// into the workspace, a one-block final launch that adds the partials in a fixed order.  Nothing is read back, no atomics.
+// Built like flow_eval.hip, from the same helpers (plane_ops.h; -ffp-contract=off; hipcc's sqrt and / are correctly rounded):
+// the planes as flat arrays of h*w pixels, four pixels per lane and step with 16-byte loads of the flow and 12- / 16-byte
+// stores, the last group of a field whose h*w is no multiple of 4 pixel by pixel, grid-stride over at most PLANE_MAX_BLOCKS
+// blocks, every block's partial result (block_reduce) into the workspace, a one-block final launch that adds the partials in a
+// fixed order.  Nothing is read back, no atomics.
 //   color_max_kernel<LAYOUT>, color_max_final_kernel   only for max_flow == 0: the largest float32 |(U,V)| of the known pixels
 //   color_kernel<LAYOUT>                                the picture; the radius from the argument or from the workspace
 //   warp_main_kernel<LAYOUT>, warp_final_kernel         the warp, the planes and *d_stats
 // The grid is a function of h*w alone, so the order of every double addition is fixed: the same inputs give the same bits
 // of sum_err on every call.
-#include "dflow_common.h"
+#include "plane_ops.h"
 #include "flow_wheel.h"
-#include "jet_lut.h"
 
-#define PIC_THREADS 256
+#define PIC_THREADS PLANE_THREADS     // plane_blocks counts blocks of this size
 #define PIC_WAVES (PIC_THREADS / 64)
-#define PIC_MAX_BLOCKS 1024           // 4 blocks of 256 threads on each of the 256 CUs
 
 __constant__ uint32_t pic_wheel[FLOW_WHEEL_N] = {FLOW_WHEEL_VALUES};
-__constant__ uint32_t pic_jet_lut[256] = {JET_LUT_VALUES};
-
-struct PicBgr4 { uint32_t a, b, c; };       // four (b, g, r) pixels: 12 bytes
-
-__device__ __forceinline__ static PicBgr4 pic_pack4(const uint32_t (&c)[4])
-{
-    PicBgr4 v;
-    v.a = c[0] | (c[1] << 24);
-    v.b = (c[1] >> 8) | (c[2] << 16);
-    v.c = (c[2] >> 16) | (c[3] << 8);
-    return v;
-}
-
-__device__ __forceinline__ static void pic_store1(uint8_t *__restrict__ bgr, size_t p, uint32_t c)
-{
-    bgr[p * 3] = (uint8_t)c; bgr[p * 3 + 1] = (uint8_t)(c >> 8); bgr[p * 3 + 2] = (uint8_t)(c >> 16);
-}
 
 // a pixel whose flow can be drawn and followed: valid, finite, and no larger than 1e9 (a NaN compares false everywhere)
 __device__ __forceinline__ static bool pic_known(float U, float V, float valid)
@@ -44,47 +26,8 @@ __device__ __forceinline__ static bool pic_known(float U, float V, float valid)
     return valid > 0.5f && fabsf(U) <= 1e9f && fabsf(V) <= 1e9f;
 }
 
-// the four pixels of group g (or the one pixel p of the tail) as U, V, valid
-template <int LAYOUT>
-__device__ __forceinline__ static void pic_load4(const float *__restrict__ flow, unsigned g, float (&U)[4], float (&V)[4], float (&valid)[4])
-{
-    if constexpr (LAYOUT == DFLOW_EVAL_UVV) {
-        const float4 *tp = reinterpret_cast<const float4 *>(flow) + (size_t)g * 3;
-        const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-        const float T[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) { U[k] = T[3 * k]; V[k] = T[3 * k + 1]; valid[k] = T[3 * k + 2]; }
-    } else {
-        const float4 *tp = reinterpret_cast<const float4 *>(flow) + (size_t)g * 2;
-        const float4 t0 = tp[0], t1 = tp[1];
-        const float T[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};           // [dy,dx]: U = dx, V = dy
-#pragma unroll
-        for (int k = 0; k < 4; k++) { U[k] = T[2 * k + 1]; V[k] = T[2 * k]; valid[k] = 1.0f; }
-    }
-}
-
-template <int LAYOUT>
-__device__ __forceinline__ static void pic_load1(const float *__restrict__ flow, unsigned p, float &U, float &V, float &valid)
-{
-    if constexpr (LAYOUT == DFLOW_EVAL_UVV) { U = flow[(size_t)p * 3]; V = flow[(size_t)p * 3 + 1]; valid = flow[(size_t)p * 3 + 2]; }
-    else { U = flow[(size_t)p * 2 + 1]; V = flow[(size_t)p * 2]; valid = 1.0f; }
-}
-
 // ---- the colour picture ---------------------------------------------------------------------------------------------
-// the block's maximum in thread 0: a shuffle tree per wave, then the waves through LDS (a maximum depends on no order)
-__device__ static float pic_block_max(float m)
-{
-    __shared__ float wave_max[PIC_WAVES];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
-    if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < PIC_WAVES; k++) m = fmaxf(m, wave_max[k]);
-    }
-    return m;
-}
+__device__ __forceinline__ static void max_merge(float &a, float b) { a = fmaxf(a, b); }
 
 __device__ __forceinline__ static float color_radius(float U, float V, float valid)
 {
@@ -99,18 +42,18 @@ __global__ void __launch_bounds__(PIC_THREADS) color_max_kernel(const float *__r
     for (unsigned g = blockIdx.x * PIC_THREADS + threadIdx.x; g < ngroups; g += gridDim.x * PIC_THREADS) {
         if (g < nfull) {
             float U[4], V[4], valid[4];
-            pic_load4<LAYOUT>(flow, g, U, V, valid);
+            flow_load4<LAYOUT>(flow, g, U, V, valid);
 #pragma unroll
             for (int k = 0; k < 4; k++) m = fmaxf(m, color_radius(U[k], V[k], valid[k]));
         } else {
             for (unsigned p = g * 4u; p < npix; p++) {
                 float U, V, valid;
-                pic_load1<LAYOUT>(flow, p, U, V, valid);
+                flow_load1<LAYOUT>(flow, p, U, V, valid);
                 m = fmaxf(m, color_radius(U, V, valid));
             }
         }
     }
-    m = pic_block_max(m);
+    m = block_reduce<PIC_WAVES>(m, max_merge);
     if (threadIdx.x == 0) partials[blockIdx.x] = m;
 }
 
@@ -119,7 +62,7 @@ __global__ void __launch_bounds__(PIC_THREADS) color_max_final_kernel(const floa
 {
     float m = 0.0f;
     for (int b = threadIdx.x; b < nblocks; b += PIC_THREADS) m = fmaxf(m, partials[b]);
-    m = pic_block_max(m);
+    m = block_reduce<PIC_WAVES>(m, max_merge);
     if (threadIdx.x == 0) *radius = m > 0.0f ? m : 1.0f;
 }
 
@@ -164,15 +107,15 @@ __global__ void __launch_bounds__(PIC_THREADS) color_kernel(const float *__restr
         if (g < nfull) {
             float U[4], V[4], valid[4];
             uint32_t c[4];
-            pic_load4<LAYOUT>(flow, g, U, V, valid);
+            flow_load4<LAYOUT>(flow, g, U, V, valid);
 #pragma unroll
             for (int k = 0; k < 4; k++) c[k] = color_pixel(U[k], V[k], valid[k], maxrad, wheel_s);
-            reinterpret_cast<PicBgr4 *>(bgr)[g] = pic_pack4(c);
+            reinterpret_cast<Bgr4 *>(bgr)[g] = bgr_pack4(c);
         } else {
             for (unsigned p = g * 4u; p < npix; p++) {
                 float U, V, valid;
-                pic_load1<LAYOUT>(flow, p, U, V, valid);
-                pic_store1(bgr, p, color_pixel(U, V, valid, maxrad, wheel_s));
+                flow_load1<LAYOUT>(flow, p, U, V, valid);
+                bgr_store1(bgr, p, color_pixel(U, V, valid, maxrad, wheel_s));
             }
         }
     }
@@ -192,28 +135,6 @@ __device__ __forceinline__ static void warp_merge(WarpPartial &a, const WarpPart
     a.sum = a.sum + b.sum;
     a.n += b.n; a.n_outside += b.n_outside; a.n_unknown += b.n_unknown; a.n_above += b.n_above;
     a.max_err = fmaxf(a.max_err, b.max_err);
-}
-
-// the block's total in thread 0: a shuffle tree per wave (64 lanes: offsets 32 .. 1), then the waves in order
-__device__ static WarpPartial warp_block_reduce(WarpPartial a)
-{
-    __shared__ WarpPartial wave_part[PIC_WAVES];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        WarpPartial b;
-        b.sum = __shfl_down(a.sum, off, 64);
-        b.n = __shfl_down(a.n, off, 64); b.n_outside = __shfl_down(a.n_outside, off, 64);
-        b.n_unknown = __shfl_down(a.n_unknown, off, 64); b.n_above = __shfl_down(a.n_above, off, 64);
-        b.max_err = __shfl_down(a.max_err, off, 64);
-        warp_merge(a, b);
-    }
-    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 1; k < PIC_WAVES; k++) warp_merge(a, wave_part[k]);
-    }
-    return a;
 }
 
 struct WarpArgs {
@@ -266,7 +187,7 @@ __global__ void __launch_bounds__(PIC_THREADS) warp_main_kernel(WarpArgs A, cons
     __shared__ uint32_t lut_s[256];
     const uint32_t *lut = nullptr;
     if (bgr) {                                          // uniform
-        lut_s[threadIdx.x] = pic_jet_lut[threadIdx.x];
+        lut_s[threadIdx.x] = plane_jet_lut[threadIdx.x];
         __syncthreads();
         lut = lut_s;
     }
@@ -276,34 +197,33 @@ __global__ void __launch_bounds__(PIC_THREADS) warp_main_kernel(WarpArgs A, cons
         int y = (int)(g * 4u / (unsigned)A.w), x = (int)(g * 4u - (unsigned)y * (unsigned)A.w);
         if (g < nfull) {
             float U[4], V[4], valid[4], e[4];
-            uint32_t wp[4], c[4];
-            pic_load4<LAYOUT>(flow, g, U, V, valid);
-            const PicBgr4 q = reinterpret_cast<const PicBgr4 *>(A.I1)[g];
-            const uint32_t i1[4] = {q.a, (q.a >> 24) | (q.b << 8), (q.b >> 16) | (q.c << 16), q.c >> 8};
+            uint32_t wp[4], c[4], i1[4];
+            flow_load4<LAYOUT>(flow, g, U, V, valid);
+            bgr_unpack4(reinterpret_cast<const Bgr4 *>(A.I1)[g], i1);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 warp_pixel(A, x, y, U[k], V[k], valid[k], i1[k], lut, acc, e[k], wp[k], c[k]);
                 if (++x == A.w) { x = 0; y++; }
             }
-            if (warped) reinterpret_cast<PicBgr4 *>(warped)[g] = pic_pack4(wp);
+            if (warped) reinterpret_cast<Bgr4 *>(warped)[g] = bgr_pack4(wp);
             if (err) reinterpret_cast<float4 *>(err)[g] = make_float4(e[0], e[1], e[2], e[3]);
-            if (bgr) reinterpret_cast<PicBgr4 *>(bgr)[g] = pic_pack4(c);
+            if (bgr) reinterpret_cast<Bgr4 *>(bgr)[g] = bgr_pack4(c);
         } else {
             // the 1..3 pixels after the last whole group
             for (unsigned p = g * 4u; p < npix; p++) {
                 float U, V, valid, e1;
                 uint32_t w1, c1;
-                pic_load1<LAYOUT>(flow, p, U, V, valid);
+                flow_load1<LAYOUT>(flow, p, U, V, valid);
                 const uint8_t *q = A.I1 + (size_t)p * 3;
                 warp_pixel(A, x, y, U, V, valid, (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16), lut, acc, e1, w1, c1);
                 if (++x == A.w) { x = 0; y++; }
-                if (warped) pic_store1(warped, p, w1);
+                if (warped) bgr_store1(warped, p, w1);
                 if (err) err[p] = e1;
-                if (bgr) pic_store1(bgr, p, c1);
+                if (bgr) bgr_store1(bgr, p, c1);
             }
         }
     }
-    acc = warp_block_reduce(acc);
+    acc = block_reduce<PIC_WAVES>(acc, warp_merge);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
@@ -313,7 +233,7 @@ __global__ void __launch_bounds__(PIC_THREADS) warp_final_kernel(const WarpParti
     WarpPartial acc = {};
     // counts of the whole field: up to 2^26, and 32 bits hold them
     for (int b = threadIdx.x; b < nblocks; b += PIC_THREADS) warp_merge(acc, partials[b]);
-    acc = warp_block_reduce(acc);
+    acc = block_reduce<PIC_WAVES>(acc, warp_merge);
     if (threadIdx.x != 0) return;
     dflow_photo_stats s = {};
     if (accumulate) s = *stats;
@@ -325,13 +245,6 @@ __global__ void __launch_bounds__(PIC_THREADS) warp_final_kernel(const WarpParti
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-static int pic_blocks(int H, int W)
-{
-    const size_t ngroups = ((size_t)H * W + 3) / 4;
-    const size_t b = (ngroups + PIC_THREADS - 1) / PIC_THREADS;
-    return (int)(b < PIC_MAX_BLOCKS ? b : PIC_MAX_BLOCKS);
-}
-
 struct ColorWs {
     float *partials;         // one maximum per block of color_max_kernel
     float *radius;           // what color_max_final_kernel leaves for color_kernel
@@ -341,7 +254,7 @@ static ColorWs color_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 {
     WsCarver c(ws);
     ColorWs w;
-    w.partials = c.take<float>((size_t)pic_blocks(H, W));
+    w.partials = c.take<float>((size_t)plane_blocks(H, W));
     w.radius = c.take<float>(1);
     if (bytes) *bytes = c.bytes;
     return w;
@@ -353,7 +266,7 @@ int launch_flow_color(int H, int W, const float *flow, int layout, float max_flo
                       hipStream_t s)
 {
     const ColorWs w = color_ws(ws, H, W);
-    const int nblocks = pic_blocks(H, W);
+    const int nblocks = plane_blocks(H, W);
     const unsigned npix = (unsigned)H * (unsigned)W;
     const bool uvv = layout == DFLOW_EVAL_UVV;
     if (!(max_flow > 0.0f)) {
@@ -374,7 +287,7 @@ static WarpWs warp_ws(void *ws, int H, int W, size_t *bytes = nullptr)
 {
     WsCarver c(ws);
     WarpWs w;
-    w.partials = c.take<WarpPartial>((size_t)pic_blocks(H, W));
+    w.partials = c.take<WarpPartial>((size_t)plane_blocks(H, W));
     if (bytes) *bytes = c.bytes;
     return w;
 }
@@ -386,7 +299,7 @@ int launch_warp_eval(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, con
                      void *ws, hipStream_t s)
 {
     const WarpWs w = warp_ws(ws, H, W);
-    const int nblocks = pic_blocks(H, W);
+    const int nblocks = plane_blocks(H, W);
     const unsigned npix = (unsigned)H * (unsigned)W;
     const WarpArgs A = {bgr1, bgr2, W, H, err_thresh, err_max};
     if (layout == DFLOW_EVAL_UVV)

@@ -1,0 +1,122 @@
+// Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
+// segments.hip, prior.hip): a block's reduction and class counts, and the four-pixel access to a flow plane and a (b, g, r)
+// picture.  They load, pack, reduce or count; every kernel keeps its own loop, launch function and workspace.
+#pragma once
+#include "dflow_common.h"
+#include "jet_lut.h"
+
+// ---- block reduce: the block's total of `a` in thread 0 (the other threads hold partial results).  A shuffle tree per wave
+// (64 lanes: offsets 32 .. 1), then lane 0 of every wave through LDS and thread 0 merges waves 1 .. WAVES - 1 in that order:
+// the order of every merge is fixed, so a double sum keeps its bits from call to call.  T travels dword by dword.
+template <int WAVES, typename T, typename Merge> __device__ static T block_reduce(T a, Merge merge)
+{
+    static_assert(sizeof(T) % 4 == 0, "block_reduce shuffles whole dwords");
+    __shared__ T wave_part[WAVES];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        uint32_t d[sizeof(T) / 4];
+        __builtin_memcpy(d, &a, sizeof(T));
+#pragma unroll
+        for (unsigned k = 0; k < sizeof(T) / 4; k++) d[k] = __shfl_down(d[k], off, 64);
+        T b;
+        __builtin_memcpy(&b, d, sizeof(T));
+        merge(a, b);
+    }
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < WAVES; k++) merge(a, wave_part[k]);
+    }
+    return a;
+}
+
+// ---- block class counts: how many lanes of the block have is[k], added to counts[offset + k]: ballots -> per-block LDS
+// counters -> one integer atomic per block and non-zero counter.  Every thread of the block calls it; counts may be NULL
+// (uniform: nothing is counted).  The second form counts the lanes whose class is k (a lane of no class passes -1).
+template <int N> __device__ static inline void block_count(const bool (&is)[N], int32_t *counts, int offset)
+{
+    __shared__ int s_cnt[N];
+    if (!counts) return;
+    if (threadIdx.x < N) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const int c = __popcll(__ballot(is[k]));
+        if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
+    }
+    __syncthreads();
+    if (threadIdx.x < N && s_cnt[threadIdx.x]) atomicAdd(&counts[offset + threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+template <int N> __device__ static inline void block_count_class(int kind, int32_t *counts, int offset)
+{
+    bool is[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) is[k] = kind == k;
+    block_count<N>(is, counts, offset);
+}
+
+// ---- a plane as a flat array of h*w pixels, four pixels per lane and step, grid-stride over at most PLANE_MAX_BLOCKS blocks
+#define PLANE_THREADS 256
+#define PLANE_MAX_BLOCKS 1024         // 4 blocks of 256 threads on each of the 256 CUs
+
+static int plane_blocks(int H, int W)
+{
+    const size_t ngroups = ((size_t)H * W + 3) / 4;
+    const size_t b = (ngroups + PLANE_THREADS - 1) / PLANE_THREADS;
+    return (int)(b < PLANE_MAX_BLOCKS ? b : PLANE_MAX_BLOCKS);
+}
+
+// the four pixels of group g of a flow plane as U, V, valid: three (DYDX: two) 16-byte loads
+template <int LAYOUT>
+__device__ __forceinline__ static void flow_load4(const float *__restrict__ flow, unsigned g, float (&U)[4], float (&V)[4], float (&valid)[4])
+{
+    if constexpr (LAYOUT == DFLOW_EVAL_UVV) {
+        const float4 *tp = reinterpret_cast<const float4 *>(flow) + (size_t)g * 3;
+        const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+        const float T[12] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w, t2.x, t2.y, t2.z, t2.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) { U[k] = T[3 * k]; V[k] = T[3 * k + 1]; valid[k] = T[3 * k + 2]; }
+    } else {
+        const float4 *tp = reinterpret_cast<const float4 *>(flow) + (size_t)g * 2;
+        const float4 t0 = tp[0], t1 = tp[1];
+        const float T[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};           // [dy,dx]: U = dx, V = dy
+#pragma unroll
+        for (int k = 0; k < 4; k++) { U[k] = T[2 * k + 1]; V[k] = T[2 * k]; valid[k] = 1.0f; }
+    }
+}
+
+// the one pixel p of the tail (the 1..3 pixels after the last whole group)
+template <int LAYOUT>
+__device__ __forceinline__ static void flow_load1(const float *__restrict__ flow, unsigned p, float &U, float &V, float &valid)
+{
+    if constexpr (LAYOUT == DFLOW_EVAL_UVV) { U = flow[(size_t)p * 3]; V = flow[(size_t)p * 3 + 1]; valid = flow[(size_t)p * 3 + 2]; }
+    else { U = flow[(size_t)p * 2 + 1]; V = flow[(size_t)p * 2]; valid = 1.0f; }
+}
+
+// four (b, g, r) pixels, 12 bytes, and a pixel as the entry b | g << 8 | r << 16
+struct Bgr4 { uint32_t a, b, c; };
+
+__device__ __forceinline__ static Bgr4 bgr_pack4(const uint32_t (&c)[4])
+{
+    Bgr4 v;
+    v.a = c[0] | (c[1] << 24);
+    v.b = (c[1] >> 8) | (c[2] << 16);
+    v.c = (c[2] >> 16) | (c[3] << 8);
+    return v;
+}
+
+// the inverse; bits 24..31 of an entry hold a neighbour's byte
+__device__ __forceinline__ static void bgr_unpack4(const Bgr4 &q, uint32_t (&c)[4])
+{
+    c[0] = q.a; c[1] = (q.a >> 24) | (q.b << 8); c[2] = (q.b >> 16) | (q.c << 16); c[3] = q.c >> 8;
+}
+
+__device__ __forceinline__ static void bgr_store1(uint8_t *__restrict__ bgr, size_t p, uint32_t c)
+{
+    bgr[p * 3] = (uint8_t)c; bgr[p * 3 + 1] = (uint8_t)(c >> 8); bgr[p * 3 + 2] = (uint8_t)(c >> 16);
+}
+
+// the colour table of both error pictures (flow_eval.hip, flow_picture.hip)
+static __constant__ uint32_t plane_jet_lut[256] = {JET_LUT_VALUES};

@@ -10,7 +10,7 @@
 // row and round), the tree is three DPP exchanges inside the half row (IEEE addition commutes, so both partners of an exchange
 // hold the same bits), then the four-element tail in sequence.
 #include <math.h>
-#include "dflow_common.h"
+#include "plane_ops.h"
 
 #define PRIOR_THREADS 256
 #define PRIOR_ROW 16                                  // lanes per pixel: one DPP row
@@ -211,9 +211,6 @@ int launch_prior(const dflow_params *p, const void *d1, const void *d2, const fl
 __global__ void __launch_bounds__(ADV_THREADS) advance_claim_kernel(int H, int W, const float *__restrict__ flow, int layout,
                                                                     uint32_t *__restrict__ win, int32_t *counts)
 {
-    __shared__ int s_cnt[2];
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
     const uint32_t n = (uint32_t)H * (uint32_t)W, i = blockIdx.x * ADV_THREADS + threadIdx.x;
     bool part = false;
     if (i < n) {
@@ -224,12 +221,9 @@ __global__ void __launch_bounds__(ADV_THREADS) advance_claim_kernel(int H, int W
             if (ty >= 0 && ty < H && tx >= 0 && tx < W) { part = true; atomicMin(&win[(size_t)ty * W + tx], i); }
         }
     }
-    if (counts) {       // [1] holds the claimants until the resolve kernel takes the claimed targets off; [2] the others
-        const int c_part = __popcll(__ballot(part)), c_out = __popcll(__ballot(i < n && !part));
-        if ((threadIdx.x & 63) == 0) { if (c_part) atomicAdd(&s_cnt[0], c_part); if (c_out) atomicAdd(&s_cnt[1], c_out); }
-        __syncthreads();
-        if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&counts[1 + threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    // counts[1] holds the claimants until the resolve kernel takes the claimed targets off; counts[2] the others
+    const bool is[2] = {part, i < n && !part};
+    block_count<2>(is, counts, 1);
 }
 
 __global__ void __launch_bounds__(ADV_THREADS) advance_resolve_kernel(int H, int W, const float *__restrict__ flow, int layout, int negate,

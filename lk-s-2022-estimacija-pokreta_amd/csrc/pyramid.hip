@@ -9,10 +9,10 @@
 //   3. the vertical pass from that plane with the one rounding, (sum + 128) >> 8; a lane makes the four bytes of one aligned dword
 //      of the output and stores them at once where all four belong to the tile, byte by byte at the tile's edges (the
 //      neighbouring tile writes the other bytes of such a dword).
-// upsample_kernel: one fine pixel per lane, the four coarse corners through flow_vector (dflow_common.h), 12 bytes out; the
-// counts as ballots -> per-block LDS counters -> three integer atomics per block, as advance_claim_kernel (prior.hip) does.
+// upsample_kernel: one fine pixel per lane, the four coarse corners through flow_good (dflow_common.h), 12 bytes out; the
+// three counts through block_count_class (plane_ops.h).
 #include <math.h>
-#include "dflow_common.h"
+#include "plane_ops.h"
 
 #define PYR_THREADS 256
 #define PYR_TW 64                                     // output tile: 64 x 16 pixels
@@ -115,31 +115,20 @@ int launch_pyr_down(int H, int W, const uint8_t *in1, const uint8_t *in2, uint8_
 // ---- flow upsampling
 #define UPS_THREADS 256
 
-// a coarse vector that can be doubled: valid under its layout and both components finite
-__device__ static inline bool ups_good(const float *__restrict__ f, int layout, size_t src, float &u, float &v)
-{
-    return flow_vector(f, layout, src, v, u) && isfinite(u) && isfinite(v);
-}
-
-struct UpsOut { float u, v, valid; };
-
 __global__ void __launch_bounds__(UPS_THREADS) upsample_kernel(int H, int W, int hc, int wc, const float *__restrict__ coarse, int layout,
-                                                               UpsOut *__restrict__ out, int32_t *counts)
+                                                               FlowOut *__restrict__ out, int32_t *counts)
 {
-    __shared__ int s_cnt[3];
-    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
     const uint32_t n = (uint32_t)H * (uint32_t)W, i = blockIdx.x * UPS_THREADS + threadIdx.x;
     int kind = -1;                                      // 0 BILINEAR, 1 NEAREST, 2 INVALID
     if (i < n) {
         const int y = (int)(i / (uint32_t)W), x = (int)(i % (uint32_t)W);
         const int y0 = y >> 1, y1 = min((y + 1) >> 1, hc - 1), x0 = x >> 1, x1 = min((x + 1) >> 1, wc - 1);
         float u00, v00, u01, v01, u10, v10, u11, v11;
-        const bool g00 = ups_good(coarse, layout, (size_t)y0 * wc + x0, u00, v00);
-        const bool g01 = ups_good(coarse, layout, (size_t)y0 * wc + x1, u01, v01);
-        const bool g10 = ups_good(coarse, layout, (size_t)y1 * wc + x0, u10, v10);
-        const bool g11 = ups_good(coarse, layout, (size_t)y1 * wc + x1, u11, v11);
-        UpsOut o = {0.0f, 0.0f, 0.0f};
+        const bool g00 = flow_good(coarse, layout, (size_t)y0 * wc + x0, u00, v00);
+        const bool g01 = flow_good(coarse, layout, (size_t)y0 * wc + x1, u01, v01);
+        const bool g10 = flow_good(coarse, layout, (size_t)y1 * wc + x0, u10, v10);
+        const bool g11 = flow_good(coarse, layout, (size_t)y1 * wc + x1, u11, v11);
+        FlowOut o = {0.0f, 0.0f, 0.0f};
         kind = 2;
         if (g00 && g01 && g10 && g11) {
             const float u = ((u00 + u01) + (u10 + u11)) * 0.5f, v = ((v00 + v01) + (v10 + v11)) * 0.5f;
@@ -151,15 +140,7 @@ __global__ void __launch_bounds__(UPS_THREADS) upsample_kernel(int H, int W, int
         }
         out[i] = o;
     }
-    if (counts) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int c = __popcll(__ballot(kind == k));
-            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-        }
-        __syncthreads();
-        if (threadIdx.x < 3 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    block_count_class<3>(kind, counts, 0);
 }
 
 int launch_flow_upsample(int H, int W, const float *coarse, int layout, float *out, int32_t *counts, hipStream_t s)
@@ -167,6 +148,6 @@ int launch_flow_upsample(int H, int W, const float *coarse, int layout, float *o
     if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), s));
     const unsigned n = (unsigned)H * (unsigned)W;
     hipLaunchKernelGGL(upsample_kernel, dim3((n + UPS_THREADS - 1) / UPS_THREADS), dim3(UPS_THREADS), 0, s, H, W, (H + 1) / 2, (W + 1) / 2,
-                       coarse, layout, reinterpret_cast<UpsOut *>(out), counts);
+                       coarse, layout, reinterpret_cast<FlowOut *>(out), counts);
     return dflow_check_launch("upsample_kernel");
 }

@@ -3,70 +3,30 @@
 // pixels removed.  This build's definition; the reference's removeSmallSegments (post.hip, dflow_remove_small_segments_host)
 // is a sequential flood fill whose result depends on its scan order and stays what it is.
 //
-// Union-find with atomicMin (Playne and Hawick; Komura): a label is the raster index of a pixel of the same segment that is
-// not larger than the pixel's own (L[i] <= i, a root has L[i] == i), and labels only ever decrease.  Four launches, whatever
-// the field holds, and no workgroup waits for another:
+// Union-find with atomicMin (union_find.h, where the invariant and the termination arguments are): a label is the raster index
+// of a pixel of the same segment that is not larger than the pixel's own.  In global memory a find hangs its start under the
+// root it found (UF_HANG).  Four launches, whatever the field holds, and no workgroup waits for another:
 //   seg_tile_kernel    one workgroup per SEG_TW x SEG_TH tile: the tile's right and down joins merged in LDS, flattened, and
 //                      every pixel's label written as the raster index of its tile-local root (-1: no member); sizes zeroed;
 //   seg_border_kernel  one lane per join that crosses a tile border: the union of the two labels in global memory;
 //   seg_root_kernel    every pixel finds its root, which becomes its label, and adds itself to size[root], a wave's adds
 //                      aggregated per distinct root first;
-//   seg_write_kernel   d_out, the optional planes and the four counts (ballots -> LDS -> one atomic per block and count).
-// The root of a segment is its smallest raster index: every link points from a larger index to a smaller one of the same
-// segment, so the smallest is never linked.  Everything is integer or a copy of input bits; -ffp-contract=off and the
-// join test is one subtraction, fabsf and addition as written.
+//   seg_write_kernel   d_out, the optional planes and the four counts (block_count, plane_ops.h).
+// The root of a segment is its smallest raster index.  Everything is integer or a copy of input bits; -ffp-contract=off and
+// the join test is one subtraction, fabsf and addition as written.
 #include <math.h>
-#include "dflow_common.h"
+#include "plane_ops.h"
+#include "union_find.h"
 
 #define SEG_TW 32
 #define SEG_TH 8
 #define SEG_THREADS (SEG_TW * SEG_TH)
 
-// a member: valid under its layout and both components finite (GOOD in dflow_flow_consistency)
-__device__ static inline bool seg_member(const float *__restrict__ f, int layout, size_t src, float &u, float &v)
-{
-    return flow_vector(f, layout, src, v, u) && isfinite(u) && isfinite(v);
-}
-
-// two members are joined: symmetric (a - b and b - a differ in sign only), and a difference that overflows gives inf, which is
-// not <= a finite thresh
+// a member is a good vector (flow_good, dflow_common.h: GOOD in dflow_flow_consistency).  Two members are joined: symmetric
+// (a - b and b - a differ in sign only), and a difference that overflows gives inf, which is not <= a finite thresh
 __device__ static inline bool seg_joined(float ua, float va, float ub, float vb, float thresh)
 {
     return fabsf(ua - ub) + fabsf(va - vb) <= thresh;
-}
-
-// The root of x.  Terminates: L[x] <= x always and a step is taken only while L[x] < x, so x strictly decreases and is >= 0.
-// Atomic loads: a parent is never taken from a stale cache line or a register while other lanes lower it.
-// In global memory the start is then hung directly under what was found (a pixel of its own set below it: an atomicMin again),
-// so that the chains a long winding segment builds across many tiles are walked once and not once per lane.
-template <int SCOPE> __device__ static inline int seg_find(int *L, int x)
-{
-    const int start = x;
-    int parent = -1;                                  // the start's own parent
-    for (;;) {
-        const int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, SCOPE);
-        if (parent < 0) parent = p;
-        if (p == x) break;
-        x = p;
-    }
-    if (SCOPE == __HIP_MEMORY_SCOPE_AGENT && parent != x) __hip_atomic_fetch_min(&L[start], x, __ATOMIC_RELAXED, SCOPE);
-    return x;
-}
-
-// Joins the sets of a and b.  Terminates: find never raises a or b; a round either returns or replaces the larger root a by
-// the value `old` < a that atomicMin returned (some other lane linked a first), so a + b strictly decreases and is >= 0.
-// Labels only ever decrease: the one write is an atomicMin with a value below the index it is written to.
-template <int SCOPE> __device__ static inline void seg_union(int *L, int a, int b)
-{
-    for (;;) {
-        a = seg_find<SCOPE>(L, a);
-        b = seg_find<SCOPE>(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = __hip_atomic_fetch_min(&L[a], b, __ATOMIC_RELAXED, SCOPE);
-        if (old == a) return;                         // a was still a root and now hangs under b
-        a = old;                                      // a hangs under old (or b, the smaller): old's set and b's remain to be joined
-    }
 }
 
 __global__ void __launch_bounds__(SEG_THREADS) seg_tile_kernel(int h, int w, const float *__restrict__ flow, int layout, float thresh,
@@ -79,21 +39,21 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_tile_kernel(int h, int w, con
     const int x = blockIdx.x * SEG_TW + lx, y = blockIdx.y * SEG_TH + ly;
     const bool inside = x < w && y < h;               // ragged edge tiles: the pixels beyond the frame are no members
     float u = 0.0f, v = 0.0f;
-    const bool member = inside && seg_member(flow, layout, (size_t)y * w + x, u, v);
+    const bool member = inside && flow_good(flow, layout, (size_t)y * w + x, u, v);
     s_u[t] = u; s_v[t] = v; s_mem[t] = member; s_lab[t] = member ? t : -1;
     __syncthreads();
     if (member) {
         if (lx + 1 < SEG_TW && s_mem[t + 1] && seg_joined(u, v, s_u[t + 1], s_v[t + 1], thresh))
-            seg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + 1);
+            uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + 1);
         if (ly + 1 < SEG_TH && s_mem[t + SEG_TW] && seg_joined(u, v, s_u[t + SEG_TW], s_v[t + SEG_TW], thresh))
-            seg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + SEG_TW);
+            uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + SEG_TW);
     }
     __syncthreads();
     if (inside) {
         int root = -1;
         if (member) {
             // the smallest tile-local index is the smallest raster index of the tile's part of the segment
-            const int r = seg_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t);
+            const int r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t);
             root = (blockIdx.y * SEG_TH + r / SEG_TW) * w + blockIdx.x * SEG_TW + r % SEG_TW;
         }
         label[(size_t)y * w + x] = root;
@@ -119,8 +79,8 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_border_kernel(int h, int w, c
         q = p + w;
     }
     float up, vp, uq, vq;
-    if (seg_member(flow, layout, (size_t)p, up, vp) && seg_member(flow, layout, (size_t)q, uq, vq) && seg_joined(up, vp, uq, vq, thresh))
-        seg_union<__HIP_MEMORY_SCOPE_AGENT>(label, p, q);
+    if (flow_good(flow, layout, (size_t)p, up, vp) && flow_good(flow, layout, (size_t)q, uq, vq) && seg_joined(up, vp, uq, vq, thresh))
+        uf_union<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(label, p, q);
 }
 
 __global__ void __launch_bounds__(SEG_THREADS) seg_root_kernel(int n, int *label, int *size)
@@ -129,7 +89,7 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_root_kernel(int n, int *label
     int root = -1;
     if (i < n && __hip_atomic_load(&label[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) {
         // no root changes any more; other lanes only replace a parent by the root above it, so either value leads there
-        root = seg_find<__HIP_MEMORY_SCOPE_AGENT>(label, i);      // and label[i] = root (seg_find)
+        root = uf_find<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(label, i);      // and label[i] = root (UF_HANG)
     }
     // one add per wave and distinct root.  Terminates: a round retires the first pending lane and every lane that shares its
     // root, so there are at most 64 rounds.
@@ -147,16 +107,12 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_root_kernel(int n, int *label
 }
 
 #define SEG_COUNTS 4                                  // segments, segments removed, members, pixels removed
-struct SegOut { float u, v, valid; };
 
 __global__ void __launch_bounds__(SEG_THREADS) seg_write_kernel(int n, const float *flow, int layout, int min_size, int keep_singletons,
                                                                 const int *__restrict__ label, const int *__restrict__ size,
                                                                 float *out, int *__restrict__ segment, int *__restrict__ size_out,
                                                                 int *counts)
 {
-    __shared__ int s_cnt[SEG_COUNTS];
-    if (threadIdx.x < SEG_COUNTS) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
     const int i = blockIdx.x * SEG_THREADS + threadIdx.x;
     bool member = false, removed = false, is_root = false;
     if (i < n) {
@@ -165,26 +121,18 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_write_kernel(int n, const flo
         is_root = root == i;
         const int sz = member ? size[root] : 0;
         removed = member && sz < min_size && !(keep_singletons && sz == 1);
-        SegOut o = {0.0f, 0.0f, 0.0f};
+        FlowOut o = {0.0f, 0.0f, 0.0f};
         if (member && !removed) {                     // the pixel's own bits; flow may be out (UVV): a lane touches its own pixel only
             float u, v;
             flow_vector(flow, layout, (size_t)i, v, u);
             o.u = u; o.v = v; o.valid = 1.0f;
         }
-        reinterpret_cast<SegOut *>(out)[i] = o;
+        reinterpret_cast<FlowOut *>(out)[i] = o;
         if (segment) segment[i] = root;
         if (size_out) size_out[i] = sz;
     }
-    if (counts) {
-        const bool kind[SEG_COUNTS] = {is_root, is_root && removed, member, removed};
-#pragma unroll
-        for (int k = 0; k < SEG_COUNTS; k++) {
-            const int c = __popcll(__ballot(kind[k]));
-            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
-        }
-        __syncthreads();
-        if (threadIdx.x < SEG_COUNTS && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    const bool is[SEG_COUNTS] = {is_root, is_root && removed, member, removed};
+    block_count<SEG_COUNTS>(is, counts, 0);
 }
 
 // a label and a size per pixel

@@ -35,8 +35,6 @@ static VarWs var_ws(void *ws, int H, int W)
 
 size_t var_ws_bytes(int H, int W) { return var_ws(nullptr, H, W).bytes; }
 
-__device__ __forceinline__ static int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // ---- preparation ----------------------------------------------------------------------------------------------------
 // Separable Gaussian of one (H,W,3) uint8 image into three float planes: both passes in one launch.  A 32x32 tile with a
 // halo of r pixels is staged in LDS (a halo cell holds the pixel at the clamped coordinate, so the row pass of a halo row is
@@ -54,7 +52,7 @@ __global__ __launch_bounds__(VAR_THREADS) void var_smooth_kernel(const uint8_t *
     for (int c = 0; c < 3; c++) {
         for (int i = threadIdx.x; i < n * n; i += VAR_THREADS) {
             const int ly = i / n, lx = i - ly * n;
-            const int gy = clampi(y0 + ly - r, H - 1), gx = clampi(x0 + lx - r, W - 1);
+            const int gy = clampi(y0 + ly - r, 0, H - 1), gx = clampi(x0 + lx - r, 0, W - 1);
             in[ly][lx] = (float)bgr[((size_t)gy * W + gx) * 3 + c];
         }
         __syncthreads();
@@ -83,11 +81,11 @@ template <typename F> __device__ __forceinline__ static float deriv5(F &&at)
 __device__ __forceinline__ static float ddx(const float *__restrict__ f, int H, int W, int y, int x)
 {
     const float *row = f + (size_t)y * W;
-    return deriv5([&](int k) { return row[clampi(x + k, W - 1)]; });
+    return deriv5([&](int k) { return row[clampi(x + k, 0, W - 1)]; });
 }
 __device__ __forceinline__ static float ddy(const float *__restrict__ f, int H, int W, int y, int x)
 {
-    return deriv5([&](int k) { return f[(size_t)clampi(y + k, H - 1) * W + x]; });
+    return deriv5([&](int k) { return f[(size_t)clampi(y + k, 0, H - 1) * W + x]; });
 }
 
 #define VAR_PIXEL() \
@@ -103,8 +101,8 @@ __global__ __launch_bounds__(VAR_THREADS) void var_omega_kernel(int H, int W, Va
         const size_t j = (size_t)yy * W + xx;
         return (0.114f * w.I1[0][j] + 0.587f * w.I1[1][j]) + 0.299f * w.I1[2][j];
     };
-    const float lx = deriv5([&](int k) { return L(y, clampi(x + k, W - 1)); });
-    const float ly = deriv5([&](int k) { return L(clampi(y + k, H - 1), x); });
+    const float lx = deriv5([&](int k) { return L(y, clampi(x + k, 0, W - 1)); });
+    const float ly = deriv5([&](int k) { return L(clampi(y + k, 0, H - 1), x); });
     w.omega[i] = expf(-5.0f * sqrtf(lx * lx + ly * ly) / 255.0f);
 }
 
@@ -178,8 +176,8 @@ __global__ __launch_bounds__(VAR_THREADS) void var_smooth_weight_kernel(int H, i
                                                                          const float *__restrict__ dv)
 {
     VAR_PIXEL();
-    const size_t l = (size_t)y * W + clampi(x - 1, W - 1), r = (size_t)y * W + clampi(x + 1, W - 1);
-    const size_t t = (size_t)clampi(y - 1, H - 1) * W + x, b = (size_t)clampi(y + 1, H - 1) * W + x;
+    const size_t l = (size_t)y * W + clampi(x - 1, 0, W - 1), r = (size_t)y * W + clampi(x + 1, 0, W - 1);
+    const size_t t = (size_t)clampi(y - 1, 0, H - 1) * W + x, b = (size_t)clampi(y + 1, 0, H - 1) * W + x;
     const float ux = 0.5f * ((w.u[r] + du[r]) - (w.u[l] + du[l])), uy = 0.5f * ((w.u[b] + du[b]) - (w.u[t] + du[t]));
     const float vx = 0.5f * ((w.v[r] + dv[r]) - (w.v[l] + dv[l])), vy = 0.5f * ((w.v[b] + dv[b]) - (w.v[t] + dv[t]));
     w.p[i] = w.omega[i] * psi_prime(((ux * ux + uy * uy) + vx * vx) + vy * vy);

@@ -104,6 +104,9 @@ def warp(img1, img2, flow, err_thresh=10.0, err_max=30.0):
 # ---------------------------------------------------------------------------------- the inputs of the GPU tests
 SHAPES = [(1, 1), (1, 7), (5, 1), (33, 65), (37, 61)]          # 37 x 61 = 2257 px: no multiple of 4, three blocks
 SCALES = (4.0, 20.0)
+# 1,052,675 px, a three-pixel tail, 1029 blocks' worth of groups: more than the 1024 blocks of the capped grid, whose first
+# blocks take a second grid-stride step; one scale, so that its references stay within a second or two
+BIG_SHAPE, BIG_SCALE = (1025, 1027), 4.0
 BIG = F(125.0)                                                  # the planted maximum: beyond 6 sigma of either scale
 
 

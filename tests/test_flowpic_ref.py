@@ -87,6 +87,20 @@ def test_gpu_inputs_keep_out_of_the_band(H, W):
         assert 0.7 * H * W < R.flow_color(flow)["known"].sum() < H * W - 5
 
 
+def test_gpu_big_input_keeps_out_of_the_band():
+    """The same for the one field beyond the capped grid, which test_gpu_flowpic.py colours with the automatic radius."""
+    (H, W), scale = R.BIG_SHAPE, R.BIG_SCALE
+    flow, where = R.color_case(H, W, scale)
+    assert len(where) == len(R.color_planted())
+    for field in (flow, R.dydx(flow)):
+        r = R.flow_color(field)
+        n = int(R.near_integer(r["c"]).sum())
+        print("%dx%d scale %g layout %d: %d of %d pixels in the band" % (H, W, scale, field.shape[2], n, H * W))
+        assert n <= 0.01 * H * W and r["maxrad"] == R.BIG
+        if field is flow:
+            assert 0.7 * H * W < r["known"].sum() < H * W - 5
+
+
 # ------------------------------------------------------------------------------------------------ the warp
 def test_warp_integer_flow_reproduces_shifted_pixels():
     rng = np.random.default_rng(3)

@@ -6,7 +6,8 @@ non-negative doubles, each an exact float32: any order of additions stays within
 (math.fsum), the bound asserted.
 Shapes: a lane takes four pixels and a block 1024: 1x1, 1x7 and 3x5 are less than one group or end in a part of one, 37x53
 (1961 px) is two blocks and no multiple of 4, 64x256 whole blocks, 131x257 several blocks and a one-pixel tail, 436x1024
-the many-block reduction."""
+the many-block reduction, 1025x1027 (1,052,675 px, a three-pixel tail) 1029 blocks' worth of groups: more than the 1024 blocks
+of the capped grid, whose first blocks take a second grid-stride step."""
 import json
 import math
 import os
@@ -20,7 +21,7 @@ from conftest import pkg
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-SHAPES = [(1, 1), (1, 7), (3, 5), (37, 53), (64, 256), (131, 257), (436, 1024)]
+SHAPES = [(1, 1), (1, 7), (3, 5), (37, 53), (64, 256), (131, 257), (436, 1024), (1025, 1027)]
 
 
 @pytest.fixture(scope="module")

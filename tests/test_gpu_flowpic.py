@@ -4,13 +4,14 @@ built on them: pipeline.flow_color / warp_eval / photo_stats, flowpicture.py and
 
 Warp: float32 with one rounding per operation on both sides: counts, max_err, the error plane (on its bits), the warped image
 and the error picture are asserted exactly; sum_err within 1e-9 relative of the reference's sequential double sum (any order
-of n <= 2257 non-negative doubles stays within n * 2^-53 = 2.5e-13) and bit-equal between two calls.
+of n <= 1,052,675 non-negative doubles stays within n * 2^-53 = 1.2e-10) and bit-equal between two calls.
 Colour: double with one rounding per operation; everything but atan2 is determined to the bit.  A byte v passes when
 v == floor(c) for the reference's unrounded c = 255 * col; where 0 < |c - rint(c)| <= 1e-6 it also passes as rint(c) or
 rint(c) - 1.  tests/test_flowpic_ref.py asserts that at most 1 % of the pixels of any field used here have a channel in that
 band; the planted pixels must match exactly.
 Shapes: a lane takes four pixels and a block 1024: 1x1, 1x7 and 5x1 are less than one group or end in a part of one, 33x65
-(2145 px) and 37x61 (2257 px) are three blocks and no multiple of 4; 436x1024 is the many-block reduction."""
+(2145 px) and 37x61 (2257 px) are three blocks and no multiple of 4; 436x1024 is the many-block reduction; 1025x1027
+(flowpic_ref.BIG_SHAPE) is more groups than the capped grid's 1024 blocks take in one step, and ends in three single pixels."""
 import json
 import os
 
@@ -74,6 +75,22 @@ def test_color_matches_the_reference(torch_, H, W):
         assert len(np.unique(img.reshape(-1, 3), axis=0)) > 100
 
 
+def test_color_beyond_the_capped_grid(torch_):
+    """color_max_kernel and color_kernel on their second grid-stride step: the automatic radius, both layouts."""
+    pipeline = pkg("pipeline")
+    (H, W), scale = R.BIG_SHAPE, R.BIG_SCALE
+    flow, planted = R.color_case(H, W, scale)
+    for name, field in fields(flow):
+        ref = R.flow_color(field)
+        img, radius = pipeline.flow_color(field, None, return_radius=True)
+        img, radius = img.cpu().numpy(), radius.cpu().numpy()
+        assert img.dtype == np.uint8 and img.shape == (H, W, 3) and radius.dtype == np.float32 and radius.shape == (1,)
+        assert radius.view(np.uint32)[0] == np.array([ref["maxrad"]], F).view(np.uint32)[0], (radius, ref["maxrad"])
+        check_color(img, ref, planted, "%dx%d scale %g %s automatic radius" % (H, W, scale, name))
+        assert np.array_equal(pipeline.flow_color(field, None).cpu().numpy(), img)
+    assert len(np.unique(img.reshape(-1, 3), axis=0)) > 100
+
+
 def test_color_automatic_radius_of_a_field_at_rest(torch_):
     pipeline = pkg("pipeline")
     flow = np.zeros((5, 7, 3), F)
@@ -135,6 +152,27 @@ def test_warp_matches_the_reference(torch_, H, W):
                 assert st["mean_err"] == st["sum_err"] / st["n"] and st["above_pct"] == st["n_above"] * 100 / st["n"]
             else:
                 assert np.isnan(st["mean_err"]) and np.isnan(st["above_pct"]) and st["max_err"] == 0.0 and st["sum_err"] == 0.0
+
+
+def test_warp_beyond_the_capped_grid(torch_):
+    """warp_main_kernel on its second grid-stride step: every optional output, both layouts."""
+    pipeline = pkg("pipeline")
+    (H, W), scale = R.BIG_SHAPE, R.BIG_SCALE
+    img1, img2, flow, _ = R.warp_case(H, W, scale)
+    for name, field in fields(flow):
+        thresh, emax = (10.0, 30.0) if name == "UVV" else (60.0, 90.0)
+        label = "%dx%d scale %g %s" % (H, W, scale, name)
+        ref = R.warp(img1, img2, field, thresh, emax)
+        stats, wp, err, pic = run_warp(img1, img2, field, err_thresh=thresh, err_max=emax)
+        st = pipeline.photo_stats(stats)
+        check_stats(st, ref, label)
+        assert err.dtype == np.float32 and err.shape == (H, W) and wp.shape == pic.shape == (H, W, 3)
+        assert same_plane(err, ref["err"], label + " err")
+        assert same_plane(wp, ref["warped"], label + " warped")
+        assert same_plane(pic, ref["bgr"], label + " error picture")
+        again = pipeline.warp_eval(img1, img2, field, thresh, emax)
+        assert again.cpu().numpy().tobytes() == stats.cpu().numpy().tobytes()
+        assert st["n"] and st["mean_err"] == st["sum_err"] / st["n"] and st["above_pct"] == st["n_above"] * 100 / st["n"]
 
 
 def test_warp_accumulates_over_two_pairs(torch_):
