@@ -12,6 +12,23 @@
  *     device memory: scratch comes from the caller's workspace (dflow_workspace_bytes).
  *   - Return 0 on success, a negative DFLOW_E* code otherwise; dflow_last_error() gives the message
  *     (thread-local).  No global state; re-entrant across devices.
+ *   - Alignment of d_ws.  A stage carves typed regions out of its workspace, each at a multiple of 256 bytes from d_ws, and
+ *     needs exactly the bytes its size function (or dflow_workspace_bytes) promises: what the workspace holds before the call
+ *     does not matter (dflow_bcd_phase / _sweep and dflow_knn_screen_stats read what dflow_bcd_prepare / dflow_knn_proposals
+ *     left), and nothing beyond those bytes is written.  d_ws must be aligned for the widest access the stage makes to a
+ *     region; a device allocation (256 bytes and more) serves every stage:
+ *       16  dflow_daisy, dflow_daisy_pair (float4 planes), dflow_knn_proposals, dflow_knn_proposals_timed,
+ *           dflow_knn_screen_stats(_n) (int4 lists), dflow_neighbour_proposals (uint32 flows: 4 would do; one value for the
+ *           buffer the main-path stages share), dflow_bcd_prepare, dflow_bcd_phase, dflow_bcd_sweep and every d_ws[i] of
+ *           dflow_bcd_phase_batch / dflow_bcd_sweep_batch (uint2 records, back-pointers staged 16 bytes at a time)
+ *        8  dflow_bcd_stats, dflow_bcd_stats_batch, dflow_flow_eval, dflow_warp_eval (partial results that hold a double),
+ *           dflow_epic_interpolate, dflow_epic_prefilter (uint64 keys updated atomically, uint64 edges)
+ *        4  dflow_canny_edges (int32 labels updated atomically), dflow_var_refine (float planes), dflow_flow_color (float
+ *           partial maxima), dflow_flow_advance (uint32 winners, atomicMin), dflow_segment_filter (int32 labels and sizes)
+ *        2  dflow_pb_edges (uint16 bins)
+ *     A d_ws that is not returns DFLOW_EINVAL ("d_ws is not N-byte aligned") before anything is launched.  Every other argument
+ *     error is reported first, and so is a NULL or too small workspace (DFLOW_ENOSPC), except by dflow_bcd_stats(_batch),
+ *     dflow_flow_advance and dflow_segment_filter, which check d_ws with their other pointers, before its size.
  *
  * Device layouts (H = pich, W = picw, LP = label_pitch >= maxnprop, multiple of 16)
  *   image      uint8   (H,W,3)   BGR, as cv2.imread returns it            daisy i flann.py:26-27,52-53
@@ -92,7 +109,9 @@ const char *dflow_last_error(void);
 /* Fills *p with the reference constants for the given geometry. */
 void dflow_default_params(dflow_params *p, int32_t pich, int32_t picw, int32_t cellh, int32_t cellw);
 
-/* Scratch bytes any entry point may need for these parameters (one buffer serves all stages). */
+/* Scratch bytes any entry point may need for these parameters (one buffer serves all stages): the largest need of the main-path
+ * stages (dflow_daisy_pair, dflow_knn_proposals where the screened search runs, dflow_neighbour_proposals, dflow_bcd_prepare and
+ * the sweeps) plus 256 spare bytes.  A stage called with less than its own need answers DFLOW_ENOSPC and names that need. */
 size_t dflow_workspace_bytes(const dflow_params *p);
 
 /* izracunajDaisy, daisy i flann.py:69-77 (cv2.xfeatures2d.DAISY_create(radius=5,q_radius=4,q_theta=4,q_hist=4)

@@ -95,13 +95,23 @@ size_t dflow_workspace_bytes(const dflow_params *p)
 }
 
 #define CHECK_PTR(x) do { if (!(x)) return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", __func__, #x); } while (0)
-#define CHECK_WS(need) do { if (!d_ws || ws_bytes < (need)) \
-    return dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", __func__, ws_bytes, (size_t)(need)); } while (0)
+// The size of d_ws, then the boundary its stage needs: the widest access a kernel of the stage makes to a region WsCarver hands out
+// (regions start at multiples of 256 bytes from d_ws).  include/dflow.h, Conventions, lists them: 16 for the main-path stages, 8
+// where a region holds doubles or uint64 (bcd_stats.hip, flow_eval.hip, flow_picture.hip's warp, epic.h), 4 for int32 / uint32 /
+// float regions (edges.hip, variational.hip, flow_picture.hip's colour, prior.hip, segments.hip), 2 for pb_edges.hip's uint16
+// plane.  A NULL or short workspace is DFLOW_ENOSPC whatever its alignment, as it always was; the entry points that have
+// always named d_ws among their aligned pointers (bcd_stats, flow_advance, segment_filter) check it there, before its size.
+#define CHECK_WS(align, need) do { \
+    if (!d_ws || ws_bytes < (need)) \
+        return dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", __func__, ws_bytes, (size_t)(need)); \
+    int rc_ws_ = check_aligned(__func__, {{"d_ws", d_ws, (align)}}); if (rc_ws_) return rc_ws_; } while (0)
+// the main-path stages carve float4, int4 and uint4 regions (daisy.hip, knn_mfma.hip, bcd.hip)
+#define WS_ALIGN_MAIN 16
 
 int dflow_daisy(const dflow_params *p, const uint8_t *d_bgr, void *d_descr, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_bgr); CHECK_PTR(d_descr); CHECK_WS(daisy_ws_bytes(p));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_descr); CHECK_WS(WS_ALIGN_MAIN, daisy_ws_bytes(p));
     return launch_daisy(p, d_bgr, d_descr, d_ws, (hipStream_t)stream);
 }
 
@@ -109,7 +119,7 @@ int dflow_daisy_pair(const dflow_params *p, const uint8_t *d_bgr1, const uint8_t
                      void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_WS(daisy_pair_ws_bytes(p));
+    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_WS(WS_ALIGN_MAIN, daisy_pair_ws_bytes(p));
     // the two images run side by side: the outputs must be two planes
     if (d_descr1 == d_descr2) return dflow_set_error(DFLOW_EINVAL, "%s: d_descr1 and d_descr2 are the same plane", __func__);
     return launch_daisy_pair(p, d_bgr1, d_bgr2, d_descr1, d_descr2, d_ws, (hipStream_t)stream);
@@ -123,7 +133,7 @@ int dflow_knn_proposals(const dflow_params *p, const void *d_descr1, const void 
     // DFLOW_FLAG_KNN_EXACT selects the brute-force VALU kernel (same results; used to cross-check the MFMA path)
     if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
         return launch_knn(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, (hipStream_t)stream);
-    CHECK_WS(knn_mfma_ws_bytes(p));
+    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
     return launch_knn_mfma(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream);
 }
 
@@ -136,7 +146,7 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
     CHECK_PTR(h_ms);
     if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
         return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
-    CHECK_WS(knn_mfma_ws_bytes(p));
+    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
     hipEvent_t ev[KNN_MFMA_EVENTS] = {};
     rc = [&]() {
         for (hipEvent_t &e : ev) DFLOW_HIP(hipEventCreate(&e));
@@ -160,7 +170,7 @@ int dflow_knn_screen_stats_n(const dflow_params *p, void *d_ws, size_t ws_bytes,
         return dflow_set_error(DFLOW_EINVAL, "%s: n_stats = %d outside 1..%d", __func__, n_stats, DFLOW_KNN_STATS_ALL_N);
     if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
         return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
-    CHECK_WS(knn_mfma_ws_bytes(p));
+    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
     int64_t all[DFLOW_KNN_STATS_ALL_N];
     rc = knn_mfma_stats(p, d_ws, (hipStream_t)stream, all);
     if (rc == DFLOW_OK) memcpy(h_stats, all, (size_t)n_stats * sizeof(int64_t));
@@ -178,7 +188,7 @@ int dflow_neighbour_proposals(const dflow_params *p, const void *d_descr1, const
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
-    CHECK_WS(neighbour_ws_bytes(p));
+    CHECK_WS(WS_ALIGN_MAIN, neighbour_ws_bytes(p));
     return launch_neighbour(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream);
 }
 
@@ -186,7 +196,7 @@ int dflow_bcd_prepare(const dflow_params *p, const uint32_t *d_proposals, const 
                       void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_WS(bcd_ws_bytes(p));
+    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
     return launch_bcd_prepare(p, d_proposals, d_lcosts, d_nprop, d_ws, (hipStream_t)stream);
 }
 
@@ -194,8 +204,9 @@ int dflow_bcd_phase(const dflow_params *p, const uint32_t *d_proposals, const in
                     int32_t phase, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_WS(bcd_ws_bytes(p));
+    CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
     if (phase < 0 || phase > 3) return dflow_set_error(DFLOW_EINVAL, "phase=%d outside [0,3]", phase);
+    CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
     return launch_bcd_phase(p, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
 
@@ -219,6 +230,9 @@ int dflow_bcd_phase_batch(const dflow_params *p, int32_t npass, const int32_t *c
     if (ws_bytes < bcd_ws_bytes(p)) return dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", __func__, ws_bytes, bcd_ws_bytes(p));
     for (int i = 0; i < npass; i++)
         if (!d_nprop[i] || !d_bestlabels[i] || !d_ws[i]) return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
+    for (int i = 0; i < npass; i++)
+        if ((uintptr_t)d_ws[i] % WS_ALIGN_MAIN)
+            return dflow_set_error(DFLOW_EINVAL, "%s: d_ws[%d] is not %d-byte aligned", __func__, i, WS_ALIGN_MAIN);
     return launch_bcd_phase_batch(p, npass, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
 
@@ -264,7 +278,7 @@ int dflow_bcd_stats_batch(const dflow_params *p, int32_t npass, const uint32_t *
         if (!d_proposals[i] || !d_lcosts[i] || !d_nprop[i] || !d_bestlabels[i])
             return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
     rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
-    CHECK_WS((size_t)npass * bcd_stats_ws_bytes(p->pich, p->picw));
+    CHECK_WS(8, (size_t)npass * bcd_stats_ws_bytes(p->pich, p->picw));
     return launch_bcd_stats_batch(p, npass, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_prev, d_prev, d_stats, d_ws,
                                   (hipStream_t)stream);
 }
@@ -276,7 +290,7 @@ int dflow_bcd_stats(const dflow_params *p, const uint32_t *d_proposals, const fl
     int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
     rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
-    CHECK_WS(bcd_stats_ws_bytes(p->pich, p->picw));
+    CHECK_WS(8, bcd_stats_ws_bytes(p->pich, p->picw));
     return launch_bcd_stats_batch(p, 1, &d_proposals, &d_lcosts, &d_nprop, &d_bestlabels, &d_prev_labels, &d_prev_out, d_stats,
                                   d_ws, (hipStream_t)stream);
 }
@@ -323,7 +337,7 @@ int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, do
     int rc = canny_check_size(__func__, h, w); if (rc) return rc;
     if (!isfinite(low) || !isfinite(high) || low < 0.0 || high < 0.0)
         return dflow_set_error(DFLOW_EINVAL, "%s: thresholds %g, %g must be finite and >= 0", __func__, low, high);
-    CHECK_PTR(d_bgr); CHECK_PTR(d_edges); CHECK_WS(canny_ws_bytes(h, w));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_edges); CHECK_WS(4, canny_ws_bytes(h, w));
     if (low > high) { const double t = low; low = high; high = t; }      // cv::Canny swaps them
     // m <= 4 * 255 * 2: larger thresholds all mean "no candidate" / "no strong pixel"
     const int lo = (int)floor(fmin(low, 1 << 20)), hi = (int)floor(fmin(high, 1 << 20));
@@ -342,7 +356,7 @@ int dflow_pb_edges(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t radius, f
     int rc = canny_check_size(__func__, h, w); if (rc) return rc;
     if (radius < 1 || radius > DFLOW_PB_MAX_RADIUS)
         return dflow_set_error(DFLOW_EINVAL, "%s: radius=%d outside [1,%d]", __func__, radius, DFLOW_PB_MAX_RADIUS);
-    CHECK_PTR(d_bgr); CHECK_PTR(d_strength); CHECK_WS(pb_ws_bytes(h, w));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_strength); CHECK_WS(2, pb_ws_bytes(h, w));
     return launch_pb(h, w, d_bgr, radius, d_strength, d_orient_strength, d_ws, (hipStream_t)stream);
 }
 
@@ -361,7 +375,7 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
     if (!isfinite(k) || !(k > 0.0)) return dflow_set_error(DFLOW_EINVAL, "%s: k=%g must be finite and > 0", __func__, k);
     if (method != DFLOW_EPIC_LA && method != DFLOW_EPIC_NW)
         return dflow_set_error(DFLOW_EINVAL, "%s: unknown method %d", __func__, method);
-    CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow); CHECK_WS(epic_ws_bytes(h, w));
+    CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow); CHECK_WS(8, epic_ws_bytes(h, w));
     return launch_epic(h, w, d_sparse, d_edges, nn, k, method, d_flow, d_seed_of, d_dist, d_lists, d_list_g, d_ws,
                        (hipStream_t)stream);
 }
@@ -388,7 +402,7 @@ int dflow_epic_prefilter(int32_t h, int32_t w, const uint8_t *d_bgr, const float
     if (saliency_th != 0.0 && !d_bgr)
         return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr is NULL with saliency_th=%g (only saliency_th = 0 runs without the image)",
                                __func__, saliency_th);
-    CHECK_PTR(d_sparse_in); CHECK_PTR(d_edges); CHECK_PTR(d_sparse_out); CHECK_WS(epic_prefilter_ws_bytes(h, w));
+    CHECK_PTR(d_sparse_in); CHECK_PTR(d_edges); CHECK_PTR(d_sparse_out); CHECK_WS(8, epic_prefilter_ws_bytes(h, w));
     return launch_epic_prefilter(h, w, d_bgr, d_sparse_in, d_edges, saliency_th, pref_nn, pref_th, k, d_sparse_out, d_reason,
                                  d_saliency, d_estimate, d_ws, (hipStream_t)stream);
 }
@@ -429,7 +443,7 @@ int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t 
     if (p->niter_solver < 1 || p->niter_solver > 10000)
         return dflow_set_error(DFLOW_EINVAL, "%s: niter_solver=%d outside [1,10000]", __func__, p->niter_solver);
     if (p->flags & ~DFLOW_VAR_FLAG_SOR_UNFUSED) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, p->flags);
-    CHECK_WS(var_ws_bytes(h, w));
+    CHECK_WS(4, var_ws_bytes(h, w));
     return launch_var(h, w, d_bgr1, d_bgr2, d_flow_in, p, d_flow_out, d_ws, (hipStream_t)stream);
 }
 
@@ -456,7 +470,7 @@ int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layo
     for (const auto &q : ptrs)
         if ((uintptr_t)q.p % q.align)
             return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", __func__, q.name, (int)q.align);
-    CHECK_WS(eval_ws_bytes(h, w));
+    CHECK_WS(8, eval_ws_bytes(h, w));
     return launch_flow_eval(h, w, d_test, test_layout, d_gt, abs_thresh, flags, d_stats, d_err, d_err_bgr, d_ws, (hipStream_t)stream);
 }
 
@@ -476,7 +490,7 @@ int dflow_flow_color(int32_t h, int32_t w, const float *d_flow, int32_t layout, 
     CHECK_PTR(d_flow); CHECK_PTR(d_bgr);
     // the kernels move four pixels per lane: 16-byte loads of the flow, 12-byte stores of the picture
     rc = check_aligned(__func__, {{"d_flow", d_flow, 16}, {"d_bgr", d_bgr, 4}, {"d_maxrad", d_maxrad, 4}}); if (rc) return rc;
-    CHECK_WS(flow_color_ws_bytes(h, w));
+    CHECK_WS(4, flow_color_ws_bytes(h, w));
     return launch_flow_color(h, w, d_flow, layout, max_flow, d_bgr, d_maxrad, d_ws, (hipStream_t)stream);
 }
 
@@ -502,7 +516,7 @@ int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *
     rc = check_aligned(__func__, {{"d_bgr1", d_bgr1, 4}, {"d_flow", d_flow, 16}, {"d_stats", d_stats, 8}, {"d_warped", d_warped, 4},
                                   {"d_err", d_err, 16}, {"d_err_bgr", d_err_bgr, 4}});
     if (rc) return rc;
-    CHECK_WS(warp_eval_ws_bytes(h, w));
+    CHECK_WS(8, warp_eval_ws_bytes(h, w));
     return launch_warp_eval(h, w, d_bgr1, d_bgr2, d_flow, layout, err_thresh, err_max, flags, d_stats, d_warped, d_err, d_err_bgr,
                             d_ws, (hipStream_t)stream);
 }
@@ -547,7 +561,7 @@ int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout
     if (rc) return rc;
     // a target's winner is read from d_flow after other targets have been written
     if (d_out == d_flow) return dflow_set_error(DFLOW_EINVAL, "%s: d_out and d_flow are the same plane", __func__);
-    CHECK_WS(flow_advance_ws_bytes(h, w));
+    CHECK_WS(4, flow_advance_ws_bytes(h, w));
     return launch_flow_advance(h, w, d_flow, layout, flags, d_out, d_counts, d_ws, (hipStream_t)stream);
 }
 
@@ -644,7 +658,7 @@ int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layo
             if (a < b + planes[j].bytes && b < a + planes[i].bytes)
                 return dflow_set_error(DFLOW_EINVAL, "%s: %s and %s overlap", __func__, planes[j].name, planes[i].name);
         }
-    CHECK_WS(need);
+    CHECK_WS(4, need);
     return launch_segment_filter(h, w, d_flow, layout, thresh, min_size, flags, d_out, d_segment, d_size, d_counts, d_ws,
                                  (hipStream_t)stream);
 }

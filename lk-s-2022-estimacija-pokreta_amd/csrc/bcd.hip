@@ -69,7 +69,10 @@ __device__ static inline void chain_geom(int phase, int chain, int H, int W, int
     else { ty = (H / 2) * 2 - 1 - 2 * chain; tx = 0; ys = 0; xs = 1; len = W; }
 }
 
-// workspace layout (all planes 256-byte aligned), shared by both kernels
+// workspace layout (all planes 256-byte aligned), shared by both kernels.  What dflow_bcd_prepare leaves: every byte of lab and
+// blkA, a function of the proposals alone; of blkBC the slots of the blocks that exist and the pool bases of the waves with "more"
+// labels, the other slots UNWRITTEN; of masks the rows that were allocated, in the order the waves reached the cursor, which
+// differs from run to run (and with it the pool bases in blkBC); back UNWRITTEN: it is the phases' scratch.
 struct BcdPlanes {
     uint8_t *back;                   // back-pointers of the running phase [chain][step][192 threads]
     uint2 *lab;                      // [pix][LP]            {biased flow, data cost}
