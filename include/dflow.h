@@ -656,6 +656,53 @@ int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layo
         int32_t *d_counts  /* NULL or int32[4] */,
         void *d_ws, size_t ws_bytes, void *stream);
 
+/* Motion-compensated frame interpolation (DESIGN.md "Frame interpolation"): the frame at time t, 0 < t < 1, between frame 1
+ * (time 0) and frame 2 (time 1), from the forward flow alone or from both flows.  This build's definition; the reference has no
+ * counterpart.  1 <= h, w <= 8192.  d_bgr1, d_bgr2 (h,w,3) uint8 BGR; d_fwd (frame 1 -> 2) and d_bwd (frame 2 -> 1, NULL: forward
+ * only) are (h,w,.) float32, each in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout (layout_bwd is not looked at without d_bwd).  A
+ * vector is GOOD as in dflow_flow_consistency, a position INSIDE, a picture sampled bilinearly and two colours compared as in
+ * dflow_warp_eval (the same formulas in the same order).  Float32, one IEEE operation per written operation; s = 1.0f - t, formed
+ * once.  n = h*w.
+ *   A. CLAIMANTS.  Source i = y*w + x of frame 1, with (U,V) of d_fwd there, TAKES PART if (U,V) is good, its end point
+ *      (x + U, y + V) is inside, and its place at time t, (tx,ty) = (rintf(x + t*U), rintf(y + t*V)) (ties to even), lies in the
+ *      frame.  Its error e is dflow_warp_eval's err of that pixel: frame 2 sampled at the end point against I1[i].  Its key is
+ *      (uint64)bits(e) << 32 | i (e is a sum of absolute values: non-negative, its bits order like its value) and it carries the
+ *      motion m = (U,V).  With d_bwd, source j of frame 2 with (Ub,Vb) of d_bwd takes part likewise: end point (x + Ub, y + Vb)
+ *      inside, place (rintf(x + s*Ub), rintf(y + s*Vb)), e the same expression with the frames' roles swapped (frame 1 sampled
+ *      against I2[j]), key bits(e) << 32 | (n + j), motion m = (-Ub, -Vb), each float negated.  Every target takes the claimant
+ *      with the smallest key: the smaller error, at equal error frame 1 before frame 2 and the smaller raster index.  d_keys
+ *      (h,w) uint64 is set to all ones by the call, written with 64-bit atomicMin and left holding the winning key, all ones
+ *      where nobody claimed; a second launch resolves the winners into the motion field, [mU, mV, 1] or [0,0,0].  The result does
+ *      not depend on the order of arrival.  Provenance src: 1 (frame 1), 2 (frame 2), 0 (none).
+ *   B. FILL.  fill_rounds Jacobi rounds, 0 <= fill_rounds <= 64: a pixel unknown before the round takes the motion of the first
+ *      of its neighbours known before the round, in the order up (y-1), left, right, down, and becomes [mU, mV, 1] with src = 3.
+ *      Every round is launched whatever the field holds.  The rounds alternate between d_motion and d_motion_tmp, both (h,w,3)
+ *      float32, and the last writes d_motion: after the call d_motion holds the final field for any fill_rounds and d_motion_tmp
+ *      (NULL allowed with fill_rounds = 0, and then untouched) the field before the last round.
+ *   C. RENDER, pixel q = (x,y).  FALLBACK, per channel: v = s*I1[q] + t*I2[q].  An unknown pixel takes the fallback.  A known
+ *      pixel with motion (U,V): side 1 is frame 1 at (x - t*U, y - t*V), side 2 frame 2 at (x + s*U, y + s*V); a side is usable
+ *      when its position is inside, and c1 / c2 is its bilinear sample.  Both usable, d = ((|c1_b-c2_b| + |c1_g-c2_g|) +
+ *      |c1_r-c2_r|) / 3: d <= occl_thresh gives v = s*c1 + t*c2 (BLENDED); otherwise (ONE-SIDED) c1 if src = 1, c2 if src = 2, and
+ *      for src = 3 c1 when t <= 0.5f, else c2.  One side usable: that side (ONE-SIDED).  No side usable: the fallback.
+ *      d_out (h,w,3) uint8 = (int)floorf(v + 0.5f).
+ * Optional outputs (NULL to skip): d_source (h,w) uint8, src after the fill (0, 1, 2 or 3); d_counts int32[8] {from frame 1, from
+ * frame 2, filled, unknown after the fill | blended, one-sided, fallback | claimants that lost}: the first four add up to h*w, so
+ * do the next three, and from frame 1 + from frame 2 + lost is the number of sources that took part; the call zeroes them itself,
+ * on the stream (integer atomics: exact in any order).  Every output is an integer or a float32 chain in a fixed order: two calls
+ * give the same bytes.
+ * There is no d_ws: the scratch is the caller's typed planes d_keys, d_motion and d_motion_tmp, which are outputs as well.
+ * DFLOW_EINVAL before anything is launched: a size or layout outside its range, t not finite or not in (0, 1), fill_rounds
+ * outside [0, 64], occl_thresh not finite or below 0, any flag bit (there are none yet), a NULL d_bgr1, d_bgr2, d_fwd, d_out,
+ * d_keys or d_motion, a NULL d_motion_tmp with fill_rounds > 0, d_keys not 8-byte aligned, a float or int32 plane not 4-byte
+ * aligned, an output equal to an input or to another output.  3 + fill_rounds launches and two memsets.  Asynchronous on
+ * `stream`, allocates nothing, reads nothing back, can be captured into a graph. */
+int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2,
+        const float *d_fwd, int32_t layout_fwd, const float *d_bwd /* NULL: forward only */, int32_t layout_bwd,
+        float t, int32_t fill_rounds, float occl_thresh, uint32_t flags,
+        uint8_t *d_out /* (h,w,3) */, uint64_t *d_keys /* (h,w) */, float *d_motion /* (h,w,3) */,
+        float *d_motion_tmp /* (h,w,3); NULL allowed when fill_rounds == 0 */,
+        uint8_t *d_source /* NULL or (h,w) */, int32_t *d_counts /* NULL or int32[8] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,8 @@ _SIGNATURES = {
     "dflow_flow_consistency": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dflow_segment_filter_workspace_bytes": (_sz, [_i32, _i32]),
     "dflow_segment_filter": (C.c_int, [_i32, _i32, _vp, _i32, _f32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dflow_frame_interp": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _i32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

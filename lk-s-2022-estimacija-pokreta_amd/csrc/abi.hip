@@ -663,6 +663,42 @@ int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layo
                                  (hipStream_t)stream);
 }
 
+int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_fwd, int32_t layout_fwd,
+                       const float *d_bwd, int32_t layout_bwd, float t, int32_t fill_rounds, float occl_thresh, uint32_t flags,
+                       uint8_t *d_out, uint64_t *d_keys, float *d_motion, float *d_motion_tmp, uint8_t *d_source, int32_t *d_counts,
+                       void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout_fwd != DFLOW_EVAL_UVV && layout_fwd != DFLOW_EVAL_DYDX)
+        return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout_fwd %d", __func__, layout_fwd);
+    if (d_bwd && layout_bwd != DFLOW_EVAL_UVV && layout_bwd != DFLOW_EVAL_DYDX)
+        return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout_bwd %d", __func__, layout_bwd);
+    if (!isfinite(t) || !(t > 0.0f && t < 1.0f)) return dflow_set_error(DFLOW_EINVAL, "%s: t=%g must lie in (0, 1)", __func__, (double)t);
+    if (fill_rounds < 0 || fill_rounds > 64) return dflow_set_error(DFLOW_EINVAL, "%s: fill_rounds=%d outside [0,64]", __func__, fill_rounds);
+    if (!isfinite(occl_thresh) || occl_thresh < 0.0f)
+        return dflow_set_error(DFLOW_EINVAL, "%s: occl_thresh=%g must be finite and >= 0", __func__, (double)occl_thresh);
+    if (flags) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_fwd); CHECK_PTR(d_out); CHECK_PTR(d_keys); CHECK_PTR(d_motion);
+    if (fill_rounds > 0 && !d_motion_tmp) return dflow_set_error(DFLOW_EINVAL, "%s: d_motion_tmp is NULL with fill_rounds > 0", __func__);
+    // the keys are updated with 64-bit atomics; every other plane is read and written a float, an int32 or a byte at a time
+    rc = check_aligned(__func__, {{"d_keys", d_keys, 8}, {"d_fwd", d_fwd, 4}, {"d_bwd", d_bwd, 4}, {"d_motion", d_motion, 4},
+                                  {"d_motion_tmp", d_motion_tmp, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // every plane is read or written by lanes other than the pixel's own
+    const struct { const char *name; const void *p; } ins[] = {{"d_bgr1", d_bgr1}, {"d_bgr2", d_bgr2}, {"d_fwd", d_fwd}, {"d_bwd", d_bwd}},
+        outs[] = {{"d_out", d_out}, {"d_keys", d_keys}, {"d_motion", d_motion}, {"d_motion_tmp", d_motion_tmp},
+                  {"d_source", d_source}, {"d_counts", d_counts}};
+    for (size_t i = 0; i < 6; i++) {
+        if (!outs[i].p) continue;
+        for (size_t j = 0; j < 4; j++)
+            if (outs[i].p == ins[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, ins[j].name);
+        for (size_t j = 0; j < i; j++)
+            if (outs[i].p == outs[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, outs[j].name);
+    }
+    return launch_frame_interp(h, w, d_bgr1, d_bgr2, d_fwd, layout_fwd, d_bwd, layout_bwd, t, fill_rounds, occl_thresh, d_out, d_keys,
+                               d_motion, d_motion_tmp, d_source, d_counts, (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -343,3 +343,8 @@ int launch_flow_consistency(int H, int W, const float *fwd, int layout_fwd, cons
 size_t segment_filter_ws_bytes(int H, int W);
 int launch_segment_filter(int H, int W, const float *flow, int layout, float thresh, int min_size, uint32_t flags, float *out,
                           int32_t *segment, int32_t *size, int32_t *counts, void *ws, hipStream_t s);
+// frame_interp.hip: the frame at time t between two frames, 3 + fill_rounds launches whatever the fields hold (arguments
+// validated by the caller); bwd, source and counts may be NULL, motion_tmp too when fill_rounds is 0
+int launch_frame_interp(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *fwd, int layout_fwd, const float *bwd,
+                        int layout_bwd, float t, int fill_rounds, float occl_thresh, uint8_t *out, uint64_t *keys, float *motion,
+                        float *motion_tmp, uint8_t *source, int32_t *counts, hipStream_t s);

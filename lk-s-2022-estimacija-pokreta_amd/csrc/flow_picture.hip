@@ -152,22 +152,12 @@ __device__ __forceinline__ static void warp_pixel(const WarpArgs &A, int x, int 
     err_out = -1.0f; warped_out = 0u; bgr_out = 0u;
     if (!pic_known(U, V, valid)) { acc.n_unknown++; return; }
     const float xs = (float)x + U, ys = (float)y + V;
-    if (!(xs >= 0.0f && xs <= (float)(A.w - 1) && ys >= 0.0f && ys <= (float)(A.h - 1))) { acc.n_outside++; return; }
-    const float xf = floorf(xs), yf = floorf(ys);
-    const float ax = xs - xf, ay = ys - yf;
-    const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, A.w - 1), y1 = min(y0 + 1, A.h - 1);
-    const uint8_t *p00 = A.I2 + ((size_t)y0 * A.w + x0) * 3, *p01 = A.I2 + ((size_t)y0 * A.w + x1) * 3;
-    const uint8_t *p10 = A.I2 + ((size_t)y1 * A.w + x0) * 3, *p11 = A.I2 + ((size_t)y1 * A.w + x1) * 3;
-    float d[3];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {                                       // b, g, r
-        const float top = (1.0f - ax) * (float)p00[c] + ax * (float)p01[c];
-        const float bot = (1.0f - ax) * (float)p10[c] + ax * (float)p11[c];
-        const float wv = (1.0f - ay) * top + ay * bot;
-        d[c] = fabsf(wv - (float)((i1 >> (8 * c)) & 255u));
-        warped_out |= (uint32_t)(int)floorf(wv + 0.5f) << (8 * c);
-    }
-    const float err = ((d[0] + d[1]) + d[2]) / 3.0f;
+    if (!bgr_inside(xs, ys, A.w, A.h)) { acc.n_outside++; return; }
+    float wv[3], own[3];                                                // b, g, r
+    bgr_bilinear(A.I2, A.w, A.h, xs, ys, wv);
+    bgr_entry_floats(i1, own);
+    warped_out = bgr_round_entry(wv);
+    const float err = bgr_mean_abs_diff(wv, own);
     err_out = err;
     acc.n++;
     acc.sum = acc.sum + (double)err;

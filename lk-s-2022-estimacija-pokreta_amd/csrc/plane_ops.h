@@ -1,6 +1,7 @@
 // Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
-// segments.hip, prior.hip): a block's reduction and class counts, and the four-pixel access to a flow plane and a (b, g, r)
-// picture.  They load, pack, reduce or count; every kernel keeps its own loop, launch function and workspace.
+// segments.hip, prior.hip, frame_interp.hip): a block's reduction and class counts, the four-pixel access to a flow plane and a
+// (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce or count;
+// every kernel keeps its own loop, launch function and workspace.
 #pragma once
 #include "dflow_common.h"
 #include "jet_lut.h"
@@ -116,6 +117,51 @@ __device__ __forceinline__ static void bgr_unpack4(const Bgr4 &q, uint32_t (&c)[
 __device__ __forceinline__ static void bgr_store1(uint8_t *__restrict__ bgr, size_t p, uint32_t c)
 {
     bgr[p * 3] = (uint8_t)c; bgr[p * 3 + 1] = (uint8_t)(c >> 8); bgr[p * 3 + 2] = (uint8_t)(c >> 16);
+}
+
+// ---- the bilinear sample of a (h,w,3) picture and the photometric error (include/dflow.h: dflow_warp_eval), float32, one IEEE
+// operation per written operation: what flow_picture.hip's warp check and frame_interp.hip sample and compare with
+// a position INSIDE the frame (a NaN is not)
+__device__ __forceinline__ static bool bgr_inside(float xs, float ys, int w, int h)
+{
+    return xs >= 0.0f && xs <= (float)(w - 1) && ys >= 0.0f && ys <= (float)(h - 1);
+}
+
+// the three channels (b, g, r) of picture I at the inside position (xs, ys)
+__device__ __forceinline__ static void bgr_bilinear(const uint8_t *__restrict__ I, int w, int h, float xs, float ys, float (&wv)[3])
+{
+    const float xf = floorf(xs), yf = floorf(ys);
+    const float ax = xs - xf, ay = ys - yf;
+    const int x0 = (int)xf, y0 = (int)yf, x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const uint8_t *p00 = I + ((size_t)y0 * w + x0) * 3, *p01 = I + ((size_t)y0 * w + x1) * 3;
+    const uint8_t *p10 = I + ((size_t)y1 * w + x0) * 3, *p11 = I + ((size_t)y1 * w + x1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float top = (1.0f - ax) * (float)p00[c] + ax * (float)p01[c];
+        const float bot = (1.0f - ax) * (float)p10[c] + ax * (float)p11[c];
+        wv[c] = (1.0f - ay) * top + ay * bot;
+    }
+}
+
+// ((|a_b - b_b| + |a_g - b_g|) + |a_r - b_r|) / 3
+__device__ __forceinline__ static float bgr_mean_abs_diff(const float (&a)[3], const float (&b)[3])
+{
+    return ((fabsf(a[0] - b[0]) + fabsf(a[1] - b[1])) + fabsf(a[2] - b[2])) / 3.0f;
+}
+
+// the channels of the entry b | g << 8 | r << 16 as floats, and (int)floorf(v + 0.5f) per channel back into an entry
+__device__ __forceinline__ static void bgr_entry_floats(uint32_t e, float (&v)[3])
+{
+#pragma unroll
+    for (int c = 0; c < 3; c++) v[c] = (float)((e >> (8 * c)) & 255u);
+}
+
+__device__ __forceinline__ static uint32_t bgr_round_entry(const float (&v)[3])
+{
+    uint32_t e = 0u;
+#pragma unroll
+    for (int c = 0; c < 3; c++) e |= (uint32_t)(int)floorf(v[c] + 0.5f) << (8 * c);
+    return e;
 }
 
 // the colour table of both error pictures (flow_eval.hip, flow_picture.hip)

@@ -802,6 +802,87 @@ def segment_filter(flow, thresh, min_size, keep_singletons=False, segments=False
     return ret if len(ret) > 1 else ret[0]
 
 
+FRAME_INTERP_COUNTS = ("from1", "from2", "filled", "unknown", "blended", "one_sided", "fallback", "lost")
+
+
+def _frame_interp_gate(fn, img1, img2, fwd, bwd, fill_rounds, occl_thresh):
+    """The inputs of frame_interp / frame_sequence through the input gate, on one device: (H, W, dev, img1, img2, fwd, bwd)."""
+    fwd = _check(fwd, fn, "fwd", torch.float32, (None, None, (2, 3)))
+    H, W, _ = fwd.shape
+    img1 = _check(img1, fn, "img1: the images", torch.uint8, (H, W, 3))
+    img2 = _check(img2, fn, "img2: the images", torch.uint8, (H, W, 3))
+    if bwd is not None:
+        bwd = _check(bwd, fn, "bwd", torch.float32, (H, W, (2, 3)))
+    if not (isinstance(fill_rounds, (int, np.integer)) and 0 <= fill_rounds <= 64):
+        raise ValueError("%s: fill_rounds must be an int in [0, 64], got %r" % (fn, fill_rounds))
+    if not (np.isfinite(occl_thresh) and occl_thresh >= 0):
+        raise ValueError("%s: occl_thresh must be finite and >= 0, got %r" % (fn, occl_thresh))
+    dev = _device_of(fwd, img1, img2, *([bwd] if bwd is not None else []))
+    ts = _on(dev, *([img1, img2, fwd] + ([bwd] if bwd is not None else [])))
+    return H, W, dev, ts[0], ts[1], ts[2], ts[3] if bwd is not None else None
+
+
+def _frame_interp_call(H, W, dev, img1, img2, fwd, bwd, t, fill_rounds, occl_thresh, planes, want_source, want_counts):
+    """One dflow_frame_interp into new outputs, with the scratch planes (keys, motion, motion_tmp) of the caller."""
+    keys, mot, tmp = planes
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    src, cnt = _out(want_source, (H, W), torch.uint8, dev), _out(want_counts, 8, torch.int32, dev)
+    _lib.call("dflow_frame_interp", H, W, img1.data_ptr(), img2.data_ptr(), fwd.data_ptr(), _layout(fwd), _ptr(bwd),
+              _layout(bwd) if bwd is not None else 0, _frame_time(t), int(fill_rounds), float(occl_thresh), 0, out.data_ptr(), keys.data_ptr(),
+              mot.data_ptr(), _ptr(tmp), _ptr(src), _ptr(cnt), _lib.stream(dev))
+    return out, src, cnt
+
+
+def _frame_time(t):
+    """t as the float32 the library receives; ValueError unless that lies in (0, 1)."""
+    t = float(np.float32(t))
+    if not (np.isfinite(t) and 0.0 < t < 1.0):
+        raise ValueError("frame_interp: t must lie in (0, 1) as a float32, got %r" % (t,))
+    return t
+
+
+def _frame_interp_planes(H, W, dev, fill_rounds):
+    return (torch.empty((H, W), dtype=torch.int64, device=dev), torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+            _out(fill_rounds > 0, (H, W, 3), torch.float32, dev))
+
+
+def frame_interp(img1, img2, fwd, bwd=None, t=0.5, fill_rounds=8, occl_thresh=30.0, motion=False, source=False, counts=False):
+    """The frame at time t, 0 < t < 1, between img1 (time 0) and img2 (time 1) (dflow_frame_interp, DESIGN.md "Frame
+    interpolation"): every pixel of img1 is carried t of the way along its forward vector, with bwd every pixel of img2 1 - t
+    of the way along its backward vector; where several land on one pixel the one whose two ends look most alike stays;
+    pixels nothing lands on take a neighbour's motion in up to fill_rounds rounds; then both frames are sampled along each
+    pixel's motion and blended s*c1 + t*c2, or, where the two samples differ by more than occl_thresh grey levels, only the
+    frame the motion came from is used.  A pixel without a motion is the plain blend of the two frames.  img1, img2: (H,W,3)
+    uint8 BGR; fwd, bwd: (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid], each on its own; the last dimension says
+    which.  Device tensors or host arrays; host data is uploaded to the current device.  Returns the (H,W,3) uint8 device
+    tensor, or a tuple in the order (frame[, motion][, source][, counts]): motion=True adds the (H,W,3) float32 field [mU, mV,
+    known] after the fill, source=True the (H,W) uint8 plane 0 none / 1 from img1 / 2 from img2 / 3 filled, counts=True the
+    int32[8] device tensor FRAME_INTERP_COUNTS.  Runs on torch's current stream and does not wait for it."""
+    _frame_time(t)
+    H, W, dev, img1, img2, fwd, bwd = _frame_interp_gate("frame_interp", img1, img2, fwd, bwd, fill_rounds, occl_thresh)
+    planes = _frame_interp_planes(H, W, dev, fill_rounds)
+    out, src, cnt = _frame_interp_call(H, W, dev, img1, img2, fwd, bwd, t, fill_rounds, occl_thresh, planes, source, counts)
+    ret = tuple(x for x in (out, planes[1] if motion else None, src, cnt) if x is not None)
+    return ret if len(ret) > 1 else out
+
+
+def frame_sequence(img1, img2, fwd, bwd=None, n=1, fill_rounds=8, occl_thresh=30.0, counts=False):
+    """The n frames at t = k / (n + 1), k = 1..n, between img1 and img2: n calls of dflow_frame_interp that share one set of
+    scratch planes (t is rounded to float32 once, as frame_interp does, so every frame equals that of a single call).
+    Arguments as frame_interp.  Returns the list of (H,W,3) uint8 device tensors, with counts=True the pair (frames, list of
+    int32[8] device tensors).  Runs on torch's current stream and does not wait for it."""
+    if not (isinstance(n, (int, np.integer)) and 1 <= n <= 1024):
+        raise ValueError("frame_sequence: n must be an int in [1, 1024], got %r" % (n,))
+    H, W, dev, img1, img2, fwd, bwd = _frame_interp_gate("frame_sequence", img1, img2, fwd, bwd, fill_rounds, occl_thresh)
+    planes = _frame_interp_planes(H, W, dev, fill_rounds)
+    frames, cnts = [], []
+    for k in range(1, n + 1):
+        out, _, cnt = _frame_interp_call(H, W, dev, img1, img2, fwd, bwd, k / (n + 1), fill_rounds, occl_thresh, planes, False, counts)
+        frames.append(out)
+        cnts.append(cnt)
+    return (frames, cnts) if counts else frames
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels

@@ -48,6 +48,11 @@ reference, is the reference's check with its transposed lookup (pipeline.fb_cons
 sparse_field_<pair>.npy, parovi_<pair>.txt, --prefilter, --epic and --eval's "sparse" row.  One line per pair gives the four
 counts, and the header of eval.json gains "segments": [MIN, T].  Both values must be given.  Without it nothing is launched
 that was not launched before.
+--midframe writes mid_<pair>.png, the frame at t = 0.5 between each pair's two images, from the pair's forward and backward flows
+(pipeline.frame_interp, DESIGN.md "Frame interpolation"; --mid-fill-rounds K and --mid-occl-thresh D set its fill rounds and
+occlusion threshold, default 8 and 30).  One line per pair gives the eight counts and the PSNR of that frame and of the plain
+blend (I1 + I2) / 2 against the true middle frame (synth.make_mid, over the pixels whose source lies inside the first image), and
+midframe.json in DIR holds the per-pair rows.  Without it nothing is launched that was not launched before.
 """
 import argparse
 import importlib
@@ -87,6 +92,10 @@ def parser():
                     help="also write flowcolor_NN.png (colour-wheel picture of the forward flow) and, with --epic, flowcolor_epic_NN.png")
     ap.add_argument("--photo", action="store_true",
                     help="warp each pair's second image by the forward and (with --epic) final flow; prints the photometric error, writes photo.json")
+    ap.add_argument("--midframe", action="store_true",
+                    help="also write mid_NN.png, the frame at t = 0.5 from the pair's two flows; prints its PSNR, writes midframe.json")
+    ap.add_argument("--mid-fill-rounds", type=int, default=None, metavar="K", help="with --midframe: fill rounds, 0..64 (default 8)")
+    ap.add_argument("--mid-occl-thresh", type=float, default=None, metavar="D", help="with --midframe: occlusion threshold (default 30)")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
     ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="with --pyramid: sweeps of the coarse levels (default: --bcd-times)")
@@ -112,6 +121,53 @@ def segments_arg(tokens):
     except ValueError:
         parser().error("--segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (tokens,))
     return min_size, thresh
+
+
+def midframe_args(a):
+    """--mid-fill-rounds and --mid-occl-thresh with their defaults; exits with status 2 if one is given without --midframe or lies
+    outside its range."""
+    if not a.midframe and (a.mid_fill_rounds is not None or a.mid_occl_thresh is not None):
+        parser().error("--mid-fill-rounds and --mid-occl-thresh need --midframe")
+    rounds = 8 if a.mid_fill_rounds is None else a.mid_fill_rounds
+    occl = 30.0 if a.mid_occl_thresh is None else a.mid_occl_thresh
+    if not 0 <= rounds <= 64:
+        parser().error("--mid-fill-rounds must lie in [0, 64], got %d" % rounds)
+    if not (np.isfinite(occl) and occl >= 0):
+        parser().error("--mid-occl-thresh must be finite and >= 0, got %r" % occl)
+    return rounds, occl
+
+
+def psnr(a, b, mask):
+    """10 log10(255^2 / MSE) of two uint8 pictures over the pixels of mask (all channels); None when nothing is compared, inf
+    when they are equal there."""
+    d = a[mask].astype(np.float64) - b[mask].astype(np.float64)
+    if d.size == 0:
+        return None
+    mse = float(np.mean(d * d))
+    return float("inf") if mse == 0 else 10.0 * np.log10(255.0 ** 2 / mse)
+
+
+def midframe_pair(s, pair, fwd, bwd, rows):
+    """--midframe of one pair: mid_<pair>.png, its printed line and its row."""
+    pipeline, synth, flowio = mod("pipeline"), mod("synth"), mod("flowio")
+    seed = synth.pair_seed(pair, 0)
+    if pair in s.images:                        # this rank's own pair: already on the device
+        on_dev = s.images[pair]
+        img1, img2 = (x.cpu().numpy() for x in on_dev)
+    else:
+        on_dev = img1, img2 = synth.make_pair(s.H, s.W, seed=seed)[:2]
+    frame, counts = pipeline.frame_interp(on_dev[0], on_dev[1], fwd, bwd, t=0.5, fill_rounds=s.a.mid_fill_rounds,
+                                          occl_thresh=s.a.mid_occl_thresh, counts=True)
+    frame, counts = frame.cpu().numpy(), counts.cpu().tolist()
+    flowio.write_png8(os.path.join(s.a.out, "mid_%02d.png" % pair), frame)
+    truth, mask = synth.make_mid(s.H, s.W, seed=seed, t=0.5)
+    half = np.float32(0.5)
+    blend = np.floor(half * img1.astype(np.float32) + half * img2.astype(np.float32) + half).astype(np.uint8)
+    row = dict(pair=pair, counts=dict(zip(pipeline.FRAME_INTERP_COUNTS, counts)), n=int(mask.sum()),
+               psnr=psnr(frame, truth, mask), psnr_blend=psnr(blend, truth, mask))
+    rows.append(row)
+    print("pair %d: middle frame %s; PSNR %.2f dB, plain blend %.2f dB, over %d px"
+          % (pair, " ".join("%s=%d" % kv for kv in row["counts"].items()), row["psnr"], row["psnr_blend"], row["n"]))
 
 
 def stats_row(st, fields):
@@ -362,6 +418,7 @@ def write_out(s, flows):
                   % (name, len(h) - 1, h[0]["energy"], h[-1]["energy"], h[-1]["n_changed"]))
     eval_rows, eval_totals = [], {}
     photo_rows, photo_totals = [], {}
+    mid_rows = []
     for pair in range(a.pairs):
         fwd = flows[2 * pair]
         sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, flows[2 * pair + 1])
@@ -377,9 +434,15 @@ def write_out(s, flows):
         if a.photo:
             tally(PHOTO, pair, [("fwd", fwd)] + dense, lambda field, **kw: pipeline.warp_eval(img1, img2, field, **kw),
                   photo_rows, photo_totals, s.dev)
+        if a.midframe:
+            midframe_pair(s, pair, fwd, flows[2 * pair + 1], mid_rows)
     head = {"size": [H, W], "bcd_times": a.bcd_times}
     if a.pyramid > 1:
         head["pyramid"] = a.pyramid
+    if a.midframe:
+        import json
+        with open(os.path.join(a.out, "midframe.json"), "w") as f:
+            json.dump(dict(head, t=0.5, fill_rounds=a.mid_fill_rounds, occl_thresh=a.mid_occl_thresh, pairs=mid_rows), f, indent=1)
     if a.photo:
         write_tally(os.path.join(a.out, "photo.json"), dict(head, err_thresh=10.0, err_max=30.0), PHOTO, photo_rows, photo_totals)
     if a.eval:
@@ -395,6 +458,7 @@ def main(argv=None):
     a.epic = a.epic or a.epic_refine or a.prefilter
     if a.segments is not None:
         a.segments = segments_arg(a.segments)
+    a.mid_fill_rounds, a.mid_occl_thresh = midframe_args(a)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)

@@ -110,12 +110,24 @@ def make_pair(H, W, seed=0, amp_x=40.0, amp_y=20.0, noise=2.0, style="dense"):
     """Returns (img1, img2, gt) with img uint8 (H,W,3) BGR and gt (H,W,2) float64 [dy,dx] = forward_gt: the true flow of
     image 1's pixels (where the warp leaves the image the field is still defined; the clipped source has no match there).
     style "dense": texture everywhere (the best case for the kNN screen); "low_texture": low_texture_regions() on top."""
+    rng, img1, sig = _first_image(H, W, seed, noise, style)
+    gt = gt_flow(H, W, seed, amp_x, amp_y)
+    img2 = _warp(img1, gt) + rng.normal(0.0, 1.0, img1.shape) * _warp(sig, gt)
+    return _to_u8(img1), _to_u8(img2), forward_gt(H, W, seed, amp_x, amp_y)
+
+
+def _to_u8(a):
+    return np.clip(np.rint(a), 0, 255).astype(np.uint8)
+
+
+def _first_image(H, W, seed, noise, style):
+    """The first image of pair `seed` before it is rounded to uint8, (H,W,3) float64, with the generator that drew it (make_pair
+    draws the second image's noise from it next) and the noise level per pixel, (H,W,1)."""
     if style not in STYLES:
         raise ValueError("style must be one of %s" % (STYLES,))
     rng = np.random.default_rng(seed)
     chans = [_smooth_noise(rng, H, W) for _ in range(3)]
     img1 = np.stack(chans, axis=-1) * 255.0
-    gt = gt_flow(H, W, seed, amp_x, amp_y)
     sig = np.full((H, W, 1), float(noise))
     if style == "low_texture":
         reg = low_texture_regions(H, W, seed)[..., None]
@@ -127,9 +139,28 @@ def make_pair(H, W, seed=0, amp_x=40.0, amp_y=20.0, noise=2.0, style="dense"):
         img1 = np.where(reg == 3, blurred, img1)
         img1 = np.where(reg == 4, pattern, img1)
         sig = np.where(reg == 2, 0.4, sig)
-    img2 = _warp(img1, gt) + rng.normal(0.0, 1.0, img1.shape) * _warp(sig, gt)
-    to_u8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)
-    return to_u8(img1), to_u8(img2), forward_gt(H, W, seed, amp_x, amp_y)
+    return rng, img1, sig
+
+
+def make_mid(H, W, seed=0, t=0.5, amp_x=40.0, amp_y=20.0, style="dense", iters=60):
+    """The true frame at time t, 0 <= t <= 1, of the pair make_pair(H, W, seed, amp_x, amp_y, noise=0, style) returns, when every
+    pixel p of image 1 moves along its flow f(p) = forward_gt at constant velocity: mid(q) = img1(p) for the p with
+    p + t f(p) = q.  Returns (mid, mask): mid (H,W,3) uint8, mask (H,W) bool, true where that p lies inside image 1 (elsewhere
+    the clamped source has no meaning).  With r = p + f(p), the place in image 2, f(p) = g(r) and q = r - (1 - t) g(r): r is the
+    fixed point of r <- q + (1 - t) g(r), iterated on the analytic field as forward_gt does, and p = q - t g(r).  t = 0 gives
+    image 1 and t = 1 image 2 without its noise."""
+    if not 0.0 <= t <= 1.0:
+        raise ValueError("make_mid: t must lie in [0, 1], got %r" % (t,))
+    _, img1, _ = _first_image(H, W, seed, 0.0, style)
+    g = _field(seed, amp_x, amp_y)
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    gy = np.zeros((H, W)); gx = np.zeros((H, W))
+    for _ in range(iters):
+        gy, gx = g((yy + (1.0 - t) * gy) / H, (xx + (1.0 - t) * gx) / W)
+    d = np.stack([t * gy, t * gx], axis=-1)
+    py, px = yy - d[..., 0], xx - d[..., 1]
+    mask = (py >= 0) & (py <= H - 1) & (px >= 0) & (px <= W - 1)
+    return _to_u8(_warp(img1, d)), mask
 
 
 def pair_seed(pair_idx, backward):
