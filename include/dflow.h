@@ -703,6 +703,43 @@ int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_
         float *d_motion_tmp /* (h,w,3); NULL allowed when fill_rounds == 0 */,
         uint8_t *d_source /* NULL or (h,w) */, int32_t *d_counts /* NULL or int32[8] */, void *stream);
 
+/* Edge-aware weighted median filter of a flow field (DESIGN.md "Weighted median filter"): every pixel gets the weighted median,
+ * per component, of the good vectors in the (2 radius + 1)^2 window around it, weighted by distance and by the similarity of a
+ * guide image (the non-local term of Sun, Roth and Black; with the guide the joint-bilateral median).  This build's definition;
+ * the reference has no counterpart.  1 <= h, w <= 8192, 1 <= radius <= 8.  d_flow is (h,w,.) float32 in DFLOW_EVAL_UVV or
+ * DFLOW_EVAL_DYDX layout; a vector is GOOD as in dflow_flow_consistency.  Everything below is an integer or a copy of input bits:
+ * the result depends on no order, and two calls give the same bytes.
+ *   SAMPLES of pixel p = (y,x): the good pixels q = (y+dy, x+dx), |dy|, |dx| <= radius, inside the frame (the window is clipped,
+ *     not padded); p itself is a sample when it is good.
+ *   WEIGHT  (uint32) wq = S * C.  S = d_wspace[|dy|*(radius+1) + |dx|], or 1 without d_wspace.  C = d_wcolor[|b_p - b_q| +
+ *     |g_p - g_q| + |r_p - r_q|] with the channels of d_bgr (h,w,3) uint8, or 1 without d_wcolor.  W = the sum of the wq, at most
+ *     289 * 255 * 255, so 2 W fits 32 bits.  A sample of weight 0 does not take part.
+ *   KEY     of a float with bits b: b ^ 0xFFFFFFFF if the sign bit is set, else b | 0x80000000: a total order in which -0 < +0.
+ *   MEDIAN  the lower weighted median, U and V each on its own: the value mU (mV) of the sample with the smallest key k such that
+ *     2 * sum{wq : key_q <= k} >= W.  The output carries that sample's own bits.
+ *   OUTPUT  d_out (h,w,3) float32 [U,V,valid].  W == 0: [0,0,0].  Otherwise, with no flag, [mU, mV, 1] whether p is good or not
+ *     (holes are filled).  DFLOW_WMED_KEEP_HOLES: a p that is not good gets [0,0,0].  DFLOW_WMED_REJECT: a p that is not good gets
+ *     [0,0,0]; a good p keeps its own [U,V,1] bits if fabsf(U - mU) + fabsf(V - mV) <= reject_thresh and becomes [0,0,0]
+ *     otherwise (float32, one IEEE operation per written operation; a difference that overflows rejects): surviving vectors are
+ *     never altered.  reject_thresh is looked at only under DFLOW_WMED_REJECT.
+ * d_counts (NULL to skip) int32[4] {good inputs, valid outputs, filled, altered}: filled counts the p that are not good and have a
+ * valid output, altered the good p whose output U or V bits differ from their own or whose output is [0,0,0]; the call zeroes them
+ * itself, on the stream (integer atomics: exact in any order).
+ * There is no workspace: the kernel needs no global scratch.
+ * DFLOW_EINVAL before anything is launched: a size, layout or radius outside its range, an unknown flag bit, reject_thresh not
+ * finite or below 0 under DFLOW_WMED_REJECT, a NULL d_flow or d_out, d_bgr and d_wcolor not both NULL or both given, a float or
+ * int32 plane not 4-byte aligned, an output equal to an input (neighbours are read) or to the other output.  One launch and the
+ * memset of the counts.  Asynchronous on `stream`, allocates nothing, reads nothing back, can be captured into a graph. */
+#define DFLOW_WMED_KEEP_HOLES 1u
+#define DFLOW_WMED_REJECT 2u
+int dflow_flow_wmedian(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        const uint8_t *d_bgr    /* guide (h,w,3); NULL iff d_wcolor is NULL */,
+        int32_t radius,
+        const uint8_t *d_wspace /* NULL (all ones) or uint8[(radius+1)*(radius+1)], [|dy|*(radius+1)+|dx|] */,
+        const uint8_t *d_wcolor /* NULL (all ones) or uint8[766], indexed by |db|+|dg|+|dr| */,
+        float reject_thresh, uint32_t flags,
+        float *d_out /* (h,w,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[4] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ PRIOR_SEED_LABELS = 1       # DFLOW_PRIOR_SEED_LABELS
 ADVANCE_NEGATE = 1          # DFLOW_ADVANCE_NEGATE
 FBC_BILINEAR = 1            # DFLOW_FBC_BILINEAR
 SEG_KEEP_SINGLETONS = 1     # DFLOW_SEG_KEEP_SINGLETONS
+WMED_KEEP_HOLES, WMED_REJECT = 1, 2     # DFLOW_WMED_KEEP_HOLES, DFLOW_WMED_REJECT
 
 
 class DflowError(RuntimeError):
@@ -115,6 +116,7 @@ _SIGNATURES = {
     "dflow_segment_filter": (C.c_int, [_i32, _i32, _vp, _i32, _f32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dflow_frame_interp": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _f32, _i32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
+    "dflow_flow_wmedian": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, C.c_uint32, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES)
 

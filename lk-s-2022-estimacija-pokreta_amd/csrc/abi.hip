@@ -699,6 +699,34 @@ int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_
                                d_motion, d_motion_tmp, d_source, d_counts, (hipStream_t)stream);
 }
 
+int dflow_flow_wmedian(int32_t h, int32_t w, const float *d_flow, int32_t layout, const uint8_t *d_bgr, int32_t radius,
+                       const uint8_t *d_wspace, const uint8_t *d_wcolor, float reject_thresh, uint32_t flags, float *d_out,
+                       int32_t *d_counts, void *stream)
+{
+    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    if (radius < 1 || radius > 8) return dflow_set_error(DFLOW_EINVAL, "%s: radius=%d outside [1,8]", __func__, radius);
+    if (flags & ~(DFLOW_WMED_KEEP_HOLES | DFLOW_WMED_REJECT)) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    if ((flags & DFLOW_WMED_REJECT) && (!isfinite(reject_thresh) || reject_thresh < 0.0f))
+        return dflow_set_error(DFLOW_EINVAL, "%s: reject_thresh=%g must be finite and >= 0", __func__, (double)reject_thresh);
+    CHECK_PTR(d_flow); CHECK_PTR(d_out);
+    if (!d_bgr != !d_wcolor) return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr and d_wcolor must both be NULL or both be given", __func__);
+    rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a pixel's neighbours are read after other pixels have been written
+    const struct { const char *name; const void *p; } ins[] = {{"d_flow", d_flow}, {"d_bgr", d_bgr}, {"d_wspace", d_wspace}, {"d_wcolor", d_wcolor}},
+        outs[] = {{"d_out", d_out}, {"d_counts", d_counts}};
+    for (size_t i = 0; i < 2; i++) {
+        if (!outs[i].p) continue;
+        for (size_t j = 0; j < 4; j++)
+            if (outs[i].p == ins[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, ins[j].name);
+        for (size_t j = 0; j < i; j++)
+            if (outs[i].p == outs[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, outs[j].name);
+    }
+    return launch_flow_wmedian(h, w, d_flow, layout, d_bgr, radius, d_wspace, d_wcolor, reject_thresh, flags, d_out, d_counts,
+                               (hipStream_t)stream);
+}
+
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)
 {
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");

@@ -348,3 +348,7 @@ int launch_segment_filter(int H, int W, const float *flow, int layout, float thr
 int launch_frame_interp(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, const float *fwd, int layout_fwd, const float *bwd,
                         int layout_bwd, float t, int fill_rounds, float occl_thresh, uint8_t *out, uint64_t *keys, float *motion,
                         float *motion_tmp, uint8_t *source, int32_t *counts, hipStream_t s);
+// flow_wmedian.hip: the weighted median filter of a flow field, one launch (arguments validated by the caller); bgr and wcolor
+// are both NULL (unguided) or both given, wspace and counts may be NULL
+int launch_flow_wmedian(int H, int W, const float *flow, int layout, const uint8_t *bgr, int radius, const uint8_t *wspace,
+                        const uint8_t *wcolor, float reject_thresh, uint32_t flags, float *out, int32_t *counts, hipStream_t s);

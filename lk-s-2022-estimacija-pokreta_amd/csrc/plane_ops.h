@@ -1,5 +1,5 @@
 // Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
-// segments.hip, prior.hip, frame_interp.hip): a block's reduction and class counts, the four-pixel access to a flow plane and a
+// segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip): a block's reduction and class counts, the four-pixel access to a flow plane and a
 // (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce or count;
 // every kernel keeps its own loop, launch function and workspace.
 #pragma once

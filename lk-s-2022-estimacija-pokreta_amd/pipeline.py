@@ -883,6 +883,97 @@ def frame_sequence(img1, img2, fwd, bwd=None, n=1, fill_rounds=8, occl_thresh=30
     return (frames, cnts) if counts else frames
 
 
+FLOW_WMEDIAN_COUNTS = ("good", "valid", "filled", "altered")
+WMEDIAN_NCOLOR = 766                    # |db| + |dg| + |dr| = 0 .. 765
+_wmedian_uploaded = {}                  # (device, radius, bytes of space, bytes of colour) -> the two device tensors
+
+
+def wmedian_tables(radius, sigma_space=None, sigma_color=None):
+    """The weight tables of flow_wmedian as (space, color), each a numpy uint8 array or None for a None sigma (all ones), computed
+    in float64: space[|dy|,|dx|] = floor(255 exp(-(dy^2 + dx^2) / (2 sigma_space^2)) + 0.5), (radius+1, radius+1);
+    color[d] = floor(255 exp(-d / (3 sigma_color)) + 0.5), d = |db| + |dg| + |dr| = 0..765 (sigma_color is in grey levels per
+    channel).  ValueError for a radius outside 1..8 or a sigma that is not finite or not positive."""
+    if not (isinstance(radius, (int, np.integer)) and 1 <= radius <= 8):
+        raise ValueError("wmedian_tables: radius must be an int in [1, 8], got %r" % (radius,))
+    for name, s in (("sigma_space", sigma_space), ("sigma_color", sigma_color)):
+        if s is not None and not (isinstance(s, (int, float, np.integer, np.floating)) and np.isfinite(s) and s > 0):
+            raise ValueError("wmedian_tables: %s must be finite and > 0, got %r" % (name, s))
+    space = color = None
+    if sigma_space is not None:
+        d2 = np.arange(radius + 1, dtype=np.float64) ** 2
+        space = np.floor(255.0 * np.exp(-(d2[:, None] + d2[None, :]) / (2.0 * float(sigma_space) ** 2)) + 0.5).astype(np.uint8)
+    if sigma_color is not None:
+        color = np.floor(255.0 * np.exp(-np.arange(WMEDIAN_NCOLOR, dtype=np.float64) / (3.0 * float(sigma_color))) + 0.5).astype(np.uint8)
+    return space, color
+
+
+def _wmedian_tables_arg(radius, tables, guided):
+    """tables=(space, color) checked -> contiguous uint8 arrays or None; an unguided call drops the colour table."""
+    if not (isinstance(tables, (tuple, list)) and len(tables) == 2):
+        raise ValueError("flow_wmedian: tables must be the pair (space, color), got %r" % (tables,))
+    out = []
+    for name, t, n in (("space", tables[0], (radius + 1) ** 2), ("color", tables[1], WMEDIAN_NCOLOR)):
+        if t is not None:
+            t = np.ascontiguousarray(t)
+            if t.dtype != np.uint8 or t.size != n:
+                raise ValueError("flow_wmedian: the %s table must be uint8 with %d entries, got %s %s" % (name, n, t.shape, t.dtype))
+        out.append(t)
+    if guided and out[1] is None:
+        out[1] = np.ones(WMEDIAN_NCOLOR, np.uint8)
+    return out[0], out[1] if guided else None
+
+
+def flow_wmedian(flow, img=None, radius=3, sigma_space=None, sigma_color=10.0, iterations=1, keep_holes=False, reject=None,
+                 counts=False, tables=None):
+    """The edge-aware weighted median filter of a flow field (dflow_flow_wmedian, DESIGN.md "Weighted median filter"): every
+    pixel gets, per component, the lower weighted median of the good vectors in the (2 radius + 1)^2 window around it, the
+    weight of a neighbour being space[|dy|,|dx|] * color[colour distance to the pixel in img] (wmedian_tables).  Holes are
+    filled from their windows.  flow is (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; img the (H,W,3) uint8 BGR guide
+    or None (unguided: sigma_color is ignored).  Device tensors or host arrays; host data is uploaded to the current device.
+    sigma_space=None weighs every distance alike; tables=(space, color) overrides both sigmas.  iterations (1..16) passes
+    ping-pong between two buffers.  keep_holes=True leaves a pixel without a good vector [0,0,0].  reject=T filters nothing:
+    a good vector stays bit for bit if |U - mU| + |V - mV| <= T and becomes [0,0,0] otherwise (one pass only).  Returns the
+    (H,W,3) float32 [U,V,valid] device tensor, with counts=True the pair (out, int32[4] device tensor FLOW_WMEDIAN_COUNTS of
+    the last pass).  Uploaded tables are kept per device and parameter set.  Runs on torch's current stream and does not wait
+    for it."""
+    flow = _check(flow, "flow_wmedian", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    guided = img is not None
+    if guided:
+        img = _check(img, "flow_wmedian", "img", torch.uint8, (H, W, 3))
+    if not (isinstance(radius, (int, np.integer)) and 1 <= radius <= 8):
+        raise ValueError("flow_wmedian: radius must be an int in [1, 8], got %r" % (radius,))
+    if not (isinstance(iterations, (int, np.integer)) and 1 <= iterations <= 16):
+        raise ValueError("flow_wmedian: iterations must be an int in [1, 16], got %r" % (iterations,))
+    flags, thresh = _lib.WMED_KEEP_HOLES if keep_holes else 0, 0.0
+    if reject is not None:
+        thresh = float(reject)
+        if not (np.isfinite(thresh) and thresh >= 0):
+            raise ValueError("flow_wmedian: reject must be finite and >= 0, got %r" % (reject,))
+        if iterations > 1:
+            raise ValueError("flow_wmedian: reject cannot be combined with iterations > 1")
+        flags |= _lib.WMED_REJECT
+    if tables is None:
+        tables = wmedian_tables(int(radius), sigma_space, sigma_color if guided else None)
+    space, color = _wmedian_tables_arg(int(radius), tables, guided)
+    dev = _device_of(flow, *([img] if guided else []))
+    ts = _on(dev, flow, *([img] if guided else []))
+    flow, img = ts[0], ts[1] if guided else None
+    key = (dev, int(radius), None if space is None else space.tobytes(), None if color is None else color.tobytes())
+    if key not in _wmedian_uploaded:
+        _wmedian_uploaded[key] = tuple(None if t is None else torch.from_numpy(t.reshape(-1)).to(dev) for t in (space, color))
+    dspace, dcolor = _wmedian_uploaded[key]
+    cnt = _out(counts, 4, torch.int32, dev)
+    bufs = [torch.empty((H, W, 3), dtype=torch.float32, device=dev) for _ in range(min(int(iterations), 2))]
+    src = flow
+    for it in range(int(iterations)):
+        out = bufs[it & 1]
+        _lib.call("dflow_flow_wmedian", H, W, src.data_ptr(), _layout(src), _ptr(img), int(radius), _ptr(dspace), _ptr(dcolor), thresh,
+                  flags, out.data_ptr(), _ptr(cnt), _lib.stream(dev))
+        src = out
+    return (src, cnt) if counts else src
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels

@@ -53,6 +53,13 @@ that was not launched before.
 occlusion threshold, default 8 and 30).  One line per pair gives the eight counts and the PSNR of that frame and of the plain
 blend (I1 + I2) / 2 against the true middle frame (synth.make_mid, over the pixels whose source lies inside the first image), and
 midframe.json in DIR holds the per-pair rows.  Without it nothing is launched that was not launched before.
+--wmedian R writes wmedian_<pair>.flo, each pair's forward flow through the weighted median filter of radius R guided by the
+pair's first image (pipeline.flow_wmedian with its default sigmas, DESIGN.md "Weighted median filter"); with --eval the pair's
+row and the totals gain the kind "filtered".  --wmedian-reject R T sends the sparse field through the same filter in reject
+mode, guided: a vector that differs from the weighted median of its window by more than T in |dU| + |dV| is removed and every
+other vector stays bit for bit, after the check and --segments and before everything that reads the sparse field (as
+--segments).  One line per pair gives the four counts; the header of eval.json gains "wmedian": R and "wmedian_reject": [R, T].
+Without them nothing is launched that was not launched before.
 """
 import argparse
 import importlib
@@ -96,6 +103,10 @@ def parser():
                     help="also write mid_NN.png, the frame at t = 0.5 from the pair's two flows; prints its PSNR, writes midframe.json")
     ap.add_argument("--mid-fill-rounds", type=int, default=None, metavar="K", help="with --midframe: fill rounds, 0..64 (default 8)")
     ap.add_argument("--mid-occl-thresh", type=float, default=None, metavar="D", help="with --midframe: occlusion threshold (default 30)")
+    ap.add_argument("--wmedian", default=None, metavar="R",
+                    help="also write wmedian_NN.flo, the forward flow through the guided weighted median filter of radius R (1..8)")
+    ap.add_argument("--wmedian-reject", nargs=2, default=None, metavar=("R", "T"),
+                    help="after the check and --segments: remove sparse vectors further than T from their window's weighted median (radius R)")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
     ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="with --pyramid: sweeps of the coarse levels (default: --bcd-times)")
@@ -121,6 +132,28 @@ def segments_arg(tokens):
     except ValueError:
         parser().error("--segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (tokens,))
     return min_size, thresh
+
+
+def wmedian_arg(token):
+    """--wmedian R -> R; exits with status 2 unless R is an integer in 1..8."""
+    try:
+        radius = int(token)
+        if not 1 <= radius <= 8:
+            raise ValueError
+    except ValueError:
+        parser().error("--wmedian needs R (an integer in 1..8), got %r" % (token,))
+    return radius
+
+
+def wmedian_reject_arg(tokens):
+    """--wmedian-reject R T -> (R, T); exits with status 2 unless R is an integer in 1..8 and T finite and >= 0."""
+    try:
+        radius, thresh = int(tokens[0]), float(tokens[1])
+        if not 1 <= radius <= 8 or not (np.isfinite(thresh) and thresh >= 0):
+            raise ValueError
+    except ValueError:
+        parser().error("--wmedian-reject needs R (an integer in 1..8) and T (finite, >= 0), got %r" % (tokens,))
+    return radius, thresh
 
 
 def midframe_args(a):
@@ -373,6 +406,13 @@ def write_pair(s, pair, fwd, bwd):
     if a.segments is not None:
         sparse_dev, seg_counts = pipeline.segment_filter(sparse_dev, a.segments[1], a.segments[0], counts=True)
         print("pair %d: %d segments, %d removed; %d consistent pixels, %d removed" % ((pair,) + tuple(seg_counts.cpu().tolist())))
+    img1 = img2 = epic = None
+    if a.edges or a.epic or a.photo or a.wmedian is not None or a.wmedian_reject is not None:
+        img1, img2 = s.images[pair] if pair in s.images else synth.make_pair(s.H, s.W, seed=synth.pair_seed(pair, 0))[:2]
+    if a.wmedian_reject is not None:
+        sparse_dev, wm_counts = pipeline.flow_wmedian(sparse_dev, img1, radius=a.wmedian_reject[0], reject=a.wmedian_reject[1], counts=True)
+        print("pair %d: weighted median rejection: %s" % (pair, " ".join("%s=%d" % kv for kv in zip(pipeline.FLOW_WMEDIAN_COUNTS,
+                                                                                                     wm_counts.cpu().tolist()))))
     sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
     sparse = sparse_dev.cpu().numpy()
     for backward, f in ((0, fwd), (1, bwd)):
@@ -380,9 +420,6 @@ def write_pair(s, pair, fwd, bwd):
     flowio.write_flo(os.path.join(a.out, flowio.flow_name(pair, 0, a.bcd_times)[:-4] + ".flo"), fwd.cpu().numpy())
     np.save(os.path.join(a.out, "sparse_field_%02d.npy" % pair), sparse)
     mod("evaluate").parovi(sparse, os.path.join(a.out, "parovi_%02d.txt" % pair))
-    img1 = img2 = epic = None
-    if a.edges or a.epic or a.photo:
-        img1, img2 = s.images[pair] if pair in s.images else synth.make_pair(s.H, s.W, seed=synth.pair_seed(pair, 0))[:2]
     if a.edges or a.epic:
         if a.edge_kind == "pb":
             ivice = pipeline.pb_edges(img1)               # e itself for the GPU steps, 1 - e in the file
@@ -423,6 +460,10 @@ def write_out(s, flows):
         fwd = flows[2 * pair]
         sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, flows[2 * pair + 1])
         dense = [("epic", epic)] if a.epic else []
+        if a.wmedian is not None:
+            filtered = pipeline.flow_wmedian(fwd, img1, radius=a.wmedian)
+            flowio.write_flo(os.path.join(a.out, "wmedian_%02d.flo" % pair), filtered[..., [1, 0]].cpu().numpy())
+            dense = [("filtered", filtered)] + dense
         if a.eval:
             gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]
             gt = torch.from_numpy(evaluate.to_uv_valid(gt) if gt.shape[2] == 2 else np.asarray(gt, np.float32)).to(s.dev)
@@ -450,6 +491,10 @@ def write_out(s, flows):
             head["check"] = a.check
         if a.segments is not None:
             head["segments"] = [a.segments[0], a.segments[1]]
+        if a.wmedian is not None:
+            head["wmedian"] = a.wmedian
+        if a.wmedian_reject is not None:
+            head["wmedian_reject"] = [a.wmedian_reject[0], a.wmedian_reject[1]]
         write_tally(os.path.join(a.out, "eval.json"), dict(head, abs_thresh=3.0), EVAL, eval_rows, eval_totals)
 
 
@@ -458,6 +503,10 @@ def main(argv=None):
     a.epic = a.epic or a.epic_refine or a.prefilter
     if a.segments is not None:
         a.segments = segments_arg(a.segments)
+    if a.wmedian is not None:
+        a.wmedian = wmedian_arg(a.wmedian)
+    if a.wmedian_reject is not None:
+        a.wmedian_reject = wmedian_reject_arg(a.wmedian_reject)
     a.mid_fill_rounds, a.mid_occl_thresh = midframe_args(a)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
