@@ -93,7 +93,9 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
                                                         const float *__restrict__ lcosts, const int32_t *__restrict__ nprop,
                                                         BcdPlanes pl)
 {
-    __shared__ uint32_t s_cols[4][192];                      // q's biased labels, per wave
+    __shared__ uint32_t s_cols[4][256];                      // q's biased labels, per wave; a whole row per index BYTE, so that the
+                                                             // empty list slot 0xFF reads inside it (8 KB of LDS per block with
+                                                             // s_list: no limit at 8 blocks of 4 waves per CU)
     __shared__ __attribute__((aligned(16))) uint8_t s_list[4][64][16];   // member lists being built, per wave and lane
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int q = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wv);
@@ -116,6 +118,15 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
         fq[j] = k < pn ? flow_bias(proposals[(size_t)q * LP + k]) : 0u;      // 0: far from every biased flow
         s_cols[wv][k] = fq[j];
     }
+    s_cols[wv][192 + lane] = 0u;                             // words 192..255: read by empty list slots, never used
+    // Lanes beyond the successor's count (or of a successor that does not exist) are loaded with 0.  That alone does NOT make
+    // their tests fail: against a column c = flow_bias(dy | dx << 16), halves dy + 32768 and dx + 32768 in [0, 65535],
+    // D = sad(c, 0) + (2^31 - tpsi) = dy + dx + 65536 + 2^31 - tpsi, at most 2^31 + 131070 (no wrap), has bit 31 set iff
+    // dy + dx >= tpsi - 65536.  That holds for the fill columns (0xFFFFFFFF: dy + dx = -2) and for every label whose target
+    // lies in a frame of at most 8192 pixels a side (dy + dx >= -16382), which is all the stages of this library ever write, but
+    // dflow_bcd_prepare takes the caller's int16 pairs as they are, and a label with dy + dx <= tpsi - 65537 (both halves
+    // within tpsi of -32768) is "compatible" with the value 0.  emit therefore masks such lanes itself (one instruction per row
+    // word, what the bare ~m would cost too) instead of relying on their flow.
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int k = lane + 64 * j;
@@ -146,8 +157,8 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
     if (!v0 && !v1) return;
     // lanes = labels of the successors (five groups of 64), q's labels come one by one as wave-uniform scalars (scalar
     // loads of q's row): D = sad + (2^31 - tpsi) has bit 31 set iff the pair is NOT compatible, v_alignbit shifts that bit
-    // into the row word.  Columns run downwards inside each 32-bit word so that column c ends up in bit c; columns >= pn
-    // (fill values) are forced to "not compatible" afterwards.
+    // into the row word.  Columns run downwards inside each 32-bit word so that column c ends up in bit c; of the columns >= pn
+    // (fill values) only those in the last chunk of 8 are tested at all, and they are forced to "not compatible" afterwards.
     const uint32_t kbias = 0x80000000u - (uint32_t)tpsi;
     const uint32_t *__restrict__ colp = proposals + (size_t)q * LP;
     uint32_t m[5][BCD_MASK_WORDS];
@@ -159,17 +170,29 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
 #pragma unroll
             for (int g = 0; g < 5; g++) m[g][j] = 0xFFFFFFFFu;
             if (32 * j < pn) {
+                const int nv = pn - 32 * j;                  // valid columns in this word (wave-uniform), 32 or more: all
+                // columns hi..hi-7.  A word starts as all ones and every column shifts one bit in, so after c columns the bits
+                // c..31 still say "not compatible": the columns run from 8*ceil(nv/8) - 1 down, the chunks above hold nothing
+                // but fill values and are not tested at all (pn = 150: 152 columns instead of 160, pn = 100: 104 instead of 128)
+                auto cols8 = [&](auto hic) {
 #pragma unroll
-                for (int cc = 31; cc >= 0; cc--) {
-                    const uint32_t col = flow_bias(colp[32 * j + cc]);
+                    for (int cc = decltype(hic)::value; cc > decltype(hic)::value - 8; cc--) {
+                        const uint32_t col = flow_bias(colp[32 * j + cc]);
 #pragma unroll
-                    for (int g = 0; g < 4; g++) m[g][j] = __builtin_amdgcn_alignbit(m[g][j], __builtin_amdgcn_sad_u16(col, f[g], kbias), 31);
-                    if (decltype(with5)::value) m[4][j] = __builtin_amdgcn_alignbit(m[4][j], __builtin_amdgcn_sad_u16(col, f[4], kbias), 31);
+                        for (int g = 0; g < 4; g++) m[g][j] = __builtin_amdgcn_alignbit(m[g][j], __builtin_amdgcn_sad_u16(col, f[g], kbias), 31);
+                        if (decltype(with5)::value) m[4][j] = __builtin_amdgcn_alignbit(m[4][j], __builtin_amdgcn_sad_u16(col, f[4], kbias), 31);
+                    }
+                };
+                if (nv > 24) cols8(IntC<31>());
+                if (nv > 16) cols8(IntC<23>());
+                if (nv > 8) cols8(IntC<15>());
+                cols8(IntC<7>());
+                // the fill columns of the last chunk
+                if (nv < 32 && (nv & 7) != 0) {
+                    const uint32_t inval = ~0u << nv;
+#pragma unroll
+                    for (int g = 0; g < 5; g++) m[g][j] |= inval;
                 }
-                const int nv = pn - 32 * j;                  // valid columns in this word (wave-uniform)
-                const uint32_t inval = nv >= 32 ? 0u : ~0u << nv;
-#pragma unroll
-                for (int g = 0; g < 5; g++) m[g][j] |= inval;
             }
         }
     };
@@ -184,8 +207,12 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
         // first block: the chain kernel reads all LP of them.
         uint32_t w[BCD_MASK_WORDS];
         int cnt = 0;
+        // a lane without a label has no members (it cannot rely on its f = 0, see the f[] loads).  One mask per group and one
+        // v_bitop3 per word; the empty asm keeps the compiler from turning it back into a v_not + v_cndmask per word
+        uint32_t dead = valid && tl < tn ? 0u : ~0u;
+        asm("" : "+v"(dead));
 #pragma unroll
-        for (int j = 0; j < BCD_MASK_WORDS; j++) { w[j] = valid && tl < tn ? ~mg[j] : 0u; cnt += __popc(w[j]); }
+        for (int j = 0; j < BCD_MASK_WORDS; j++) { w[j] = __builtin_amdgcn_bitop3_b32(mg[j], dead, 0u, 0x03); cnt += __popc(w[j]); }   // ~(mg | dead)
         // the first 15 members as bytes: every lane appends to its 16-byte row in LDS (one ds_write_b8 and a pointer
         // increment per member; a shift register in VGPRs costs four instructions per member of the wave's LONGEST list) and
         // reads the row back in place
@@ -205,6 +232,8 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
                 for (int j = BCD_MASK_WORDS - 1; j >= 0; j--)
                     while (extra > 0 && wt[j]) { wt[j] &= ~(0x80000000u >> __clz(wt[j])); extra--; }
             }
+            // (one pointer bump per word and constant store offsets, four rounds per turn: 5 VALU per round instead of 7, same
+            // kernel time, DESIGN.md 5.4 round 6: the rounds are not priced in VALU instructions)
             uint8_t *ap = row;
 #pragma unroll
             for (int j = 0; j < BCD_MASK_WORDS; j++) {
@@ -218,12 +247,15 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
         // longest list): |dy-dy'| + |dx-dx'| against the member's flow; empty slots (0xFF) read a valid word and are zeroed
         uint32_t c0 = 0u, c1 = 0u;
         if (any) {
+            // No guard per slot: an empty slot (0xFF) reads word 255 of the wave's 256-word row and its "cost" may be any
+            // 17-bit number.  The slots fill in increasing order, so what it spills over are nibbles of higher, equally empty
+            // slots of the same 32-bit half; all of them are cleared at once below.
             auto slots = [&](auto lo, auto hi) {
 #pragma unroll
                 for (int e = decltype(lo)::value; e < decltype(hi)::value; e++) {
                     const uint32_t word = e < 4 ? l0 : (e < 8 ? l1 : (e < 12 ? l2 : l3));
                     const uint32_t k = (word >> (8 * (e & 3))) & 0xFFu;
-                    const uint32_t psi = e < n ? flow_l1_biased(me, s_cols[wv][min(k, 191u)]) : 0u;    // k < 160, or 0xFF (empty slot) -> 191: inside the row
+                    const uint32_t psi = flow_l1_biased(me, s_cols[wv][k]);
                     if (e < 8) c0 |= psi << (4 * e); else c1 |= psi << (4 * (e - 8));
                 }
             };
@@ -234,8 +266,9 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
                 if (__ballot(n > 2 * BCD_BLK)) slots(IntC<2 * BCD_BLK>(), IntC<BCD_LIST>());
             }
         }
-        // bytes 0..3 | 4, 5..8 | 9, 10..13 | 14 and nibbles 0..4, 5..9, 10..14 -> the three blocks
-        const unsigned long long pp = ((unsigned long long)c1 << 32) | c0;
+        // bytes 0..3 | 4, 5..8 | 9, 10..13 | 14 and nibbles 0..4, 5..9, 10..14 -> the three blocks; the nibbles of the slots
+        // n..14 are cleared here (4 n <= 60), before the flag bits go into the first block's cost field
+        const unsigned long long pp = (((unsigned long long)c1 << 32) | c0) & ~(~0ull << (4 * n));
         // second / third blocks: compacted per 64-label wave of a pixel in lane order (rank = number of lower lanes of the
         // same pixel that own one); the first BCD_CAP_B / BCD_CAP_C owners get a slot
         const unsigned long long hasB = __ballot(cnt > BCD_BLK), hasC = __ballot(cnt > 2 * BCD_BLK);

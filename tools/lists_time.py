@@ -1,17 +1,29 @@
-import sys, os, importlib, torch
+"""dflow_bcd_prepare (bcd_lists_kernel) alone on the bench's first pair, between HIP events, median and minimum of 20 calls, on the
+dense and the low_texture frame: python tools/lists_time.py [variant.so ...]  (no argument: the built library; several: one
+child process each, in the order given, so that parent and change can alternate)"""
+import sys, os, importlib, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
+if len(sys.argv) > 2:
+    for name in sys.argv[1:]:
+        subprocess.run([sys.executable, os.path.abspath(__file__), name], check=True, timeout=300)
+    sys.exit(0)
+import torch
 _lib = importlib.import_module("lk-s-2022-estimacija-pokreta_amd._lib")
 if len(sys.argv) > 1: _lib.LIB_PATH = os.path.join(ROOT, "tools", "prof_build", sys.argv[1])
 synth = importlib.import_module("lk-s-2022-estimacija-pokreta_amd.synth")
 pl = importlib.import_module("lk-s-2022-estimacija-pokreta_amd.pipeline")
 H, W = 436, 1024
-img1, img2, gt = synth.make_pair(H, W, seed=0)
-df = pl.DiscreteFlow(H, W, seed=0)
-df.load_pair(torch.from_numpy(img1).cuda(), torch.from_numpy(img2).cuda()); df.generisi(); df.nasumicni()
-def t(fn, n=5):
+def t(fn, n=20):
     fn(); torch.cuda.synchronize(); ts = []
     for _ in range(n):
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record(); fn(); e1.record(); torch.cuda.synchronize(); ts.append(e0.elapsed_time(e1))
-    return min(ts)
-print(sys.argv[1:], "pakovanje %.3f ms" % t(df.pakovanje))
+    ts.sort()
+    return 0.5 * (ts[n // 2 - 1] + ts[n // 2]), ts[0]
+out = []
+for style in synth.STYLES:
+    img1, img2, gt = synth.make_pair(H, W, seed=synth.pair_seed(0, 0), style=style)
+    df = pl.DiscreteFlow(H, W, seed=0)
+    df.load_pair(torch.from_numpy(img1).cuda(), torch.from_numpy(img2).cuda()); df.generisi(); df.nasumicni()
+    out.append("%s %.3f (min %.3f)" % ((style,) + t(df.pakovanje)))
+print(sys.argv[1:], "pakovanje ms, median of 20:", ", ".join(out), flush=True)

@@ -8,7 +8,8 @@ extra=""
 case $src in knn_mfma.hip) extra="-fno-honor-nans -fno-slp-vectorize";; bcd.hip) extra="-fno-honor-nans";; esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function $extra "$@" -c $src -o /tmp/variant_$name.o
 objs=""
-for f in abi bcd knn knn_mfma knn_pca neighbour daisy post; do
+for h in *.hip; do
+  f=${h%.hip}
   if [ "$f.hip" = "$src" ]; then objs="$objs /tmp/variant_$name.o"; else objs="$objs $f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../../tools/prof_build/$name.so $objs
