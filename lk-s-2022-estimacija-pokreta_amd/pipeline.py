@@ -240,14 +240,23 @@ class DiscreteFlow:
                   self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), _ptr(cnt), self._stream())
         return cnt
 
-    def run(self, pic3, pic4, bcd_times, prior=None, prior_stride=2):
-        """daisy i flann.py main (:406-422, without the file writes) followed by ceoBCD; returns the flow tensor.  prior: a
-        flow to start from (prior_proposals, with seeded labels); None: the reference's pass."""
+    def front_end(self, pic3, pic4, prior=None, prior_stride=2, seed_labels=True, counts=False, pack=False):
+        """Everything of a pass before its sweeps, daisy i flann.py main (:406-422, without the file writes): load_pair, generisi,
+        nasumicni, with a prior prior_proposals(prior, prior_stride, seed_labels, counts), with pack=True pakovanje (for passes
+        whose sweeps are batched: the compat matrices are then built here, on the front end's stream).  Returns what
+        prior_proposals returned, None without a prior."""
         self.load_pair(pic3, pic4)
         self.generisi()
         self.nasumicni()
-        if prior is not None:
-            self.prior_proposals(prior, stride=prior_stride)
+        cnt = None if prior is None else self.prior_proposals(prior, stride=prior_stride, seed_labels=seed_labels, counts=counts)
+        if pack:
+            self.pakovanje()
+        return cnt
+
+    def run(self, pic3, pic4, bcd_times, prior=None, prior_stride=2):
+        """front_end followed by ceoBCD; returns the flow tensor.  prior: a flow to start from (prior_proposals, with seeded
+        labels); None: the reference's pass."""
+        self.front_end(pic3, pic4, prior, prior_stride)
         self.ceoBCD(bcd_times)
         return self.vratiKonacniFlow()
 
@@ -1001,6 +1010,16 @@ def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=Non
     return out
 
 
+def image_pyramid(levels, pic3, pic4):
+    """[(img1, img2)] per DiscreteFlow of `levels` (level 0, the finest, first) as device tensors: one dflow_pyr_down launch per
+    coarse level, for both images."""
+    df = levels[0]
+    pyr = [(df._device_image(pic3, df._img), df._device_image(pic4, df._img2))]
+    for _ in levels[1:]:
+        pyr.append(pyr_down(*pyr[-1]))
+    return pyr
+
+
 class PyramidFlow:
     """Coarse-to-fine passes (DESIGN.md "Coarse to fine"): one DiscreteFlow per level (self.levels, level 0 the finest, geometry
     by pyramid_levels' rule); the coarsest level runs as DiscreteFlow.run does, every finer one starts from the upsampled flow of
@@ -1019,116 +1038,96 @@ class PyramidFlow:
         return p.pich, p.picw
 
     def image_pyramid(self, pic3, pic4):
-        """[(img1, img2)] per level as device tensors: one dflow_pyr_down launch per coarse level, for both images."""
-        df = self.levels[0]
-        pyr = [(df._device_image(pic3, df._img), df._device_image(pic4, df._img2))]
-        for _ in self.levels[1:]:
-            pyr.append(pyr_down(*pyr[-1]))
-        return pyr
+        """The module's image_pyramid for this run's levels."""
+        return image_pyramid(self.levels, pic3, pic4)
 
     def run_level(self, level, imgs, bcd_times, prior=None, prior_stride=2, seed_labels=True, counts=False):
-        """One level's pass on its images; prior None: DiscreteFlow.run.  Returns (the level's flow tensor, the int32[4] counts of
+        """One level's pass on its images; prior None: the calls of DiscreteFlow.run.  Returns (the level's flow tensor, the int32[4] counts of
         its prior step as a device tensor, or None without a prior or with counts=False)."""
         df = self.levels[level]
-        if prior is None:
-            return df.run(imgs[0], imgs[1], bcd_times), None
-        df.load_pair(*imgs)
-        df.generisi()
-        df.nasumicni()
-        cnt = df.prior_proposals(prior, stride=prior_stride, seed_labels=seed_labels, counts=counts)
+        cnt = df.front_end(imgs[0], imgs[1], prior, prior_stride, seed_labels, counts)
         df.ceoBCD(bcd_times)
         return df.vratiKonacniFlow(), cnt
 
-    def coarse_prior(self, pyramid, bcd_times, prior_stride=2, seed_labels=True, counts=False, gate=None, gate_bilinear=False,
-                     pair=False):
-        """Levels len - 1 .. 1 run to completion on `pyramid` (image_pyramid); returns the upsampled flow of level 1, the prior of
-        level 0 ((H,W,3) [U,V,valid]), or None with one level.  With counts=True self.counts is started anew and receives one
-        entry (level, int32[3] of flow_upsample, int32[4] of prior_proposals) per coarse level that had a prior, and last the
-        entry (0, int32[3] of the upsampling for level 0): the caller that runs level 0's prior step adds its counts.
-        pair=True: every coarse level runs forward and then backward (the images swapped) and the pair of priors is returned;
-        the entries of self.counts then hold pairs (forward, backward) in place of the tensors.  gate=T (needs pair): the two
-        flows of a coarse level go through flow_consistency(.., T, both=True) before they are upsampled, T in pixels of that
-        level; a gated-out vector is invalid, so the finer level's prior step skips what the upsampling cannot fill from its
-        neighbours.  With counts=True self.gate_counts holds (level, int32[2,5] of flow_consistency) per coarse level."""
-        if pair or gate is not None:
-            return self._coarse_prior_pair(pyramid, bcd_times, prior_stride, seed_labels, counts, gate, gate_bilinear, pair)
-        prior, ups = None, None
-        self.counts = []
-        for level in range(len(self.levels) - 1, 0, -1):
-            flow, cnt = self.run_level(level, pyramid[level], bcd_times, prior, prior_stride, seed_labels, counts)
-            if counts and prior is not None:
-                self.counts.append((level, ups, cnt))
-            prior = flow_upsample(flow, self.size(level - 1), counts=counts)
-            if counts:
-                prior, ups = prior
-        if counts and prior is not None:
-            self.counts.append((0, ups))
-        return prior
+    FORWARD, BACKWARD = (0, 1), (1, 0)      # a direction: the order in which a pass takes the two images of a level
 
-    def _run_level_pair(self, level, imgs, bcd_times, priors, prior_stride, seed_labels, counts):
-        """run_level forward, then backward with the images swapped, on the level's one DiscreteFlow; vratiKonacniFlow returns
-        the object's buffer, so each flow is cloned before the object is used again.  Returns ([flows], [prior counts])."""
-        flows, cnts = [], []
-        for prior, (a, b) in zip(priors, ((imgs[0], imgs[1]), (imgs[1], imgs[0]))):
-            flow, cnt = self.run_level(level, (a, b), bcd_times, prior, prior_stride, seed_labels, counts)
-            flows.append(flow.clone())
-            cnts.append(cnt)
-        return flows, cnts
-
-    def _coarse_prior_pair(self, pyramid, bcd_times, prior_stride, seed_labels, counts, gate, gate_bilinear, pair):
-        if not pair:
-            raise ValueError("PyramidFlow.coarse_prior: gate needs pair=True (the check needs both directions)")
-        priors, ups = (None, None), None
+    def _descend(self, pyramid, dirs, last, bcd_times, coarse_bcd_times, prior_stride, seed_labels, counts, gate=None,
+                 gate_bilinear=False):
+        """THE coarse-to-fine loop of run, run_pair and coarse_prior: levels len - 1 .. last, each through self.run_level once
+        per direction of `dirs`, one prior carried per direction.  Returns the tuple of level 0's flows when last == 0, else the
+        tuple of priors of level last - 1 (None without a coarser level).  vratiKonacniFlow returns the level's own buffer, so a
+        flow is cloned when, and only when, more than one direction shares the level's DiscreteFlow.  With counts=True an entry
+        of self.counts is begun as (level, upsample counts per direction) when the level's priors are made and completed with
+        the prior_proposals counts per direction when the level has run; the callers document the rest."""
+        priors = (None,) * len(dirs)
         self.counts, self.gate_counts = [], []
-        for level in range(len(self.levels) - 1, 0, -1):
-            flows, cnts = self._run_level_pair(level, pyramid[level], bcd_times, priors, prior_stride, seed_labels, counts)
+        for level in range(len(self.levels) - 1, last - 1, -1):
+            flows, cnts = [], []
+            for prior, (a, b) in zip(priors, dirs):
+                flow, cnt = self.run_level(level, (pyramid[level][a], pyramid[level][b]), bcd_times if level == 0 else coarse_bcd_times,
+                                           prior, prior_stride, seed_labels, counts)
+                flows.append(flow.clone() if len(dirs) > 1 else flow)
+                cnts.append(cnt)
             if counts and priors[0] is not None:
-                self.counts.append((level, ups, tuple(cnts)))
+                self.counts[-1] += (tuple(cnts),)
+            if level == 0:
+                return tuple(flows)
             if gate is not None:
                 res = flow_consistency(flows[0], flows[1], gate, bilinear=gate_bilinear, both=True, counts=counts)
                 flows = res[:2]
                 if counts:
                     self.gate_counts.append((level, res[2]))
-            res = [flow_upsample(f, self.size(level - 1), counts=counts) for f in flows]
-            priors, ups = (tuple(r[0] for r in res), tuple(r[1] for r in res)) if counts else (tuple(res), None)
-        if counts and priors[0] is not None:
-            self.counts.append((0, ups))
+            priors = tuple(flow_upsample(f, self.size(level - 1), counts=counts) for f in flows)
+            if counts:
+                self.counts.append((level - 1, tuple(r[1] for r in priors)))
+                priors = tuple(r[0] for r in priors)
         return priors
+
+    def _one_direction(self, res):
+        """The edge of a single-direction run: its entry of the tuple `res`, and self.counts' 1-tuples replaced by their tensors."""
+        self.counts = [(e[0],) + tuple(t[0] for t in e[1:]) for e in self.counts]
+        return res[0]
+
+    def coarse_prior(self, pyramid, bcd_times, prior_stride=2, seed_labels=True, counts=False, gate=None, gate_bilinear=False,
+                     pair=False):
+        """Levels len - 1 .. 1 run to completion on `pyramid` (image_pyramid), bcd_times sweeps each; returns the upsampled flow of
+        level 1, the prior of level 0 ((H,W,3) [U,V,valid]), or None with one level.  With counts=True self.counts is started
+        anew and receives one entry (level, int32[3] of flow_upsample, int32[4] of prior_proposals) per coarse level that had a
+        prior, and last the entry (0, int32[3] of the upsampling for level 0): the caller that runs level 0's prior step adds its
+        counts.  pair=True: the same loop with two directions, every coarse level runs forward and then backward (the images
+        swapped), and the pair of priors is returned; the entries of self.counts then hold pairs (forward, backward) in place of
+        the tensors.  gate=T (needs pair): the two flows of a coarse level go through flow_consistency(.., T, both=True) before
+        they are upsampled, T in pixels of that level; a gated-out vector is invalid, so the finer level's prior step skips what
+        the upsampling cannot fill from its neighbours.  With counts=True self.gate_counts holds (level, int32[2,5] of
+        flow_consistency) per coarse level."""
+        if gate is not None and not pair:
+            raise ValueError("PyramidFlow.coarse_prior: gate needs pair=True (the check needs both directions)")
+        dirs = (self.FORWARD, self.BACKWARD) if pair else (self.FORWARD,)
+        priors = self._descend(pyramid, dirs, 1, None, bcd_times, prior_stride, seed_labels, counts, gate, gate_bilinear)
+        return priors if pair else self._one_direction(priors)
 
     def run_pair(self, pic3, pic4, bcd_times, coarse_bcd_times=None, gate=None, gate_bilinear=False, prior_stride=2, seed_labels=True,
                  counts=False):
         """Both directions of a pair: returns (forward flow, backward flow) of level 0, as tensors of their own.  The image
-        pyramid is built once; every level runs forward (pic3 -> pic4) and then backward (pic4 -> pic3).  gate=None: the flows
-        of run(pic3, pic4, ..) and run(pic4, pic3, ..).  gate=T: the two flows of every coarse level go through
-        flow_consistency(.., T, both=True[, bilinear=gate_bilinear]) before they are upsampled, so a coarse vector that fails the
-        forward/backward check is no prior (coarse_prior; T in pixels of the level it is applied at).  The other arguments and
-        self.counts as in run and coarse_prior(pair=True)."""
+        pyramid is built once; the loop of run then takes every level forward (pic3 -> pic4) and backward (pic4 -> pic3).
+        gate=None: the flows of run(pic3, pic4, ..) and run(pic4, pic3, ..).  gate=T: the two flows of every coarse level go
+        through flow_consistency(.., T, both=True[, bilinear=gate_bilinear]) before they are upsampled, so a coarse vector that
+        fails the forward/backward check is no prior (coarse_prior; T in pixels of the level it is applied at).  The other
+        arguments and self.counts as in run and coarse_prior(pair=True).  With one level these are the calls of two plain runs."""
         if gate is not None:
             gate = float(gate)
             if not (np.isfinite(gate) and gate >= 0):
                 raise ValueError("PyramidFlow.run_pair: gate must be None or finite and >= 0, got %r" % gate)
-        pyramid = self.image_pyramid(pic3, pic4)
-        priors = (None, None)
-        self.counts, self.gate_counts = [], []
-        if len(self.levels) > 1:
-            priors = self.coarse_prior(pyramid, bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride, seed_labels,
-                                       counts, gate, gate_bilinear, pair=True)
-        flows, cnts = self._run_level_pair(0, pyramid[0], bcd_times, priors, prior_stride, seed_labels, counts)
-        if counts and priors[0] is not None:
-            self.counts[-1] += (tuple(cnts),)
-        return tuple(flows)
+        return self._descend(self.image_pyramid(pic3, pic4), (self.FORWARD, self.BACKWARD), 0, bcd_times,
+                             bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride, seed_labels, counts, gate,
+                             gate_bilinear)
 
     def run(self, pic3, pic4, bcd_times, coarse_bcd_times=None, prior_stride=2, seed_labels=True, counts=False):
-        """The whole run; returns level 0's flow tensor.  coarse_bcd_times: the sweeps of the coarse levels (None: bcd_times).
-        prior_stride and seed_labels as in DiscreteFlow.prior_proposals, for every level that has a prior.  With counts=True
-        self.counts holds, per level that had a prior, (level, int32[3] of flow_upsample, int32[4] of prior_proposals) as device
-        tensors.  Everything runs on torch's current stream; nothing is read back.  With one level these are exactly the
-        calls of DiscreteFlow.run."""
-        if len(self.levels) == 1:
-            return self.levels[0].run(pic3, pic4, bcd_times)
-        pyramid = self.image_pyramid(pic3, pic4)
-        prior = self.coarse_prior(pyramid, bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride, seed_labels, counts)
-        flow, cnt = self.run_level(0, pyramid[0], bcd_times, prior, prior_stride, seed_labels, counts)
-        if counts:
-            self.counts[-1] += (cnt,)
-        return flow
+        """The whole run, one direction; returns level 0's flow tensor (the level's own buffer: nothing is copied).
+        coarse_bcd_times: the sweeps of the coarse levels (None: bcd_times).  prior_stride and seed_labels as in
+        DiscreteFlow.prior_proposals, for every level that has a prior.  With counts=True self.counts holds, per level that had a
+        prior, (level, int32[3] of flow_upsample, int32[4] of prior_proposals) as device tensors.  Everything runs on torch's
+        current stream; nothing is read back.  With one level these are exactly the calls of DiscreteFlow.run."""
+        return self._one_direction(self._descend(self.image_pyramid(pic3, pic4), (self.FORWARD,), 0, bcd_times,
+                                                 bcd_times if coarse_bcd_times is None else coarse_bcd_times, prior_stride,
+                                                 seed_labels, counts))

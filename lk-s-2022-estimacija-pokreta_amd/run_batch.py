@@ -267,100 +267,59 @@ def setup(a):
     s.group = max(1, min(a.group, len(mine)))
     flags = mod("_lib").FLAG_DESCR_F16 if a.fp16_descriptors else 0
     ch, cw = (int(v) for v in a.cell.lower().split("x")) if a.cell else (None, None)
+    # per pass of a group its DiscreteFlow objects, level 0 first; a plain run has the one level, and its object is built with
+    # the cells as given (PyramidFlow clips them to the image), so the library still refuses what it refused
     if a.pyramid > 1:
-        s.pfs = [pipeline.PyramidFlow(s.H, s.W, a.pyramid, ch, cw, device=s.dev, seed=s.rank, fine_window=a.fine_window, flags=flags)
-                 for _ in range(s.group)]
-        s.dfs = [pf.levels[0] for pf in s.pfs]
+        s.levels = [pipeline.PyramidFlow(s.H, s.W, a.pyramid, ch, cw, device=s.dev, seed=s.rank, fine_window=a.fine_window, flags=flags).levels
+                    for _ in range(s.group)]
     else:
-        s.dfs = [pipeline.DiscreteFlow(s.H, s.W, ch, cw, device=s.dev, seed=s.rank, flags=flags) for _ in range(s.group)]
+        s.levels = [[pipeline.DiscreteFlow(s.H, s.W, ch, cw, device=s.dev, seed=s.rank, flags=flags)] for _ in range(s.group)]
+    s.dfs = [stack[0] for stack in s.levels]
     s.front = [torch.cuda.Stream(device=s.dev) for _ in range(min(3, s.group))]     # front ends of a group's passes side by side
     return s
 
 
-def compute_many_pyramid(s, descs):
-    """compute_many with --pyramid L: per group, level L-1 .. 0 for all its passes.  A level's front ends (at the coarsest level
-    after the image pyramid, at the others with the prior step) run on the front streams, its sweeps as one batch on the main
-    stream, where its flows are then upsampled into the next level's priors."""
+def compute_many(s, descs):
+    """The flows of this rank's passes `descs`, group by group: per group, the levels from the coarsest to level 0 (a plain run
+    has only that one) for all its passes.  A level's front ends (at the coarsest level after the image pyramid, at the others
+    with the prior step) run on the front streams, its sweeps as one batch on the main stream, where its flows are then
+    upsampled into the next level's priors.  With a stop rule the histories of level 0 go to s.histories."""
     import torch
     pipeline = mod("pipeline")
     flows = []
     main = torch.cuda.current_stream(s.dev)
-    nlev = s.a.pyramid
     coarse_times = s.a.bcd_times if s.a.coarse_bcd_times is None else s.a.coarse_bcd_times
     for g0 in range(0, len(descs), s.group):
         part = descs[g0:g0 + s.group]
-        pfs = s.pfs[:len(part)]
+        stacks = s.levels[:len(part)]
         pyramids, priors = [None] * len(part), [None] * len(part)
-        for level in range(nlev - 1, -1, -1):
+        for level in range(len(stacks[0]) - 1, -1, -1):
             start = torch.cuda.Event()
             start.record(main)                               # the previous group's read-out, or the next coarser level, is done
             done = []
-            for j, (pf, (pair, backward)) in enumerate(zip(pfs, part)):
-                img1, img2 = s.images[pair]
-                if backward:
-                    img1, img2 = img2, img1
+            for j, (stack, (pair, backward)) in enumerate(zip(stacks, part)):
                 st = s.front[j % len(s.front)]
                 with torch.cuda.stream(st):
                     st.wait_event(start)
                     if pyramids[j] is None:
-                        pyramids[j] = pf.image_pyramid(img1, img2)
-                    df = pf.levels[level]
-                    df.load_pair(*pyramids[j][level])
-                    df.generisi()
-                    df.nasumicni()
+                        pyramids[j] = pipeline.image_pyramid(stack, *(s.images[pair][::-1] if backward else s.images[pair]))
                     if priors[j] is not None:
                         priors[j].record_stream(st)          # made on the main stream
-                        df.prior_proposals(priors[j])
-                    df.pakovanje()
+                    stack[level].front_end(*pyramids[j][level], prior=priors[j], pack=True)
                     e = torch.cuda.Event()
                     e.record(st)
                     done.append(e)
             for e in done:
                 main.wait_event(e)
-            dfs = [pf.levels[level] for pf in pfs]
+            dfs = [stack[level] for stack in stacks]
             hist = pipeline.ceoBCD_batch(dfs, s.a.bcd_times if level == 0 else coarse_times, stop=s.stop if level == 0 else None)
             if level > 0:
-                priors = [pipeline.flow_upsample(df.vratiKonacniFlow(), pf.size(level - 1)) for df, pf in zip(dfs, pfs)]
+                priors = [pipeline.flow_upsample(df.vratiKonacniFlow(), (stack[level - 1].p.pich, stack[level - 1].p.picw))
+                          for df, stack in zip(dfs, stacks)]
         if hist is not None:
             for desc, h in zip(part, hist):
                 s.histories[s.passes.index(desc)] = h
         flows += [df.vratiKonacniFlow().clone() for df in dfs]
-    return flows
-
-
-def compute_many(s, descs):
-    """The flows of this rank's passes `descs`, group by group; with a stop rule their histories go to s.histories."""
-    import torch
-    if s.a.pyramid > 1:
-        return compute_many_pyramid(s, descs)
-    flows = []
-    main = torch.cuda.current_stream(s.dev)
-    for g0 in range(0, len(descs), s.group):
-        part = descs[g0:g0 + s.group]
-        start = torch.cuda.Event()
-        start.record(main)                                   # the previous group's read-out is done
-        done = []
-        for j, (df, (pair, backward)) in enumerate(zip(s.dfs, part)):
-            img1, img2 = s.images[pair]
-            if backward:
-                img1, img2 = img2, img1
-            st = s.front[j % len(s.front)]
-            with torch.cuda.stream(st):
-                st.wait_event(start)
-                df.load_pair(img1, img2)
-                df.generisi()
-                df.nasumicni()
-                df.pakovanje()
-                e = torch.cuda.Event()
-                e.record(st)
-                done.append(e)
-        for e in done:
-            main.wait_event(e)
-        hist = mod("pipeline").ceoBCD_batch(s.dfs[:len(part)], s.a.bcd_times, stop=s.stop)
-        if hist is not None:
-            for desc, h in zip(part, hist):
-                s.histories[s.passes.index(desc)] = h
-        flows += [df.vratiKonacniFlow().clone() for df in s.dfs[:len(part)]]
     return flows
 
 

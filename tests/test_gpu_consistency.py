@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import consistency_ref as R
+from call_log import BACK, BATCH_FLOWS, FRONT, record_calls
 from conftest import PKG, ROOT, pkg
 
 pytestmark = pytest.mark.gpu
@@ -170,15 +171,6 @@ def test_return_shapes(torch_):
 H, W, CH, CW, SEED = 40, 48, 5, 6, 7
 
 
-def record_calls(monkeypatch):
-    L = pkg("_lib")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
-    return names
-
-
-FRONT = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-BACK = ["dflow_bcd_prepare", "dflow_bcd_sweep", "dflow_bcd_sweep", "dflow_labels_to_flow"]
 PYRAMID_RUN = ["dflow_pyr_down"] + FRONT + BACK + ["dflow_flow_upsample"] + FRONT + ["dflow_prior_proposals"] + BACK
 
 
@@ -202,6 +194,28 @@ def test_run_pair_without_a_gate_is_two_runs(torch_, synth, monkeypatch):
     assert names == 2 * (FRONT + BACK)
     df = P.DiscreteFlow(H, W, CH, CW, seed=SEED)
     assert np.array_equal(f1.cpu().numpy(), df.run(img1, img2, 2).cpu().numpy()) and np.array_equal(b1.cpu().numpy(), df.run(img2, img1, 2).cpu().numpy())
+
+
+def test_run_pair_on_three_levels_is_two_runs(torch_, synth, monkeypatch):
+    """The pair of priors carried across two coarse levels: flows and, per level and direction, the counts of the single runs."""
+    P = pkg("pipeline")
+    img1, img2, _ = synth.make_pair(H, W, seed=SEED, amp_x=8.0, amp_y=4.0)
+    singles = []
+    for a, b in ((img1, img2), (img2, img1)):
+        one = P.PyramidFlow(H, W, 3, CH, CW, seed=SEED)
+        flow = one.run(a, b, 2, counts=True).cpu().numpy().copy()
+        singles.append((flow, [(lv, ups.cpu().tolist(), prior.cpu().tolist()) for lv, ups, prior in one.counts]))
+    names = record_calls(monkeypatch)
+    pf = P.PyramidFlow(H, W, 3, CH, CW, seed=SEED)
+    flows = pf.run_pair(img1, img2, 2, counts=True)
+    with_prior = 2 * ["dflow_flow_upsample"] + 2 * (FRONT + ["dflow_prior_proposals"] + BACK)
+    assert names == 2 * ["dflow_pyr_down"] + 2 * (FRONT + BACK) + 2 * with_prior
+    assert [entry[0] for entry in pf.counts] == [1, 0] and pf.gate_counts == []
+    for d, (flow, counts) in enumerate(singles):
+        assert np.array_equal(flows[d].cpu().numpy(), flow), "flow of direction %d" % d
+        assert [(lv, ups[d].cpu().tolist(), prior[d].cpu().tolist()) for lv, ups, prior in pf.counts] == counts, "counts of direction %d" % d
+        assert all(prior[0] > 0 for _, _, prior in counts), "every prior appended labels"
+        print("direction %d: %d of %d vectors are not zero" % (d, int(np.any(flow != 0, axis=-1).sum()), H * W))
 
 
 @pytest.fixture(scope="module")
@@ -290,10 +304,6 @@ def test_spremi_za_epic_natural_check(torch_, synth, tmp_path, monkeypatch, caps
     assert np.array_equal(epic[..., ::-1], P.epic_interpolate(want, ivice).cpu().numpy())
     assert spz.main(six + ["--gpu-epic", "--natural-check"]) == 2
     capsys.readouterr()
-
-
-BATCH_PASS = FRONT + ["dflow_bcd_prepare"]
-BATCH_FLOWS = 2 * BATCH_PASS + 2 * ["dflow_bcd_sweep_batch"] + 2 * ["dflow_labels_to_flow"]
 
 
 def test_run_batch_check_natural(torch_, synth, tmp_path, monkeypatch, capsys):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import flow_wmedian_ref as R
+from call_log import BATCH_FLOWS, record_calls
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -167,13 +168,6 @@ def test_captured_into_a_graph_on_a_side_stream(torch_):
 
 
 # ---- the command lines
-def record_calls(monkeypatch):
-    L = pkg("_lib")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
-    return names
-
-
 def test_flowfilter_cli_equals_the_definition(torch_, tmp_path, monkeypatch, capsys):
     flowio, ff = pkg("flowio"), pkg("flowfilter")
     h, w = 33, 65
@@ -203,10 +197,6 @@ def test_flowfilter_cli_equals_the_definition(torch_, tmp_path, monkeypatch, cap
     assert np.load("rej.npy").tobytes() == want[0].tobytes() and capsys.readouterr().out.split()[3] == "altered=%d" % want[1][3]
     assert ff.main(["sparse.npy", "keep.npy", "--keep-holes"]) == 0
     assert np.load("keep.npy").tobytes() == R.flow_wmedian(f, radius=3, flags=R.KEEP_HOLES)[0].tobytes()
-
-
-FRONT = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-BATCH_FLOWS = 2 * (FRONT + ["dflow_bcd_prepare"]) + 2 * ["dflow_bcd_sweep_batch"] + 2 * ["dflow_labels_to_flow"]
 
 
 def test_run_batch_wmedian(torch_, synth, tmp_path, monkeypatch, capsys):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import frame_interp_ref as R
+from call_log import BATCH_FLOWS, record_calls
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -213,13 +214,6 @@ def test_frame_sequence_equals_single_calls(torch_):
 
 
 # ---- the command lines
-def record_calls(monkeypatch):
-    L = pkg("_lib")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
-    return names
-
-
 def test_midframe_cli_equals_the_wrapper(torch_, tmp_path, monkeypatch, capsys):
     P, flowio, mf = pkg("pipeline"), pkg("flowio"), pkg("midframe")
     h, w = 33, 65
@@ -251,10 +245,6 @@ def test_midframe_cli_equals_the_wrapper(torch_, tmp_path, monkeypatch, capsys):
         single, c1 = P.frame_interp(img1, img2, f, t=k / 3, counts=True)
         assert np.array_equal(flowio.read_image("seq_%02d.png" % k), single.cpu().numpy())
         assert lines[k - 1] == mf.count_line(float(F(k / 3)), c1.cpu().tolist())
-
-
-FRONT = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-BATCH_FLOWS = 2 * (FRONT + ["dflow_bcd_prepare"]) + 2 * ["dflow_bcd_sweep_batch"] + 2 * ["dflow_labels_to_flow"]
 
 
 def test_run_batch_midframe(torch_, synth, tmp_path, monkeypatch, capsys):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import prior_ref as R
+from call_log import BACK, FRONT, record_calls
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -227,20 +228,62 @@ def test_batched_sweeps_of_two_seeded_passes_equal_separate_runs(torch_, synth, 
 
 
 def test_run_without_a_prior_issues_the_calls_it_always_did(get_pass, monkeypatch):
-    L = pkg("_lib")
     ps = get_pass("40x48")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
+    names = record_calls(monkeypatch)
     flow0 = ps.df.run(ps.img1, ps.img2, 2).cpu().numpy().copy()
-    front = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-    back = ["dflow_bcd_prepare", "dflow_bcd_sweep", "dflow_bcd_sweep", "dflow_labels_to_flow"]
-    assert names == front + back
+    assert names == FRONT + BACK
     del names[:]
     flow1 = ps.df.run(ps.img1, ps.img2, 2, prior=None, prior_stride=5).cpu().numpy().copy()
-    assert names == front + back and np.array_equal(flow0, flow1)
+    assert names == FRONT + BACK and np.array_equal(flow0, flow1)
     del names[:]
     ps.df.run(ps.img1, ps.img2, 2, prior=ps.gt)
-    assert names == front + ["dflow_prior_proposals"] + back
+    assert names == FRONT + ["dflow_prior_proposals"] + BACK
+
+
+def same_state(a, b):
+    sa, sb = a.host_state(), b.host_state()
+    return all(np.array_equal(sa[k], sb[k]) for k in ("proposals", "lcosts", "nprop", "bestlabels"))
+
+
+def test_front_end_is_its_stages_called_by_hand(torch_, synth, monkeypatch):
+    """DiscreteFlow.front_end on one object against load_pair, generisi, nasumicni[, prior_proposals] on another: the calls
+    and the state, without a prior, with one, and with pack=True, after which ceoBCD does not build the matrices again."""
+    H, W, ch, cw, ax, ay = GEOMS["40x48"]
+    P = pkg("pipeline")
+    img1, img2, gt = synth.make_pair(H, W, seed=SEED, amp_x=ax, amp_y=ay)
+    prior = np.ascontiguousarray(gt, dtype=np.float32)
+    df, hand = (P.DiscreteFlow(H, W, ch, cw, seed=SEED) for _ in range(2))
+
+    def by_hand(**prior_args):
+        hand.load_pair(img1, img2)
+        hand.generisi()
+        hand.nasumicni()
+        return hand.prior_proposals(prior, **prior_args) if prior_args else None
+
+    names = record_calls(monkeypatch)
+    assert df.front_end(img1, img2) is None
+    assert names == FRONT
+    by_hand()
+    assert same_state(df, hand)
+    del names[:]
+    cnt = df.front_end(img1, img2, prior=prior, prior_stride=3, seed_labels=False, counts=True)
+    assert names == FRONT + ["dflow_prior_proposals"]
+    want = by_hand(stride=3, seed_labels=False, counts=True)
+    assert cnt.cpu().tolist() == want.cpu().tolist() and cnt.cpu().tolist()[0] > 0, "the prior appended labels"
+    assert same_state(df, hand)
+    del names[:]
+    assert df.front_end(img1, img2, pack=True) is None
+    assert names == FRONT + ["dflow_bcd_prepare"]
+    del names[:]
+    assert df.front_end(img1, img2, prior=prior, pack=True) is None, "no counts asked for"
+    assert names == FRONT + ["dflow_prior_proposals", "dflow_bcd_prepare"]
+    by_hand(stride=2)
+    assert same_state(df, hand), "the defaults are prior_proposals' own: stride 2, seeded labels"
+    del names[:]
+    df.ceoBCD(2)
+    assert names == 2 * ["dflow_bcd_sweep"], "packed by the front end: no second dflow_bcd_prepare"
+    hand.ceoBCD(2)
+    assert same_state(df, hand)
 
 
 @pytest.mark.parametrize("negate", [False, True])

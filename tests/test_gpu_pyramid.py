@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import pyramid_ref as R
+from call_log import BACK, BATCH_PASS, FRONT, record_calls
 from conftest import PKG, ROOT, pkg
 
 pytestmark = pytest.mark.gpu
@@ -157,17 +158,6 @@ def test_reach_beyond_the_window_of_every_level(torch_, synth):
 
 
 # ---- the calls
-def record_calls(monkeypatch):
-    L = pkg("_lib")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
-    return names
-
-
-FRONT = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-BACK = ["dflow_bcd_prepare", "dflow_bcd_sweep", "dflow_bcd_sweep", "dflow_labels_to_flow"]
-
-
 def test_one_level_issues_the_calls_of_a_plain_run(torch_, synth, monkeypatch):
     P = pkg("pipeline")
     H, W, ch, cw = 40, 48, 5, 6
@@ -186,7 +176,6 @@ def test_one_level_issues_the_calls_of_a_plain_run(torch_, synth, monkeypatch):
                      + FRONT + ["dflow_prior_proposals"] + BACK)
 
 
-BATCH_PASS = FRONT + ["dflow_bcd_prepare"]
 BATCH_PLAIN = 2 * BATCH_PASS + 2 * ["dflow_bcd_sweep_batch"] + 2 * ["dflow_labels_to_flow"] + ["dflow_fb_consistency"]
 
 
@@ -206,6 +195,27 @@ def test_run_batch_without_pyramid_issues_the_calls_it_always_did(torch_, tmp_pa
     for backward in (0, 1):
         name = flowio.flow_name(0, backward, 2)
         assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+
+
+@pytest.mark.parametrize("pyramid", [(), ("--pyramid", "2", "--coarse-bcd-times", "3")], ids=["plain", "pyramid"])
+def test_run_batch_in_ragged_groups_writes_the_files_of_one_group(torch_, tmp_path, monkeypatch, pyramid):
+    """4 passes as groups of 3 and 1 against one group of 4: what lies between two groups (the start event after the previous
+    group's read-out, the first len(part) objects of the last group) changes no byte of any file."""
+    rb = pkg("run_batch")
+    names = record_calls(monkeypatch)
+    for group in ("3", "4"):
+        rb.main(["--pairs", "2", "--size", "40x48", "--cell", "5x6", "--bcd-times", "2", "--group", group,
+                 "--out", str(tmp_path / group)] + list(pyramid))
+        if group == "3" and not pyramid:
+            assert names == (3 * BATCH_PASS + 2 * ["dflow_bcd_sweep_batch"] + 3 * ["dflow_labels_to_flow"]
+                             + BATCH_PASS + 2 * ["dflow_bcd_sweep_batch"] + ["dflow_labels_to_flow"] + 2 * ["dflow_fb_consistency"])
+    files = sorted(os.listdir(tmp_path / "3"))
+    assert files == sorted(os.listdir(tmp_path / "4"))
+    flowio = pkg("flowio")
+    for pair in (0, 1):
+        assert {flowio.flow_name(pair, 0, 2), flowio.flow_name(pair, 1, 2), "sparse_field_%02d.npy" % pair, "parovi_%02d.txt" % pair} <= set(files)
+    for name in files:
+        assert open(tmp_path / "3" / name, "rb").read() == open(tmp_path / "4" / name, "rb").read(), name
 
 
 def test_run_batch_pyramid_equals_pyramid_flow(torch_, synth, tmp_path, monkeypatch):

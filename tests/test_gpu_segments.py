@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import segments_ref as R
+from call_log import BATCH_FLOWS, record_calls
 from conftest import pkg
 from segments_ref import golden_fields, uvv
 
@@ -308,13 +309,6 @@ def test_a_larger_random_field(torch_):
 
 
 # ---- the command lines
-def record_calls(monkeypatch):
-    L = pkg("_lib")
-    names, real = [], L.call
-    monkeypatch.setattr(L, "call", lambda name, *args: (names.append(name), real(name, *args))[1])
-    return names
-
-
 def test_spremi_za_epic_segments(torch_, synth, tmp_path, monkeypatch, capsys):
     spz = pkg("spremiZaEpic")
     h, w = 40, 48
@@ -353,10 +347,6 @@ def test_spremi_za_epic_segments(torch_, synth, tmp_path, monkeypatch, capsys):
     assert np.array_equal(epic[..., ::-1], pkg("pipeline").epic_interpolate(want[0], ivice).cpu().numpy())
     assert np.array_equal(np.load("sparse_field.npy"), want[0])
     capsys.readouterr()
-
-
-FRONT = ["dflow_daisy_pair", "dflow_knn_proposals", "dflow_neighbour_proposals"]
-BATCH_FLOWS = 2 * (FRONT + ["dflow_bcd_prepare"]) + 2 * ["dflow_bcd_sweep_batch"] + 2 * ["dflow_labels_to_flow"]
 
 
 def test_run_batch_segments(torch_, tmp_path, monkeypatch, capsys):
