@@ -1,5 +1,11 @@
 // C-ABI entry points of libdflow.so (declared in include/dflow.h): parameter validation, workspace
 // accounting and dispatch to the per-stage launchers.  No torch types, no allocation, no synchronisation.
+//
+// A gate is a sequence of the checks defined below dflow_check_launch, each called with __func__ and returning DFLOW_OK or what
+// dflow_set_error returned: check_frame_size, check_layout, check_flags, check_finite_ge0 / check_finite_gt0, check_int_range,
+// CHECK_PTR, check_aligned, check_distinct (outputs against inputs and each other) and, last but where d_ws has always been among
+// the aligned pointers, CHECK_WS; FRAME_WS_BYTES defines an image-plane stage's size function.  A new entry point's gate is
+// assembled from these, and its refusals are added to tests/test_abi_refusals.py, which pins every status, text and the order.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -26,6 +32,89 @@ int dflow_check_launch(const char *what)
     return DFLOW_OK;
 }
 
+// The checks the gates are made of.  `fn` is the entry point's __func__: the message starts with it.
+static int check_frame_size(const char *fn, int32_t h, int32_t w)
+{
+    return h < 1 || w < 1 || h > 8192 || w > 8192 ? dflow_set_error(DFLOW_EINVAL, "%s: image size %dx%d outside [1,8192]", fn, w, h) : DFLOW_OK;
+}
+
+// `name` is what the message calls the argument: layout, test_layout, layout_fwd, ...
+static int check_layout(const char *fn, const char *name, int32_t layout)
+{
+    return layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX ? dflow_set_error(DFLOW_EINVAL, "%s: unknown %s %d", fn, name, layout) : DFLOW_OK;
+}
+
+static int check_flags(const char *fn, uint32_t flags, uint32_t known)
+{
+    return flags & ~known ? dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", fn, flags) : DFLOW_OK;
+}
+
+// `note` ends the message where 0 has a meaning of its own
+static int check_finite_ge0(const char *fn, const char *name, double v, const char *note = "")
+{
+    return !isfinite(v) || v < 0.0 ? dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and >= 0%s", fn, name, v, note) : DFLOW_OK;
+}
+
+static int check_finite_gt0(const char *fn, const char *name, double v)
+{
+    return !isfinite(v) || !(v > 0.0) ? dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and > 0", fn, name, v) : DFLOW_OK;
+}
+
+// fn may be NULL: the fields of dflow_params, and phase and npass of the BCD entry points, are reported without a prefix
+static int check_int_range(const char *fn, const char *name, int v, int lo, int hi)
+{
+    if (v < lo || v > hi) return dflow_set_error(DFLOW_EINVAL, "%s%s%s=%d outside [%d,%d]", fn ? fn : "", fn ? ": " : "", name, v, lo, hi);
+    return DFLOW_OK;
+}
+
+// a pointer the kernels move several elements of at a time; NULL (an optional output left out) passes
+struct AlignedPtr { const char *name; const void *p; uintptr_t align; };
+static int check_aligned(const char *fn, std::initializer_list<AlignedPtr> ptrs)
+{
+    for (const AlignedPtr &q : ptrs)
+        if ((uintptr_t)q.p % q.align) return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", fn, q.name, (int)q.align);
+    return DFLOW_OK;
+}
+
+// no output that is given is the plane of an input or of an output listed before it
+struct NamedPlane { const char *name; const void *p; };
+static int check_distinct(const char *fn, std::initializer_list<NamedPlane> ins, std::initializer_list<NamedPlane> outs)
+{
+    for (const NamedPlane *o = outs.begin(); o != outs.end(); o++) {
+        const NamedPlane *same = nullptr;
+        for (const NamedPlane &q : ins)
+            if (!same && q.p == o->p) same = &q;
+        for (const NamedPlane *q = outs.begin(); q != o; q++)
+            if (!same && q->p == o->p) same = q;
+        if (o->p && same) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", fn, o->name, same->name);
+    }
+    return DFLOW_OK;
+}
+
+static int check_ws_size(const char *fn, const void *d_ws, size_t ws_bytes, size_t need)
+{
+    return !d_ws || ws_bytes < need ? dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need) : DFLOW_OK;
+}
+
+// The size of d_ws, then the boundary its stage needs: the widest access a kernel of the stage makes to a region WsCarver hands out
+// (regions start at multiples of 256 bytes from d_ws).  include/dflow.h, Conventions, lists them: 16 for the main-path stages, 8
+// where a region holds doubles or uint64 (bcd_stats.hip, flow_eval.hip, flow_picture.hip's warp, epic.h), 4 for int32 / uint32 /
+// float regions (edges.hip, variational.hip, flow_picture.hip's colour, prior.hip, segments.hip), 2 for pb_edges.hip's uint16
+// plane.  A NULL or short workspace is DFLOW_ENOSPC whatever its alignment, as it always was; the entry points that have
+// always named d_ws among their aligned pointers (bcd_stats, flow_advance, segment_filter) check it there, before its size.
+static int check_ws(const char *fn, const void *d_ws, size_t ws_bytes, uintptr_t align, size_t need)
+{
+    int rc = check_ws_size(fn, d_ws, ws_bytes, need);
+    return rc ? rc : check_aligned(fn, {{"d_ws", d_ws, align}});
+}
+#define CHECK_PTR(x) do { if (!(x)) return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", __func__, #x); } while (0)
+#define CHECK_WS(align, need) do { int rc_ws_ = check_ws(__func__, d_ws, ws_bytes, (align), (need)); if (rc_ws_) return rc_ws_; } while (0)
+// the main-path stages carve float4, int4 and uint4 regions (daisy.hip, knn_mfma.hip, bcd.hip)
+#define WS_ALIGN_MAIN 16
+// the size function of an image-plane stage: 0, and the message, outside the frame sizes the stage takes
+#define FRAME_WS_BYTES(entry, stage_bytes) \
+    size_t entry(int32_t h, int32_t w) { return check_frame_size(#entry, h, w) == DFLOW_OK ? stage_bytes(h, w) : 0; }
+
 int dflow_check_params(const dflow_params *p)
 {
     if (!p) return dflow_set_error(DFLOW_EINVAL, "params is NULL");
@@ -35,15 +124,16 @@ int dflow_check_params(const dflow_params *p)
         return dflow_set_error(DFLOW_EINVAL, "cell size %dx%d does not fit the image", p->cellw, p->cellh);
     if (p->knn != 5) return dflow_set_error(DFLOW_EINVAL, "knn=%d unsupported (kernels are built for 5)", p->knn);
     if (p->cellh * p->cellw < p->knn) return dflow_set_error(DFLOW_EINVAL, "cells hold fewer than knn points");
-    if (p->window < 0 || p->window > 2) return dflow_set_error(DFLOW_EINVAL, "window=%d outside [0,2]", p->window);
-    if (p->ngauss < 0 || p->ngauss > 64) return dflow_set_error(DFLOW_EINVAL, "ngauss=%d outside [0,64]", p->ngauss);
+    int rc;
+    if ((rc = check_int_range(NULL, "window", p->window, 0, 2))) return rc;
+    if ((rc = check_int_range(NULL, "ngauss", p->ngauss, 0, 64))) return rc;
     int maxknn = (2 * p->window + 1) * (2 * p->window + 1) * p->knn;
     if (p->maxnprop < maxknn + p->ngauss || p->maxnprop > DFLOW_MAX_LABELS)
         return dflow_set_error(DFLOW_EINVAL, "maxnprop=%d must be in [%d,%d]", p->maxnprop, maxknn + p->ngauss, DFLOW_MAX_LABELS);
     if (p->label_pitch < p->maxnprop || p->label_pitch % 16 != 0 || p->label_pitch > DFLOW_MAX_LABELS)
         return dflow_set_error(DFLOW_EINVAL, "label_pitch=%d must be a multiple of 16 in [maxnprop,%d]", p->label_pitch, DFLOW_MAX_LABELS);
     // pair costs below tpsi travel as 3-bit fields in the BCD label records (bcd.hip)
-    if (p->tpsi < 1 || p->tpsi > 8) return dflow_set_error(DFLOW_EINVAL, "tpsi=%d outside [1,8]", p->tpsi);
+    if ((rc = check_int_range(NULL, "tpsi", p->tpsi, 1, 8))) return rc;
     // the chain kernel picks the fallback predecessor as an unsigned minimum over the bit patterns of tpsi + dp (bcd.hip),
     // which orders like the doubles only while they are >= 0; the reference starts that minimum (and the end label's) at
     // 800000 (python bcd.py:152-157,231): dp stays in [0, 800000) for every chain when the last rule holds (include/dflow.h)
@@ -59,15 +149,6 @@ int dflow_check_params(const dflow_params *p)
     if (!(p->sigma > 0.0f) || p->sigma > 8.0f) return dflow_set_error(DFLOW_EINVAL, "sigma=%g outside (0,8]", (double)p->sigma);
     if (p->max_attempts < p->ngauss) return dflow_set_error(DFLOW_EINVAL, "max_attempts < ngauss");
     if (p->flags & ~(DFLOW_FLAG_KNN_EXACT | DFLOW_FLAG_DESCR_F16)) return dflow_set_error(DFLOW_EINVAL, "unknown flags 0x%x", (unsigned)p->flags);
-    return DFLOW_OK;
-}
-
-// a pointer the kernels move several elements of at a time; NULL (an optional output left out) passes
-struct AlignedPtr { const char *name; const void *p; uintptr_t align; };
-static int check_aligned(const char *fn, std::initializer_list<AlignedPtr> ptrs)
-{
-    for (const AlignedPtr &q : ptrs)
-        if ((uintptr_t)q.p % q.align) return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", fn, q.name, (int)q.align);
     return DFLOW_OK;
 }
 
@@ -94,20 +175,6 @@ size_t dflow_workspace_bytes(const dflow_params *p)
     return m + DFLOW_WS_SLACK;
 }
 
-#define CHECK_PTR(x) do { if (!(x)) return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", __func__, #x); } while (0)
-// The size of d_ws, then the boundary its stage needs: the widest access a kernel of the stage makes to a region WsCarver hands out
-// (regions start at multiples of 256 bytes from d_ws).  include/dflow.h, Conventions, lists them: 16 for the main-path stages, 8
-// where a region holds doubles or uint64 (bcd_stats.hip, flow_eval.hip, flow_picture.hip's warp, epic.h), 4 for int32 / uint32 /
-// float regions (edges.hip, variational.hip, flow_picture.hip's colour, prior.hip, segments.hip), 2 for pb_edges.hip's uint16
-// plane.  A NULL or short workspace is DFLOW_ENOSPC whatever its alignment, as it always was; the entry points that have
-// always named d_ws among their aligned pointers (bcd_stats, flow_advance, segment_filter) check it there, before its size.
-#define CHECK_WS(align, need) do { \
-    if (!d_ws || ws_bytes < (need)) \
-        return dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", __func__, ws_bytes, (size_t)(need)); \
-    int rc_ws_ = check_aligned(__func__, {{"d_ws", d_ws, (align)}}); if (rc_ws_) return rc_ws_; } while (0)
-// the main-path stages carve float4, int4 and uint4 regions (daisy.hip, knn_mfma.hip, bcd.hip)
-#define WS_ALIGN_MAIN 16
-
 int dflow_daisy(const dflow_params *p, const uint8_t *d_bgr, void *d_descr, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
@@ -125,15 +192,23 @@ int dflow_daisy_pair(const dflow_params *p, const uint8_t *d_bgr1, const uint8_t
     return launch_daisy_pair(p, d_bgr1, d_bgr2, d_descr1, d_descr2, d_ws, (hipStream_t)stream);
 }
 
+// DFLOW_FLAG_KNN_EXACT selects the brute-force VALU kernel (same results; used to cross-check the MFMA path)
+static bool knn_is_screened(const dflow_params *p) { return !(p->flags & DFLOW_FLAG_KNN_EXACT) && knn_mfma_supported(p); }
+
+// The end of the gate of whatever needs the MFMA-screened search: that it runs for *p, then its workspace.
+static int knn_check_screened(const char *fn, const dflow_params *p, const void *d_ws, size_t ws_bytes)
+{
+    if (!knn_is_screened(p)) return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", fn);
+    return check_ws(fn, d_ws, ws_bytes, WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
+}
+
 int dflow_knn_proposals(const dflow_params *p, const void *d_descr1, const void *d_descr2, uint32_t *d_proposals,
                         float *d_lcosts, int32_t *d_nprop, int32_t *d_bestlabels, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
-    // DFLOW_FLAG_KNN_EXACT selects the brute-force VALU kernel (same results; used to cross-check the MFMA path)
-    if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
-        return launch_knn(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, (hipStream_t)stream);
-    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
+    if (!knn_is_screened(p)) return launch_knn(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, (hipStream_t)stream);
+    if ((rc = knn_check_screened(__func__, p, d_ws, ws_bytes))) return rc;
     return launch_knn_mfma(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream);
 }
 
@@ -144,9 +219,7 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
     CHECK_PTR(h_ms);
-    if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
-        return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
-    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
+    if ((rc = knn_check_screened(__func__, p, d_ws, ws_bytes))) return rc;
     hipEvent_t ev[KNN_MFMA_EVENTS] = {};
     rc = [&]() {
         for (hipEvent_t &e : ev) DFLOW_HIP(hipEventCreate(&e));
@@ -168,9 +241,7 @@ int dflow_knn_screen_stats_n(const dflow_params *p, void *d_ws, size_t ws_bytes,
     CHECK_PTR(h_stats);
     if (n_stats < 1 || n_stats > DFLOW_KNN_STATS_ALL_N)
         return dflow_set_error(DFLOW_EINVAL, "%s: n_stats = %d outside 1..%d", __func__, n_stats, DFLOW_KNN_STATS_ALL_N);
-    if ((p->flags & DFLOW_FLAG_KNN_EXACT) || !knn_mfma_supported(p))
-        return dflow_set_error(DFLOW_EINVAL, "%s: the MFMA-screened search does not run for these parameters", __func__);
-    CHECK_WS(WS_ALIGN_MAIN, knn_mfma_ws_bytes(p));
+    if ((rc = knn_check_screened(__func__, p, d_ws, ws_bytes))) return rc;
     int64_t all[DFLOW_KNN_STATS_ALL_N];
     rc = knn_mfma_stats(p, d_ws, (hipStream_t)stream, all);
     if (rc == DFLOW_OK) memcpy(h_stats, all, (size_t)n_stats * sizeof(int64_t));
@@ -205,7 +276,7 @@ int dflow_bcd_phase(const dflow_params *p, const uint32_t *d_proposals, const in
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
-    if (phase < 0 || phase > 3) return dflow_set_error(DFLOW_EINVAL, "phase=%d outside [0,3]", phase);
+    if ((rc = check_int_range(NULL, "phase", phase, 0, 3))) return rc;
     CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
     return launch_bcd_phase(p, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
@@ -225,9 +296,10 @@ int dflow_bcd_phase_batch(const dflow_params *p, int32_t npass, const int32_t *c
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_ws);
-    if (npass < 1 || npass > 1024) return dflow_set_error(DFLOW_EINVAL, "npass=%d outside [1,1024]", npass);
-    if (phase < 0 || phase > 3) return dflow_set_error(DFLOW_EINVAL, "phase=%d outside [0,3]", phase);
-    if (ws_bytes < bcd_ws_bytes(p)) return dflow_set_error(DFLOW_ENOSPC, "%s: workspace %zu < %zu bytes", __func__, ws_bytes, bcd_ws_bytes(p));
+    if ((rc = check_int_range(NULL, "npass", npass, 1, 1024))) return rc;
+    if ((rc = check_int_range(NULL, "phase", phase, 0, 3))) return rc;
+    // one size for every pass, before the passes' own pointers
+    if ((rc = check_ws_size(__func__, d_ws, ws_bytes, bcd_ws_bytes(p)))) return rc;
     for (int i = 0; i < npass; i++)
         if (!d_nprop[i] || !d_bestlabels[i] || !d_ws[i]) return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
     for (int i = 0; i < npass; i++)
@@ -250,15 +322,21 @@ int dflow_bcd_sweep_batch(const dflow_params *p, int32_t npass, const int32_t *c
 static int bcd_stats_check_params(const char *fn, const dflow_params *p)
 {
     if (!p) return dflow_set_error(DFLOW_EINVAL, "%s: params is NULL", fn);
-    if (p->pich < 1 || p->picw < 1 || p->pich > 8192 || p->picw > 8192)
-        return dflow_set_error(DFLOW_EINVAL, "%s: image size %dx%d outside [1,8192]", fn, p->picw, p->pich);
+    int rc = check_frame_size(fn, p->pich, p->picw); if (rc) return rc;
     if (p->label_pitch < 16 || p->label_pitch % 16 != 0 || p->label_pitch > DFLOW_MAX_LABELS)
         return dflow_set_error(DFLOW_EINVAL, "%s: label_pitch=%d must be a multiple of 16 in [16,%d]", fn, p->label_pitch, DFLOW_MAX_LABELS);
     if (p->maxnprop < 1 || p->maxnprop > p->label_pitch)
         return dflow_set_error(DFLOW_EINVAL, "%s: maxnprop=%d outside [1,label_pitch=%d]", fn, p->maxnprop, p->label_pitch);
-    if (p->tpsi < 1 || p->tpsi > 8) return dflow_set_error(DFLOW_EINVAL, "%s: tpsi=%d outside [1,8]", fn, p->tpsi);
-    if (!isfinite(p->tphi) || p->tphi < 0.0f) return dflow_set_error(DFLOW_EINVAL, "%s: tphi=%g must be finite and >= 0", fn, (double)p->tphi);
-    return DFLOW_OK;
+    if ((rc = check_int_range(fn, "tpsi", p->tpsi, 1, 8))) return rc;
+    return check_finite_ge0(fn, "tphi", p->tphi);
+}
+
+// The end of the gates of dflow_bcd_stats and dflow_bcd_stats_batch.  d_stats and d_ws both hold doubles; d_ws has always been
+// named among the aligned pointers here, so its alignment is checked before its size.
+static int bcd_stats_check_out(const char *fn, const dflow_params *p, int32_t npass, const void *d_stats, const void *d_ws, size_t ws_bytes)
+{
+    int rc = check_aligned(fn, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;
+    return check_ws(fn, d_ws, ws_bytes, 8, (size_t)npass * bcd_stats_ws_bytes(p->pich, p->picw));
 }
 
 size_t dflow_bcd_stats_workspace_bytes(const dflow_params *p)
@@ -272,13 +350,12 @@ int dflow_bcd_stats_batch(const dflow_params *p, int32_t npass, const uint32_t *
                           struct dflow_bcd_stats *d_stats, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
-    if (npass < 1 || npass > 1024) return dflow_set_error(DFLOW_EINVAL, "%s: npass=%d outside [1,1024]", __func__, npass);
+    if ((rc = check_int_range(__func__, "npass", npass, 1, 1024))) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
     for (int i = 0; i < npass; i++)
         if (!d_proposals[i] || !d_lcosts[i] || !d_nprop[i] || !d_bestlabels[i])
             return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
-    rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
-    CHECK_WS(8, (size_t)npass * bcd_stats_ws_bytes(p->pich, p->picw));
+    if ((rc = bcd_stats_check_out(__func__, p, npass, d_stats, d_ws, ws_bytes))) return rc;
     return launch_bcd_stats_batch(p, npass, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_prev, d_prev, d_stats, d_ws,
                                   (hipStream_t)stream);
 }
@@ -289,8 +366,7 @@ int dflow_bcd_stats(const dflow_params *p, const uint32_t *d_proposals, const fl
 {
     int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
-    rc = check_aligned(__func__, {{"d_stats", d_stats, 8}, {"d_ws", d_ws, 8}}); if (rc) return rc;     // both hold doubles
-    CHECK_WS(8, bcd_stats_ws_bytes(p->pich, p->picw));
+    if ((rc = bcd_stats_check_out(__func__, p, 1, d_stats, d_ws, ws_bytes))) return rc;
     return launch_bcd_stats_batch(p, 1, &d_proposals, &d_lcosts, &d_nprop, &d_bestlabels, &d_prev_labels, &d_prev_out, d_stats,
                                   d_ws, (hipStream_t)stream);
 }
@@ -319,22 +395,13 @@ int dflow_pack_compat(const dflow_params *p, const uint32_t *d_proposals, const 
     return launch_pack_compat(p, d_proposals, d_nprop, d_packed, (hipStream_t)stream);
 }
 
-static int canny_check_size(const char *fn, int32_t h, int32_t w)
-{
-    if (h < 1 || w < 1 || h > 8192 || w > 8192) return dflow_set_error(DFLOW_EINVAL, "%s: image size %dx%d outside [1,8192]", fn, w, h);
-    return DFLOW_OK;
-}
-
-size_t dflow_canny_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return canny_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_canny_workspace_bytes, canny_ws_bytes)
 
 int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, double high, uint8_t *d_edges, float *d_ivice,
                       void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    // one message names both thresholds
     if (!isfinite(low) || !isfinite(high) || low < 0.0 || high < 0.0)
         return dflow_set_error(DFLOW_EINVAL, "%s: thresholds %g, %g must be finite and >= 0", __func__, low, high);
     CHECK_PTR(d_bgr); CHECK_PTR(d_edges); CHECK_WS(4, canny_ws_bytes(h, w));
@@ -344,35 +411,26 @@ int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, do
     return launch_canny(h, w, d_bgr, lo, hi, d_edges, d_ivice, d_ws, (hipStream_t)stream);
 }
 
-size_t dflow_pb_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return pb_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_pb_workspace_bytes, pb_ws_bytes)
 
 int dflow_pb_edges(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t radius, float *d_strength, float *d_orient_strength,
                    void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (radius < 1 || radius > DFLOW_PB_MAX_RADIUS)
-        return dflow_set_error(DFLOW_EINVAL, "%s: radius=%d outside [1,%d]", __func__, radius, DFLOW_PB_MAX_RADIUS);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "radius", radius, 1, DFLOW_PB_MAX_RADIUS))) return rc;
     CHECK_PTR(d_bgr); CHECK_PTR(d_strength); CHECK_WS(2, pb_ws_bytes(h, w));
     return launch_pb(h, w, d_bgr, radius, d_strength, d_orient_strength, d_ws, (hipStream_t)stream);
 }
 
-size_t dflow_epic_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return epic_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_epic_workspace_bytes, epic_ws_bytes)
 
 int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const float *d_edges, int32_t nn, double k,
                            int32_t method, float *d_flow, int32_t *d_seed_of, uint32_t *d_dist, int32_t *d_lists,
                            uint64_t *d_list_g, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (nn < 1 || nn > 256) return dflow_set_error(DFLOW_EINVAL, "%s: nn=%d outside [1,256]", __func__, nn);
-    if (!isfinite(k) || !(k > 0.0)) return dflow_set_error(DFLOW_EINVAL, "%s: k=%g must be finite and > 0", __func__, k);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "nn", nn, 1, 256))) return rc;
+    if ((rc = check_finite_gt0(__func__, "k", k))) return rc;
     if (method != DFLOW_EPIC_LA && method != DFLOW_EPIC_NW)
         return dflow_set_error(DFLOW_EINVAL, "%s: unknown method %d", __func__, method);
     CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow); CHECK_WS(8, epic_ws_bytes(h, w));
@@ -382,23 +440,17 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
 
 int dflow_epic_last_stats(int32_t *rounds, float *stage_ms) { return epic_last_stats(rounds, stage_ms); }
 
-size_t dflow_epic_prefilter_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return epic_prefilter_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_epic_prefilter_workspace_bytes, epic_prefilter_ws_bytes)
 
 int dflow_epic_prefilter(int32_t h, int32_t w, const uint8_t *d_bgr, const float *d_sparse_in, const float *d_edges,
                          double saliency_th, int32_t pref_nn, double pref_th, double k, float *d_sparse_out, uint8_t *d_reason,
                          float *d_saliency, float *d_estimate, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (!isfinite(saliency_th) || saliency_th < 0.0)
-        return dflow_set_error(DFLOW_EINVAL, "%s: saliency_th=%g must be finite and >= 0", __func__, saliency_th);
-    if (pref_nn < 0 || pref_nn > 255) return dflow_set_error(DFLOW_EINVAL, "%s: pref_nn=%d outside [0,255]", __func__, pref_nn);
-    if (!isfinite(pref_th) || pref_th < 0.0)
-        return dflow_set_error(DFLOW_EINVAL, "%s: pref_th=%g must be finite and >= 0", __func__, pref_th);
-    if (!isfinite(k) || !(k > 0.0)) return dflow_set_error(DFLOW_EINVAL, "%s: k=%g must be finite and > 0", __func__, k);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_finite_ge0(__func__, "saliency_th", saliency_th))) return rc;
+    if ((rc = check_int_range(__func__, "pref_nn", pref_nn, 0, 255))) return rc;
+    if ((rc = check_finite_ge0(__func__, "pref_th", pref_th))) return rc;
+    if ((rc = check_finite_gt0(__func__, "k", k))) return rc;
     if (saliency_th != 0.0 && !d_bgr)
         return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr is NULL with saliency_th=%g (only saliency_th = 0 runs without the image)",
                                __func__, saliency_th);
@@ -417,76 +469,55 @@ void dflow_var_default_params(dflow_var_params *p)
     p->niter_outer = 5; p->niter_inner = 1; p->niter_solver = 30;
 }
 
-size_t dflow_var_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return var_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_var_workspace_bytes, var_ws_bytes)
 
 int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow_in,
                      const dflow_var_params *p, float *d_flow_out, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
     CHECK_PTR(p); CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_flow_in); CHECK_PTR(d_flow_out);
-    const struct { const char *name; float v; } weights[] = {{"alpha", p->alpha}, {"gamma", p->gamma}, {"delta", p->delta}};
-    for (const auto &f : weights)
-        if (!isfinite(f.v) || f.v < 0.0f)
-            return dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and >= 0", __func__, f.name, (double)f.v);
+    if ((rc = check_finite_ge0(__func__, "alpha", p->alpha))) return rc;
+    if ((rc = check_finite_ge0(__func__, "gamma", p->gamma))) return rc;
+    if ((rc = check_finite_ge0(__func__, "delta", p->delta))) return rc;
     if (!isfinite(p->sigma) || p->sigma < 0.0f || p->sigma > 5.0f)
         return dflow_set_error(DFLOW_EINVAL, "%s: sigma=%g outside [0,5]", __func__, (double)p->sigma);
     if (!(p->sor_omega > 0.0f && p->sor_omega < 2.0f))
         return dflow_set_error(DFLOW_EINVAL, "%s: sor_omega=%g outside (0,2)", __func__, (double)p->sor_omega);
-    if (p->niter_outer < 0 || p->niter_outer > 1000)
-        return dflow_set_error(DFLOW_EINVAL, "%s: niter_outer=%d outside [0,1000]", __func__, p->niter_outer);
-    if (p->niter_inner < 1 || p->niter_inner > 1000)
-        return dflow_set_error(DFLOW_EINVAL, "%s: niter_inner=%d outside [1,1000]", __func__, p->niter_inner);
-    if (p->niter_solver < 1 || p->niter_solver > 10000)
-        return dflow_set_error(DFLOW_EINVAL, "%s: niter_solver=%d outside [1,10000]", __func__, p->niter_solver);
-    if (p->flags & ~DFLOW_VAR_FLAG_SOR_UNFUSED) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, p->flags);
+    if ((rc = check_int_range(__func__, "niter_outer", p->niter_outer, 0, 1000))) return rc;
+    if ((rc = check_int_range(__func__, "niter_inner", p->niter_inner, 1, 1000))) return rc;
+    if ((rc = check_int_range(__func__, "niter_solver", p->niter_solver, 1, 10000))) return rc;
+    if ((rc = check_flags(__func__, p->flags, DFLOW_VAR_FLAG_SOR_UNFUSED))) return rc;
     CHECK_WS(4, var_ws_bytes(h, w));
     return launch_var(h, w, d_bgr1, d_bgr2, d_flow_in, p, d_flow_out, d_ws, (hipStream_t)stream);
 }
 
-size_t dflow_eval_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return eval_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_eval_workspace_bytes, eval_ws_bytes)
 
 int dflow_flow_eval(int32_t h, int32_t w, const float *d_test, int32_t test_layout, const float *d_gt, float abs_thresh,
                     uint32_t flags, dflow_eval_stats *d_stats, float *d_err, uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes,
                     void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (test_layout != DFLOW_EVAL_UVV && test_layout != DFLOW_EVAL_DYDX)
-        return dflow_set_error(DFLOW_EINVAL, "%s: unknown test_layout %d", __func__, test_layout);
-    if (!isfinite(abs_thresh) || abs_thresh < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: abs_thresh=%g must be finite and >= 0", __func__, (double)abs_thresh);
-    if (flags & ~DFLOW_EVAL_FLAG_ACCUMULATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "test_layout", test_layout))) return rc;
+    if ((rc = check_finite_ge0(__func__, "abs_thresh", abs_thresh))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_EVAL_FLAG_ACCUMULATE))) return rc;
     CHECK_PTR(d_test); CHECK_PTR(d_gt); CHECK_PTR(d_stats);
     // the kernel moves four pixels per lane with 16-byte loads and stores
-    const struct { const char *name; const void *p; uintptr_t align; } ptrs[] = {
-        {"d_test", d_test, 16}, {"d_gt", d_gt, 16}, {"d_stats", d_stats, 8}, {"d_err", d_err, 16}, {"d_err_bgr", d_err_bgr, 4}};
-    for (const auto &q : ptrs)
-        if ((uintptr_t)q.p % q.align)
-            return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", __func__, q.name, (int)q.align);
+    rc = check_aligned(__func__, {{"d_test", d_test, 16}, {"d_gt", d_gt, 16}, {"d_stats", d_stats, 8}, {"d_err", d_err, 16},
+                                  {"d_err_bgr", d_err_bgr, 4}});
+    if (rc) return rc;
     CHECK_WS(8, eval_ws_bytes(h, w));
     return launch_flow_eval(h, w, d_test, test_layout, d_gt, abs_thresh, flags, d_stats, d_err, d_err_bgr, d_ws, (hipStream_t)stream);
 }
 
-size_t dflow_flow_color_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return flow_color_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_flow_color_workspace_bytes, flow_color_ws_bytes)
 
 int dflow_flow_color(int32_t h, int32_t w, const float *d_flow, int32_t layout, float max_flow, uint8_t *d_bgr, float *d_maxrad,
                      void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (!isfinite(max_flow) || max_flow < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: max_flow=%g must be finite and >= 0 (0: the field's own maximum)", __func__, (double)max_flow);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_finite_ge0(__func__, "max_flow", max_flow, " (0: the field's own maximum)"))) return rc;
     CHECK_PTR(d_flow); CHECK_PTR(d_bgr);
     // the kernels move four pixels per lane: 16-byte loads of the flow, 12-byte stores of the picture
     rc = check_aligned(__func__, {{"d_flow", d_flow, 16}, {"d_bgr", d_bgr, 4}, {"d_maxrad", d_maxrad, 4}}); if (rc) return rc;
@@ -494,23 +525,17 @@ int dflow_flow_color(int32_t h, int32_t w, const float *d_flow, int32_t layout, 
     return launch_flow_color(h, w, d_flow, layout, max_flow, d_bgr, d_maxrad, d_ws, (hipStream_t)stream);
 }
 
-size_t dflow_warp_eval_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return warp_eval_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_warp_eval_workspace_bytes, warp_eval_ws_bytes)
 
 int dflow_warp_eval(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t *d_bgr2, const float *d_flow, int32_t layout,
                     float err_thresh, float err_max, uint32_t flags, dflow_photo_stats *d_stats, uint8_t *d_warped, float *d_err,
                     uint8_t *d_err_bgr, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (!isfinite(err_thresh) || err_thresh < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: err_thresh=%g must be finite and >= 0", __func__, (double)err_thresh);
-    if (!isfinite(err_max) || !(err_max > 0.0f))
-        return dflow_set_error(DFLOW_EINVAL, "%s: err_max=%g must be finite and > 0", __func__, (double)err_max);
-    if (flags & ~DFLOW_WARP_FLAG_ACCUMULATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_finite_ge0(__func__, "err_thresh", err_thresh))) return rc;
+    if ((rc = check_finite_gt0(__func__, "err_max", err_max))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_WARP_FLAG_ACCUMULATE))) return rc;
     CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_flow); CHECK_PTR(d_stats);
     // the kernel moves four pixels per lane: 16-byte loads and stores of the float planes, 12-byte ones of the uint8 planes
     rc = check_aligned(__func__, {{"d_bgr1", d_bgr1, 4}, {"d_flow", d_flow, 16}, {"d_stats", d_stats, 8}, {"d_warped", d_warped, 4},
@@ -526,9 +551,9 @@ int dflow_prior_proposals(const dflow_params *p, const void *d_descr1, const voi
                           int32_t *d_bestlabels, int32_t *d_counts, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (stride < 0 || stride > 8192) return dflow_set_error(DFLOW_EINVAL, "%s: stride=%d outside [0,8192]", __func__, stride);
-    if (flags & ~DFLOW_PRIOR_SEED_LABELS) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_int_range(__func__, "stride", stride, 0, 8192))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_PRIOR_SEED_LABELS))) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_prior); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop);
     CHECK_PTR(d_bestlabels);
     // the kernel reads the label rows and the descriptors' tails 16 bytes at a time
@@ -544,18 +569,14 @@ int dflow_prior_proposals(const dflow_params *p, const void *d_descr1, const voi
                         (hipStream_t)stream);
 }
 
-size_t dflow_flow_advance_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return flow_advance_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_flow_advance_workspace_bytes, flow_advance_ws_bytes)
 
 int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout, uint32_t flags, float *d_out, int32_t *d_counts,
                        void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (flags & ~DFLOW_ADVANCE_NEGATE) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_ADVANCE_NEGATE))) return rc;
     CHECK_PTR(d_flow); CHECK_PTR(d_out);
     rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}, {"d_ws", d_ws, 4}});
     if (rc) return rc;
@@ -567,7 +588,7 @@ int dflow_flow_advance(int32_t h, int32_t w, const float *d_flow, int32_t layout
 
 int dflow_pyr_down(int32_t h, int32_t w, const uint8_t *d_in1, const uint8_t *d_in2, uint8_t *d_out1, uint8_t *d_out2, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
     CHECK_PTR(d_in1); CHECK_PTR(d_out1);
     if ((d_in2 == NULL) != (d_out2 == NULL))
         return dflow_set_error(DFLOW_EINVAL, "%s: d_in2 and d_out2 must both be NULL or both be given", __func__);
@@ -584,8 +605,8 @@ int dflow_pyr_down(int32_t h, int32_t w, const uint8_t *d_in1, const uint8_t *d_
 
 int dflow_flow_upsample(int32_t h, int32_t w, const float *d_coarse, int32_t layout, float *d_out, int32_t *d_counts, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
     CHECK_PTR(d_coarse); CHECK_PTR(d_out);
     rc = check_aligned(__func__, {{"d_coarse", d_coarse, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
     if (rc) return rc;
@@ -600,12 +621,11 @@ int dflow_flow_consistency(int32_t h, int32_t w, const float *d_fwd, int32_t lay
                            float thresh, uint32_t flags, float *d_out_fwd, float *d_out_bwd, float *d_err_fwd, float *d_err_bwd,
                            int32_t *d_counts, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    for (int layout : {layout_fwd, layout_bwd})
-        if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (flags & ~DFLOW_FBC_BILINEAR) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
-    if (!isfinite(thresh) || thresh < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: thresh=%g must be finite and >= 0", __func__, (double)thresh);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout_fwd))) return rc;     // neither message says which of the two it is
+    if ((rc = check_layout(__func__, "layout", layout_bwd))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_FBC_BILINEAR))) return rc;
+    if ((rc = check_finite_ge0(__func__, "thresh", thresh))) return rc;
     CHECK_PTR(d_fwd); CHECK_PTR(d_bwd); CHECK_PTR(d_out_fwd);
     if (d_err_bwd && !d_out_bwd) return dflow_set_error(DFLOW_EINVAL, "%s: d_err_bwd needs d_out_bwd", __func__);
     rc = check_aligned(__func__, {{"d_fwd", d_fwd, 4}, {"d_bwd", d_bwd, 4}, {"d_out_fwd", d_out_fwd, 4}, {"d_out_bwd", d_out_bwd, 4},
@@ -624,20 +644,15 @@ int dflow_flow_consistency(int32_t h, int32_t w, const float *d_fwd, int32_t lay
                                    d_counts, (hipStream_t)stream);
 }
 
-size_t dflow_segment_filter_workspace_bytes(int32_t h, int32_t w)
-{
-    if (canny_check_size(__func__, h, w) != DFLOW_OK) return 0;
-    return segment_filter_ws_bytes(h, w);
-}
+FRAME_WS_BYTES(dflow_segment_filter_workspace_bytes, segment_filter_ws_bytes)
 
 int dflow_segment_filter(int32_t h, int32_t w, const float *d_flow, int32_t layout, float thresh, int32_t min_size, uint32_t flags,
                          float *d_out, int32_t *d_segment, int32_t *d_size, int32_t *d_counts, void *d_ws, size_t ws_bytes, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (flags & ~DFLOW_SEG_KEEP_SINGLETONS) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
-    if (!isfinite(thresh) || thresh < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: thresh=%g must be finite and >= 0", __func__, (double)thresh);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_SEG_KEEP_SINGLETONS))) return rc;
+    if ((rc = check_finite_ge0(__func__, "thresh", thresh))) return rc;
     if (min_size < 0) return dflow_set_error(DFLOW_EINVAL, "%s: min_size=%d must be >= 0", __func__, min_size);
     CHECK_PTR(d_flow); CHECK_PTR(d_out);
     rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_segment", d_segment, 4}, {"d_size", d_size, 4},
@@ -668,16 +683,13 @@ int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_
                        uint8_t *d_out, uint64_t *d_keys, float *d_motion, float *d_motion_tmp, uint8_t *d_source, int32_t *d_counts,
                        void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout_fwd != DFLOW_EVAL_UVV && layout_fwd != DFLOW_EVAL_DYDX)
-        return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout_fwd %d", __func__, layout_fwd);
-    if (d_bwd && layout_bwd != DFLOW_EVAL_UVV && layout_bwd != DFLOW_EVAL_DYDX)
-        return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout_bwd %d", __func__, layout_bwd);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout_fwd", layout_fwd))) return rc;
+    if (d_bwd && (rc = check_layout(__func__, "layout_bwd", layout_bwd))) return rc;
     if (!isfinite(t) || !(t > 0.0f && t < 1.0f)) return dflow_set_error(DFLOW_EINVAL, "%s: t=%g must lie in (0, 1)", __func__, (double)t);
-    if (fill_rounds < 0 || fill_rounds > 64) return dflow_set_error(DFLOW_EINVAL, "%s: fill_rounds=%d outside [0,64]", __func__, fill_rounds);
-    if (!isfinite(occl_thresh) || occl_thresh < 0.0f)
-        return dflow_set_error(DFLOW_EINVAL, "%s: occl_thresh=%g must be finite and >= 0", __func__, (double)occl_thresh);
-    if (flags) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
+    if ((rc = check_int_range(__func__, "fill_rounds", fill_rounds, 0, 64))) return rc;
+    if ((rc = check_finite_ge0(__func__, "occl_thresh", occl_thresh))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
     CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_fwd); CHECK_PTR(d_out); CHECK_PTR(d_keys); CHECK_PTR(d_motion);
     if (fill_rounds > 0 && !d_motion_tmp) return dflow_set_error(DFLOW_EINVAL, "%s: d_motion_tmp is NULL with fill_rounds > 0", __func__);
     // the keys are updated with 64-bit atomics; every other plane is read and written a float, an int32 or a byte at a time
@@ -685,16 +697,10 @@ int dflow_frame_interp(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_
                                   {"d_motion_tmp", d_motion_tmp, 4}, {"d_counts", d_counts, 4}});
     if (rc) return rc;
     // every plane is read or written by lanes other than the pixel's own
-    const struct { const char *name; const void *p; } ins[] = {{"d_bgr1", d_bgr1}, {"d_bgr2", d_bgr2}, {"d_fwd", d_fwd}, {"d_bwd", d_bwd}},
-        outs[] = {{"d_out", d_out}, {"d_keys", d_keys}, {"d_motion", d_motion}, {"d_motion_tmp", d_motion_tmp},
-                  {"d_source", d_source}, {"d_counts", d_counts}};
-    for (size_t i = 0; i < 6; i++) {
-        if (!outs[i].p) continue;
-        for (size_t j = 0; j < 4; j++)
-            if (outs[i].p == ins[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, ins[j].name);
-        for (size_t j = 0; j < i; j++)
-            if (outs[i].p == outs[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, outs[j].name);
-    }
+    rc = check_distinct(__func__, {{"d_bgr1", d_bgr1}, {"d_bgr2", d_bgr2}, {"d_fwd", d_fwd}, {"d_bwd", d_bwd}},
+                        {{"d_out", d_out}, {"d_keys", d_keys}, {"d_motion", d_motion}, {"d_motion_tmp", d_motion_tmp},
+                         {"d_source", d_source}, {"d_counts", d_counts}});
+    if (rc) return rc;
     return launch_frame_interp(h, w, d_bgr1, d_bgr2, d_fwd, layout_fwd, d_bwd, layout_bwd, t, fill_rounds, occl_thresh, d_out, d_keys,
                                d_motion, d_motion_tmp, d_source, d_counts, (hipStream_t)stream);
 }
@@ -703,26 +709,19 @@ int dflow_flow_wmedian(int32_t h, int32_t w, const float *d_flow, int32_t layout
                        const uint8_t *d_wspace, const uint8_t *d_wcolor, float reject_thresh, uint32_t flags, float *d_out,
                        int32_t *d_counts, void *stream)
 {
-    int rc = canny_check_size(__func__, h, w); if (rc) return rc;
-    if (layout != DFLOW_EVAL_UVV && layout != DFLOW_EVAL_DYDX) return dflow_set_error(DFLOW_EINVAL, "%s: unknown layout %d", __func__, layout);
-    if (radius < 1 || radius > 8) return dflow_set_error(DFLOW_EINVAL, "%s: radius=%d outside [1,8]", __func__, radius);
-    if (flags & ~(DFLOW_WMED_KEEP_HOLES | DFLOW_WMED_REJECT)) return dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", __func__, flags);
-    if ((flags & DFLOW_WMED_REJECT) && (!isfinite(reject_thresh) || reject_thresh < 0.0f))
-        return dflow_set_error(DFLOW_EINVAL, "%s: reject_thresh=%g must be finite and >= 0", __func__, (double)reject_thresh);
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_int_range(__func__, "radius", radius, 1, 8))) return rc;
+    if ((rc = check_flags(__func__, flags, DFLOW_WMED_KEEP_HOLES | DFLOW_WMED_REJECT))) return rc;
+    if ((flags & DFLOW_WMED_REJECT) && (rc = check_finite_ge0(__func__, "reject_thresh", reject_thresh))) return rc;
     CHECK_PTR(d_flow); CHECK_PTR(d_out);
     if (!d_bgr != !d_wcolor) return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr and d_wcolor must both be NULL or both be given", __func__);
     rc = check_aligned(__func__, {{"d_flow", d_flow, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
     if (rc) return rc;
     // a pixel's neighbours are read after other pixels have been written
-    const struct { const char *name; const void *p; } ins[] = {{"d_flow", d_flow}, {"d_bgr", d_bgr}, {"d_wspace", d_wspace}, {"d_wcolor", d_wcolor}},
-        outs[] = {{"d_out", d_out}, {"d_counts", d_counts}};
-    for (size_t i = 0; i < 2; i++) {
-        if (!outs[i].p) continue;
-        for (size_t j = 0; j < 4; j++)
-            if (outs[i].p == ins[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, ins[j].name);
-        for (size_t j = 0; j < i; j++)
-            if (outs[i].p == outs[j].p) return dflow_set_error(DFLOW_EINVAL, "%s: %s is the same plane as %s", __func__, outs[i].name, outs[j].name);
-    }
+    rc = check_distinct(__func__, {{"d_flow", d_flow}, {"d_bgr", d_bgr}, {"d_wspace", d_wspace}, {"d_wcolor", d_wcolor}},
+                        {{"d_out", d_out}, {"d_counts", d_counts}});
+    if (rc) return rc;
     return launch_flow_wmedian(h, w, d_flow, layout, d_bgr, radius, d_wspace, d_wcolor, reject_thresh, flags, d_out, d_counts,
                                (hipStream_t)stream);
 }
