@@ -7,8 +7,9 @@
 //                      between label tl of p and label k of p's predecessor on that chain } -- the reference's
 //                      packedksets (Q8), restricted to the two neighbours that are ever used and already transposed
 //                      for the direction in which the chain runs.  One wave per PREDECESSOR pixel: its labels are
-//                      wave-uniform, lanes = the labels of its two successors (column chain, row chain); one v_sad_u16 +
-//                      one v_alignbit per 64 pairs builds the 160-bit rows in registers.  What
+//                      wave-uniform, lanes = the labels of its two successors (column chain, row chain); the 160-bit rows come
+//                      from range lookups in the rotated coordinates dy + dx, dy - dx (two small tables per wave in LDS), or,
+//                      for labels spread too wide for the tables, from one v_sad_u16 + one v_alignbit per 64 pairs.  What
 //                      the chain kernel streams is compact: per (pixel, direction, label) ONE 8-byte block with the first 5
 //                      members (index bytes + their pair costs) and the member count; labels with more than 5 (21 %) /
 //                      more than 10 (2.6 %) members own a second / third block, stored COMPACTED per 64-label wave (ballot
@@ -89,14 +90,126 @@ struct BcdPlanes {
 // of q's row are shared, and the labels 128..159 of the two successors (22 of 32 in use) share ONE group of 64 lanes:
 // 5 lane groups for 300 labels where one wave per (pixel, direction) had 6.  (The bench responds to this kernel's VALU
 // count one to one)  A pixel that starts a chain has no predecessor: its empty rows are written by its own wave.
-__global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, int tpsi, const uint32_t *__restrict__ proposals,
+//
+// The rows come from RANGE LOOKUPS, not from pair tests.  For integers |a| + |b| = max(|a + b|, |a - b|), so with u = dy + dx and
+// v = dy - dx per label, |dy-dy'| + |dx-dx'| < tpsi is exactly |u-u'| < tpsi and |v-v'| < tpsi: the members of a label are q's
+// labels inside a box in (u, v), a box is two 1-D ranges, and a 1-D range over q's <= 160 labels is the difference of two
+// prefix sets.  Per wave and axis, two tables in LDS:
+//   C[x]  (bytes, x relative to the wave's smallest coordinate)  the number of q's labels with coordinate < x: one
+//         ds_add_rtn_u32 per label into byte counters packed four to a dword (counts <= 160: no carry), then a prefix sum over the
+//         bytes.  All coordinates are below BCD_RANGE_R = the table's last byte, so that byte holds pn and a query clamps to
+//         [0, BCD_RANGE_R] with one v_med3.
+//   P[r]  (5 words, r = 0..pn)  the set of the r labels of smallest coordinate.  A label's place is C[its value] + its arrival
+//         order among equal values (the byte the atomic returned); that order differs from run to run and never reaches the
+//         output, because P is only read at r = C[x], where equal values are all in or all out.  Every label writes the entry
+//         after its place (one bit), a prefix OR over the entries follows.
+// A successor label at us then owns P[C[us + tpsi]] \ P[C[us - tpsi + 1]] on that axis; the AND of the two axes, inverted, is the
+// row the emit half consumes.  u runs first and its result waits in the row registers while v reuses the tables.  C overlays the
+// LDS of the wave's member lists (dead until emit).  A wave whose labels span BCD_RANGE_R or more on either axis (no pixel of the bench
+// frames) takes the all-pairs loop: the general path and the reference of this one.
+#ifndef BCD_RANGE_BYTES
+#define BCD_RANGE_BYTES 768              // rank table per wave, a multiple of 256.  The spread of a pixel's labels on the bench frames:
+                                         // median 363, at most 539
+#endif
+#define BCD_RANGE_R (BCD_RANGE_BYTES - 1)
+#ifndef BCD_RANGE_PITCH
+#define BCD_RANGE_PITCH 5                // words per prefix-set entry: 8 (b128 + b32 accesses), 6 (b64 + b64 + b32) or 5 (b32 only)
+#endif
+#define BCD_RANGE_ENTRIES (DFLOW_MAX_LABELS + 1)
+// LDS per wave: the rank table, behind it the prefix sets; emit's member lists (64 rows of 16 bytes) then take the front.  With
+// 768 + 161 * 20 bytes inside 4 KB, and the 4 KB of s_cols, a block of four waves has 20 KB: eight blocks per CU, as many
+// waves per SIMD as 64 VGPRs allow (7 waves per SIMD: + 6 % kernel time, 6: + 15 %, 5: + 28 %)
+#ifndef BCD_LISTS_WAVE_LDS
+#define BCD_LISTS_WAVE_LDS 4096
+#endif
+static_assert(BCD_RANGE_BYTES % 256 == 0 && BCD_RANGE_BYTES >= 256 && BCD_RANGE_BYTES <= 1024, "rank table: 1..4 dwords per lane");
+static_assert(BCD_RANGE_BYTES + BCD_RANGE_ENTRIES * BCD_RANGE_PITCH * 4 <= BCD_LISTS_WAVE_LDS && BCD_LISTS_WAVE_LDS >= 1024, "a wave's LDS");
+static_assert(BCD_RANGE_PITCH >= BCD_MASK_WORDS && BCD_RANGE_PITCH <= 8, "prefix-set entry pitch");
+
+// What one lane wrote to LDS, every lane of the same wave may read after this (LDS serves a wave's requests in order: nothing to
+// wait for, the compiler just must not move the accesses across)
+__device__ static inline void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// the value of the lane CTRL points at; 0 where there is no such lane or the row is not in ROWS
+template <int CTRL, int ROWS = 0xF> __device__ static inline uint32_t dpp_or0(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, false);
+}
+// inclusive scans over the 64 lanes: row_shr 1, 2, 4, 8, then lane 15 of a row into the next row, lane 31 into rows 2 and 3
+__device__ static inline uint32_t wave_scan_add(uint32_t x)
+{
+    x += dpp_or0<0x111>(x); x += dpp_or0<0x112>(x); x += dpp_or0<0x114>(x); x += dpp_or0<0x118>(x);
+    x += dpp_or0<0x142, 0xA>(x); x += dpp_or0<0x143, 0xC>(x);
+    return x;
+}
+// (the words of a set step by step side by side: a DPP operand wants two idle states after its write, other words fill them)
+template <int CTRL, int ROWS = 0xF> __device__ static inline void sets_or_step(uint32_t (&x)[BCD_MASK_WORDS])
+{
+#pragma unroll
+    for (int w = 0; w < BCD_MASK_WORDS; w++) x[w] |= dpp_or0<CTRL, ROWS>(x[w]);
+}
+__device__ static inline void wave_scan_or(uint32_t (&x)[BCD_MASK_WORDS])
+{
+    sets_or_step<0x111>(x); sets_or_step<0x112>(x); sets_or_step<0x114>(x); sets_or_step<0x118>(x);
+    sets_or_step<0x142, 0xA>(x); sets_or_step<0x143, 0xC>(x);
+}
+template <int CTRL, int ROWS = 0xF> __device__ static inline int dpp_min(int v)
+{
+    return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xF, false));
+}
+__device__ static inline int wave_min(int x)                 // wave-uniform
+{
+    x = dpp_min<0x111>(x); x = dpp_min<0x112>(x); x = dpp_min<0x114>(x); x = dpp_min<0x118>(x);
+    x = dpp_min<0x142, 0xA>(x); x = dpp_min<0x143, 0xC>(x);
+    return __builtin_amdgcn_readlane(x, 63);
+}
+__device__ static inline void sets_load(const uint32_t *e, uint32_t (&w)[BCD_MASK_WORDS])
+{
+    if constexpr (BCD_RANGE_PITCH % 4 == 0) {
+        const uint4 a = *reinterpret_cast<const uint4 *>(e);
+        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+    } else if constexpr (BCD_RANGE_PITCH % 2 == 0) {
+        const uint2 a = *reinterpret_cast<const uint2 *>(e), b = *reinterpret_cast<const uint2 *>(e + 2);
+        w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y;
+    } else {
+        w[0] = e[0]; w[1] = e[1]; w[2] = e[2]; w[3] = e[3];
+    }
+    w[4] = e[4];
+}
+__device__ static inline void sets_store(uint32_t *e, const uint32_t (&w)[BCD_MASK_WORDS])
+{
+    if constexpr (BCD_RANGE_PITCH % 4 == 0) {
+        *reinterpret_cast<uint4 *>(e) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else if constexpr (BCD_RANGE_PITCH % 2 == 0) {
+        *reinterpret_cast<uint2 *>(e) = make_uint2(w[0], w[1]); *reinterpret_cast<uint2 *>(e + 2) = make_uint2(w[2], w[3]);
+    } else {
+        e[0] = w[0]; e[1] = w[1]; e[2] = w[2]; e[3] = w[3];
+    }
+    e[4] = w[4];
+}
+// u (AX = 0) and v (AX = 1) of a biased flow, both in [0, 131070] (v moved up by 65535; the bias cancels in every difference)
+template <int AX> __device__ static inline int range_coord(uint32_t f)
+{
+    const int lo = (int)(f & 0xFFFFu), hi = (int)(f >> 16);
+    return AX ? lo - hi + 65535 : lo + hi;
+}
+
+#ifndef BCD_LISTS_WAVES
+#define BCD_LISTS_WAVES 8                // waves per SIMD the kernel is compiled for: 64 VGPRs
+#endif
+__global__ void __launch_bounds__(256, BCD_LISTS_WAVES) bcd_lists_kernel(int H, int W, int LP, int tpsi, const uint32_t *__restrict__ proposals,
                                                         const float *__restrict__ lcosts, const int32_t *__restrict__ nprop,
                                                         BcdPlanes pl)
 {
     __shared__ uint32_t s_cols[4][256];                      // q's biased labels, per wave; a whole row per index BYTE, so that the
-                                                             // empty list slot 0xFF reads inside it (8 KB of LDS per block with
-                                                             // s_list: no limit at 8 blocks of 4 waves per CU)
-    __shared__ __attribute__((aligned(16))) uint8_t s_list[4][64][16];   // member lists being built, per wave and lane
+                                                             // empty list slot 0xFF reads inside it (20 KB of LDS per block with
+                                                             // s_wave: 8 blocks of 4 waves per CU)
+    __shared__ __attribute__((aligned(16))) uint8_t s_wave[4][BCD_LISTS_WAVE_LDS];   // per wave: the rank table C and the prefix
+                                                             // sets P; then the member lists being built, 16 bytes per lane
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int q = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wv);
     if (q >= H * W) return;
@@ -155,6 +268,7 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
         }
     }
     if (!v0 && !v1) return;
+    // The all-pairs build, for waves whose labels do not fit the rank table (and the reference of the range path below):
     // lanes = labels of the successors (five groups of 64), q's labels come one by one as wave-uniform scalars (scalar
     // loads of q's row): D = sad + (2^31 - tpsi) has bit 31 set iff the pair is NOT compatible, v_alignbit shifts that bit
     // into the row word.  Columns run downwards inside each 32-bit word so that column c ends up in bit c; of the columns >= pn
@@ -196,7 +310,125 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
             }
         }
     };
-    if (fifth) build(IntC<1>()); else build(IntC<0>());
+    // The range path (header of this section).  q's coordinates relative to the wave's smallest, per axis; a wave whose labels
+    // do not fit the rank table on both axes takes the all-pairs loop.
+    const int pt = min(pn, DFLOW_MAX_LABELS);                // the rows have 160 columns
+    int cq[2][3], org[2];
+    bool wide = false;
+#pragma unroll
+    for (int j = 0; j < 3; j++) { cq[0][j] = range_coord<0>(fq[j]); cq[1][j] = range_coord<1>(fq[j]); }
+#pragma unroll
+    for (int ax = 0; ax < 2; ax++) {
+        int mn = 1 << 18;                                    // no label: above every coordinate, every query clamps to 0
+#pragma unroll
+        for (int j = 0; j < 3; j++) if (lane + 64 * j < pt) mn = min(mn, cq[ax][j]);
+        org[ax] = wave_min(mn);
+#pragma unroll
+        for (int j = 0; j < 3; j++) { cq[ax][j] -= org[ax]; wide |= lane + 64 * j < pt && cq[ax][j] >= BCD_RANGE_R; }
+    }
+    if (__ballot(wide)) {                                    // wave-uniform
+        if (fifth) build(IntC<1>()); else build(IntC<0>());
+    } else {
+        constexpr int NW = BCD_RANGE_BYTES / 256;            // dwords of the rank table per lane
+        uint32_t *const cw = reinterpret_cast<uint32_t *>(&s_wave[wv][0]);
+        const uint8_t *const cb = &s_wave[wv][0];
+        uint32_t *const sets = reinterpret_cast<uint32_t *>(&s_wave[wv][BCD_RANGE_BYTES]);
+        auto axis = [&](auto axc) {
+            constexpr int AX = decltype(axc)::value;
+            // C: byte counters, one atomic per label; the byte it returns is the label's arrival order among equal values
+#pragma unroll
+            for (int i = 0; i < NW; i++) cw[lane * NW + i] = 0u;
+            wave_lds_sync();
+            uint32_t ord[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                ord[j] = 0u;
+                if (lane + 64 * j < pt) {
+                    const uint32_t rel = (uint32_t)cq[AX][j], sh = 8u * (rel & 3u);
+                    ord[j] = (atomicAdd(&cw[rel >> 2], 1u << sh) >> sh) & 0xFFu;
+                }
+            }
+            wave_lds_sync();
+            // exclusive prefix sum over the bytes: inside a dword by two shifted additions, across the lane's dwords and the
+            // lanes by a scan of the dword totals.  No byte exceeds pn <= 160.  (Shifts and a byte permute, not products with
+            // 0x01010101: a 32-bit multiplication runs at a quarter of the rate)
+            uint32_t t[NW], before[NW], tot = 0u;
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                t[i] = cw[lane * NW + i];
+                t[i] += t[i] << 8; t[i] += t[i] << 16;       // byte b = the sum of the bytes 0..b
+                before[i] = tot; tot += t[i] >> 24;
+            }
+            const uint32_t lower = wave_scan_add(tot) - tot;
+#pragma unroll
+            for (int i = 0; i < NW; i++) {
+                const uint32_t base = lower + before[i];
+                cw[lane * NW + i] = (t[i] << 8) + __builtin_amdgcn_perm(base, base, 0x00000000u);      // base in all four bytes
+            }
+            if (lane == 0) {
+                const uint32_t none[BCD_MASK_WORDS] = {0u, 0u, 0u, 0u, 0u};
+                sets_store(sets, none);
+            }
+            wave_lds_sync();
+            // P: the label at place r owns bit k of entry r + 1 ...
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                if (lane + 64 * j < pt) {
+                    const uint32_t r = (uint32_t)cb[cq[AX][j]] + ord[j], bit = 1u << (lane & 31);
+                    uint32_t one[BCD_MASK_WORDS] = {0u, 0u, 0u, 0u, 0u};
+                    one[2 * j] = half ? 0u : bit;
+                    if (j < 2) one[2 * j + 1] = half ? bit : 0u;          // k = 128 + lane < 160: word 4 only
+                    sets_store(sets + (r + 1u) * BCD_RANGE_PITCH, one);
+                }
+            }
+            wave_lds_sync();
+            // ... and a prefix OR over the entries 0..pn, three consecutive ones per lane
+            uint32_t a[3][BCD_MASK_WORDS];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+#pragma unroll
+                for (int w = 0; w < BCD_MASK_WORDS; w++) a[i][w] = 0u;
+                if (3 * lane + i <= pt) sets_load(sets + (3 * lane + i) * BCD_RANGE_PITCH, a[i]);
+            }
+#pragma unroll
+            for (int w = 0; w < BCD_MASK_WORDS; w++) { a[1][w] |= a[0][w]; a[2][w] |= a[1][w]; }
+            wave_scan_or(a[2]);                              // the lane's last entry is final with that
+#pragma unroll
+            for (int w = 0; w < BCD_MASK_WORDS; w++) {
+                const uint32_t lower_lanes = dpp_or0<0x138>(a[2][w]);                    // wave_shr:1
+                a[0][w] |= lower_lanes; a[1][w] |= lower_lanes;
+            }
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+                if (3 * lane + i <= pt) sets_store(sets + (3 * lane + i) * BCD_RANGE_PITCH, a[i]);
+            wave_lds_sync();
+            // the successors' labels: the set inside (us - tpsi, us + tpsi) = P[C[us + tpsi]] without P[C[us - tpsi + 1]].
+            // Columns >= pn are in no set, so the inverted row has them as "not compatible" without further ado.
+#pragma unroll
+            for (int g = 0; g < 5; g++) {
+                if (g < 4 || fifth) {
+                    const int c = range_coord<AX>(f[g]) - org[AX];
+                    const int hi = min(max(c + tpsi, 0), BCD_RANGE_R), lo = min(max(c - tpsi + 1, 0), BCD_RANGE_R);      // v_med3_i32
+                    uint32_t in[BCD_MASK_WORDS], out[BCD_MASK_WORDS];
+                    sets_load(sets + (uint32_t)cb[hi] * BCD_RANGE_PITCH, in);
+                    sets_load(sets + (uint32_t)cb[lo] * BCD_RANGE_PITCH, out);
+#pragma unroll
+                    for (int w = 0; w < BCD_MASK_WORDS; w++) {
+                        if (AX == 0) m[g][w] = in[w] & ~out[w];
+                        else m[g][w] = ~(m[g][w] & in[w] & ~out[w]);
+                        asm("" : "+v"(m[g][w]));             // here, not after the last group's loads: one register, not two or three
+                    }
+                } else {
+#pragma unroll
+                    for (int w = 0; w < BCD_MASK_WORDS; w++) m[g][w] = 0xFFFFFFFFu;   // no label in the fifth group
+                }
+                if (g & 1) __builtin_amdgcn_sched_barrier(0);            // two groups' sets in flight, not all five: registers
+            }
+            wave_lds_sync();                                 // v, then emit, write where these lanes have read
+        };
+        axis(IntC<0>());
+        axis(IntC<1>());
+    }
 
     // One group of 64 labels: member lists, blocks, pool rows.  MERGED = the fifth group (two pixels, 32 labels each): label,
     // count and output rows are per lane, ranks are taken inside each half.
@@ -216,7 +448,7 @@ __global__ void __launch_bounds__(256) bcd_lists_kernel(int H, int W, int LP, in
         // the first 15 members as bytes: every lane appends to its 16-byte row in LDS (one ds_write_b8 and a pointer
         // increment per member; a shift register in VGPRs costs four instructions per member of the wave's LONGEST list) and
         // reads the row back in place
-        uint8_t *row = &s_list[wv][lane][0];
+        uint8_t *row = &s_wave[wv][16 * lane];
         *reinterpret_cast<uint4 *>(row) = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
         const int n = min(cnt, BCD_LIST);
         const bool any = __ballot(cnt > 0) != 0ull;           // wave-uniform
