@@ -740,6 +740,79 @@ int dflow_flow_wmedian(int32_t h, int32_t w, const float *d_flow, int32_t layout
         float reject_thresh, uint32_t flags,
         float *d_out /* (h,w,3) [U,V,valid] */, int32_t *d_counts /* NULL or int32[4] */, void *stream);
 
+/* Robust global-motion fit of a flow field (DESIGN.md "Global-motion fit"): the affine map or the homography that most vectors of
+ * a flow field agree with, found by random minimal samples (RANSAC with local rounds and a least-squares polish), with the
+ * inlier / outlier classes, the model's own dense flow and the residual flow.  This build's definition; the reference has no
+ * counterpart.  1 <= h, w <= 8192, n = h*w.  d_flow is (h,w,.) float32 in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout; a vector is
+ * GOOD as in dflow_flow_consistency.  d_exclude (NULL: nothing) is (h,w) uint8, non-zero = the pixel takes no part.  Pixel i = y*w
+ * + x TAKES PART if its vector (U,V) is good and it is not excluded; it is SCORED if it takes part and y % step == 0 && x % step
+ * == 0.  xf = (float)x, yf = (float)y, and its target is tx = xf + U, ty = yf + V (float32).  A model is float32[9], row-major M:
+ * (x,y,1) -> (X,Y,W), the position in frame 2 being (X/W, Y/W).  Float32 and float64 chains are one IEEE operation per written
+ * operation; everything else is an integer.  The result depends on no order of arrival, and two calls give the same bytes.
+ *   INLIER of model m (float32): X = (m0*xf + m1*yf) + m2, Y = (m3*xf + m4*yf) + m5, W = (m6*xf + m7*yf) + m8, ex = X - W*tx,
+ *     ey = Y - W*ty; inlier iff W > 0 && ex*ex + ey*ey <= (thresh*W)*(thresh*W).  A NaN anywhere makes it false.
+ *   A. HYPOTHESES.  The current model starts as the identity.  Rounds r = 0 .. lo_rounds, hypotheses j = 0 .. n_hyp-1, each of
+ *     m = 3 (DFLOW_MOTION_AFFINE) or 4 (DFLOW_MOTION_HOMOGRAPHY) points.  Point k = 0 .. m-1 tries attempts a = 0 .. 15: Philox4x32-10
+ *     with counter (j, (r*4 + k)*16 + a, 0, 0) and key (seed & 0xFFFFFFFF, seed >> 32), word 0 = u, i = ((uint64)u * n) >> 32.  The
+ *     first i is accepted that takes part, differs from the points accepted before it and, in rounds r > 0, is an inlier of the
+ *     current model (the best of the rounds before; the identity if there is none).  A point without one in 16 attempts makes the
+ *     hypothesis DEGENERATE.  Solve, in float64: P = the smallest power of two >= max(h,w), s = 1/P, cx = (w-1)/2, cy = (h-1)/2,
+ *     a_k = (xf - cx)*s, b_k = (yf - cy)*s, p_k = (tx - cx)*s, q_k = (ty - cy)*s.  Affine: rows [a_k, b_k, 1 | p_k, q_k], k = 0..2,
+ *     one elimination with two right-hand sides -> N = [[n0,n1,n2],[n3,n4,n5],[0,0,1]].  Homography: rows 2k = [a,b,1,0,0,0,
+ *     -(a*p), -(b*p) | p] and 2k+1 = [0,0,0,a,b,1, -(a*q), -(b*q) | q], k = 0..3 -> N = [[n0,n1,n2],[n3,n4,n5],[n6,n7,1]].
+ *     ELIMINATION of an N x N system: for column c = 0.., the pivot is the row r >= c with the largest |A[r][c]|, the first such
+ *     row winning; a pivot that is not >= 2^-40 makes the hypothesis degenerate; rows c and pivot are swapped; for every row r > c:
+ *     f = A[r][c] / A[c][c], A[r][k] = A[r][k] - f*A[c][k] for k > c.  Back substitution from the last row: t = rhs[r]; for k =
+ *     r+1.. ascending t = t - A[r][k]*x[k]; x[r] = t / A[r][r].  To pixel coordinates, row i of N: r0 = n_i0*s, r1 = n_i1*s, r2 =
+ *     (n_i2 - r0*cx) - r1*cy -> R; M_0c = P*R_0c + cx*R_2c, M_1c = P*R_1c + cy*R_2c, M_2c = R_2c; each entry is then cast to
+ *     float32 (for affine the last row is exactly (0,0,1)).  Also degenerate: a float32 entry that is not finite; for a homography,
+ *     W <= 0 (in the float32 expression above) at one of its own sample points.  A degenerate hypothesis stores the identity and
+ *     its count is 0.
+ *   B. SCORE.  d_hyp_counts[j] = the number of scored pixels that are inliers of hypothesis j (int32, integer adds).
+ *   C. BEST.  Every hypothesis that is not degenerate offers the key (uint64)count << 32 | (0xFFFFFFFF - (r*65536 + j)) to a
+ *     64-bit maximum in d_state[0], which starts at 0 and is kept across the rounds: the larger count wins, at equal counts the
+ *     earlier round, then the smaller j.  After a round whose hypothesis holds the maximum, that hypothesis is the current model.
+ *     d_state[0] == 0 (every hypothesis of every round degenerate): the model is the identity, the best round and index are -1, and
+ *     there is no polish.
+ *   E. POLISH, affine only (`polish` is ignored for a homography: its sums would overflow int64), `polish` times: over the
+ *     scored inliers of the current model with fabsf(tx) <= 32768 && fabsf(ty) <= 32768 (the others are counted as skipped, once
+ *     per step), the int64 sums N, Sa, Sb, Saa, Sab, Sbb, Sp, Sap, Sbp, Sq, Saq, Sbq of a = 2x - (w-1), b = 2y - (h-1), p =
+ *     llrintf(tx*64), q = llrintf(ty*64) (|a|, |b| < 2^13, |p|, |q| <= 2^21, at most 2^26 pixels: every sum stays below 2^60).
+ *     Each sum is converted to float64 (one rounding), then c00 = Sbb*N - Sb*Sb, c01 = Sb*Sa - Sab*N, c02 = Sab*Sb - Sbb*Sa, c11 =
+ *     Saa*N - Sa*Sa, c12 = Sa*Sab - Saa*Sb, c22 = Saa*Sbb - Sab*Sab, det = (Saa*c00 + Sab*c01) + Sa*c02; for (r0,r1,r2) = (Sap,
+ *     Sbp, Sp): x0 = ((c00*r0 + c01*r1) + c02*r2)/det, x1 = ((c01*r0 + c11*r1) + c12*r2)/det, x2 = ((c02*r0 + c12*r1) +
+ *     c22*r2)/det, m0 = (float)(x0*0.03125), m1 = (float)(x1*0.03125), m2 = (float)(((x2 - x0*(w-1)) - x1*(h-1))*0.015625); m3..m5
+ *     likewise from (Saq, Sbq, Sq); last row (0,0,1).  N < 3, det zero or not finite, or an entry not finite: the current model
+ *     stays.  Otherwise the candidate's scored inliers are counted and it becomes the current model iff its count >= the current
+ *     model's.
+ *   F. APPLY, every pixel whatever `step` is, each output optional (NULL to skip).  d_class (h,w) uint8: 0 not good, 1 inlier of
+ *     the final model, 2 outlier, 3 good but excluded.  d_model_flow (h,w,3) float32: [X/W - xf, Y/W - yf, 1] if W > 0, else
+ *     [0,0,0], at every pixel, good or not.  d_residual (h,w,3) float32: [U - Um, V - Vm, 1] at a good pixel with W > 0, else
+ *     [0,0,0].  d_counts int32[8], zeroed by the call on the stream: {scored pixels, scored inliers of the final model, degenerate
+ *     hypotheses of all rounds, best round (-1: none), best j (-1: none), the best hypothesis' count, polish steps accepted, pixels
+ *     skipped by the polish range, summed over the steps}.
+ * d_model receives the final model; d_models (n_hyp*9) and d_hyp_counts (n_hyp) hold the hypotheses of the last round and their
+ * counts.  There is no d_ws: the scratch is the caller's typed planes d_models, d_hyp_counts and d_state (int64[32]: [0] the best
+ * key, the rest counters, the polish sums and the candidate), which are outputs as well.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout; model outside
+ * [0,1]; thresh not finite or not > 0; n_hyp outside [1,65536]; lo_rounds outside [0,4]; polish outside [0,4]; step outside
+ * [1,64]; any flag bit (there are none yet); a NULL d_flow, d_model, d_models, d_hyp_counts or d_state; d_state not 8-byte
+ * aligned, a float or int32 plane not 4-byte aligned; an output or scratch plane equal to an input or to one listed before it.
+ * 3 + 4 (lo_rounds + 1) + 4 polish launches (polish counted as 0 for a homography) and one or two memsets, whatever the field
+ * holds.  Asynchronous on `stream`, allocates nothing, reads nothing back, can be captured into a graph. */
+#define DFLOW_MOTION_AFFINE 0      /* 3-point minimal sample */
+#define DFLOW_MOTION_HOMOGRAPHY 1  /* 4-point minimal sample */
+int dflow_motion_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        const uint8_t *d_exclude /* NULL or (h,w): non-zero = take no part */,
+        int32_t model, float thresh, int32_t n_hyp /* 1..65536 */, int32_t lo_rounds /* 0..4 */,
+        int32_t polish /* 0..4 */, int32_t step /* 1..64 */, uint64_t seed, uint32_t flags /* none yet */,
+        float *d_model       /* float32[9] */,
+        float *d_models      /* scratch+output float32[n_hyp*9]: the last round's hypotheses */,
+        int32_t *d_hyp_counts /* scratch+output int32[n_hyp]: their inlier counts, 0 for a degenerate one */,
+        int64_t *d_state     /* scratch+output int64[32], 8-byte aligned */,
+        uint8_t *d_class     /* NULL or (h,w) */, float *d_model_flow /* NULL or (h,w,3) */,
+        float *d_residual    /* NULL or (h,w,3) */, int32_t *d_counts /* NULL or int32[8] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ ADVANCE_NEGATE = 1          # DFLOW_ADVANCE_NEGATE
 FBC_BILINEAR = 1            # DFLOW_FBC_BILINEAR
 SEG_KEEP_SINGLETONS = 1     # DFLOW_SEG_KEEP_SINGLETONS
 WMED_KEEP_HOLES, WMED_REJECT = 1, 2     # DFLOW_WMED_KEEP_HOLES, DFLOW_WMED_REJECT
+MOTION_AFFINE, MOTION_HOMOGRAPHY = 0, 1     # DFLOW_MOTION_AFFINE, DFLOW_MOTION_HOMOGRAPHY
 
 
 class DflowError(RuntimeError):
@@ -62,6 +63,13 @@ class BcdStats(C.Structure):
 
 _vp, _sz, _i32, _f32, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_double
 _pp = C.POINTER(Params)
+
+
+class _u64(C.c_uint64):
+    """A uint64_t argument that is no byte count (a seed).  ctypes' c_uint64 is c_size_t itself on LP64, and in this table a
+    c_size_t is a ws_bytes: a type of its own keeps the two apart."""
+
+
 # every C-ABI function: name -> (return type, argument types)
 _SIGNATURES = {
     "dflow_version": (C.c_int, []),
@@ -118,7 +126,13 @@ _SIGNATURES = {
                                      _vp, _vp]),
     "dflow_flow_wmedian": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, C.c_uint32, _vp, _vp, _vp]),
 }
-SYMBOLS = tuple(_SIGNATURES)
+# Entry points whose gates are made of abi.hip's shared checks alone (no refusal text of their own): the tables of
+# tests/test_abi_refusals.py cover _SIGNATURES, these have their refusals pinned by their own test file (tests/test_abi_motion.py).
+_SIGNATURES_SHARED_GATE = {
+    "dflow_motion_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, _i32, _i32, _i32, _u64, C.c_uint32, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE)
 
 
 def build(force=False):
@@ -144,7 +158,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_SIGNATURES_SHARED_GATE.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         _lib = L

@@ -352,3 +352,8 @@ int launch_frame_interp(int H, int W, const uint8_t *bgr1, const uint8_t *bgr2, 
 // are both NULL (unguided) or both given, wspace and counts may be NULL
 int launch_flow_wmedian(int H, int W, const float *flow, int layout, const uint8_t *bgr, int radius, const uint8_t *wspace,
                         const uint8_t *wcolor, float reject_thresh, uint32_t flags, float *out, int32_t *counts, hipStream_t s);
+// motion_fit.hip: the robust fit of an affine map or a homography to a flow field, 3 + 4 (lo_rounds + 1) + 4 polish launches
+// whatever the field holds (arguments validated by the caller); exclude, cls, model_flow, residual and counts may be NULL
+int launch_motion_fit(int H, int W, const float *flow, int layout, const uint8_t *exclude, int model, float thresh, int n_hyp,
+                      int lo_rounds, int polish, int step, uint64_t seed, float *d_model, float *models, int32_t *hyp_counts,
+                      int64_t *state, uint8_t *cls, float *model_flow, float *residual, int32_t *counts, hipStream_t s);

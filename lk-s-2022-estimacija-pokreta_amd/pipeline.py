@@ -983,6 +983,95 @@ def flow_wmedian(flow, img=None, radius=3, sigma_space=None, sigma_color=10.0, i
     return (src, cnt) if counts else src
 
 
+MOTION_MODELS = {"affine": _lib.MOTION_AFFINE, "homography": _lib.MOTION_HOMOGRAPHY}
+MOTION_FIT_COUNTS = ("scored", "inliers", "degenerate", "best_round", "best_j", "best_count", "accepted", "skipped")
+
+
+def _motion_fit_gate(fn, flow, model, thresh, n_hyp, lo_rounds, polish, step, seed, exclude):
+    """The arguments of motion_fit / motion_layers through the input gate, before any device is touched: (flow, exclude)."""
+    flow = _check(flow, fn, "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    if exclude is not None:
+        exclude = _check(exclude, fn, "exclude", torch.uint8, (H, W))
+    if model not in MOTION_MODELS:
+        raise ValueError("%s: model must be 'affine' or 'homography', got %r" % (fn, model))
+    if not (isinstance(thresh, (int, float, np.integer, np.floating)) and np.isfinite(np.float32(thresh)) and np.float32(thresh) > 0):
+        raise ValueError("%s: thresh must be finite and > 0 as a float32, got %r" % (fn, thresh))
+    for name, v, lo, hi in (("n_hyp", n_hyp, 1, 65536), ("lo_rounds", lo_rounds, 0, 4), ("polish", polish, 0, 4), ("step", step, 1, 64),
+                            ("seed", seed, 0, 2 ** 64 - 1)):
+        if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+            raise ValueError("%s: %s must be an int in [%d, %d], got %r" % (fn, name, lo, hi, v))
+    return flow, exclude
+
+
+def _motion_fit_call(flow, exclude, model, thresh, n_hyp, lo_rounds, polish, step, seed, scratch, classes, model_flow, residual, counts):
+    """One dflow_motion_fit on device tensors with the caller's scratch planes (models, hyp_counts, state) into new outputs."""
+    H, W, _ = flow.shape
+    dev = flow.device
+    models, hyp_counts, state = scratch
+    out = torch.empty(9, dtype=torch.float32, device=dev)
+    extra = [_out(classes, (H, W), torch.uint8, dev), _out(model_flow, (H, W, 3), torch.float32, dev),
+             _out(residual, (H, W, 3), torch.float32, dev), _out(counts, 8, torch.int32, dev)]
+    _lib.call("dflow_motion_fit", H, W, flow.data_ptr(), _layout(flow), _ptr(exclude), MOTION_MODELS[model], float(thresh), int(n_hyp),
+              int(lo_rounds), int(polish), int(step), int(seed), 0, out.data_ptr(), models.data_ptr(), hyp_counts.data_ptr(),
+              state.data_ptr(), _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]), _ptr(extra[3]), _lib.stream(dev))
+    return out.view(3, 3), extra
+
+
+def _motion_fit_scratch(n_hyp, dev):
+    return (torch.empty(int(n_hyp) * 9, dtype=torch.float32, device=dev), torch.empty(int(n_hyp), dtype=torch.int32, device=dev),
+            torch.empty(32, dtype=torch.int64, device=dev))
+
+
+def motion_fit(flow, model="affine", thresh=1.0, n_hyp=1024, lo_rounds=1, polish=2, step=1, seed=0, exclude=None, classes=False,
+               model_flow=False, residual=False, counts=False):
+    """The dominant motion of a flow field (dflow_motion_fit, DESIGN.md "Global-motion fit"): the affine map or the homography
+    M: (x,y,1) -> (X,Y,W), position in the second frame (X/W, Y/W), that most vectors agree with to within thresh pixels, found
+    from n_hyp random minimal samples per round, lo_rounds further rounds sampled among the best model's inliers and, for an
+    affine map, `polish` least-squares steps.  flow is (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; exclude an (H,W)
+    uint8 mask, non-zero = the pixel takes no part, or None.  Device tensors or host arrays; host data is uploaded to the current
+    device.  step > 1 scores only every step-th row and column.  Returns the (3,3) float32 device tensor, the identity when no
+    model was found, or a tuple in the order (model[, classes][, model_flow][, residual][, counts]): classes=True adds the (H,W)
+    uint8 plane 0 no vector / 1 inlier / 2 outlier / 3 excluded, model_flow=True the model's own (H,W,3) [U,V,valid] flow (a
+    prior for DiscreteFlow.front_end), residual=True the (H,W,3) flow minus the model's, counts=True the int32[8] device tensor
+    MOTION_FIT_COUNTS.  Runs on torch's current stream and does not wait for it."""
+    flow, exclude = _motion_fit_gate("motion_fit", flow, model, thresh, n_hyp, lo_rounds, polish, step, seed, exclude)
+    dev = _device_of(flow, *([exclude] if exclude is not None else []))
+    ts = _on(dev, flow, *([exclude] if exclude is not None else []))
+    out, extra = _motion_fit_call(ts[0], ts[1] if exclude is not None else None, model, thresh, n_hyp, lo_rounds, polish, step, seed,
+                                  _motion_fit_scratch(n_hyp, dev), classes, model_flow, residual, counts)
+    ret = tuple(t for t in [out] + extra if t is not None)
+    return ret if len(ret) > 1 else out
+
+
+def motion_layers(flow, k, exclude=None, **fit_args):
+    """k successive motion fits of one flow field: the inliers of each fit are excluded from the fits after it, on the device,
+    with nothing read back in between.  fit_args are motion_fit's (model, thresh, n_hyp, lo_rounds, polish, step, seed).  Returns
+    (models, layers): the list of k (3,3) float32 device tensors and the (H,W) uint8 device plane, 0 = no layer, i = inlier of
+    fit i (1-based).  Runs on torch's current stream and does not wait for it."""
+    if not (isinstance(k, (int, np.integer)) and 1 <= k <= 255):
+        raise ValueError("motion_layers: k must be an int in [1, 255], got %r" % (k,))
+    unknown = set(fit_args) - {"model", "thresh", "n_hyp", "lo_rounds", "polish", "step", "seed"}
+    if unknown:
+        raise ValueError("motion_layers: unknown arguments %s" % sorted(unknown))
+    args = dict(dict(model="affine", thresh=1.0, n_hyp=1024, lo_rounds=1, polish=2, step=1, seed=0), **fit_args)
+    flow, exclude = _motion_fit_gate("motion_layers", flow, exclude=exclude, **args)
+    dev = _device_of(flow, *([exclude] if exclude is not None else []))
+    flow, = _on(dev, flow)
+    H, W, _ = flow.shape
+    taken = (_on(dev, exclude)[0] != 0).to(torch.uint8) if exclude is not None else torch.zeros((H, W), dtype=torch.uint8, device=dev)
+    layers = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+    scratch = _motion_fit_scratch(args["n_hyp"], dev)
+    models = []
+    for i in range(1, int(k) + 1):
+        m, extra = _motion_fit_call(flow, taken, scratch=scratch, classes=True, model_flow=False, residual=False, counts=False, **args)
+        inl = extra[0] == 1
+        layers[inl] = i
+        taken = taken | inl.to(torch.uint8)
+        models.append(m)
+    return models, layers
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels

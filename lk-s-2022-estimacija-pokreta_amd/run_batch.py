@@ -60,6 +60,10 @@ mode, guided: a vector that differs from the weighted median of its window by mo
 other vector stays bit for bit, after the check and --segments and before everything that reads the sparse field (as
 --segments).  One line per pair gives the four counts; the header of eval.json gains "wmedian": R and "wmedian_reject": [R, T].
 Without them nothing is launched that was not launched before.
+--motion MODEL (affine or homography) fits the dominant motion of every pair's forward flow (pipeline.motion_fit with its
+defaults, DESIGN.md "Global-motion fit"; --motion-thresh T is its inlier threshold in pixels, default 1) and writes
+residual_<pair>.flo, the forward flow minus the model's, and motion.json in DIR with the per-pair rows {pair, matrix, scored,
+inliers}.  One line per pair gives the inlier share.  Without it nothing is launched that was not launched before.
 """
 import argparse
 import importlib
@@ -107,6 +111,9 @@ def parser():
                     help="also write wmedian_NN.flo, the forward flow through the guided weighted median filter of radius R (1..8)")
     ap.add_argument("--wmedian-reject", nargs=2, default=None, metavar=("R", "T"),
                     help="after the check and --segments: remove sparse vectors further than T from their window's weighted median (radius R)")
+    ap.add_argument("--motion", default=None, metavar="MODEL",
+                    help="also fit the dominant motion (affine or homography) of each forward flow; writes motion.json and residual_NN.flo")
+    ap.add_argument("--motion-thresh", default=None, metavar="T", help="with --motion: the inlier threshold in pixels (default 1)")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
     ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="with --pyramid: sweeps of the coarse levels (default: --bcd-times)")
@@ -154,6 +161,22 @@ def wmedian_reject_arg(tokens):
     except ValueError:
         parser().error("--wmedian-reject needs R (an integer in 1..8) and T (finite, >= 0), got %r" % (tokens,))
     return radius, thresh
+
+
+def motion_args(a):
+    """--motion MODEL and --motion-thresh T -> (MODEL or None, T); exits with status 2 for an unknown model, a threshold that is
+    not finite and > 0, or a threshold without --motion."""
+    if a.motion is None and a.motion_thresh is not None:
+        parser().error("--motion-thresh needs --motion")
+    if a.motion is not None and a.motion not in ("affine", "homography"):
+        parser().error("--motion needs MODEL (affine or homography), got %r" % (a.motion,))
+    try:
+        thresh = 1.0 if a.motion_thresh is None else float(a.motion_thresh)
+        if not (np.isfinite(thresh) and thresh > 0):
+            raise ValueError
+    except ValueError:
+        parser().error("--motion-thresh needs T (finite, > 0), got %r" % (a.motion_thresh,))
+    return a.motion, thresh
 
 
 def midframe_args(a):
@@ -415,8 +438,16 @@ def write_out(s, flows):
     eval_rows, eval_totals = [], {}
     photo_rows, photo_totals = [], {}
     mid_rows = []
+    motion_rows = []
     for pair in range(a.pairs):
         fwd = flows[2 * pair]
+        if a.motion is not None:
+            matrix, residual, counts = pipeline.motion_fit(fwd, model=a.motion, thresh=a.motion_thresh, residual=True, counts=True)
+            flowio.write_flo(os.path.join(a.out, "residual_%02d.flo" % pair), residual[..., [1, 0]].cpu().numpy())
+            counts = counts.cpu().tolist()
+            motion_rows.append(dict(pair=pair, matrix=matrix.cpu().numpy().tolist(), scored=counts[0], inliers=counts[1]))
+            print("pair %d: %s motion: %d of %d vectors within %g px (%.2f%%)"
+                  % (pair, a.motion, counts[1], counts[0], a.motion_thresh, 100.0 * counts[1] / max(counts[0], 1)))
         sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, flows[2 * pair + 1])
         dense = [("epic", epic)] if a.epic else []
         if a.wmedian is not None:
@@ -439,6 +470,10 @@ def write_out(s, flows):
     head = {"size": [H, W], "bcd_times": a.bcd_times}
     if a.pyramid > 1:
         head["pyramid"] = a.pyramid
+    if a.motion is not None:
+        import json
+        with open(os.path.join(a.out, "motion.json"), "w") as f:
+            json.dump(dict(head, model=a.motion, thresh=a.motion_thresh, pairs=motion_rows), f, indent=1)
     if a.midframe:
         import json
         with open(os.path.join(a.out, "midframe.json"), "w") as f:
@@ -467,6 +502,7 @@ def main(argv=None):
     if a.wmedian_reject is not None:
         a.wmedian_reject = wmedian_reject_arg(a.wmedian_reject)
     a.mid_fill_rounds, a.mid_occl_thresh = midframe_args(a)
+    a.motion, a.motion_thresh = motion_args(a)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)
