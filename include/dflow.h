@@ -813,6 +813,57 @@ int dflow_motion_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout,
         uint8_t *d_class     /* NULL or (h,w) */, float *d_model_flow /* NULL or (h,w,3) */,
         float *d_residual    /* NULL or (h,w,3) */, int32_t *d_counts /* NULL or int32[8] */, void *stream);
 
+/* Per-pixel confidence of a labelling (DESIGN.md "Label confidence"): how far the chosen label's local energy lies below the best
+ * competing motion, the naive peak margin / local min-energy gap of a discrete labelling.  This build's definition; the reference
+ * has no counterpart.  It reads the state the sweeps leave on the device and nothing of a pass's workspace.
+ * Notation: LP = label_pitch; l = d_bestlabels[p]; n_p = min(d_nprop[p], LP); slot k of pixel p has flow f_k (unpacked as
+ * everywhere else) and cost c_k = d_lcosts[p*LP+k].
+ *   - p is LABELLED when 0 <= l < n_p.
+ *   - s_k = sum over the 4-neighbours q of p that lie inside the frame and are labelled of min(tpsi, |f_k - g_q|_1), where g_q is
+ *     the flow of q's chosen label.  An unlabelled neighbour adds nothing, as in dflow_bcd_stats.
+ *   - e_k is computed in double, one IEEE operation per written operation, with no fused multiply-add.
+ *       DFLOW_CONF_LOCAL: e_k = lamda * (double)c_k + (double)s_k.
+ *       DFLOW_CONF_DATA:  e_k = (double)c_k.  This is the matching cost alone.  It is meaningful before any sweep and does not
+ *                         need the neighbours.
+ *   - Alternatives: A = { k < n_p : |f_k - f_l|_1 > min_sep }.  Duplicates and near-duplicates of the chosen motion do not
+ *     compete.  The CLI default is 1, because the +-1 px neighbours of a motion have nearly its DAISY cost.
+ *   - alt is the k in A with the smallest (e_k, k), so the smaller index wins a tie.
+ *   - margin = (float)(e_alt - e_l): a subtraction in double, then one rounding to float32.
+ *   - A negative margin is legal.  A BCD phase minimises chains, not pixels.
+ *   - If A is empty: alt = -1, margin = +Inf.  If p is not labelled: alt = -1, margin = -Inf.
+ *   - The costs of used slots are what the stages write: finite and >= 0 (no stage writes -0.0), as dflow_bcd_prepare already
+ *     requires.  With anything else the values are unspecified, but nothing outside the arrays is touched.
+ *   - Slots at or beyond n_p are never part of the result.
+ * Outputs, each optional (NULL to skip) but not all four: d_margin (H,W) float32; d_alt (H,W) int32; d_sparse (H,W,3) float32,
+ * [dx, dy, 1] where p is labelled and margin >= thresh (a float32 compare), [0,0,0] elsewhere; d_counts int32[DFLOW_CONF_COUNTS],
+ * zeroed by the call on the stream = {labelled, not labelled, labelled with A empty, labelled with margin < 0, labelled with
+ * margin == 0, kept}; kept is counted whether or not d_sparse is given.  All outputs are exact and independent of any order: the
+ * same inputs give the same bytes on every call.
+ * Of *p only pich, picw, maxnprop, label_pitch, tpsi and lamda are read and checked.  DFLOW_EINVAL before anything is launched,
+ * checked in this order: the parameters as dflow_bcd_stats checks them (1 <= pich, picw <= 8192, label_pitch a multiple of 16 in
+ * [16, DFLOW_MAX_LABELS], 1 <= maxnprop <= label_pitch, 1 <= tpsi <= 8); lamda not finite or < 0; mode outside [0,1]; min_sep
+ * outside [0,1024]; thresh NaN (infinities are allowed); all four outputs NULL; a NULL input; d_proposals, d_lcosts or d_sparse not
+ * 16-byte aligned, another plane not 4-byte aligned; an output equal to an input or to an output listed before it.
+ * There is no workspace.  One launch and at most one memset; asynchronous on `stream`, allocates nothing, reads nothing back, can be
+ * captured into a graph. */
+#define DFLOW_CONF_LOCAL 0   /* e_k = lamda * c_k + s_k */
+#define DFLOW_CONF_DATA  1   /* e_k = c_k */
+#define DFLOW_CONF_COUNTS 6
+int dflow_label_confidence(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
+                           const int32_t *d_bestlabels, int32_t mode, int32_t min_sep, float thresh,
+                           float *d_margin, int32_t *d_alt, float *d_sparse, int32_t *d_counts, void *stream);
+
+/* The gate of a flow field by a score plane (DESIGN.md "Label confidence"): a GOOD vector (as in dflow_flow_consistency) of d_flow,
+ * (h,w,.) float32 in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout, whose score, d_score (h,w) float32, has lo <= score <= hi (float32
+ * compares: a NaN score fails) is written to d_out (h,w,3) as [U,V,1] with its bits unchanged; every other pixel becomes [0,0,0].
+ * Under DFLOW_EVAL_UVV d_out may be d_flow.  d_counts (NULL to skip) int32[2], zeroed by the call on the stream = {good, kept}.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout; lo or hi NaN
+ * (infinities are allowed); lo > hi; a NULL d_flow, d_score or d_out; d_flow, d_score or d_out not 16-byte aligned (four pixels
+ * per lane), d_counts not 4-byte aligned; an output equal to an input (but for d_out = d_flow as above) or to the other output.
+ * One launch; asynchronous on `stream`, allocates nothing, reads nothing back, can be captured into a graph. */
+int dflow_flow_gate(int32_t h, int32_t w, const float *d_flow, int32_t layout, const float *d_score, float lo, float hi,
+                    float *d_out, int32_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

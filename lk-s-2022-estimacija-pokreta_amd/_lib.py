@@ -21,6 +21,8 @@ FBC_BILINEAR = 1            # DFLOW_FBC_BILINEAR
 SEG_KEEP_SINGLETONS = 1     # DFLOW_SEG_KEEP_SINGLETONS
 WMED_KEEP_HOLES, WMED_REJECT = 1, 2     # DFLOW_WMED_KEEP_HOLES, DFLOW_WMED_REJECT
 MOTION_AFFINE, MOTION_HOMOGRAPHY = 0, 1     # DFLOW_MOTION_AFFINE, DFLOW_MOTION_HOMOGRAPHY
+CONF_LOCAL, CONF_DATA = 0, 1                # DFLOW_CONF_LOCAL, DFLOW_CONF_DATA
+CONF_COUNTS = 6                             # DFLOW_CONF_COUNTS
 
 
 class DflowError(RuntimeError):
@@ -127,10 +129,13 @@ _SIGNATURES = {
     "dflow_flow_wmedian": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _f32, C.c_uint32, _vp, _vp, _vp]),
 }
 # Entry points whose gates are made of abi.hip's shared checks alone (no refusal text of their own): the tables of
-# tests/test_abi_refusals.py cover _SIGNATURES, these have their refusals pinned by their own test file (tests/test_abi_motion.py).
+# tests/test_abi_refusals.py cover _SIGNATURES, these have their refusals pinned by their own test files (tests/test_abi_motion.py,
+# tests/test_abi_label_conf.py).
 _SIGNATURES_SHARED_GATE = {
     "dflow_motion_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, _i32, _i32, _i32, _u64, C.c_uint32, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_label_confidence": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_flow_gate": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, _f32, _vp, _vp, _vp]),
 }
 SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE)
 

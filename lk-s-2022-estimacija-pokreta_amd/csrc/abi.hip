@@ -3,7 +3,7 @@
 //
 // A gate is a sequence of the checks defined below dflow_check_launch, each called with __func__ and returning DFLOW_OK or what
 // dflow_set_error returned: check_frame_size, check_layout, check_flags, check_finite_ge0 / check_finite_gt0, check_int_range,
-// CHECK_PTR, check_aligned, check_distinct (outputs against inputs and each other) and, last but where d_ws has always been among
+// check_not_nan, check_ordered, check_any_given, CHECK_PTR, check_aligned, check_distinct (outputs against inputs and each other) and, last but where d_ws has always been among
 // the aligned pointers, CHECK_WS; FRAME_WS_BYTES defines an image-plane stage's size function.  A new entry point's gate is
 // assembled from these, and its refusals are added to tests/test_abi_refusals.py, which pins every status, text and the order.
 #include <math.h>
@@ -49,15 +49,34 @@ static int check_flags(const char *fn, uint32_t flags, uint32_t known)
     return flags & ~known ? dflow_set_error(DFLOW_EINVAL, "%s: unknown flags 0x%x", fn, flags) : DFLOW_OK;
 }
 
-// `note` ends the message where 0 has a meaning of its own
+// a value outside what its argument takes: `must` says what that is, `note` ends the message where a value has a meaning of its own
+static int refuse_value(const char *fn, const char *name, double v, const char *must, const char *note = "")
+{
+    return dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be %s%s", fn, name, v, must, note);
+}
+
 static int check_finite_ge0(const char *fn, const char *name, double v, const char *note = "")
 {
-    return !isfinite(v) || v < 0.0 ? dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and >= 0%s", fn, name, v, note) : DFLOW_OK;
+    return !isfinite(v) || v < 0.0 ? refuse_value(fn, name, v, "finite and >= 0", note) : DFLOW_OK;
 }
 
 static int check_finite_gt0(const char *fn, const char *name, double v)
 {
-    return !isfinite(v) || !(v > 0.0) ? dflow_set_error(DFLOW_EINVAL, "%s: %s=%g must be finite and > 0", fn, name, v) : DFLOW_OK;
+    return !isfinite(v) || !(v > 0.0) ? refuse_value(fn, name, v, "finite and > 0") : DFLOW_OK;
+}
+
+// a value that may be infinite but not NaN
+static int check_not_nan(const char *fn, const char *name, double v)
+{
+    return isnan(v) ? refuse_value(fn, name, v, "a number") : DFLOW_OK;
+}
+
+// the two ends of a closed range
+static int check_ordered(const char *fn, const char *lo_name, double lo, const char *hi_name, double hi)
+{
+    char must[64];
+    snprintf(must, sizeof(must), "<= %s=%g", hi_name, hi);
+    return lo > hi ? refuse_value(fn, lo_name, lo, must) : DFLOW_OK;
 }
 
 // fn may be NULL: the fields of dflow_params, and phase and npass of the BCD entry points, are reported without a prefix
@@ -65,6 +84,15 @@ static int check_int_range(const char *fn, const char *name, int v, int lo, int 
 {
     if (v < lo || v > hi) return dflow_set_error(DFLOW_EINVAL, "%s%s%s=%d outside [%d,%d]", fn ? fn : "", fn ? ": " : "", name, v, lo, hi);
     return DFLOW_OK;
+}
+
+// a required pointer, or a group of optional outputs of which a call needs at least one (`names` lists them for the message)
+static int refuse_null(const char *fn, const char *name) { return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", fn, name); }
+static int check_any_given(const char *fn, const char *names, std::initializer_list<const void *> ptrs)
+{
+    for (const void *q : ptrs)
+        if (q) return DFLOW_OK;
+    return refuse_null(fn, names);
 }
 
 // a pointer the kernels move several elements of at a time; NULL (an optional output left out) passes
@@ -107,7 +135,7 @@ static int check_ws(const char *fn, const void *d_ws, size_t ws_bytes, uintptr_t
     int rc = check_ws_size(fn, d_ws, ws_bytes, need);
     return rc ? rc : check_aligned(fn, {{"d_ws", d_ws, align}});
 }
-#define CHECK_PTR(x) do { if (!(x)) return dflow_set_error(DFLOW_EINVAL, "%s: %s is NULL", __func__, #x); } while (0)
+#define CHECK_PTR(x) do { if (!(x)) return refuse_null(__func__, #x); } while (0)
 #define CHECK_WS(align, need) do { int rc_ws_ = check_ws(__func__, d_ws, ws_bytes, (align), (need)); if (rc_ws_) return rc_ws_; } while (0)
 // the main-path stages carve float4, int4 and uint4 regions (daisy.hip, knn_mfma.hip, bcd.hip)
 #define WS_ALIGN_MAIN 16
@@ -318,8 +346,8 @@ int dflow_bcd_sweep_batch(const dflow_params *p, int32_t npass, const int32_t *c
     return DFLOW_OK;
 }
 
-// the fields of *p a labelling's statistics depend on; no cell grid, so frames below 8 x 8 pass
-static int bcd_stats_check_params(const char *fn, const dflow_params *p)
+// the fields of *p that say how a labelling's state is laid out and compared; no cell grid, so frames below 8 x 8 pass
+static int labelling_check_params(const char *fn, const dflow_params *p)
 {
     if (!p) return dflow_set_error(DFLOW_EINVAL, "%s: params is NULL", fn);
     int rc = check_frame_size(fn, p->pich, p->picw); if (rc) return rc;
@@ -327,8 +355,14 @@ static int bcd_stats_check_params(const char *fn, const dflow_params *p)
         return dflow_set_error(DFLOW_EINVAL, "%s: label_pitch=%d must be a multiple of 16 in [16,%d]", fn, p->label_pitch, DFLOW_MAX_LABELS);
     if (p->maxnprop < 1 || p->maxnprop > p->label_pitch)
         return dflow_set_error(DFLOW_EINVAL, "%s: maxnprop=%d outside [1,label_pitch=%d]", fn, p->maxnprop, p->label_pitch);
-    if ((rc = check_int_range(fn, "tpsi", p->tpsi, 1, 8))) return rc;
-    return check_finite_ge0(fn, "tphi", p->tphi);
+    return check_int_range(fn, "tpsi", p->tpsi, 1, 8);
+}
+
+// the fields of *p a labelling's statistics depend on
+static int bcd_stats_check_params(const char *fn, const dflow_params *p)
+{
+    int rc = labelling_check_params(fn, p);
+    return rc ? rc : check_finite_ge0(fn, "tphi", p->tphi);
 }
 
 // The end of the gates of dflow_bcd_stats and dflow_bcd_stats_batch.  d_stats and d_ws both hold doubles; d_ws has always been
@@ -753,6 +787,49 @@ int dflow_motion_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout, 
     if (rc) return rc;
     return launch_motion_fit(h, w, d_flow, layout, d_exclude, model, thresh, n_hyp, lo_rounds, polish, step, seed, d_model, d_models,
                              d_hyp_counts, d_state, d_class, d_model_flow, d_residual, d_counts, (hipStream_t)stream);
+}
+
+int dflow_label_confidence(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
+                           const int32_t *d_bestlabels, int32_t mode, int32_t min_sep, float thresh, float *d_margin, int32_t *d_alt,
+                           float *d_sparse, int32_t *d_counts, void *stream)
+{
+    int rc = labelling_check_params(__func__, p); if (rc) return rc;
+    if ((rc = check_finite_ge0(__func__, "lamda", p->lamda))) return rc;
+    if ((rc = check_int_range(__func__, "mode", mode, DFLOW_CONF_LOCAL, DFLOW_CONF_DATA))) return rc;
+    if ((rc = check_int_range(__func__, "min_sep", min_sep, 0, 1024))) return rc;
+    if ((rc = check_not_nan(__func__, "thresh", thresh))) return rc;
+    if ((rc = check_any_given(__func__, "each of d_margin, d_alt, d_sparse and d_counts", {d_margin, d_alt, d_sparse, d_counts}))) return rc;
+    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
+    // the kernel reads the label and cost rows 16 bytes at a time
+    rc = check_aligned(__func__, {{"d_proposals", d_proposals, 16}, {"d_lcosts", d_lcosts, 16}, {"d_sparse", d_sparse, 16},
+                                  {"d_nprop", d_nprop, 4}, {"d_bestlabels", d_bestlabels, 4}, {"d_margin", d_margin, 4},
+                                  {"d_alt", d_alt, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a pixel's neighbours are read while other pixels are written
+    rc = check_distinct(__func__, {{"d_proposals", d_proposals}, {"d_lcosts", d_lcosts}, {"d_nprop", d_nprop}, {"d_bestlabels", d_bestlabels}},
+                        {{"d_margin", d_margin}, {"d_alt", d_alt}, {"d_sparse", d_sparse}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_label_confidence(p, d_proposals, d_lcosts, d_nprop, d_bestlabels, mode, min_sep, thresh, d_margin, d_alt, d_sparse,
+                                   d_counts, (hipStream_t)stream);
+}
+
+int dflow_flow_gate(int32_t h, int32_t w, const float *d_flow, int32_t layout, const float *d_score, float lo, float hi, float *d_out,
+                    int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_not_nan(__func__, "lo", lo))) return rc;
+    if ((rc = check_not_nan(__func__, "hi", hi))) return rc;
+    if ((rc = check_ordered(__func__, "lo", lo, "hi", hi))) return rc;
+    CHECK_PTR(d_flow); CHECK_PTR(d_score); CHECK_PTR(d_out);
+    // the kernel moves four pixels per lane with 16-byte loads and stores
+    rc = check_aligned(__func__, {{"d_flow", d_flow, 16}, {"d_score", d_score, 16}, {"d_out", d_out, 16}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a lane reads its own four pixels before it writes them: under [U,V,valid], where the pitches agree, d_out may be d_flow
+    rc = check_distinct(__func__, {{"d_flow", d_flow}, {"d_score", d_score}},
+                        {{"d_out", layout == DFLOW_EVAL_UVV && d_out == d_flow ? nullptr : d_out}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_flow_gate(h, w, d_flow, layout, d_score, lo, hi, d_out, d_counts, (hipStream_t)stream);
 }
 
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)

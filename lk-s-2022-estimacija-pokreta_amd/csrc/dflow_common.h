@@ -357,3 +357,10 @@ int launch_flow_wmedian(int H, int W, const float *flow, int layout, const uint8
 int launch_motion_fit(int H, int W, const float *flow, int layout, const uint8_t *exclude, int model, float thresh, int n_hyp,
                       int lo_rounds, int polish, int step, uint64_t seed, float *d_model, float *models, int32_t *hyp_counts,
                       int64_t *state, uint8_t *cls, float *model_flow, float *residual, int32_t *counts, hipStream_t s);
+// label_conf.hip: the per-pixel margin of a labelling and the score gate of a flow field, one launch each (arguments validated by
+// the caller); margin, alt, sparse and counts may be NULL (not all four), the gate's counts too
+int launch_label_confidence(const dflow_params *p, const uint32_t *proposals, const float *lcosts, const int32_t *nprop,
+                            const int32_t *labels, int mode, int min_sep, float thresh, float *margin, int32_t *alt, float *sparse,
+                            int32_t *counts, hipStream_t s);
+int launch_flow_gate(int H, int W, const float *flow, int layout, const float *score, float lo, float hi, float *out, int32_t *counts,
+                     hipStream_t s);

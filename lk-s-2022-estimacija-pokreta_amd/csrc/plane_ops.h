@@ -1,5 +1,5 @@
 // Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
-// segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip): a block's reduction and class counts, the four-pixel access to a flow plane and a
+// segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip, label_conf.hip): a block's reduction and class counts, the exchanges of a 16-lane row, the four-pixel access to a flow plane and a
 // (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce or count;
 // every kernel keeps its own loop, launch function and workspace.
 #pragma once
@@ -56,6 +56,24 @@ template <int N> __device__ static inline void block_count_class(int kind, int32
 #pragma unroll
     for (int k = 0; k < N; k++) is[k] = kind == k;
     block_count<N>(is, counts, offset);
+}
+
+// ---- a pixel per 16-lane DPP row (prior.hip, label_conf.hip): exchanges inside the row and the row's minimum
+// DPP controls (GFX9 encoding): quad_perm, row_ror:n, row_half_mirror
+#define DPP_QUAD_PERM(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
+#define DPP_ROW_ROR(n) (0x120 + (n))
+#define DPP_ROW_HALF_MIRROR 0x141
+template <int CTRL> __device__ static inline int dpp_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
+template <int CTRL> __device__ static inline float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
+
+// the minimum over the 16 lanes of a row, in every lane of it
+__device__ static inline int row_min16(int v)
+{
+    v = min(v, dpp_i<DPP_ROW_ROR(8)>(v));
+    v = min(v, dpp_i<DPP_ROW_ROR(4)>(v));
+    v = min(v, dpp_i<DPP_ROW_ROR(2)>(v));
+    v = min(v, dpp_i<DPP_ROW_ROR(1)>(v));
+    return v;
 }
 
 // ---- a plane as a flat array of h*w pixels, four pixels per lane and step, grid-stride over at most PLANE_MAX_BLOCKS blocks

@@ -17,23 +17,6 @@
 #define PRIOR_MAXCAND 5
 #define PRIOR_NONE 0x7FFFFFFF
 
-// DPP controls (GFX9 encoding): quad_perm, row_ror:n, row_half_mirror
-#define DPP_QUAD_PERM(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
-#define DPP_ROW_ROR(n) (0x120 + (n))
-#define DPP_ROW_HALF_MIRROR 0x141
-template <int CTRL> __device__ static inline int dpp_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
-template <int CTRL> __device__ static inline float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-
-// the minimum over the 16 lanes of a row, in every lane of it
-__device__ static inline int row_min16(int v)
-{
-    v = min(v, dpp_i<DPP_ROW_ROR(8)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(4)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(2)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(1)>(v));
-    return v;
-}
-
 // The vector of pixel `src` of a flow plane as a label (rules 2 and 3 of the definition): false when it is invalid under
 // [U,V,valid], when a component is not finite, or when a rounded component lies outside [-32767, 32767].
 __device__ static inline bool prior_vector(const float *__restrict__ f, int layout, size_t src, int &dy, int &dx)

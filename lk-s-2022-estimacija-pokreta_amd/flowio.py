@@ -27,6 +27,11 @@ def labels_name(picindex, backward, sweep):
     return "Bestlabels fajl slike %s backward=%s posle %02d BCD.npy" % (pic_prefix(picindex), backward, sweep)
 
 
+def margin_name(picindex, backward, sweep):
+    """The margin plane of the labelling after `sweep` sweeps (python bcd.py --confidence): (H,W) float32."""
+    return "Margin slike %s backward=%s posle %02d BCD.npy" % (pic_prefix(picindex), backward, sweep)
+
+
 def stage_name(picindex, backward, what):
     """daisy i flann.py:251-253,308: what in {proposals_nakon_gausa, lcosts_nakon_gausa, nprop, packedksets}."""
     return "Daisy output slike %s backward=%s %s.npy" % (pic_prefix(picindex), backward, what)

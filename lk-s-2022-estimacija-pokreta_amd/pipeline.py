@@ -240,6 +240,27 @@ class DiscreteFlow:
                   self.lcosts.data_ptr(), self.nprop.data_ptr(), self.bestlabels.data_ptr(), _ptr(cnt), self._stream())
         return cnt
 
+    def confidence(self, mode="local", min_sep=1, thresh=None, alt=False, sparse=False, counts=False):
+        """dflow_label_confidence of the current state (DESIGN.md "Label confidence"): per pixel the margin by which the chosen
+        label's energy lies below the best competing motion of its own label set, a label competing when its flow is more than
+        min_sep (0..1024, |.|_1) away from the chosen one.  mode "local": e_k = lamda * cost_k + the truncated-L1 smoothness
+        against the four neighbours' chosen flows; "data": the matching cost alone (meaningful before any sweep).  Returns the
+        (H,W) float32 device tensor (+Inf: no competitor, -Inf: no label in range), or a tuple in the order (margin[, alt][,
+        sparse][, counts]): alt=True adds the (H,W) int32 plane of the competitor's slot (-1: none), sparse=True the (H,W,3)
+        float32 [U,V,valid] field of the labelled pixels with margin >= thresh, counts=True the int32[6] device tensor
+        LABEL_CONF_COUNTS.  thresh=None counts `kept` against -Inf (every labelled pixel) and refuses sparse=True.  Runs on
+        torch's current stream and does not wait for it; the BCD records in self.ws stay valid."""
+        mode, min_sep, thresh = _confidence_gate("confidence", mode, min_sep, thresh, sparse)
+        H, W = self.p.pich, self.p.picw
+        margin = torch.empty((H, W), dtype=torch.float32, device=self.device)
+        extra = [_out(alt, (H, W), torch.int32, self.device), _out(sparse, (H, W, 3), torch.float32, self.device),
+                 _out(counts, _lib.CONF_COUNTS, torch.int32, self.device)]
+        _lib.call("dflow_label_confidence", self._pp(), self.proposals.data_ptr(), self.lcosts.data_ptr(), self.nprop.data_ptr(),
+                  self.bestlabels.data_ptr(), mode, min_sep, thresh, margin.data_ptr(), _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]),
+                  self._stream())
+        ret = tuple(t for t in [margin] + extra if t is not None)
+        return ret if len(ret) > 1 else margin
+
     def front_end(self, pic3, pic4, prior=None, prior_stride=2, seed_labels=True, counts=False, pack=False):
         """Everything of a pass before its sweeps, daisy i flann.py main (:406-422, without the file writes): load_pair, generisi,
         nasumicni, with a prior prior_proposals(prior, prior_stride, seed_labels, counts), with pack=True pakovanje (for passes
@@ -376,6 +397,25 @@ def ceoBCD_batch(passes, bcd_times, on_sweep=None, stop=None):
         if on_sweep is not None:
             on_sweep(w)
     return None if stop is None else histories
+
+
+CONF_MODES = {"local": _lib.CONF_LOCAL, "data": _lib.CONF_DATA}
+LABEL_CONF_COUNTS = ("labelled", "not_labelled", "no_alternative", "negative", "zero", "kept")
+
+
+def _confidence_gate(fn, mode, min_sep, thresh, sparse=False):
+    """The arguments of DiscreteFlow.confidence as the library takes them, (mode, min_sep, thresh), before any device is touched."""
+    if mode not in CONF_MODES:
+        raise ValueError("%s: mode must be 'local' or 'data', got %r" % (fn, mode))
+    if not (isinstance(min_sep, (int, np.integer)) and 0 <= min_sep <= 1024):
+        raise ValueError("%s: min_sep must be an int in [0, 1024], got %r" % (fn, min_sep))
+    if thresh is None:
+        if sparse:
+            raise ValueError("%s: sparse=True needs a thresh" % fn)
+        thresh = float("-inf")
+    if not isinstance(thresh, (int, float, np.integer, np.floating)) or np.isnan(np.float32(thresh)):
+        raise ValueError("%s: thresh must be a number, not NaN, got %r" % (fn, thresh))
+    return CONF_MODES[mode], int(min_sep), float(np.float32(thresh))
 
 
 def fb_consistency(fwd, bwd, tresh, p=None):
@@ -981,6 +1021,31 @@ def flow_wmedian(flow, img=None, radius=3, sigma_space=None, sigma_color=10.0, i
                   flags, out.data_ptr(), _ptr(cnt), _lib.stream(dev))
         src = out
     return (src, cnt) if counts else src
+
+
+def flow_gate(flow, score, lo=float("-inf"), hi=float("inf"), counts=False):
+    """The gate of a flow field by a score plane (dflow_flow_gate, DESIGN.md "Label confidence"): a good vector (valid and finite)
+    whose score lies in [lo, hi] stays bit for bit, every other pixel becomes [0,0,0]; a NaN score fails.  flow is (H,W,2) float32
+    [dy,dx] or (H,W,3) float32 [U,V,valid], the last dimension says which; score is (H,W) float32, the margin of
+    DiscreteFlow.confidence or any other plane (the err plane of flow_consistency with hi=T).  Device tensors or host arrays; host
+    data is uploaded to the current device.  lo and hi may be infinite, not NaN, lo <= hi.  Returns the (H,W,3) float32 [U,V,valid]
+    device tensor, with counts=True the pair (out, int32[2] device tensor {good, kept}).  The input is not modified.  Runs on
+    torch's current stream and does not wait for it."""
+    flow = _check(flow, "flow_gate", "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    score = _check(score, "flow_gate", "score", torch.float32, (H, W))
+    for name, v in (("lo", lo), ("hi", hi)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or np.isnan(np.float32(v)):
+            raise ValueError("flow_gate: %s must be a number, not NaN, got %r" % (name, v))
+    lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if lo > hi:
+        raise ValueError("flow_gate: lo=%g is above hi=%g" % (lo, hi))
+    dev = _device_of(flow, score)
+    flow, score = _on(dev, flow, score)
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    cnt = _out(counts, 2, torch.int32, dev)
+    _lib.call("dflow_flow_gate", H, W, flow.data_ptr(), _layout(flow), score.data_ptr(), lo, hi, out.data_ptr(), _ptr(cnt), _lib.stream(dev))
+    return (out, cnt) if counts else out
 
 
 MOTION_MODELS = {"affine": _lib.MOTION_AFFINE, "homography": _lib.MOTION_HOMOGRAPHY}

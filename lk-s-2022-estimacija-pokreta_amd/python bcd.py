@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's second CLI (README.md:15-21, python bcd.py:13-17):
 
-    python "python bcd.py" <idx <= 99> <backward 0|1> <bcd_times> [--device cuda:N]
+    python "python bcd.py" <idx <= 99> <backward 0|1> <bcd_times> [--device cuda:N] [--confidence [--conf-mode M] [--conf-sep S]]
 
 Loads the files the first CLI wrote (ucitajSvePodatkeDoBCD, python bcd.py:67-81; always the "posle 00"
 labels), runs bcd_times BCD sweeps on the GPU and, after every sweep, writes the reference's two .npy files
@@ -16,6 +16,12 @@ sweep; without them the run issues exactly the launches it always did.
 
 --labels FILE starts from the labels in that .npy instead of "posle 00": the labels_prior file `daisy i flann.py --prior` (or --pyramid) writes,
 or any (H,W) integer labelling with 0 <= label < nprop.
+
+--confidence writes, next to the flow of the last sweep that ran, "Margin slike <idx> backward=<b> posle <w> BCD.npy"
+(flowio.margin_name): the (H,W) float32 margin plane of the final labelling (DiscreteFlow.confidence, DESIGN.md "Label
+confidence"), +Inf where no label competes.  --conf-mode local|data picks the energy (default local), --conf-sep S the L1 distance
+up to which a label counts as the chosen motion itself (0..1024, default 1).  Without it nothing is launched that was not
+launched before.
 """
 import argparse
 import importlib
@@ -34,11 +40,14 @@ def parser():
     ap.add_argument("--cell"); ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--labels", metavar="FILE", help="start from these labels (an (H,W) integer .npy) instead of \"posle 00\"")
     importlib.import_module(PKG + ".bcdstats").add_cli_options(ap, "--stats")
+    importlib.import_module(PKG + ".labelconf").add_cli_options(ap, with_threshold=False)
     return ap
 
 
 def main(argv=None):
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
+    conf_mode, conf_sep = importlib.import_module(PKG + ".labelconf").from_args(ap, a)
     bcdstats = importlib.import_module(PKG + ".bcdstats")
     stop = bcdstats.stop_from_args(a)
     pipeline = importlib.import_module(PKG + ".pipeline")
@@ -64,6 +73,9 @@ def main(argv=None):
         print("uradjen bcd broj", w)
 
     history = df.ceoBCD(a.bcd_times, on_sweep=save, stop=stop)
+    if a.confidence:
+        last = a.bcd_times if history is None else len(history) - 1
+        np.save(flowio.margin_name(idx, a.backward, last), df.confidence(mode=conf_mode, min_sep=conf_sep).cpu().numpy())
     if history is not None:
         for h in history:
             print(bcdstats.format_row(h))

@@ -64,6 +64,13 @@ Without them nothing is launched that was not launched before.
 defaults, DESIGN.md "Global-motion fit"; --motion-thresh T is its inlier threshold in pixels, default 1) and writes
 residual_<pair>.flo, the forward flow minus the model's, and motion.json in DIR with the per-pair rows {pair, matrix, scored,
 inliers}.  One line per pair gives the inlier share.  Without it nothing is launched that was not launched before.
+--confidence T takes every pass's label margin after its sweeps (DiscreteFlow.confidence, DESIGN.md "Label confidence"; --conf-mode
+local|data and --conf-sep S as in "python bcd.py", default local and 1); the margin travels to rank 0 as a third channel of the
+pass's flow.  There every pair's checked sparse field is gated with the forward margin (pipeline.flow_gate, margin >= T), after
+the check, --segments and --wmedian-reject and before everything that reads the sparse field; one line per pair gives the counts,
+and margin_<pair>.npy holds the forward margin.  --eval gains the kind "confident", the forward flow gated by its margin alone,
+with no backward pass involved, and the header of eval.json "confidence": [T, mode, S].  Without it nothing is launched that was
+not launched before, and the flows travel as (H,W,2).
 """
 import argparse
 import importlib
@@ -115,6 +122,7 @@ def parser():
                     help="also fit the dominant motion (affine or homography) of each forward flow; writes motion.json and residual_NN.flo")
     ap.add_argument("--motion-thresh", default=None, metavar="T", help="with --motion: the inlier threshold in pixels (default 1)")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
+    mod("labelconf").add_cli_options(ap, with_threshold=True)
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
     ap.add_argument("--coarse-bcd-times", type=int, default=None, metavar="N", help="with --pyramid: sweeps of the coarse levels (default: --bcd-times)")
     ap.add_argument("--fine-window", type=int, default=None, metavar="W", help="with --pyramid: kNN window (0..2) of the full-size level")
@@ -342,7 +350,11 @@ def compute_many(s, descs):
         if hist is not None:
             for desc, h in zip(part, hist):
                 s.histories[s.passes.index(desc)] = h
-        flows += [df.vratiKonacniFlow().clone() for df in dfs]
+        if s.a.confidence is None:
+            flows += [df.vratiKonacniFlow().clone() for df in dfs]
+        else:                                                # [dy, dx, margin]: one tensor per pass to gather
+            flows += [torch.cat([df.vratiKonacniFlow(), df.confidence(mode=s.a.conf_mode, min_sep=s.a.conf_sep)[..., None]], dim=2)
+                      for df in dfs]
     return flows
 
 
@@ -353,8 +365,10 @@ def run_passes(s):
     import torch.distributed as dist
     a, H, W = s.a, s.H, s.W
 
+    like = s.dfs[0].flow if a.confidence is None else torch.empty((H, W, 3), dtype=torch.float32, device=s.dev)
+
     def run():
-        return mod("sharding").run_passes(s.passes, None, s.world, s.rank, s.dfs[0].flow, compute_many=lambda descs: compute_many(s, descs))
+        return mod("sharding").run_passes(s.passes, None, s.world, s.rank, like, compute_many=lambda descs: compute_many(s, descs))
 
     def settle():
         torch.cuda.synchronize()
@@ -379,9 +393,10 @@ def run_passes(s):
     return flows
 
 
-def write_pair(s, pair, fwd, bwd):
+def write_pair(s, pair, fwd, bwd, margin=None):
     """The flow, sparse-field, edge and Epic files of one pair and its printed line; returns the sparse field on the device,
-    the final dense flow (None without --epic) and the pair's images (None unless a stage asked for them)."""
+    the final dense flow (None without --epic) and the pair's images (None unless a stage asked for them).  margin: the
+    forward pass's margin plane under --confidence."""
     a = s.a
     pipeline, synth, flowio = mod("pipeline"), mod("synth"), mod("flowio")
     sparse_dev = pipeline.flow_consistency(fwd, bwd, a.thresh) if a.check == "natural" else pipeline.fb_consistency(fwd, bwd, a.thresh)
@@ -395,6 +410,10 @@ def write_pair(s, pair, fwd, bwd):
         sparse_dev, wm_counts = pipeline.flow_wmedian(sparse_dev, img1, radius=a.wmedian_reject[0], reject=a.wmedian_reject[1], counts=True)
         print("pair %d: weighted median rejection: %s" % (pair, " ".join("%s=%d" % kv for kv in zip(pipeline.FLOW_WMEDIAN_COUNTS,
                                                                                                      wm_counts.cpu().tolist()))))
+    if margin is not None:
+        sparse_dev, gate_counts = pipeline.flow_gate(sparse_dev, margin, lo=a.confidence, counts=True)
+        print("pair %d: confidence gate at margin >= %g: %d of %d checked vectors stay" % ((pair, a.confidence) + tuple(gate_counts.cpu().tolist()[::-1])))
+        np.save(os.path.join(a.out, "margin_%02d.npy" % pair), margin.cpu().numpy())
     sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
     sparse = sparse_dev.cpu().numpy()
     for backward, f in ((0, fwd), (1, bwd)):
@@ -440,7 +459,9 @@ def write_out(s, flows):
     mid_rows = []
     motion_rows = []
     for pair in range(a.pairs):
-        fwd = flows[2 * pair]
+        fwd, bwd, margin = flows[2 * pair], flows[2 * pair + 1], None
+        if a.confidence is not None:            # [dy, dx, margin] per pass
+            fwd, bwd, margin = fwd[..., :2].contiguous(), bwd[..., :2].contiguous(), fwd[..., 2].contiguous()
         if a.motion is not None:
             matrix, residual, counts = pipeline.motion_fit(fwd, model=a.motion, thresh=a.motion_thresh, residual=True, counts=True)
             flowio.write_flo(os.path.join(a.out, "residual_%02d.flo" % pair), residual[..., [1, 0]].cpu().numpy())
@@ -448,7 +469,7 @@ def write_out(s, flows):
             motion_rows.append(dict(pair=pair, matrix=matrix.cpu().numpy().tolist(), scored=counts[0], inliers=counts[1]))
             print("pair %d: %s motion: %d of %d vectors within %g px (%.2f%%)"
                   % (pair, a.motion, counts[1], counts[0], a.motion_thresh, 100.0 * counts[1] / max(counts[0], 1)))
-        sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, flows[2 * pair + 1])
+        sparse_raw, epic, img1, img2 = write_pair(s, pair, fwd, bwd, margin)
         dense = [("epic", epic)] if a.epic else []
         if a.wmedian is not None:
             filtered = pipeline.flow_wmedian(fwd, img1, radius=a.wmedian)
@@ -457,7 +478,8 @@ def write_out(s, flows):
         if a.eval:
             gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]
             gt = torch.from_numpy(evaluate.to_uv_valid(gt) if gt.shape[2] == 2 else np.asarray(gt, np.float32)).to(s.dev)
-            tally(EVAL, pair, [("fwd", fwd), ("sparse", sparse_raw)] + dense, lambda field, **kw: pipeline.flow_eval(field, gt, **kw),
+            confident = [("confident", pipeline.flow_gate(fwd, margin, lo=a.confidence))] if margin is not None else []
+            tally(EVAL, pair, [("fwd", fwd), ("sparse", sparse_raw)] + confident + dense, lambda field, **kw: pipeline.flow_eval(field, gt, **kw),
                   eval_rows, eval_totals, s.dev)
         if a.pictures:
             for name, field in [("flowcolor", fwd)] + [("flowcolor_" + kind, f) for kind, f in dense]:
@@ -466,7 +488,7 @@ def write_out(s, flows):
             tally(PHOTO, pair, [("fwd", fwd)] + dense, lambda field, **kw: pipeline.warp_eval(img1, img2, field, **kw),
                   photo_rows, photo_totals, s.dev)
         if a.midframe:
-            midframe_pair(s, pair, fwd, flows[2 * pair + 1], mid_rows)
+            midframe_pair(s, pair, fwd, bwd, mid_rows)
     head = {"size": [H, W], "bcd_times": a.bcd_times}
     if a.pyramid > 1:
         head["pyramid"] = a.pyramid
@@ -489,11 +511,17 @@ def write_out(s, flows):
             head["wmedian"] = a.wmedian
         if a.wmedian_reject is not None:
             head["wmedian_reject"] = [a.wmedian_reject[0], a.wmedian_reject[1]]
+        if a.confidence is not None:
+            head["confidence"] = [a.confidence, a.conf_mode, a.conf_sep]
         write_tally(os.path.join(a.out, "eval.json"), dict(head, abs_thresh=3.0), EVAL, eval_rows, eval_totals)
 
 
 def main(argv=None):
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
+    a.conf_mode, a.conf_sep = mod("labelconf").from_args(ap, a)
+    if a.confidence is not None:
+        a.confidence = mod("labelconf").threshold(a.confidence, ap.error)
     a.epic = a.epic or a.epic_refine or a.prefilter
     if a.segments is not None:
         a.segments = segments_arg(a.segments)

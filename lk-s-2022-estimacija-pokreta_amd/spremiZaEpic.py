@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Drop-in for the reference's third step (README.md:25-67, spremiZaEpic.py:1-28):
 
-    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--natural-check] [--segments MIN T] [--gpu-epic [--prefilter] [--refine]]
+    python spremiZaEpic.py <img1> <img2> <forward flow .npy> <backward flow .npy> <con_tresh> canny|sed|pb [--natural-check] [--segments MIN T] [--margin FILE T] [--gpu-epic [--prefilter] [--refine]]
 
 Same positional arguments, same files in the current directory: sparse_field.npy (postProcessing, through
 dflow_fb_consistency on the GPU), parovi.txt (napravi_parove.parovi) and ivice.bin (edge.canny_ivice of img1, through
@@ -31,6 +31,10 @@ filter"): segments of fewer than MIN pixels, grown over neighbours whose vectors
 This is part of postProcessing, where the reference has the call commented out (postprocessing.py:132): unlike --prefilter,
 sparse_field.npy, parovi.txt and everything after them come from the filtered field.  Both values must be given: MIN an integer
 >= 0, T finite and >= 0.
+With the three tokens --margin FILE T directly after --segments MIN T if that is there, else where --segments would stand, and
+before --gpu-epic, vectors whose forward margin is below T are dropped from the checked (and segment-filtered) field
+(pipeline.flow_gate; DESIGN.md "Label confidence"): FILE is the (H,W) float32 .npy that `"python bcd.py" --confidence` wrote for the
+forward pass.  Like --segments it comes before everything that reads sparse_field.npy.  T is a number, infinite perhaps, not NaN.
 """
 import importlib
 import os
@@ -85,12 +89,44 @@ def take_segments(argv):
     return argv[:6] + argv[9:], (min_size, thresh)
 
 
+def take_margin(argv):
+    """The optional tokens --margin FILE T after the six positional ones (--natural-check and --segments already taken): (the
+    command line without them, (FILE, T) or None), or the exit status 2 after saying why."""
+    if argv[6:7] != ["--margin"]:
+        return argv, None
+    try:
+        path, thresh = argv[7], float(argv[8])
+        if np.isnan(thresh):
+            raise ValueError
+    except (IndexError, ValueError):
+        print("spremiZaEpic: --margin needs FILE and T (a number, not NaN), got %r" % (argv[7:9],), file=sys.stderr)
+        return 2
+    return argv[:6] + argv[9:], (path, thresh)
+
+
+def load_margin(path, shape):
+    """The margin plane of --margin: an (H,W) float32 .npy of the flow's size, or None after saying why not."""
+    try:
+        m = np.load(path)
+    except (OSError, ValueError) as e:
+        print("spremiZaEpic: --margin %s: %s" % (path, e), file=sys.stderr)
+        return None
+    if m.dtype != np.float32 or m.shape != tuple(shape):
+        print("spremiZaEpic: --margin %s holds %s %s, expected float32 %s" % (path, m.dtype, m.shape, tuple(shape)), file=sys.stderr)
+        return None
+    return m
+
+
 def main(argv=None):
     argv, natural = take_natural(sys.argv[1:] if argv is None else list(argv))
     taken = take_segments(argv)
     if taken == 2:
         return 2
     argv, segments = taken
+    taken = take_margin(argv)
+    if taken == 2:
+        return 2
+    argv, margin = taken
     parsed = parse(argv)
     if parsed == 2:
         return 2
@@ -103,15 +139,22 @@ def main(argv=None):
         except NotImplementedError as e:
             print("spremiZaEpic: %s" % e, file=sys.stderr)
             return 2
+    fwd_host = np.load(foward).astype(np.float32)
+    if margin is not None:
+        margin_plane = load_margin(margin[0], fwd_host.shape[:2])
+        if margin_plane is None:
+            return 2
     import torch
     pipeline = importlib.import_module(PKG + ".pipeline")
     evaluate = importlib.import_module(PKG + ".evaluate")
     dev = torch.device("cuda", torch.cuda.current_device())
-    fwd = torch.from_numpy(np.load(foward).astype(np.float32)).to(dev)
+    fwd = torch.from_numpy(fwd_host).to(dev)
     bwd = torch.from_numpy(np.load(backward).astype(np.float32)).to(dev)
     sparse_dev = pipeline.flow_consistency(fwd, bwd, con_tresh) if natural else pipeline.fb_consistency(fwd, bwd, con_tresh)
     if segments is not None:
         sparse_dev = pipeline.segment_filter(sparse_dev, segments[1], segments[0])
+    if margin is not None:
+        sparse_dev = pipeline.flow_gate(sparse_dev, margin_plane, lo=margin[1])
     sparse = sparse_dev.cpu().numpy()                                      # postProcessing, :15
     np.save("sparse_field.npy", sparse)
     evaluate.parovi(sparse, "parovi.txt")                                  # :17
