@@ -31,7 +31,7 @@
 //   screen    (knn_screen_kernel) pass 1: w = G^ - bounds - h - S_c <= tau for every (query, candidate) of a (64-query wave,
 //             candidate cell).  Every lane keeps the 5 largest maxima of its 16-value tile columns -> a5 <= the 5th largest
 //             tau of the query.  pass 2: v = G^ + bounds - h + S_c >= tau.  Only candidates with v >= a5 - s (s: rounding
-//             of the canonical float32 distance) can be among the exact 5 NN: these "events" (a 16-bit row mask per lane
+//             of the canonical float32 distance, with room: KM_SWIDTH) can be among the exact 5 NN: these "events" (a 16-bit row mask per lane
 //             and tile) go to per-lane lists in the workspace (capacity = the tiles of the largest cell + 1, at most
 //             KM_EVROWS_MAX: a list can overflow only in cells of more than 2880 points).
 //             Events per (query, cell) on the bench frame: 5.7 (5 is the minimum).
@@ -101,6 +101,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define KM_MAXPTS 65535         // candidate index must fit 16 bits
 #define KM_LIST_WORDS(evrows) (2 * (evrows) * 64)       // one event list: [group][entry][lane] uint32
 #define KM_ETA 7.62939453125e-6                  // eta = 2^-17: allowance for the f32 accumulation inside the matrix core
+#define KM_SWIDTH 3.5e-5f                         // width of the event test relative to hq - a5 (see the end of pass 1)
 
 struct KmGeom {
     Geom g;
@@ -208,15 +209,22 @@ __global__ void __launch_bounds__(256) knn_prep_kernel(const T *__restrict__ d1,
         z0[orow] = make_float2(zd.l2, zd.l1());
     }
     double sxall = 0.0;
-    bool bad = false;
+    uint32_t top = 0u;                                // largest |value| of the row as an integer: inf and NaN sort above every finite value
 #pragma unroll
     for (int k = 0; k < DFLOW_DESC; k++) {
+        const uint32_t bits = __float_as_uint(x[k]) & 0x7FFFFFFFu;
+        top = bits > top ? bits : top;
         const float sc = KM_ALPHA * x[k];             // exact
-        bad |= (__float_as_uint(sc) & 0x7FFFFFFFu) >= 0x7F800000u;      // inf, NaN (tested on the bits: -fno-honor-nans)
         x[k] = sc;
         sxall = fma((double)sc, (double)sc, sxall);          // |x|^2; |V^T x|^2 = |x|^2 (1 +- PCA_DELTA_MAX)
     }
-    bad |= !(sxall < KM_NORM2_MAX);
+    // inf, NaN.  This file is compiled with -fno-honor-nans: a test written on a float's bits next to the float itself is
+    // folded into a float comparison and then loses its NaN half (|v| == inf; and !(sxall < MAX) becomes sxall >= MAX, false
+    // for NaN), so a NaN row passed as a good one (tests/test_gpu_knn_screen_rows.py).  The maximum is taken on integers and
+    // hidden from the optimiser before it is compared.
+    asm volatile("" : "+v"(top));
+    bool bad = top >= 0x7F800000u;
+    bad |= !(sxall < KM_NORM2_MAX);                   // also 64 x overflowing to inf
     const bool zero = sxall == 0.0;                   // every value +-0: ties with every other such row for every query
     double ss = 0.0, sx = 0.0, se = 0.0;        // |y~|^2, |y^|^2, |y~ - y^|^2 over the KM_KD leading components
     auto component = [&](int j) -> _Float16 {
@@ -597,9 +605,14 @@ __global__ void __launch_bounds__(KM_THREADS, 4) knn_screen_kernel(KmGeom a, KmS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // drain the over-staged chunks before the buffers are reused
         __builtin_amdgcn_s_barrier();
         if (pass == 0) {
-            // merge the two half-lanes of every query; pass-2 values v qualify iff v >= a5 - s, where s covers the rounding of
-            // the canonical float32 distance (relative < 1.1e-5) and |y_q - y_c|^2 = |x_q - x_c|^2 (1 +- 2e-6): twice
-            // 1.35e-5 of 64^2 d^2 / 2 = 0.5 |x_q|^2 - tau <= hq - a5
+            // merge the two half-lanes of every query; pass-2 values v qualify iff v >= a5 - s with s = KM_SWIDTH (hq - a5),
+            // hq - a5 >= 0.5 |y_q|^2 - tau_5 = half the fifth smallest |y_q - y_c|^2.  So every candidate whose |x_q - x_c|^2 is
+            // within 3e-5 (relative) of the fifth smallest is an event: |y_q - y_c|^2 = |x_q - x_c|^2 (1 +- 2e-6), and
+            // (1 + 3e-5) (1 + 2e-6) / (1 - 2e-6) < 1 + 3.5e-5.  That is three times what the rounding of the canonical float32
+            // distance needs (relative < 1.1e-5 on either side), and it is the width the lists are checked against
+            // (tests/knn_screen_ref.py, EVENT_WIDTH).  The factor was 2.7e-5 until that check existed, which in x guarantees
+            // 2.3e-5 only: exact, but a full-scale query against a cell of near-zero rows (all distances within 1e-5 of each
+            // other) left out candidates at 2.99e-5.
 #pragma unroll
             for (int gq = 0; gq < 2; gq++) {
                 float o[5];
@@ -608,9 +621,9 @@ __global__ void __launch_bounds__(KM_THREADS, 4) knn_screen_kernel(KmGeom a, KmS
 #pragma unroll
                 for (int i = 0; i < 5; i++) top5_insert_desc(a5[gq], o[i]);
                 const float a5v = a5[gq][4];
-                const float x = a5v - 2.7e-5f * fmaxf(hq[gq] - a5v, 0.0f);
+                const float x = a5v - KM_SWIDTH * fmaxf(hq[gq] - a5v, 0.0f);
                 // (the float32 roundings of x itself: a few ulp of its two terms)
-                float th = fmaxf(x - 1e-6f * (fabsf(a5v) + 2.7e-5f * hq[gq]), -55000.0f);   // real values are > -50000, sentinel rows -60000
+                float th = fmaxf(x - 1e-6f * (fabsf(a5v) + KM_SWIDTH * hq[gq]), -55000.0f);   // real values are > -50000, sentinel rows -60000
                 // an all-zero query takes the cell's own list (knn_cell_post_kernel): no events
                 if (qzero[gq]) th = 60000.0f;
                 // Pass 2 subtracts the threshold inside the matrix core: two f16 pieces of th' (22 bits) times the 1.0 the
