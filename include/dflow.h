@@ -29,6 +29,52 @@
  *     A d_ws that is not returns DFLOW_EINVAL ("d_ws is not N-byte aligned") before anything is launched.  Every other argument
  *     error is reported first, and so is a NULL or too small workspace (DFLOW_ENOSPC), except by dflow_bcd_stats(_batch),
  *     dflow_flow_advance and dflow_segment_filter, which check d_ws with their other pointers, before its size.
+ *   - Alignment of data planes.  A plane needs exactly the bytes of its layout (below, and at each entry point): nothing before
+ *     or beyond them is read or written.  Its address must be a multiple of the widest access a kernel makes to it, never less
+ *     than the element size, and the state planes of a pass have one number wherever they are passed: 16 for descriptor planes
+ *     in both storages (rows move as float4 / 8 x binary16 and through 16-byte LDS-DMA) and for proposals and lcosts (rows are
+ *     read 16 bytes at a time; dflow_prior_proposals, which writes costs a float at a time, keeps the 4 it has always asked of
+ *     d_lcosts), 8 for (H,W,2) flows that move as float2 and for uint64 / double planes, 4 for other float, int32 and uint32
+ *     planes, 1 for images and byte planes unless a stage moves them four pixels at a time.  A device allocation (256 bytes and
+ *     more) serves every plane, and so does a view at a multiple of 16 bytes into one.  NULL optional outputs pass.  Per entry
+ *     point (d_ws above; planes that are not named need 1):
+ *       dflow_daisy                 d_descr 16
+ *       dflow_daisy_pair            d_descr1, d_descr2 16
+ *       dflow_knn_proposals, dflow_knn_proposals_timed, dflow_neighbour_proposals
+ *                                   d_descr1, d_descr2, d_proposals, d_lcosts 16; d_nprop, d_bestlabels 4
+ *       dflow_bcd_prepare           d_proposals, d_lcosts 16; d_nprop 4
+ *       dflow_bcd_phase, dflow_bcd_sweep
+ *                                   d_proposals 16 (not read: what the stages that read it ask); d_nprop, d_bestlabels 4
+ *       dflow_bcd_phase_batch, dflow_bcd_sweep_batch
+ *                                   every d_nprop[i], d_bestlabels[i] 4
+ *       dflow_bcd_stats             d_proposals, d_lcosts 16; d_nprop, d_bestlabels, d_prev_labels, d_prev_out 4; d_stats 8
+ *       dflow_bcd_stats_batch       every d_proposals[i], d_lcosts[i] 16; d_nprop[i], d_bestlabels[i], d_prev[i] 4; d_stats 8
+ *       dflow_labels_to_flow        d_proposals 16; d_bestlabels 4; d_flow 8 (float2 stores)
+ *       dflow_fb_consistency        d_fwd, d_bwd 8 (float2 loads); d_sparse 4
+ *       dflow_pack_compat           d_proposals 16; d_nprop 4; d_packed 1
+ *       dflow_canny_edges           d_ivice 4; d_bgr, d_edges 1
+ *       dflow_pb_edges              d_strength, d_orient_strength 4; d_bgr 1
+ *       dflow_epic_interpolate      d_sparse, d_edges, d_flow, d_seed_of, d_dist, d_lists 4; d_list_g 8
+ *       dflow_epic_prefilter        d_sparse_in, d_edges, d_sparse_out, d_saliency, d_estimate 4; d_bgr, d_reason 1
+ *       dflow_var_refine            d_flow_in, d_flow_out 8 (float2); d_bgr1, d_bgr2 1
+ *       dflow_flow_eval             d_test, d_gt, d_err 16; d_stats 8; d_err_bgr 4
+ *       dflow_flow_color            d_flow 16; d_bgr, d_maxrad 4
+ *       dflow_warp_eval             d_flow, d_err 16; d_stats 8; d_bgr1, d_warped, d_err_bgr 4; d_bgr2 1
+ *       dflow_prior_proposals       d_descr1, d_descr2, d_proposals 16; d_prior, d_lcosts, d_nprop, d_bestlabels, d_counts 4
+ *       dflow_flow_advance          d_flow, d_out, d_counts 4
+ *       dflow_pyr_down              d_in1, d_in2, d_out1, d_out2 4
+ *       dflow_flow_upsample         d_coarse, d_out, d_counts 4
+ *       dflow_flow_consistency      d_fwd, d_bwd, d_out_fwd, d_out_bwd, d_err_fwd, d_err_bwd, d_counts 4
+ *       dflow_segment_filter        d_flow, d_out, d_segment, d_size, d_counts 4
+ *       dflow_frame_interp          d_keys 8; d_fwd, d_bwd, d_motion, d_motion_tmp, d_counts 4; d_bgr1, d_bgr2, d_out, d_source 1
+ *       dflow_flow_wmedian          d_flow, d_out, d_counts 4; d_bgr, d_wspace, d_wcolor 1
+ *       dflow_motion_fit            d_state 8; d_flow, d_model, d_models, d_hyp_counts, d_model_flow, d_residual, d_counts 4;
+ *                                   d_exclude, d_class 1
+ *       dflow_label_confidence      d_proposals, d_lcosts, d_sparse 16; d_nprop, d_bestlabels, d_margin, d_alt, d_counts 4
+ *       dflow_flow_gate             d_flow, d_score, d_out 16; d_counts 4
+ *     A plane below its number returns DFLOW_EINVAL ("NAME is not N-byte aligned", the batch forms name the entry NAME[i]) before
+ *     anything is launched, after the NULL checks and before the workspace is looked at (the batch forms of the sweeps check the
+ *     one size of their workspaces before any per-pass pointer, as they always have).
  *
  * Device layouts (H = pich, W = picw, LP = label_pitch >= maxnprop, multiple of 16)
  *   image      uint8   (H,W,3)   BGR, as cv2.imread returns it            daisy i flann.py:26-27,52-53

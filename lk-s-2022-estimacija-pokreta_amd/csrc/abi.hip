@@ -3,7 +3,7 @@
 //
 // A gate is a sequence of the checks defined below dflow_check_launch, each called with __func__ and returning DFLOW_OK or what
 // dflow_set_error returned: check_frame_size, check_layout, check_flags, check_finite_ge0 / check_finite_gt0, check_int_range,
-// check_not_nan, check_ordered, check_any_given, CHECK_PTR, check_aligned, check_distinct (outputs against inputs and each other) and, last but where d_ws has always been among
+// check_not_nan, check_ordered, check_any_given, CHECK_PTR, check_aligned (CHECK_ALIGNED; check_aligned_entry for one entry of a batch form's arrays), check_distinct (outputs against inputs and each other) and, last but where d_ws has always been among
 // the aligned pointers, CHECK_WS; FRAME_WS_BYTES defines an image-plane stage's size function.  A new entry point's gate is
 // assembled from these, and its refusals are added to tests/test_abi_refusals.py, which pins every status, text and the order.
 #include <math.h>
@@ -103,6 +103,28 @@ static int check_aligned(const char *fn, std::initializer_list<AlignedPtr> ptrs)
         if ((uintptr_t)q.p % q.align) return dflow_set_error(DFLOW_EINVAL, "%s: %s is not %d-byte aligned", fn, q.name, (int)q.align);
     return DFLOW_OK;
 }
+
+// entry i of a batch form's host array of device pointers: the message names it name[i]
+static int check_aligned_entry(const char *fn, const char *name, int i, const void *p, uintptr_t align)
+{
+    char entry[48];
+    snprintf(entry, sizeof(entry), "%s[%d]", name, i);
+    return check_aligned(fn, {{entry, p, align}});
+}
+
+// The boundaries of the data planes (include/dflow.h, "Alignment of data planes"): the widest access a kernel makes to the plane,
+// one number per plane wherever it is passed.  Descriptor rows move as float4 / 8 x binary16 and through 16-byte LDS-DMA
+// (dflow_common.h desc_load_row, knn.hip, row_stage.h); label and cost rows are read 16 bytes at a time (prior.hip,
+// label_conf.hip); [dy,dx] flows move as float2 (post.hip, variational.hip); the EPIC distance lists hold uint64.
+#define ALIGN_DESCR 16
+#define ALIGN_LABEL_ROWS 16
+#define ALIGN_FLOW2 8
+#define ALIGN_WORD 4
+// the state of a pass: the planes every main-path stage and the statistics share
+#define STATE_ROWS_ALIGNED {"d_proposals", d_proposals, ALIGN_LABEL_ROWS}, {"d_lcosts", d_lcosts, ALIGN_LABEL_ROWS}
+#define STATE_COUNTS_ALIGNED {"d_nprop", d_nprop, ALIGN_WORD}, {"d_bestlabels", d_bestlabels, ALIGN_WORD}
+#define DESCR_PAIR_ALIGNED {"d_descr1", d_descr1, ALIGN_DESCR}, {"d_descr2", d_descr2, ALIGN_DESCR}
+#define CHECK_ALIGNED(...) do { int rc_al_ = check_aligned(__func__, {__VA_ARGS__}); if (rc_al_) return rc_al_; } while (0)
 
 // no output that is given is the plane of an input or of an output listed before it
 struct NamedPlane { const char *name; const void *p; };
@@ -206,7 +228,9 @@ size_t dflow_workspace_bytes(const dflow_params *p)
 int dflow_daisy(const dflow_params *p, const uint8_t *d_bgr, void *d_descr, void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_bgr); CHECK_PTR(d_descr); CHECK_WS(WS_ALIGN_MAIN, daisy_ws_bytes(p));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_descr);
+    CHECK_ALIGNED({"d_descr", d_descr, ALIGN_DESCR});
+    CHECK_WS(WS_ALIGN_MAIN, daisy_ws_bytes(p));
     return launch_daisy(p, d_bgr, d_descr, d_ws, (hipStream_t)stream);
 }
 
@@ -214,7 +238,9 @@ int dflow_daisy_pair(const dflow_params *p, const uint8_t *d_bgr1, const uint8_t
                      void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_WS(WS_ALIGN_MAIN, daisy_pair_ws_bytes(p));
+    CHECK_PTR(d_bgr1); CHECK_PTR(d_bgr2); CHECK_PTR(d_descr1); CHECK_PTR(d_descr2);
+    CHECK_ALIGNED(DESCR_PAIR_ALIGNED);
+    CHECK_WS(WS_ALIGN_MAIN, daisy_pair_ws_bytes(p));
     // the two images run side by side: the outputs must be two planes
     if (d_descr1 == d_descr2) return dflow_set_error(DFLOW_EINVAL, "%s: d_descr1 and d_descr2 are the same plane", __func__);
     return launch_daisy_pair(p, d_bgr1, d_bgr2, d_descr1, d_descr2, d_ws, (hipStream_t)stream);
@@ -235,6 +261,7 @@ int dflow_knn_proposals(const dflow_params *p, const void *d_descr1, const void 
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
+    CHECK_ALIGNED(DESCR_PAIR_ALIGNED, STATE_ROWS_ALIGNED, STATE_COUNTS_ALIGNED);
     if (!knn_is_screened(p)) return launch_knn(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, (hipStream_t)stream);
     if ((rc = knn_check_screened(__func__, p, d_ws, ws_bytes))) return rc;
     return launch_knn_mfma(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream);
@@ -247,6 +274,7 @@ int dflow_knn_proposals_timed(const dflow_params *p, const void *d_descr1, const
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
     CHECK_PTR(h_ms);
+    CHECK_ALIGNED(DESCR_PAIR_ALIGNED, STATE_ROWS_ALIGNED, STATE_COUNTS_ALIGNED);
     if ((rc = knn_check_screened(__func__, p, d_ws, ws_bytes))) return rc;
     hipEvent_t ev[KNN_MFMA_EVENTS] = {};
     rc = [&]() {
@@ -287,6 +315,7 @@ int dflow_neighbour_proposals(const dflow_params *p, const void *d_descr1, const
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_descr1); CHECK_PTR(d_descr2); CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
+    CHECK_ALIGNED(DESCR_PAIR_ALIGNED, STATE_ROWS_ALIGNED, STATE_COUNTS_ALIGNED);
     CHECK_WS(WS_ALIGN_MAIN, neighbour_ws_bytes(p));
     return launch_neighbour(p, d_descr1, d_descr2, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_ws, (hipStream_t)stream);
 }
@@ -295,7 +324,9 @@ int dflow_bcd_prepare(const dflow_params *p, const uint32_t *d_proposals, const 
                       void *d_ws, size_t ws_bytes, void *stream)
 {
     int rc = dflow_check_params(p); if (rc) return rc;
-    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
+    CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop);
+    CHECK_ALIGNED(STATE_ROWS_ALIGNED, {"d_nprop", d_nprop, ALIGN_WORD});
+    CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
     return launch_bcd_prepare(p, d_proposals, d_lcosts, d_nprop, d_ws, (hipStream_t)stream);
 }
 
@@ -305,6 +336,8 @@ int dflow_bcd_phase(const dflow_params *p, const uint32_t *d_proposals, const in
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels);
     if ((rc = check_int_range(NULL, "phase", phase, 0, 3))) return rc;
+    // d_proposals is not read (the records of dflow_bcd_prepare hold the flows): it is held to what the stages that read it ask
+    CHECK_ALIGNED({"d_proposals", d_proposals, ALIGN_LABEL_ROWS}, STATE_COUNTS_ALIGNED);
     CHECK_WS(WS_ALIGN_MAIN, bcd_ws_bytes(p));
     return launch_bcd_phase(p, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
@@ -330,9 +363,12 @@ int dflow_bcd_phase_batch(const dflow_params *p, int32_t npass, const int32_t *c
     if ((rc = check_ws_size(__func__, d_ws, ws_bytes, bcd_ws_bytes(p)))) return rc;
     for (int i = 0; i < npass; i++)
         if (!d_nprop[i] || !d_bestlabels[i] || !d_ws[i]) return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
+    for (int i = 0; i < npass; i++) {
+        if ((rc = check_aligned_entry(__func__, "d_nprop", i, d_nprop[i], ALIGN_WORD))) return rc;
+        if ((rc = check_aligned_entry(__func__, "d_bestlabels", i, d_bestlabels[i], ALIGN_WORD))) return rc;
+    }
     for (int i = 0; i < npass; i++)
-        if ((uintptr_t)d_ws[i] % WS_ALIGN_MAIN)
-            return dflow_set_error(DFLOW_EINVAL, "%s: d_ws[%d] is not %d-byte aligned", __func__, i, WS_ALIGN_MAIN);
+        if ((rc = check_aligned_entry(__func__, "d_ws", i, d_ws[i], WS_ALIGN_MAIN))) return rc;
     return launch_bcd_phase_batch(p, npass, d_nprop, d_bestlabels, phase, d_ws, (hipStream_t)stream);
 }
 
@@ -389,6 +425,13 @@ int dflow_bcd_stats_batch(const dflow_params *p, int32_t npass, const uint32_t *
     for (int i = 0; i < npass; i++)
         if (!d_proposals[i] || !d_lcosts[i] || !d_nprop[i] || !d_bestlabels[i])
             return dflow_set_error(DFLOW_EINVAL, "%s: pass %d has a NULL pointer", __func__, i);
+    for (int i = 0; i < npass; i++) {
+        if ((rc = check_aligned_entry(__func__, "d_proposals", i, d_proposals[i], ALIGN_LABEL_ROWS))) return rc;
+        if ((rc = check_aligned_entry(__func__, "d_lcosts", i, d_lcosts[i], ALIGN_LABEL_ROWS))) return rc;
+        if ((rc = check_aligned_entry(__func__, "d_nprop", i, d_nprop[i], ALIGN_WORD))) return rc;
+        if ((rc = check_aligned_entry(__func__, "d_bestlabels", i, d_bestlabels[i], ALIGN_WORD))) return rc;
+        if (d_prev && (rc = check_aligned_entry(__func__, "d_prev", i, d_prev[i], ALIGN_WORD))) return rc;
+    }
     if ((rc = bcd_stats_check_out(__func__, p, npass, d_stats, d_ws, ws_bytes))) return rc;
     return launch_bcd_stats_batch(p, npass, d_proposals, d_lcosts, d_nprop, d_bestlabels, d_prev, d_prev, d_stats, d_ws,
                                   (hipStream_t)stream);
@@ -400,6 +443,7 @@ int dflow_bcd_stats(const dflow_params *p, const uint32_t *d_proposals, const fl
 {
     int rc = bcd_stats_check_params(__func__, p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_lcosts); CHECK_PTR(d_nprop); CHECK_PTR(d_bestlabels); CHECK_PTR(d_stats);
+    CHECK_ALIGNED(STATE_ROWS_ALIGNED, STATE_COUNTS_ALIGNED, {"d_prev_labels", d_prev_labels, ALIGN_WORD}, {"d_prev_out", d_prev_out, ALIGN_WORD});
     if ((rc = bcd_stats_check_out(__func__, p, 1, d_stats, d_ws, ws_bytes))) return rc;
     return launch_bcd_stats_batch(p, 1, &d_proposals, &d_lcosts, &d_nprop, &d_bestlabels, &d_prev_labels, &d_prev_out, d_stats,
                                   d_ws, (hipStream_t)stream);
@@ -410,6 +454,8 @@ int dflow_labels_to_flow(const dflow_params *p, const uint32_t *d_proposals, con
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_bestlabels); CHECK_PTR(d_flow);
+    // labels_to_flow_kernel stores a pixel's [dy,dx] as one float2
+    CHECK_ALIGNED({"d_proposals", d_proposals, ALIGN_LABEL_ROWS}, {"d_bestlabels", d_bestlabels, ALIGN_WORD}, {"d_flow", d_flow, ALIGN_FLOW2});
     return launch_labels_to_flow(p, d_proposals, d_bestlabels, d_flow, (hipStream_t)stream);
 }
 
@@ -418,6 +464,8 @@ int dflow_fb_consistency(const dflow_params *p, const float *d_fwd, const float 
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_fwd); CHECK_PTR(d_bwd); CHECK_PTR(d_sparse);
+    // fb_consistency_kernel loads a pixel's [dy,dx] as one float2 and stores [U,V,valid] a float at a time
+    CHECK_ALIGNED({"d_fwd", d_fwd, ALIGN_FLOW2}, {"d_bwd", d_bwd, ALIGN_FLOW2}, {"d_sparse", d_sparse, ALIGN_WORD});
     return launch_fb_consistency(p, d_fwd, d_bwd, tresh, d_sparse, (hipStream_t)stream);
 }
 
@@ -426,6 +474,8 @@ int dflow_pack_compat(const dflow_params *p, const uint32_t *d_proposals, const 
 {
     int rc = dflow_check_params(p); if (rc) return rc;
     CHECK_PTR(d_proposals); CHECK_PTR(d_nprop); CHECK_PTR(d_packed);
+    // d_packed is written byte by byte
+    CHECK_ALIGNED({"d_proposals", d_proposals, ALIGN_LABEL_ROWS}, {"d_nprop", d_nprop, ALIGN_WORD});
     return launch_pack_compat(p, d_proposals, d_nprop, d_packed, (hipStream_t)stream);
 }
 
@@ -438,7 +488,10 @@ int dflow_canny_edges(int32_t h, int32_t w, const uint8_t *d_bgr, double low, do
     // one message names both thresholds
     if (!isfinite(low) || !isfinite(high) || low < 0.0 || high < 0.0)
         return dflow_set_error(DFLOW_EINVAL, "%s: thresholds %g, %g must be finite and >= 0", __func__, low, high);
-    CHECK_PTR(d_bgr); CHECK_PTR(d_edges); CHECK_WS(4, canny_ws_bytes(h, w));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_edges);
+    // the image and d_edges move byte by byte
+    CHECK_ALIGNED({"d_ivice", d_ivice, ALIGN_WORD});
+    CHECK_WS(4, canny_ws_bytes(h, w));
     if (low > high) { const double t = low; low = high; high = t; }      // cv::Canny swaps them
     // m <= 4 * 255 * 2: larger thresholds all mean "no candidate" / "no strong pixel"
     const int lo = (int)floor(fmin(low, 1 << 20)), hi = (int)floor(fmin(high, 1 << 20));
@@ -452,7 +505,9 @@ int dflow_pb_edges(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t radius, f
 {
     int rc = check_frame_size(__func__, h, w); if (rc) return rc;
     if ((rc = check_int_range(__func__, "radius", radius, 1, DFLOW_PB_MAX_RADIUS))) return rc;
-    CHECK_PTR(d_bgr); CHECK_PTR(d_strength); CHECK_WS(2, pb_ws_bytes(h, w));
+    CHECK_PTR(d_bgr); CHECK_PTR(d_strength);
+    CHECK_ALIGNED({"d_strength", d_strength, ALIGN_WORD}, {"d_orient_strength", d_orient_strength, ALIGN_WORD});
+    CHECK_WS(2, pb_ws_bytes(h, w));
     return launch_pb(h, w, d_bgr, radius, d_strength, d_orient_strength, d_ws, (hipStream_t)stream);
 }
 
@@ -467,7 +522,12 @@ int dflow_epic_interpolate(int32_t h, int32_t w, const float *d_sparse, const fl
     if ((rc = check_finite_gt0(__func__, "k", k))) return rc;
     if (method != DFLOW_EPIC_LA && method != DFLOW_EPIC_NW)
         return dflow_set_error(DFLOW_EINVAL, "%s: unknown method %d", __func__, method);
-    CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow); CHECK_WS(8, epic_ws_bytes(h, w));
+    CHECK_PTR(d_sparse); CHECK_PTR(d_edges); CHECK_PTR(d_flow);
+    // every plane moves an element at a time: floats and int32, and the uint64 distances of d_list_g
+    CHECK_ALIGNED({"d_sparse", d_sparse, ALIGN_WORD}, {"d_edges", d_edges, ALIGN_WORD}, {"d_flow", d_flow, ALIGN_WORD},
+                  {"d_seed_of", d_seed_of, ALIGN_WORD}, {"d_dist", d_dist, ALIGN_WORD}, {"d_lists", d_lists, ALIGN_WORD},
+                  {"d_list_g", d_list_g, 8});
+    CHECK_WS(8, epic_ws_bytes(h, w));
     return launch_epic(h, w, d_sparse, d_edges, nn, k, method, d_flow, d_seed_of, d_dist, d_lists, d_list_g, d_ws,
                        (hipStream_t)stream);
 }
@@ -488,7 +548,11 @@ int dflow_epic_prefilter(int32_t h, int32_t w, const uint8_t *d_bgr, const float
     if (saliency_th != 0.0 && !d_bgr)
         return dflow_set_error(DFLOW_EINVAL, "%s: d_bgr is NULL with saliency_th=%g (only saliency_th = 0 runs without the image)",
                                __func__, saliency_th);
-    CHECK_PTR(d_sparse_in); CHECK_PTR(d_edges); CHECK_PTR(d_sparse_out); CHECK_WS(8, epic_prefilter_ws_bytes(h, w));
+    CHECK_PTR(d_sparse_in); CHECK_PTR(d_edges); CHECK_PTR(d_sparse_out);
+    // the image and d_reason move byte by byte, the float planes a float at a time
+    CHECK_ALIGNED({"d_sparse_in", d_sparse_in, ALIGN_WORD}, {"d_edges", d_edges, ALIGN_WORD}, {"d_sparse_out", d_sparse_out, ALIGN_WORD},
+                  {"d_saliency", d_saliency, ALIGN_WORD}, {"d_estimate", d_estimate, ALIGN_WORD});
+    CHECK_WS(8, epic_prefilter_ws_bytes(h, w));
     return launch_epic_prefilter(h, w, d_bgr, d_sparse_in, d_edges, saliency_th, pref_nn, pref_th, k, d_sparse_out, d_reason,
                                  d_saliency, d_estimate, d_ws, (hipStream_t)stream);
 }
@@ -521,6 +585,8 @@ int dflow_var_refine(int32_t h, int32_t w, const uint8_t *d_bgr1, const uint8_t 
     if ((rc = check_int_range(__func__, "niter_inner", p->niter_inner, 1, 1000))) return rc;
     if ((rc = check_int_range(__func__, "niter_solver", p->niter_solver, 1, 10000))) return rc;
     if ((rc = check_flags(__func__, p->flags, DFLOW_VAR_FLAG_SOR_UNFUSED))) return rc;
+    // var_split_kernel and var_join_kernel move a pixel's [dy,dx] as one float2; the images are read byte by byte
+    CHECK_ALIGNED({"d_flow_in", d_flow_in, ALIGN_FLOW2}, {"d_flow_out", d_flow_out, ALIGN_FLOW2});
     CHECK_WS(4, var_ws_bytes(h, w));
     return launch_var(h, w, d_bgr1, d_bgr2, d_flow_in, p, d_flow_out, d_ws, (hipStream_t)stream);
 }

@@ -453,7 +453,11 @@ def _device_of(*tensors):
 
 
 def _on(dev, *tensors):
-    return [t.to(dev).contiguous() for t in tensors]
+    """The tensors on `dev`, contiguous, each starting on a 16-byte boundary, the most include/dflow.h asks of a data plane.  A
+    caller's device tensor that already is all that stays as it is; a contiguous view that starts lower (flows[1] of a stack of
+    (H,W,3) fields whose H*W*12 is no multiple of 16) is cloned: an allocation starts on 256 bytes."""
+    out = [t.to(dev).contiguous() for t in tensors]
+    return [t.clone() if t.data_ptr() % 16 else t for t in out]
 
 
 def _out(cond, shape, dtype, dev):

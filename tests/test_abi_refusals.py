@@ -65,6 +65,9 @@ def af_base(**kw):
 WS_ROWS = [("ws_null", {"d_ws": None, "ws_bytes": BIG}, SOLO), ("ws_short", {"d_ws": WS}, SOLO), ("ws_short_and_misaligned", {"ws_bytes": 0}),
            ("ws_misaligned", {"ws_bytes": BIG}, SOLO)]
 KNN_PTRS = "d_descr1 d_descr2 d_proposals d_lcosts d_nprop d_bestlabels"
+# the data planes' boundaries (include/dflow.h, "Alignment of data planes"), after the NULL checks and before the workspace
+KNN_MIS = [mis("d_descr1", 8), mis("d_descr2", 4), mis("d_proposals", 8), mis("d_lcosts", 4), mis("d_nprop", 2), mis("d_bestlabels", 1)]
+BCD_MIS = [mis("d_proposals", 8), mis("d_nprop", 2), mis("d_bestlabels", 2)]
 KNN_BASE = ws_base(16, p=GEOM, d_descr1=A, d_descr2=B, d_proposals=D, d_lcosts=E, d_nprop=F, d_bestlabels=G)
 BCD_BASE = ws_base(16, p=GEOM, d_proposals=A, d_nprop=B, d_bestlabels=D, phase=0)
 BATCH_BASE = dict(p=GEOM, npass=2, d_nprop=[A, B], d_bestlabels=[D, E], phase=0, d_ws=[WS, WS + 4096], ws_bytes=0, stream=None)
@@ -72,7 +75,10 @@ BATCH_HEAD = P_ROWS + [null("d_nprop"), null("d_bestlabels"), null("d_ws"), ("np
 # the size comes before the per-pass pointers
 BATCH_TAIL = [("ws_short", {"ws_bytes": 0}), ("ws_short_by_one", {"ws_bytes": 255}, SOLO),
               ("pass_0_bestlabels_null", {"d_bestlabels": [None, E], "ws_bytes": BIG}), ("pass_1_nprop_null", {"d_nprop": [A, None], "ws_bytes": BIG}),
-              ("pass_1_ws_null", {"d_ws": [WS, None], "ws_bytes": BIG}), ("pass_1_ws_plus8", {"d_ws": [WS, WS + 4096 + 8], "ws_bytes": BIG}),
+              ("pass_1_ws_null", {"d_ws": [WS, None], "ws_bytes": BIG}),
+              # a pass's planes are checked pass by pass, d_nprop[i] before d_bestlabels[i]
+              ("pass_0_nprop_plus2", {"d_nprop": [A + 2, B], "ws_bytes": BIG}), ("pass_1_bestlabels_plus1", {"d_bestlabels": [D, E + 1], "ws_bytes": BIG}),
+              ("pass_1_ws_plus8", {"d_ws": [WS, WS + 4096 + 8], "ws_bytes": BIG}),
               ("pass_0_ws_plus1", {"d_ws": [WS + 1, WS + 4096], "ws_bytes": BIG}, SOLO)]
 STATS_P_ROWS = [("p_null", {"p": None}), ("p_pich_0", {"p.pich": 0}), ("p_picw_8193", {"p.picw": 8193}, SOLO), ("p_label_pitch_8", {"p.label_pitch": 8}),
                 ("p_label_pitch_24", {"p.label_pitch": 24}), ("p_maxnprop_0", {"p.maxnprop": 0}), ("p_tpsi_9", {"p.tpsi": 9}),
@@ -94,27 +100,27 @@ TABLES = {
         ("sigma_0", {"p.sigma": 0.0}), ("sigma_9", {"p.sigma": 9.0}, SOLO), ("max_attempts_1", {"p.max_attempts": 1}),
         ("flags_64", {"p.flags": 64, "p.max_attempts": 1 << 16}, SOLO), ("flags_2", {"p.flags": 2, "p.max_attempts": 1 << 16}, SOLO)]),
     "dflow_daisy": ("p d_bgr d_descr d_ws ws_bytes stream", ws_base(16, p=GEOM, d_bgr=A, d_descr=B),
-                    P_ROWS + [null("d_bgr"), null("d_descr")] + WS_ROWS),
+                    P_ROWS + [null("d_bgr"), null("d_descr"), mis("d_descr", 8)] + WS_ROWS),
     "dflow_daisy_pair": ("p d_bgr1 d_bgr2 d_descr1 d_descr2 d_ws ws_bytes stream", ws_base(16, p=GEOM, d_bgr1=A, d_bgr2=B, d_descr1=D, d_descr2=E),
-                         P_ROWS + [null("d_bgr1"), null("d_bgr2"), null("d_descr1"), null("d_descr2")] + WS_ROWS
+                         P_ROWS + [null("d_bgr1"), null("d_bgr2"), null("d_descr1"), null("d_descr2"), mis("d_descr1", 4), mis("d_descr2", 8)] + WS_ROWS
                          + [same("d_descr2", "d_descr1", d_ws=WS, ws_bytes=BIG) + (SOLO,)]),
     # never with DFLOW_FLAG_KNN_EXACT: the brute-force search takes no workspace and would run
-    "dflow_knn_proposals": ("p " + KNN_PTRS + " d_ws ws_bytes stream", KNN_BASE, P_ROWS + [null(n) for n in KNN_PTRS.split()] + WS_ROWS),
+    "dflow_knn_proposals": ("p " + KNN_PTRS + " d_ws ws_bytes stream", KNN_BASE, P_ROWS + [null(n) for n in KNN_PTRS.split()] + KNN_MIS + WS_ROWS),
     "dflow_knn_proposals_timed": ("p " + KNN_PTRS + " d_ws ws_bytes stream h_ms h_mfma_issued", dict(KNN_BASE, h_ms="ms", h_mfma_issued=None),
-                                  P_ROWS + [null(n) for n in KNN_PTRS.split()] + [null("h_ms"), ("knn_exact", {"p.flags": KNN_EXACT})] + WS_ROWS),
+                                  P_ROWS + [null(n) for n in KNN_PTRS.split()] + [null("h_ms")] + KNN_MIS + [("knn_exact", {"p.flags": KNN_EXACT})] + WS_ROWS),
     "dflow_knn_screen_stats": ("p d_ws ws_bytes stream h_stats", ws_base(16, p=GEOM, h_stats="stats"),
                                P_ROWS + [null("h_stats"), ("knn_exact", {"p.flags": KNN_EXACT})] + WS_ROWS),
     "dflow_knn_screen_stats_n": ("p d_ws ws_bytes stream h_stats n_stats", ws_base(16, p=GEOM, h_stats="stats", n_stats=14),
                                  P_ROWS + [null("h_stats"), ("n_stats_0", {"n_stats": 0}), ("n_stats_15", {"n_stats": 15}),
                                            ("knn_exact", {"p.flags": KNN_EXACT})] + WS_ROWS),
-    "dflow_neighbour_proposals": ("p " + KNN_PTRS + " d_ws ws_bytes stream", KNN_BASE, P_ROWS + [null(n) for n in KNN_PTRS.split()] + WS_ROWS),
+    "dflow_neighbour_proposals": ("p " + KNN_PTRS + " d_ws ws_bytes stream", KNN_BASE, P_ROWS + [null(n) for n in KNN_PTRS.split()] + KNN_MIS + WS_ROWS),
     "dflow_bcd_prepare": ("p d_proposals d_lcosts d_nprop d_ws ws_bytes stream", ws_base(16, p=GEOM, d_proposals=A, d_lcosts=B, d_nprop=D),
-                          P_ROWS + [null("d_proposals"), null("d_lcosts"), null("d_nprop")] + WS_ROWS),
+                          P_ROWS + [null("d_proposals"), null("d_lcosts"), null("d_nprop"), mis("d_proposals", 4), mis("d_lcosts", 8), mis("d_nprop", 1)] + WS_ROWS),
     "dflow_bcd_phase": ("p d_proposals d_nprop d_bestlabels phase d_ws ws_bytes stream", BCD_BASE,
                         P_ROWS + [null("d_proposals"), null("d_nprop"), null("d_bestlabels"), ("phase_negative", {"phase": -1}), ("phase_4", {"phase": 4})]
-                        + WS_ROWS),
+                        + BCD_MIS + WS_ROWS),
     "dflow_bcd_sweep": ("p d_proposals d_nprop d_bestlabels d_ws ws_bytes stream", BCD_BASE,
-                        P_ROWS + [null("d_proposals"), null("d_nprop"), null("d_bestlabels")] + WS_ROWS),
+                        P_ROWS + [null("d_proposals"), null("d_nprop"), null("d_bestlabels")] + BCD_MIS + WS_ROWS),
     "dflow_bcd_phase_batch": ("p npass d_nprop d_bestlabels phase d_ws ws_bytes stream", BATCH_BASE,
                               BATCH_HEAD + [("phase_negative", {"phase": -1}), ("phase_4", {"phase": 4})] + BATCH_TAIL),
     "dflow_bcd_sweep_batch": ("p npass d_nprop d_bestlabels d_ws ws_bytes stream", BATCH_BASE, BATCH_HEAD + BATCH_TAIL),
@@ -123,47 +129,60 @@ TABLES = {
     "dflow_bcd_stats": ("p d_proposals d_lcosts d_nprop d_bestlabels d_prev_labels d_prev_out d_stats d_ws ws_bytes stream",
                         af_base(p=GEOM, d_proposals=A, d_lcosts=B, d_nprop=D, d_bestlabels=E, d_prev_labels=None, d_prev_out=None, d_stats=F),
                         [("p_null", {"p": None}), ("p_tphi_nan", {"p.tphi": NAN})]
-                        + [null(n) for n in "d_proposals d_lcosts d_nprop d_bestlabels d_stats".split()] + STATS_TAIL),
+                        + [null(n) for n in "d_proposals d_lcosts d_nprop d_bestlabels d_stats".split()]
+                        + [mis("d_proposals", 8), mis("d_lcosts", 8), mis("d_nprop", 2), mis("d_bestlabels", 2), ("d_prev_labels_plus2", {"d_prev_labels": G + 2}),
+                           ("d_prev_out_plus1", {"d_prev_out": H + 1})] + STATS_TAIL),
     "dflow_bcd_stats_batch": ("p npass d_proposals d_lcosts d_nprop d_bestlabels d_prev d_stats d_ws ws_bytes stream",
                               af_base(p=GEOM, npass=2, d_proposals=[A, A], d_lcosts=[B, B], d_nprop=[D, D], d_bestlabels=[E, E], d_prev=None,
                                    d_stats=F),
                               [("p_null", {"p": None}), ("p_tphi_nan", {"p.tphi": NAN}), ("npass_0", {"npass": 0}), ("npass_1025", {"npass": 1025})]
                               + [null(n) for n in "d_proposals d_lcosts d_nprop d_bestlabels d_stats".split()]
                               + [("pass_0_proposals_null", {"d_proposals": [None, A]}), ("pass_1_bestlabels_null", {"d_bestlabels": [E, None]})]
+                              # pass by pass, in the order of the arguments; a NULL d_prev[i] passes
+                              + [("pass_0_proposals_plus8", {"d_proposals": [A + 8, A]}), ("pass_0_lcosts_plus4", {"d_lcosts": [B + 4, B]}),
+                                 ("pass_0_nprop_plus2", {"d_nprop": [D + 2, D]}), ("pass_0_bestlabels_plus2", {"d_bestlabels": [E + 2, E]}),
+                                 ("pass_1_prev_plus2", {"d_prev": [None, G + 2]})]
                               + STATS_TAIL),
-    # no workspace: the base call leaves out the last pointer that is checked
-    "dflow_labels_to_flow": ("p d_proposals d_bestlabels d_flow stream", dict(p=GEOM, d_proposals=A, d_bestlabels=B, d_flow=None, stream=None),
-                             P_ROWS + [null("d_proposals"), null("d_bestlabels"), null("d_flow")]),
-    "dflow_fb_consistency": ("p d_fwd d_bwd tresh d_sparse stream", dict(p=GEOM, d_fwd=A, d_bwd=B, tresh=1.0, d_sparse=None, stream=None),
-                             P_ROWS + [null("d_fwd"), null("d_bwd"), null("d_sparse")]),
-    "dflow_pack_compat": ("p d_proposals d_nprop d_packed stream", dict(p=GEOM, d_proposals=A, d_nprop=B, d_packed=None, stream=None),
-                          P_ROWS + [null("d_proposals"), null("d_nprop"), null("d_packed")]),
+    # no workspace: in the base call the last plane that is checked is off its boundary (d_packed moves byte by byte)
+    "dflow_labels_to_flow": ("p d_proposals d_bestlabels d_flow stream", dict(p=GEOM, d_proposals=A, d_bestlabels=B, d_flow=D + 4, stream=None),
+                             P_ROWS + [null("d_proposals"), null("d_bestlabels"), null("d_flow"), mis("d_proposals", 8), mis("d_bestlabels", 2),
+                                       ("d_flow_plus4", {})]),
+    "dflow_fb_consistency": ("p d_fwd d_bwd tresh d_sparse stream", dict(p=GEOM, d_fwd=A, d_bwd=B, tresh=1.0, d_sparse=D + 2, stream=None),
+                             P_ROWS + [null("d_fwd"), null("d_bwd"), null("d_sparse"), mis("d_fwd", 4), mis("d_bwd", 4), ("d_sparse_plus2", {})]),
+    "dflow_pack_compat": ("p d_proposals d_nprop d_packed stream", dict(p=GEOM, d_proposals=A, d_nprop=B + 2, d_packed=D, stream=None),
+                          P_ROWS + [null("d_proposals"), null("d_nprop"), null("d_packed"), mis("d_proposals", 8), ("d_nprop_plus2", {})]),
     # runs on the host, on h_sparse: the base call has no columns
     "dflow_remove_small_segments_host": ("h_sparse dim0 dim1 tresh min_segment_size", dict(h_sparse=A, dim0=4, dim1=0, tresh=1.0, min_segment_size=3),
                                          [null("h_sparse"), ("dim0_0", {"dim0": 0}), ("dim0_negative", {"dim0": -1}, SOLO), ("dim1_0", {"dim1": 0})]),
     "dflow_canny_edges": ("h w d_bgr low high d_edges d_ivice d_ws ws_bytes stream", ws_base(4, h=HH, w=WW, d_bgr=A, low=100.0, high=200.0, d_edges=B, d_ivice=None),
                           SIZE_ROWS + [("low_nan", {"low": NAN}), ("high_negative", {"high": -1.0}, SOLO), ("high_inf", {"high": float("inf")}, SOLO),
-                                       null("d_bgr"), null("d_edges")] + WS_ROWS),
+                                       null("d_bgr"), null("d_edges"), ("d_ivice_plus2", {"d_ivice": D + 2})] + WS_ROWS),
     "dflow_pb_edges": ("h w d_bgr radius d_strength d_orient_strength d_ws ws_bytes stream",
                        ws_base(2, h=HH, w=WW, d_bgr=A, radius=5, d_strength=B, d_orient_strength=None),
-                       SIZE_ROWS + [("radius_0", {"radius": 0}), ("radius_8", {"radius": 8}), null("d_bgr"), null("d_strength")] + WS_ROWS),
+                       SIZE_ROWS + [("radius_0", {"radius": 0}), ("radius_8", {"radius": 8}), null("d_bgr"), null("d_strength"), mis("d_strength", 2),
+                                    ("d_orient_strength_plus2", {"d_orient_strength": D + 2})] + WS_ROWS),
     "dflow_epic_interpolate": ("h w d_sparse d_edges nn k method d_flow d_seed_of d_dist d_lists d_list_g d_ws ws_bytes stream",
                                ws_base(8, h=HH, w=WW, d_sparse=A, d_edges=B, nn=16, k=0.8, method=0, d_flow=D, d_seed_of=None, d_dist=None,
                                     d_lists=None, d_list_g=None),
                                SIZE_ROWS + [("nn_0", {"nn": 0}), ("nn_257", {"nn": 257}), ("k_0", {"k": 0.0}), ("k_inf", {"k": float("inf")}, SOLO),
-                                            ("method_2", {"method": 2}), null("d_sparse"), null("d_edges"), null("d_flow")] + WS_ROWS),
+                                            ("method_2", {"method": 2}), null("d_sparse"), null("d_edges"), null("d_flow"), mis("d_sparse", 2), mis("d_edges", 1), mis("d_flow", 2),
+                                            ("d_seed_of_plus2", {"d_seed_of": E + 2}), ("d_dist_plus2", {"d_dist": F + 2}),
+                                            ("d_lists_plus1", {"d_lists": G + 1}), ("d_list_g_plus4", {"d_list_g": H + 4})] + WS_ROWS),
     "dflow_epic_prefilter": ("h w d_bgr d_sparse_in d_edges saliency_th pref_nn pref_th k d_sparse_out d_reason d_saliency d_estimate d_ws ws_bytes stream",
                              ws_base(8, h=HH, w=WW, d_bgr=A, d_sparse_in=B, d_edges=D, saliency_th=0.045, pref_nn=25, pref_th=5.0, k=0.8, d_sparse_out=E,
                                   d_reason=None, d_saliency=None, d_estimate=None),
                              SIZE_ROWS + [("saliency_th_negative", {"saliency_th": -1.0}), ("pref_nn_negative", {"pref_nn": -1}),
                                           ("pref_nn_256", {"pref_nn": 256}), ("pref_th_nan", {"pref_th": NAN}), ("k_negative", {"k": -0.5}),
-                                          null("d_bgr"), null("d_sparse_in"), null("d_edges"), null("d_sparse_out")] + WS_ROWS),
+                                          null("d_bgr"), null("d_sparse_in"), null("d_edges"), null("d_sparse_out"), mis("d_sparse_in", 2), mis("d_edges", 2),
+                                          mis("d_sparse_out", 1), ("d_saliency_plus2", {"d_saliency": F + 2}),
+                                          ("d_estimate_plus2", {"d_estimate": G + 2})] + WS_ROWS),
     "dflow_var_refine": ("h w d_bgr1 d_bgr2 d_flow_in p d_flow_out d_ws ws_bytes stream", VAR,
                          SIZE_ROWS + [null("p"), null("d_bgr1"), null("d_bgr2"), null("d_flow_in"), null("d_flow_out"),
                                       ("alpha_negative", {"p.alpha": -1.0}), ("gamma_nan", {"p.gamma": NAN}), ("delta_inf", {"p.delta": float("inf")}),
                                       ("sigma_6", {"p.sigma": 6.0}), ("sigma_nan", {"p.sigma": NAN}, SOLO), ("sor_omega_2", {"p.sor_omega": 2.0}),
                                       ("sor_omega_nan", {"p.sor_omega": NAN}, SOLO), ("niter_outer_negative", {"p.niter_outer": -1}),
-                                      ("niter_inner_0", {"p.niter_inner": 0}), ("niter_solver_10001", {"p.niter_solver": 10001}), ("flags_2", {"p.flags": 2})]
+                                      ("niter_inner_0", {"p.niter_inner": 0}), ("niter_solver_10001", {"p.niter_solver": 10001}), ("flags_2", {"p.flags": 2}),
+                                      mis("d_flow_in", 4), mis("d_flow_out", 4)]
                          + WS_ROWS),
     "dflow_flow_eval": ("h w d_test test_layout d_gt abs_thresh flags d_stats d_err d_err_bgr d_ws ws_bytes stream",
                         ws_base(8, h=HH, w=WW, d_test=A, test_layout=0, d_gt=B, abs_thresh=3.0, flags=0, d_stats=D, d_err=E, d_err_bgr=F),

@@ -152,7 +152,7 @@ def test_prefilter_rejects_bad_calls_before_any_launch(L):
     ws = lib.dflow_epic_prefilter_workspace_bytes(20, 30)
     nan, inf = float("nan"), float("inf")
 
-    def call(h=20, w=30, bgr=1, sparse=1, edges=1, sal=0.045, nn=25, th=5.0, k=0.8, out=1, d_ws=1, wsb=None):
+    def call(h=20, w=30, bgr=1, sparse=1 << 20, edges=1 << 20, sal=0.045, nn=25, th=5.0, k=0.8, out=1 << 20, d_ws=1, wsb=None):
         rc = lib.dflow_epic_prefilter(h, w, bgr, sparse, edges, sal, nn, th, k, out, None, None, None, d_ws,
                                       ws if wsb is None else wsb, None)
         return rc, lib.dflow_last_error()

@@ -152,7 +152,7 @@ def test_epic_interpolate_rejects_bad_calls_before_any_launch(L):
     lib = L.lib()
     ws = lib.dflow_epic_workspace_bytes(20, 30)
 
-    def call(h=20, w=30, sparse=1, edges=1, nn=100, k=0.8, method=0, flow=1, d_ws=1, wsb=ws):
+    def call(h=20, w=30, sparse=1 << 20, edges=1 << 20, nn=100, k=0.8, method=0, flow=1 << 20, d_ws=1, wsb=ws):
         return lib.dflow_epic_interpolate(h, w, sparse, edges, nn, k, method, flow, None, None, None, None, d_ws, wsb, None)
     assert call(h=0) == -1 and b"image size" in lib.dflow_last_error()
     assert call(w=8193) == -1 and b"image size" in lib.dflow_last_error()

@@ -105,16 +105,17 @@ def test_run_batch_parses_edge_kind(capsys):
 def test_abi_rejections_happen_before_any_launch(L):
     lib = L.lib()
     EINVAL, ENOSPC = -1, -2
+    P = 1 << 20                                         # a stand-in float plane on its 4-byte boundary
     for h, w in ((0, 8), (8, 0), (-1, 8), (8193, 8), (8, 8193)):
         assert lib.dflow_pb_workspace_bytes(h, w) == 0 and b"image size" in lib.dflow_last_error()
-        assert lib.dflow_pb_edges(h, w, 1, 5, 1, 1, 1, 1 << 40, None) == EINVAL and b"image size" in lib.dflow_last_error()
+        assert lib.dflow_pb_edges(h, w, 1, 5, P, P, 1, 1 << 40, None) == EINVAL and b"image size" in lib.dflow_last_error()
     assert lib.dflow_pb_workspace_bytes(1, 1) > 0 and lib.dflow_pb_workspace_bytes(8192, 8192) >= 2 * 8192 * 8192
     wsb = lib.dflow_pb_workspace_bytes(40, 56)
     assert wsb >= 2 * 40 * 56
     for radius in (0, -1, 8, 100):
-        assert lib.dflow_pb_edges(40, 56, 1, radius, 1, 1, 1, wsb, None) == EINVAL and b"radius" in lib.dflow_last_error()
-    assert lib.dflow_pb_edges(40, 56, None, 5, 1, 1, 1, wsb, None) == EINVAL and b"d_bgr is NULL" in lib.dflow_last_error()
-    assert lib.dflow_pb_edges(40, 56, 1, 5, None, 1, 1, wsb, None) == EINVAL and b"d_strength is NULL" in lib.dflow_last_error()
-    assert lib.dflow_pb_edges(40, 56, 1, 5, 1, None, None, wsb, None) == ENOSPC and b"workspace" in lib.dflow_last_error()
-    assert lib.dflow_pb_edges(40, 56, 1, 5, 1, None, 1, wsb - 1, None) == ENOSPC and b"workspace" in lib.dflow_last_error()
-    assert lib.dflow_pb_edges(40, 56, 1, 5, 1, 1, 1, 0, None) == ENOSPC
+        assert lib.dflow_pb_edges(40, 56, 1, radius, P, P, 1, wsb, None) == EINVAL and b"radius" in lib.dflow_last_error()
+    assert lib.dflow_pb_edges(40, 56, None, 5, P, P, 1, wsb, None) == EINVAL and b"d_bgr is NULL" in lib.dflow_last_error()
+    assert lib.dflow_pb_edges(40, 56, 1, 5, None, P, 1, wsb, None) == EINVAL and b"d_strength is NULL" in lib.dflow_last_error()
+    assert lib.dflow_pb_edges(40, 56, 1, 5, P, None, None, wsb, None) == ENOSPC and b"workspace" in lib.dflow_last_error()
+    assert lib.dflow_pb_edges(40, 56, 1, 5, P, None, 1, wsb - 1, None) == ENOSPC and b"workspace" in lib.dflow_last_error()
+    assert lib.dflow_pb_edges(40, 56, 1, 5, P, P, 1, 0, None) == ENOSPC

@@ -95,7 +95,10 @@ def L():
     return lib
 
 
-def _refine(L, h=64, w=64, ptrs=(1, 1, 1, 1, 1), ws_bytes=1 << 62, **kw):
+FLOW = 1 << 20          # a stand-in flow plane on its 8-byte boundary
+
+
+def _refine(L, h=64, w=64, ptrs=(1, 1, FLOW, FLOW, 1), ws_bytes=1 << 62, **kw):
     p = L.VarParams()
     L.lib().dflow_var_default_params(C.byref(p))
     for k, v in kw.items():
@@ -132,7 +135,7 @@ def test_var_refine_refuses_on_the_host(L):
         rc, err = _refine(L, **kw)
         assert rc == -1 and msg in err, (kw, rc, err)
     for i, name in enumerate((b"d_bgr1", b"d_bgr2", b"d_flow_in", b"d_flow_out")):
-        ptrs = [1] * 5
+        ptrs = [1, 1, FLOW, FLOW, 1]
         ptrs[i] = None
         rc, err = _refine(L, ptrs=tuple(ptrs))
         assert rc == -1 and name in err and b"NULL" in err
@@ -141,10 +144,10 @@ def test_var_refine_refuses_on_the_host(L):
     assert need >= 49 * 64 * 64 * 4 and lib.dflow_var_workspace_bytes(128, 128) == 4 * need           # linear in h*w
     assert lib.dflow_var_workspace_bytes(0, 64) == 0 and lib.dflow_var_workspace_bytes(64, 8193) == 0
     assert lib.dflow_var_workspace_bytes(1, 1) > 0 and lib.dflow_var_workspace_bytes(8192, 8192) > 0
-    for kw in (dict(ws_bytes=need - 1), dict(ptrs=(1, 1, 1, 1, None))):
+    for kw in (dict(ws_bytes=need - 1), dict(ptrs=(1, 1, FLOW, FLOW, None))):
         rc, err = _refine(L, **kw)
         assert rc == -2 and b"workspace" in err          # DFLOW_ENOSPC, as for every stage's workspace
-    assert lib.dflow_var_refine(64, 64, 1, 1, 1, None, 1, 1, need, None) == -1 and b"NULL" in lib.dflow_last_error()
+    assert lib.dflow_var_refine(64, 64, 1, 1, FLOW, None, FLOW, 1, need, None) == -1 and b"NULL" in lib.dflow_last_error()
 
 
 def test_var_refine_accepts_each_bound_itself(L):
