@@ -72,6 +72,10 @@
  *                                   d_exclude, d_class 1
  *       dflow_label_confidence      d_proposals, d_lcosts, d_sparse 16; d_nprop, d_bestlabels, d_margin, d_alt, d_counts 4
  *       dflow_flow_gate             d_flow, d_score, d_out 16; d_counts 4
+ *       dflow_track_advance         d_pos_in, d_pos_out 8 (a position moves as one float2); d_fwd, d_bwd, d_state_in, d_state_out,
+ *                                   d_err, d_counts 4
+ *       dflow_track_seed            d_pos 8; d_state, d_birth, d_n, d_scan, d_counts 4; d_mask 1
+ *       dflow_track_flow            d_pos_a, d_pos_b 8; d_state_a, d_state_b, d_owner, d_out, d_counts 4
  *     A plane below its number returns DFLOW_EINVAL ("NAME is not N-byte aligned", the batch forms name the entry NAME[i]) before
  *     anything is launched, after the NULL checks and before the workspace is looked at (the batch forms of the sweeps check the
  *     one size of their workspaces before any per-pass pointer, as they always have).
@@ -909,6 +913,84 @@ int dflow_label_confidence(const dflow_params *p, const uint32_t *d_proposals, c
  * One launch; asynchronous on `stream`, allocates nothing, reads nothing back, can be captured into a graph. */
 int dflow_flow_gate(int32_t h, int32_t w, const float *d_flow, int32_t layout, const float *d_score, float lo, float hi,
                     float *d_out, int32_t *d_counts, void *stream);
+
+/* Point trajectories through a frame sequence (DESIGN.md "Point trajectories"): tracks chained through the forward flows of
+ * consecutive pairs and ended where the backward flow does not undo the step, the dense point trajectories of Sundaram, Brox and
+ * Keutzer.  This build's definitions; the reference has no counterpart.  1 <= h, w <= 8192.  Flow fields are (h,w,.) float32 in
+ * DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout; a vector is GOOD as in dflow_flow_consistency.  A position (x, y) is INSIDE when
+ * x >= 0 && x <= (float)(w-1) && y >= 0 && y <= (float)(h-1) (a NaN is not).  Arithmetic is float32, one IEEE operation per
+ * written operation; every result is an integer or a fixed float32 chain per track, independent of any order, and two calls give
+ * the same bytes.
+ * A TRACK SET of capacity cap, 1 <= cap <= 2^26: d_pos (cap,2) float32 [x,y], 8-byte aligned; d_state (cap) int32; d_birth (cap)
+ * int32, the frame a track started in; d_n device int32[1], the number of slots handed out so far.  States: DFLOW_TRACK_FREE 0
+ * (what a zeroed array holds), _LIVE 1, _LEFT 2 (it left the frame), _NOFLOW 3 (it met a forward vector that is not good),
+ * _NOBACK 4 (it met a backward vector that is not good), _INCONSISTENT 5 (it failed the forward/backward test).  States >= 2 are
+ * terminal: a slot is never reused and a terminal state never changes, so a track that is LIVE in two snapshots of a set is the
+ * same trajectory throughout.
+ * There is no workspace: scratch is passed as typed planes.  All three are asynchronous on `stream`, allocate nothing, read nothing
+ * back and can be captured into a graph.
+ *
+ * ADVANCE.  A slot whose state is not LIVE is copied through, position bits included.  A LIVE slot at (x, y) takes the first of:
+ *   LEFT          (x, y) is not inside.  Checked before anything is sampled: no value of d_pos_in makes a kernel read outside a plane.
+ *   NOFLOW        the SAMPLE of d_fwd at (x, y) meets a vector that is not good.  SAMPLE of field F at an inside (x, y): y0 =
+ *                 (int)floorf(y), ay = y - (float)y0, y1 = ay > 0 ? y0+1 : y0; x0, ax, x1 likewise (a corner of weight zero is not
+ *                 looked at: it is the corner beside it); with Fij = F[yi][xj]: t = F00 + ax*(F01 - F00), b = F10 + ax*(F11 - F10),
+ *                 value = t + ay*(b - t), for U and for V.
+ *   LEFT          nx = x + U, ny = y + V, and (nx, ny) is not inside.
+ *   with d_bwd:
+ *   NOBACK        the sample (bu, bv) of d_bwd at (nx, ny) meets a vector that is not good.
+ *   INCONSISTENT  du = U + bu, dv = V + bv, e2 = du*du + dv*dv, m2 = (U*U + V*V) + (bu*bu + bv*bv); not e2 <= rel*m2 + abs
+ *                 (Sundaram-Brox: rel 0.01, abs 0.5).
+ *   LIVE          otherwise; the position becomes (nx, ny).  A track that ends keeps its last position.
+ * d_err (NULL to skip) (cap) float32: e2 where it was formed, -1 elsewhere.  d_counts (NULL to skip) int32[6], zeroed by the call on
+ * the stream = {live after, left, noflow, noback, inconsistent, not live before}; they add up to cap.  d_pos_out may be d_pos_in
+ * and d_state_out may be d_state_in (a lane touches only its own slot).  One launch and at most one memset.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout_fwd, with d_bwd
+ * an unknown layout_bwd; cap outside [1,2^26]; rel, then abs, not finite or < 0; any flag bit (there are none yet); a NULL d_fwd,
+ * d_pos_in, d_state_in, d_pos_out or d_state_out; d_pos_in or d_pos_out not 8-byte aligned, another plane not 4-byte aligned; an
+ * output equal to an input (but for the two pairs above) or to an output listed before it. */
+#define DFLOW_TRACK_FREE 0
+#define DFLOW_TRACK_LIVE 1
+#define DFLOW_TRACK_LEFT 2
+#define DFLOW_TRACK_NOFLOW 3
+#define DFLOW_TRACK_NOBACK 4
+#define DFLOW_TRACK_INCONSISTENT 5
+int dflow_track_advance(int32_t h, int32_t w, const float *d_fwd, int32_t layout_fwd,
+                        const float *d_bwd /* NULL: no check */, int32_t layout_bwd, int32_t cap,
+                        const float *d_pos_in, const int32_t *d_state_in, float rel, float abs, uint32_t flags /* none yet */,
+                        float *d_pos_out, int32_t *d_state_out, float *d_err /* NULL or (cap) */,
+                        int32_t *d_counts /* NULL or int32[6] */, void *stream);
+
+/* SEED: new tracks where no live one is.  1 <= step <= 256; the CELLS are the gh x gw grid, gh = ceil(h/step), gw = ceil(w/step).
+ * n = clamp(*d_n, 0, cap), read on the device.  A LIVE track among the slots i < n whose position is inside covers the cell
+ * ((int)rintf(y) / step, (int)rintf(x) / step); one that is not inside covers nothing.  The SEED PIXEL of cell (cy, cx) is sx =
+ * min(cx*step + step/2, w-1), sy = min(cy*step + step/2, h-1).  A cell is SEEDABLE when no track covers it and d_mask is NULL or
+ * d_mask[sy*w + sx] != 0 (d_mask: (h,w) uint8).  The r-th seedable cell in raster order, r from 0, gets slot n + r if that is below
+ * cap: position ((float)sx, (float)sy), LIVE, d_birth = frame; otherwise it is dropped.  Afterwards *d_n = min(cap, n + seedable).
+ * d_counts (NULL to skip) int32[4], zeroed by the call on the stream = {covered cells, seedable cells, seeded, dropped}.
+ * d_scan is int32 scratch of gh*gw + ceil(gh*gw / 1024) + 1 elements: the cells, a sum per 1024 cells, the n the call began with.
+ * Two memsets (one without d_counts) and four launches whatever the set holds: mark (every writer of a cell stores the same
+ * value), count per block, one block that scans the block sums, emit.  No workgroup waits for another.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; cap outside [1,2^26]; step
+ * outside [1,256]; a NULL d_pos, d_state, d_birth, d_n or d_scan; d_pos not 8-byte aligned, another int32 plane not 4-byte
+ * aligned; a plane equal to d_mask or to one listed before it (d_pos, d_state, d_birth, d_n, d_scan, d_counts). */
+int dflow_track_seed(int32_t h, int32_t w, int32_t cap, int32_t step, int32_t frame,
+                     const uint8_t *d_mask /* NULL or (h,w) */, float *d_pos, int32_t *d_state, int32_t *d_birth, int32_t *d_n,
+                     int32_t *d_scan /* int32 scratch, see above */, int32_t *d_counts /* NULL or int32[4] */, void *stream);
+
+/* FLOW: the displacement of every track that is LIVE in snapshot a and in snapshot b of one set, as a sparse field a -> b in the
+ * format dflow_epic_interpolate, dflow_segment_filter and dflow_flow_eval take.  Track i TAKES PART if d_state_a[i] and
+ * d_state_b[i] are both LIVE and its position in a is inside.  It claims pixel ((int)rintf(y_a), (int)rintf(x_a)) by an integer
+ * minimum of i on d_owner (h,w) int32, which the call sets to 0x7fffffff first and leaves holding the winners: the smallest index
+ * wins a shared pixel.  d_out (h,w,3) float32: [x_b - x_a, y_b - y_a, 1] of the winner at a claimed pixel, [0,0,0] elsewhere.
+ * d_counts (NULL to skip) int32[3], zeroed by the call on the stream = {pixels set, tracks that lost their pixel, tracks that took
+ * no part}; they add up to cap.  Two memsets (one without d_counts) and two launches.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; cap outside [1,2^26]; a NULL
+ * d_pos_a, d_state_a, d_pos_b, d_state_b, d_owner or d_out; d_pos_a or d_pos_b not 8-byte aligned, another plane not 4-byte
+ * aligned; d_owner, d_out or d_counts equal to a snapshot plane or to one listed before it (the two snapshots may be one). */
+int dflow_track_flow(int32_t h, int32_t w, int32_t cap, const float *d_pos_a, const int32_t *d_state_a, const float *d_pos_b,
+                     const int32_t *d_state_b, int32_t *d_owner /* (h,w) int32 */, float *d_out /* (h,w,3) */,
+                     int32_t *d_counts /* NULL or int32[3] */, void *stream);
 
 #ifdef __cplusplus
 }

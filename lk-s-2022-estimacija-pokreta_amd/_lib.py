@@ -23,6 +23,9 @@ WMED_KEEP_HOLES, WMED_REJECT = 1, 2     # DFLOW_WMED_KEEP_HOLES, DFLOW_WMED_REJE
 MOTION_AFFINE, MOTION_HOMOGRAPHY = 0, 1     # DFLOW_MOTION_AFFINE, DFLOW_MOTION_HOMOGRAPHY
 CONF_LOCAL, CONF_DATA = 0, 1                # DFLOW_CONF_LOCAL, DFLOW_CONF_DATA
 CONF_COUNTS = 6                             # DFLOW_CONF_COUNTS
+# DFLOW_TRACK_FREE .. DFLOW_TRACK_INCONSISTENT: the states of a track
+TRACK_FREE, TRACK_LIVE, TRACK_LEFT, TRACK_NOFLOW, TRACK_NOBACK, TRACK_INCONSISTENT = range(6)
+TRACK_CAP_MAX = 1 << 26                     # a track set's largest capacity
 
 
 class DflowError(RuntimeError):
@@ -137,7 +140,14 @@ _SIGNATURES_SHARED_GATE = {
     "dflow_label_confidence": (C.c_int, [_pp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "dflow_flow_gate": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, _f32, _vp, _vp, _vp]),
 }
-SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE)
+# The track calls (csrc/tracks.hip): shared checks alone as well, their refusals pinned by tests/test_abi_tracks.py.  A table of
+# their own: the key sets of the two above are compared against fixed tables by the tests that cover them.
+_SIGNATURES_TRACKS = {
+    "dflow_track_advance": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _f32, _f32, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_track_seed": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_track_flow": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS)
 
 
 def build(force=False):
@@ -163,9 +173,10 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_SIGNATURES_SHARED_GATE.items()):
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
+        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS):
+            for name, (restype, argtypes) in table.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 

@@ -14,6 +14,16 @@
 #include <initializer_list>
 #include "dflow_common.h"
 
+// tracks.hip: a track set carried one frame on, new tracks in the uncovered cells, the sparse flow between two snapshots (arguments
+// validated by the caller); bwd, err, mask and counts may be NULL.  Declared here: dflow_common.h is part of every device build.
+int launch_track_advance(int H, int W, const float *fwd, int layout_fwd, const float *bwd, int layout_bwd, int cap, const float *pos_in,
+                         const int32_t *state_in, float rel, float abs_tol, float *pos_out, int32_t *state_out, float *err,
+                         int32_t *counts, hipStream_t s);
+int launch_track_seed(int H, int W, int cap, int step, int frame, const uint8_t *mask, float *pos, int32_t *state, int32_t *birth,
+                      int32_t *d_n, int32_t *scan, int32_t *counts, hipStream_t s);
+int launch_track_flow(int H, int W, int cap, const float *pos_a, const int32_t *state_a, const float *pos_b, const int32_t *state_b,
+                      int32_t *owner, float *out, int32_t *counts, hipStream_t s);
+
 static thread_local char g_err[512] = "";
 
 int dflow_set_error(int code, const char *fmt, ...)
@@ -896,6 +906,67 @@ int dflow_flow_gate(int32_t h, int32_t w, const float *d_flow, int32_t layout, c
                         {{"d_out", layout == DFLOW_EVAL_UVV && d_out == d_flow ? nullptr : d_out}, {"d_counts", d_counts}});
     if (rc) return rc;
     return launch_flow_gate(h, w, d_flow, layout, d_score, lo, hi, d_out, d_counts, (hipStream_t)stream);
+}
+
+// a track set's capacity, and the planes every track call names; positions move as one float2 per track
+#define TRACK_CAP_MAX (1 << 26)
+
+int dflow_track_advance(int32_t h, int32_t w, const float *d_fwd, int32_t layout_fwd, const float *d_bwd, int32_t layout_bwd, int32_t cap,
+                        const float *d_pos_in, const int32_t *d_state_in, float rel, float abs, uint32_t flags, float *d_pos_out,
+                        int32_t *d_state_out, float *d_err, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout_fwd", layout_fwd))) return rc;
+    if (d_bwd && (rc = check_layout(__func__, "layout_bwd", layout_bwd))) return rc;
+    if ((rc = check_int_range(__func__, "cap", cap, 1, TRACK_CAP_MAX))) return rc;
+    if ((rc = check_finite_ge0(__func__, "rel", rel))) return rc;
+    if ((rc = check_finite_ge0(__func__, "abs", abs))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_fwd); CHECK_PTR(d_pos_in); CHECK_PTR(d_state_in); CHECK_PTR(d_pos_out); CHECK_PTR(d_state_out);
+    rc = check_aligned(__func__, {{"d_pos_in", d_pos_in, ALIGN_FLOW2}, {"d_pos_out", d_pos_out, ALIGN_FLOW2}, {"d_fwd", d_fwd, 4},
+                                  {"d_bwd", d_bwd, 4}, {"d_state_in", d_state_in, 4}, {"d_state_out", d_state_out, 4}, {"d_err", d_err, 4},
+                                  {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a lane reads its own slot before it writes it: d_pos_out may be d_pos_in and d_state_out may be d_state_in, nothing else
+    rc = check_distinct(__func__, {{"d_fwd", d_fwd}, {"d_bwd", d_bwd}, {"d_pos_in", d_pos_in}, {"d_state_in", d_state_in}},
+                        {{"d_pos_out", d_pos_out == d_pos_in ? nullptr : d_pos_out},
+                         {"d_state_out", d_state_out == d_state_in ? nullptr : d_state_out}, {"d_err", d_err}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_track_advance(h, w, d_fwd, layout_fwd, d_bwd, layout_bwd, cap, d_pos_in, d_state_in, rel, abs, d_pos_out, d_state_out,
+                                d_err, d_counts, (hipStream_t)stream);
+}
+
+int dflow_track_seed(int32_t h, int32_t w, int32_t cap, int32_t step, int32_t frame, const uint8_t *d_mask, float *d_pos, int32_t *d_state,
+                     int32_t *d_birth, int32_t *d_n, int32_t *d_scan, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "cap", cap, 1, TRACK_CAP_MAX))) return rc;
+    if ((rc = check_int_range(__func__, "step", step, 1, 256))) return rc;
+    CHECK_PTR(d_pos); CHECK_PTR(d_state); CHECK_PTR(d_birth); CHECK_PTR(d_n); CHECK_PTR(d_scan);
+    rc = check_aligned(__func__, {{"d_pos", d_pos, ALIGN_FLOW2}, {"d_state", d_state, 4}, {"d_birth", d_birth, 4}, {"d_n", d_n, 4},
+                                  {"d_scan", d_scan, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the set is read by the launches that come before the ones that write it
+    rc = check_distinct(__func__, {{"d_mask", d_mask}},
+                        {{"d_pos", d_pos}, {"d_state", d_state}, {"d_birth", d_birth}, {"d_n", d_n}, {"d_scan", d_scan}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_track_seed(h, w, cap, step, frame, d_mask, d_pos, d_state, d_birth, d_n, d_scan, d_counts, (hipStream_t)stream);
+}
+
+int dflow_track_flow(int32_t h, int32_t w, int32_t cap, const float *d_pos_a, const int32_t *d_state_a, const float *d_pos_b,
+                     const int32_t *d_state_b, int32_t *d_owner, float *d_out, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "cap", cap, 1, TRACK_CAP_MAX))) return rc;
+    CHECK_PTR(d_pos_a); CHECK_PTR(d_state_a); CHECK_PTR(d_pos_b); CHECK_PTR(d_state_b); CHECK_PTR(d_owner); CHECK_PTR(d_out);
+    rc = check_aligned(__func__, {{"d_pos_a", d_pos_a, ALIGN_FLOW2}, {"d_pos_b", d_pos_b, ALIGN_FLOW2}, {"d_state_a", d_state_a, 4},
+                                  {"d_state_b", d_state_b, 4}, {"d_owner", d_owner, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the two snapshots may be one; the winners and the field are written while the snapshots are read
+    rc = check_distinct(__func__, {{"d_pos_a", d_pos_a}, {"d_state_a", d_state_a}, {"d_pos_b", d_pos_b}, {"d_state_b", d_state_b}},
+                        {{"d_owner", d_owner}, {"d_out", d_out}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_track_flow(h, w, cap, d_pos_a, d_state_a, d_pos_b, d_state_b, d_owner, d_out, d_counts, (hipStream_t)stream);
 }
 
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)

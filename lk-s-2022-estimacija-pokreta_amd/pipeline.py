@@ -1141,6 +1141,212 @@ def motion_layers(flow, k, exclude=None, **fit_args):
     return models, layers
 
 
+# ---------------------------------------------------------------------- point trajectories (csrc/tracks.hip)
+TRACK_STATES = ("free", "live", "left", "noflow", "noback", "inconsistent")
+TRACK_ADVANCE_COUNTS = ("live", "left", "noflow", "noback", "inconsistent", "not_live")
+TRACK_SEED_COUNTS = ("covered", "seedable", "seeded", "dropped")
+TRACK_FLOW_COUNTS = ("set", "lost", "no_part")
+
+
+def track_scan_len(h, w, step):
+    """The int32 elements of dflow_track_seed's d_scan for an (h, w) frame: the cells, a sum per 1024 cells, one more."""
+    ncells = -(-int(h) // int(step)) * -(-int(w) // int(step))
+    return ncells + -(-ncells // 1024) + 1
+
+
+def _track_frame(fn, h, w):
+    for name, v in (("h", h), ("w", w)):
+        if not (isinstance(v, (int, np.integer)) and 1 <= v <= 8192):
+            raise ValueError("%s: %s must be an int in [1, 8192], got %r" % (fn, name, v))
+    return int(h), int(w)
+
+
+def _track_set(fn, pos, state, names=("pos", "state"), cap=None):
+    """A set's positions and states through the input gate: (cap,2) float32 and (cap) int32, 1 <= cap <= 2^26."""
+    pos = _check(pos, fn, names[0], torch.float32, (cap, 2))
+    cap = pos.shape[0]
+    if not 1 <= cap <= _lib.TRACK_CAP_MAX:
+        raise ValueError("%s: a track set holds 1 to 2^26 slots, got %d" % (fn, cap))
+    return pos, _check(state, fn, names[1], torch.int32, (cap,))
+
+
+def _track_tol(fn, name, v):
+    if not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(np.float32(v)) and np.float32(v) >= 0):
+        raise ValueError("%s: %s must be finite and >= 0 as a float32, got %r" % (fn, name, v))
+    return float(np.float32(v))
+
+
+def _track_planes(dev, *tensors):
+    """The tensors on `dev`, contiguous, on an 8-byte boundary (a row of a stack of snapshots is, its positions being float2);
+    a caller's device tensor that is all that stays the caller's, so that dflow_track_seed writes into it."""
+    out = [t.to(dev).contiguous() for t in tensors]
+    return [t.clone() if t.data_ptr() % 8 else t for t in out]
+
+
+def track_advance(h, w, pos, state, fwd, bwd=None, rel=0.01, abs=0.5, inplace=False, err=False, counts=False):
+    """A track set carried one frame forward (dflow_track_advance, DESIGN.md "Point trajectories"): every LIVE track moves by
+    the bilinear sample of the forward flow at its position, and ends, keeping its position, when it leaves the (h, w) frame
+    (LEFT), meets a forward vector that is not good (NOFLOW), or, with bwd, meets a backward vector that is not good (NOBACK) or
+    fails e2 <= rel * m2 + abs, e2 = |f + b|^2, m2 = |f|^2 + |b|^2 (INCONSISTENT).  pos is (cap,2) float32 [x,y], state (cap)
+    int32 (TRACK_STATES); fwd and bwd are (h,w,2) float32 [dy,dx] or (h,w,3) float32 [U,V,valid], each on its own.  Device
+    tensors or host arrays; host data is uploaded to the current device.  Returns (pos, state[, err][, counts]): new device
+    tensors, or with inplace=True the set's own where those are device tensors; err=True adds the (cap) float32 plane of e2 (-1
+    where it was not formed), counts=True the int32[6] device tensor TRACK_ADVANCE_COUNTS.  Runs on torch's current stream and
+    does not wait for it."""
+    fn = "track_advance"
+    h, w = _track_frame(fn, h, w)
+    pos, state = _track_set(fn, pos, state)
+    fwd = _check(fwd, fn, "fwd", torch.float32, (h, w, (2, 3)))
+    if bwd is not None:
+        bwd = _check(bwd, fn, "bwd", torch.float32, (h, w, (2, 3)))
+    rel, abs = _track_tol(fn, "rel", rel), _track_tol(fn, "abs", abs)
+    dev = _device_of(pos, state, fwd, *([bwd] if bwd is not None else []))
+    ts = _on(dev, fwd, *([bwd] if bwd is not None else []))
+    fwd, bwd = ts[0], ts[1] if bwd is not None else None
+    pos, state = _track_planes(dev, pos, state)
+    cap = pos.shape[0]
+    pos_out, state_out = (pos, state) if inplace else (torch.empty_like(pos), torch.empty_like(state))
+    extra = [_out(err, cap, torch.float32, dev), _out(counts, 6, torch.int32, dev)]
+    _lib.call("dflow_track_advance", h, w, fwd.data_ptr(), _layout(fwd), _ptr(bwd), _layout(bwd) if bwd is not None else 0, cap,
+              pos.data_ptr(), state.data_ptr(), rel, abs, 0, pos_out.data_ptr(), state_out.data_ptr(), _ptr(extra[0]), _ptr(extra[1]),
+              _lib.stream(dev))
+    return tuple(t for t in [pos_out, state_out] + extra if t is not None)
+
+
+def track_seed(h, w, pos, state, birth, n, step=4, frame=0, mask=None, counts=False, scan=None):
+    """New tracks where no live one is (dflow_track_seed): the frame is cut into step x step cells; every cell that holds no
+    LIVE track among the first n slots, and whose centre pixel is non-zero in mask ((h,w) uint8, or None), starts a track at its
+    centre pixel in the next free slot, in raster order, with birth = frame; cells beyond the set's capacity are dropped.  pos
+    (cap,2) float32, state (cap) int32, birth (cap) int32; n the int32[1] tensor of the slots handed out so far, or an int.
+    Device tensors or host arrays; the set is written in place where it is given as contiguous device tensors, and is returned
+    either way: (pos, state, birth, n[, counts]), n an int32[1] device tensor, counts=True adding the int32[4] device tensor
+    TRACK_SEED_COUNTS.  scan: an int32 device tensor of track_scan_len(h, w, step) elements to reuse, or None.  Runs on
+    torch's current stream and does not wait for it."""
+    fn = "track_seed"
+    h, w = _track_frame(fn, h, w)
+    pos, state = _track_set(fn, pos, state)
+    cap = pos.shape[0]
+    birth = _check(birth, fn, "birth", torch.int32, (cap,))
+    if not (isinstance(step, (int, np.integer)) and 1 <= step <= 256):
+        raise ValueError("%s: step must be an int in [1, 256], got %r" % (fn, step))
+    if not (isinstance(frame, (int, np.integer)) and -2 ** 31 <= frame < 2 ** 31):
+        raise ValueError("%s: frame must be an int32, got %r" % (fn, frame))
+    if isinstance(n, (int, np.integer)):
+        n = torch.tensor([min(max(int(n), -2 ** 31), 2 ** 31 - 1)], dtype=torch.int32)
+    n = _check(n, fn, "n", torch.int32, (1,))
+    if mask is not None:
+        mask = _check(mask, fn, "mask", torch.uint8, (h, w))
+    need = track_scan_len(h, w, step)
+    if scan is not None and not (isinstance(scan, torch.Tensor) and scan.dtype == torch.int32 and scan.dim() == 1 and scan.numel() >= need
+                                 and scan.is_contiguous() and scan.is_cuda):
+        raise ValueError("%s: scan must be a contiguous int32 device tensor of at least %d elements" % (fn, need))
+    dev = _device_of(pos, state, birth, n, *([scan] if scan is not None else []))
+    pos, state, birth, n = _track_planes(dev, pos, state, birth, n)
+    if mask is not None:
+        mask, = _on(dev, mask)
+    if scan is None:
+        scan = torch.empty(need, dtype=torch.int32, device=dev)
+    cnt = _out(counts, 4, torch.int32, dev)
+    _lib.call("dflow_track_seed", h, w, cap, int(step), int(frame), _ptr(mask), pos.data_ptr(), state.data_ptr(), birth.data_ptr(),
+              n.data_ptr(), scan.data_ptr(), _ptr(cnt), _lib.stream(dev))
+    return (pos, state, birth, n) + ((cnt,) if counts else ())
+
+
+def track_flow(h, w, pos_a, state_a, pos_b, state_b, owner=False, counts=False):
+    """The sparse flow a -> b of the tracks that are LIVE in two snapshots of one set (dflow_track_flow): every such track whose
+    position in a lies inside the frame claims the pixel nearest to it, the smallest index winning a shared pixel, and the pixel
+    receives [x_b - x_a, y_b - y_a, 1]; every other pixel is [0,0,0].  The (h,w,3) float32 [U,V,valid] field is what
+    epic_interpolate, segment_filter and flow_eval take.  Snapshots: (cap,2) float32 and (cap) int32, device tensors or host
+    arrays.  Returns the device tensor, or a tuple in the order (flow[, owner][, counts]): owner=True adds the (h,w) int32 plane
+    of winners (0x7fffffff: none), counts=True the int32[3] device tensor TRACK_FLOW_COUNTS.  Runs on torch's current stream
+    and does not wait for it."""
+    fn = "track_flow"
+    h, w = _track_frame(fn, h, w)
+    pos_a, state_a = _track_set(fn, pos_a, state_a, ("pos_a", "state_a"))
+    pos_b, state_b = _track_set(fn, pos_b, state_b, ("pos_b", "state_b"), cap=pos_a.shape[0])
+    dev = _device_of(pos_a, state_a, pos_b, state_b)
+    pos_a, state_a, pos_b, state_b = _track_planes(dev, pos_a, state_a, pos_b, state_b)
+    own = torch.empty((h, w), dtype=torch.int32, device=dev)
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    cnt = _out(counts, 3, torch.int32, dev)
+    _lib.call("dflow_track_flow", h, w, pos_a.shape[0], pos_a.data_ptr(), state_a.data_ptr(), pos_b.data_ptr(), state_b.data_ptr(),
+              own.data_ptr(), out.data_ptr(), _ptr(cnt), _lib.stream(dev))
+    ret = tuple(t for t in (out, own if owner else None, cnt) if t is not None)
+    return ret if len(ret) > 1 else out
+
+
+class TrackSet:
+    """Point trajectories through a frame sequence, on the device: seed() starts tracks at the current frame, advance(fwd, bwd)
+    carries the set to the next frame and keeps a snapshot per frame, flow(a, b) is the sparse flow between two frames' snapshots,
+    read() the one read-back.  Slots are never reused, so index i is one trajectory in every snapshot.  cap defaults to four
+    times the number of step x step cells."""
+
+    def __init__(self, h, w, cap=None, step=4, rel=0.01, abs=0.5, device=None):
+        fn = "TrackSet"
+        self.h, self.w = _track_frame(fn, h, w)
+        if not (isinstance(step, (int, np.integer)) and 1 <= step <= 256):
+            raise ValueError("%s: step must be an int in [1, 256], got %r" % (fn, step))
+        self.step = int(step)
+        if cap is None:
+            cap = min(4 * -(-self.h // self.step) * -(-self.w // self.step), _lib.TRACK_CAP_MAX)
+        if not (isinstance(cap, (int, np.integer)) and 1 <= cap <= _lib.TRACK_CAP_MAX):
+            raise ValueError("%s: cap must be an int in [1, 2^26], got %r" % (fn, cap))
+        self.cap = int(cap)
+        self.rel, self.abs = _track_tol(fn, "rel", rel), _track_tol(fn, "abs", abs)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.pos = torch.zeros((self.cap, 2), dtype=torch.float32, device=dev)
+        self.state = torch.zeros(self.cap, dtype=torch.int32, device=dev)
+        self.birth = torch.zeros(self.cap, dtype=torch.int32, device=dev)
+        self.n = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.scan = torch.empty(track_scan_len(self.h, self.w, self.step), dtype=torch.int32, device=dev)
+        self.frame = 0
+        self.snapshots = [(self.pos, self.state)]     # per frame; the last one is the current set, which seed() writes
+        self._counts = {"seed": None, "advance": None}
+
+    def seed(self, mask=None):
+        """Starts a track in every cell no live track covers (track_seed) at the current frame."""
+        out = track_seed(self.h, self.w, self.pos, self.state, self.birth, self.n, step=self.step, frame=self.frame, mask=mask,
+                         counts=True, scan=self.scan)
+        assert out[0].data_ptr() == self.pos.data_ptr() and out[3].data_ptr() == self.n.data_ptr()
+        self._counts["seed"] = out[4]
+        return self
+
+    def advance(self, fwd, bwd=None):
+        """Carries the set along fwd (the flow from the current frame to the next; bwd the flow back, or None for no check) and
+        makes the result the current frame."""
+        pos, state, cnt = track_advance(self.h, self.w, self.pos, self.state, fwd, bwd, rel=self.rel, abs=self.abs, counts=True)
+        self.pos, self.state = pos, state
+        self.snapshots.append((pos, state))
+        self.frame += 1
+        self._counts["advance"] = cnt
+        return self
+
+    def flow(self, a, b, owner=False, counts=False):
+        """The sparse flow from frame a to frame b (track_flow) of the tracks alive in both."""
+        for name, v in (("a", a), ("b", b)):
+            if not (isinstance(v, (int, np.integer)) and 0 <= v <= self.frame):
+                raise ValueError("TrackSet.flow: %s must be a frame in [0, %d], got %r" % (name, self.frame, v))
+        (pa, sa), (pb, sb) = self.snapshots[a], self.snapshots[b]
+        return track_flow(self.h, self.w, pa, sa, pb, sb, owner=owner, counts=counts)
+
+    def counts(self):
+        """The int32 device tensors of the last seed() (TRACK_SEED_COUNTS) and the last advance() (TRACK_ADVANCE_COUNTS), None
+        where there was none: {"seed": ..., "advance": ...}.  Nothing is read back."""
+        return dict(self._counts)
+
+    def read(self):
+        """The one read-back: dict(pos (T,n,2) float32, NaN before a track's birth and its last position repeated after its
+        end; state (T,n) int32; birth (n) int32; length (n) int32, the frames a track is live in), T = frames so far, n = slots
+        handed out."""
+        n = min(max(int(self.n.cpu()[0]), 0), self.cap)
+        pos = torch.stack([p[:n] for p, _ in self.snapshots]).cpu().numpy()
+        state = torch.stack([s[:n] for _, s in self.snapshots]).cpu().numpy()
+        birth = self.birth[:n].cpu().numpy()
+        pos[np.arange(len(self.snapshots))[:, None] < birth[None, :]] = np.nan
+        return dict(pos=pos, state=state, birth=birth, length=(state == _lib.TRACK_LIVE).sum(0).astype(np.int32))
+
+
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
     """The geometry of a coarse-to-fine run, level 0 the finest: a list of dicts of DiscreteFlow's arguments (pich, picw, cellh,
     cellw and the overrides).  THE RULE: level l+1 has the size ((H+1)//2, (W+1)//2) of level l and the SAME cell size in pixels
