@@ -70,6 +70,7 @@
  *       dflow_flow_wmedian          d_flow, d_out, d_counts 4; d_bgr, d_wspace, d_wcolor 1
  *       dflow_motion_fit            d_state 8; d_flow, d_model, d_models, d_hyp_counts, d_model_flow, d_residual, d_counts 4;
  *                                   d_exclude, d_class 1
+ *       dflow_epipolar_fit          d_state 8; d_flow, d_model, d_models, d_hyp_counts, d_residual, d_counts 4; d_exclude, d_class 1
  *       dflow_label_confidence      d_proposals, d_lcosts, d_sparse 16; d_nprop, d_bestlabels, d_margin, d_alt, d_counts 4
  *       dflow_flow_gate             d_flow, d_score, d_out 16; d_counts 4
  *       dflow_track_advance         d_pos_in, d_pos_out 8 (a position moves as one float2); d_fwd, d_bwd, d_state_in, d_state_out,
@@ -862,6 +863,82 @@ int dflow_motion_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout,
         int64_t *d_state     /* scratch+output int64[32], 8-byte aligned */,
         uint8_t *d_class     /* NULL or (h,w) */, float *d_model_flow /* NULL or (h,w,3) */,
         float *d_residual    /* NULL or (h,w,3) */, int32_t *d_counts /* NULL or int32[8] */, void *stream);
+
+/* Epipolar-geometry fit of a flow field (DESIGN.md "Epipolar-geometry fit"): the fundamental matrix that most vectors of a flow
+ * field agree with, x'^T F x = 0 for a pixel x and its target x', found by random 7-point samples (RANSAC with local rounds), with
+ * the inlier / outlier classes and the per-pixel Sampson distance.  It is the model of a camera moving through a rigid scene with
+ * depth, where dflow_motion_fit's homography fits one plane only.  This build's definition; the reference has no counterpart.
+ * 1 <= h, w <= 8192, n = h*w.  d_flow, GOOD, d_exclude, TAKES PART, SCORED, xf, yf, tx, ty, thresh (pixels), step and seed are
+ * dflow_motion_fit's, unchanged.  Float32 and float64 chains are one IEEE operation per written operation; everything else is an
+ * integer.  The result depends on no order of arrival, and two calls give the same bytes.
+ *   COORDINATES.  P = the smallest power of two >= max(h,w), s = 1/P, cx = (w-1)/2, cy = (h-1)/2 (all exact in float32).  In
+ *     float32: a = (xf - cx)*s, b = (yf - cy)*s (exact), p = (tx - cx)*s, q = (ty - cy)*s.  A model is F^ in these coordinates,
+ *     float32[9], row-major, with (p,q,1) F^ (a,b,1)^T = 0: scoring in pixel coordinates would cancel in float32.  The fundamental
+ *     matrix in pixels is T^T F^ T, T = [[s,0,-cx*s],[0,s,-cy*s],[0,0,1]] (the host's business: pipeline.epipolar_geometry).
+ *   INLIER of model F (float32): l0 = (F0*a + F1*b) + F2, l1 = (F3*a + F4*b) + F5, l2 = (F6*a + F7*b) + F8, e = (p*l0 + q*l1) + l2,
+ *     m0 = (F0*p + F3*q) + F6, m1 = (F1*p + F4*q) + F7, den = ((l0*l0 + l1*l1) + m0*m0) + m1*m1, t = thresh*s; inlier iff
+ *     0 < den < +Inf && e*e <= (t*t)*den: the Sampson distance is at most thresh pixels, with no division.  A NaN anywhere makes
+ *     it false, and so does a den that overflowed (a vector of 1e30 pixels agrees with nothing).
+ *   A. SAMPLES.  There is no current model at the start (d_model all zeros: nothing is its inlier).  Rounds r = 0 .. lo_rounds,
+ *     samples j = 0 .. n_hyp-1, each of 7 points.  Point k = 0 .. 6 tries attempts t = 0 .. 15: Philox4x32-10 with counter
+ *     (j, (r*8 + k)*16 + t, 0, 0) and key (seed & 0xFFFFFFFF, seed >> 32), word 0 = u, i = ((uint64)u * n) >> 32.  The first i is
+ *     accepted that takes part, differs from the points accepted before it and, in rounds r > 0, is an inlier of the current model
+ *     (the best of the rounds before).  A point without one in 16 attempts makes the three slots of the sample DEGENERATE.
+ *     In float64, with a_k = ((double)xf - cx)*s, b_k, p_k = ((double)tx - cx)*s, q_k likewise: row k of the 7 x 9 system A is
+ *     [p*a, p*b, p, q*a, q*b, q, a, b, 1].
+ *     ELIMINATION with complete pivoting: for c = 0..6 the pivot is the largest |A[r][k]| over r >= c, k >= c, the first in
+ *     row-major order winning; a pivot that is not >= 2^-40 makes the sample degenerate; rows c and r are swapped, then columns c
+ *     and k (in all seven rows; the permutation is remembered); for every row r > c: f = A[r][c] / A[c][c], A[r][k] = A[r][k] -
+ *     f*A[c][k] for k > c.  The columns left at positions 7 and 8 are the free variables.  Solution 1 has (x7,x8) = (1,0) and t =
+ *     -A[r][7], solution 2 has (0,1) and t = -A[r][8]; back substitution from row 6: for k = r+1 .. 6 ascending t = t - A[r][k]*x[k];
+ *     x[r] = t / A[r][r].  With the column permutation undone they are F1 and F2.  (A fixed choice of free columns would be
+ *     systematically degenerate for a pure forward or a pure sideways translation, whose F has exact zeros.)
+ *     CUBIC.  det M = (M0*(M4*M8 - M5*M7) - M1*(M3*M8 - M5*M6)) + M2*(M3*M7 - M4*M6), one expression.  k3 = det F1, k0 = det F2,
+ *     dp = det(F1 + F2), dm = det(F2 - F1) (entrywise sums), k2 = (dp + dm)*0.5 - k0, k1 = (dp - dm)*0.5 - k3: det(x F1 + F2) =
+ *     ((k3*x + k2)*x + k1)*x + k0.  A coefficient that is not finite: no model.
+ *     ROOTS over the whole projective line, each once: the roots x of (k3,k2,k1,k0) in [-1,1] give F = x*F1 + F2; then the roots
+ *     x of the reversed cubic (k0,k1,k2,k3) in the open (-1,1) give F = F1 + x*F2 (entrywise, two operations).  Roots of
+ *     (c3,c2,c1,c0) with g(x) = ((c3*x + c2)*x + c1)*x + c0: qa = 3*c3, qb = 2*c2, disc = qb*qb - (4*qa)*c1; if disc > 0: sq =
+ *     sqrt(disc), qq = -0.5*(qb + (qb < 0 ? -sq : sq)), x1 = qq/qa, x2 = c1/qq, and those of min, max (x1 < x2 ? ...) that lie
+ *     strictly inside (-1,1) split [-1,1], in that order, into monotone pieces.  g(-1) == 0 is a root of the closed interval.  For
+ *     each piece [u,v] in ascending order: g(v) == 0 makes v a root (not v = 1 of the open interval); otherwise, if g(u) and g(v)
+ *     are non-zero with opposite signs, 60 times: mid = 0.5*(lo + hi); (g(mid) < 0) == (g(u) < 0) ? lo = mid : hi = mid; the root
+ *     is 0.5*(lo + hi).  No cbrt, acos or pow.  The first three roots, in this order, are the models of the slots 3j, 3j+1, 3j+2.
+ *     CANONICAL SCALE.  Each entry is divided by the entry of largest magnitude (the first such entry; it becomes +1), then cast
+ *     to float32.  A slot without a root, or with an entry that is not finite, is DEGENERATE: it stores zeros and its count is 0.
+ *   B. SCORE.  d_hyp_counts[slot] = the number of scored pixels that are inliers of the slot's model (int32, integer adds).
+ *   C. BEST.  Every slot that is not degenerate offers the key (uint64)count << 32 | (0xFFFFFFFF - (r*65536 + slot)) to a 64-bit
+ *     maximum in d_state[0], which starts at 0 and is kept across the rounds: the larger count wins, at equal counts the earlier
+ *     round, then the smaller slot.  After a round whose slot holds the maximum, that model is the current model.  There is no
+ *     polish: a least-squares F needs an eigen-solve, and its float sums would depend on the order of arrival.
+ *     NO MODEL.  d_state[0] == 0 (every slot of every round degenerate): d_model is all zeros, the best round and slot are -1, and
+ *     every good pixel is class 2.  This is the answer for a still camera (zero flow: the system has rank 6), for a line of
+ *     pixels, and for fewer than 7 pixels that take part.
+ *   D. APPLY, every pixel whatever `step` is, each output optional (NULL to skip).  d_class (h,w) uint8: 0 not good, 1 inlier of
+ *     the final model, 2 outlier, 3 good but excluded.  d_residual (h,w) float32: the Sampson distance in pixels, sqrtf((e*e)/den)*P,
+ *     at a good pixel with 0 < den < +Inf; +Inf at any other good pixel; -1 at a pixel that is not good.  d_counts int32[8], zeroed
+ *     by the call on the stream: {scored pixels, scored inliers of the final model, degenerate slots of all rounds, best round
+ *     (-1: none), best slot (-1: none), the best slot's count, (1000 * models of round 0) / n_hyp, 0}.
+ * d_model receives the final F^; d_models (3*n_hyp*9) and d_hyp_counts (3*n_hyp) hold the slots of the last round and their counts.
+ * There is no d_ws: the scratch is the caller's typed planes d_models, d_hyp_counts and d_state (int64[32]: [0] the best key, the
+ * rest counters), which are outputs as well.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout; thresh not
+ * finite or not > 0; n_hyp outside [1,21845] (3*n_hyp slots fit the key's 16-bit index); lo_rounds outside [0,4]; step outside
+ * [1,64]; any flag bit (there are none yet); a NULL d_flow, d_model, d_models, d_hyp_counts or d_state; d_state not 8-byte
+ * aligned, a float or int32 plane not 4-byte aligned; an output or scratch plane equal to an input or to one listed before it.
+ * 3 + 4 (lo_rounds + 1) launches and one or two memsets, whatever the field holds.  Asynchronous on `stream`, allocates nothing,
+ * reads nothing back, can be captured into a graph. */
+#define DFLOW_EPIPOLAR_MAX_HYP 21845
+int dflow_epipolar_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        const uint8_t *d_exclude /* NULL or (h,w): non-zero = take no part */,
+        float thresh, int32_t n_hyp /* 1..21845 */, int32_t lo_rounds /* 0..4 */, int32_t step /* 1..64 */,
+        uint64_t seed, uint32_t flags /* none yet */,
+        float *d_model       /* float32[9]: F^, all zeros when there is no model */,
+        float *d_models      /* scratch+output float32[3*n_hyp*9]: the last round's slots */,
+        int32_t *d_hyp_counts /* scratch+output int32[3*n_hyp]: their inlier counts, 0 for a degenerate one */,
+        int64_t *d_state     /* scratch+output int64[32], 8-byte aligned */,
+        uint8_t *d_class     /* NULL or (h,w) */, float *d_residual /* NULL or (h,w) */,
+        int32_t *d_counts    /* NULL or int32[8] */, void *stream);
 
 /* Per-pixel confidence of a labelling (DESIGN.md "Label confidence"): how far the chosen label's local energy lies below the best
  * competing motion, the naive peak margin / local min-energy gap of a discrete labelling.  This build's definition; the reference

@@ -26,6 +26,7 @@ CONF_COUNTS = 6                             # DFLOW_CONF_COUNTS
 # DFLOW_TRACK_FREE .. DFLOW_TRACK_INCONSISTENT: the states of a track
 TRACK_FREE, TRACK_LIVE, TRACK_LEFT, TRACK_NOFLOW, TRACK_NOBACK, TRACK_INCONSISTENT = range(6)
 TRACK_CAP_MAX = 1 << 26                     # a track set's largest capacity
+EPIPOLAR_MAX_HYP = 21845                    # DFLOW_EPIPOLAR_MAX_HYP: three slots per sample in a 16-bit index
 
 
 class DflowError(RuntimeError):
@@ -147,7 +148,12 @@ _SIGNATURES_TRACKS = {
     "dflow_track_seed": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dflow_track_flow": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
-SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS)
+# The epipolar fit (csrc/epipolar.hip): shared checks alone, its refusals pinned by tests/test_abi_epipolar.py.
+_SIGNATURES_EPIPOLAR = {
+    "dflow_epipolar_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _i32, _u64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp]),
+}
+SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS) + tuple(_SIGNATURES_EPIPOLAR)
 
 
 def build(force=False):
@@ -173,7 +179,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS):
+        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

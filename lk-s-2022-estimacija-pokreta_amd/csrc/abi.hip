@@ -865,6 +865,32 @@ int dflow_motion_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout, 
                              d_hyp_counts, d_state, d_class, d_model_flow, d_residual, d_counts, (hipStream_t)stream);
 }
 
+int dflow_epipolar_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout, const uint8_t *d_exclude, float thresh, int32_t n_hyp,
+                       int32_t lo_rounds, int32_t step, uint64_t seed, uint32_t flags, float *d_model, float *d_models,
+                       int32_t *d_hyp_counts, int64_t *d_state, uint8_t *d_class, float *d_residual, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_finite_gt0(__func__, "thresh", thresh))) return rc;
+    // three slots per sample, and a slot's index has 16 bits of the best key
+    if ((rc = check_int_range(__func__, "n_hyp", n_hyp, 1, 21845))) return rc;
+    if ((rc = check_int_range(__func__, "lo_rounds", lo_rounds, 0, 4))) return rc;
+    if ((rc = check_int_range(__func__, "step", step, 1, 64))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_flow); CHECK_PTR(d_model); CHECK_PTR(d_models); CHECK_PTR(d_hyp_counts); CHECK_PTR(d_state);
+    // the best key and the counters are updated with 64-bit atomics
+    rc = check_aligned(__func__, {{"d_state", d_state, 8}, {"d_flow", d_flow, 4}, {"d_model", d_model, 4}, {"d_models", d_models, 4},
+                                  {"d_hyp_counts", d_hyp_counts, 4}, {"d_residual", d_residual, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the field is read in every launch, after the planes of the launches before it have been written
+    rc = check_distinct(__func__, {{"d_flow", d_flow}, {"d_exclude", d_exclude}},
+                        {{"d_model", d_model}, {"d_models", d_models}, {"d_hyp_counts", d_hyp_counts}, {"d_state", d_state},
+                         {"d_class", d_class}, {"d_residual", d_residual}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_epipolar_fit(h, w, d_flow, layout, d_exclude, thresh, n_hyp, lo_rounds, step, seed, d_model, d_models, d_hyp_counts,
+                               d_state, d_class, d_residual, d_counts, (hipStream_t)stream);
+}
+
 int dflow_label_confidence(const dflow_params *p, const uint32_t *d_proposals, const float *d_lcosts, const int32_t *d_nprop,
                            const int32_t *d_bestlabels, int32_t mode, int32_t min_sep, float thresh, float *d_margin, int32_t *d_alt,
                            float *d_sparse, int32_t *d_counts, void *stream)

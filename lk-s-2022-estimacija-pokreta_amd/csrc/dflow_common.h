@@ -357,6 +357,11 @@ int launch_flow_wmedian(int H, int W, const float *flow, int layout, const uint8
 int launch_motion_fit(int H, int W, const float *flow, int layout, const uint8_t *exclude, int model, float thresh, int n_hyp,
                       int lo_rounds, int polish, int step, uint64_t seed, float *d_model, float *models, int32_t *hyp_counts,
                       int64_t *state, uint8_t *cls, float *model_flow, float *residual, int32_t *counts, hipStream_t s);
+// epipolar.hip: the robust fit of a fundamental matrix to a flow field, 3 + 4 (lo_rounds + 1) launches whatever the field holds
+// (arguments validated by the caller); exclude, cls, residual and counts may be NULL
+int launch_epipolar_fit(int H, int W, const float *flow, int layout, const uint8_t *exclude, float thresh, int n_hyp, int lo_rounds,
+                        int step, uint64_t seed, float *d_model, float *models, int32_t *hyp_counts, int64_t *state, uint8_t *cls,
+                        float *residual, int32_t *counts, hipStream_t s);
 // label_conf.hip: the per-pixel margin of a labelling and the score gate of a flow field, one launch each (arguments validated by
 // the caller); margin, alt, sparse and counts may be NULL (not all four), the gate's counts too
 int launch_label_confidence(const dflow_params *p, const uint32_t *proposals, const float *lcosts, const int32_t *nprop,

@@ -22,6 +22,7 @@
 #include <math.h>
 #include "plane_ops.h"
 #include "philox.h"
+#include "fit_common.h"      // MfArgs, mf_part, mf_grid_pixel, mf_load_model, mf_block_add: shared with epipolar.hip
 
 #define MF_THREADS 256
 #define MF_CHUNK 2048                                 // scored pixels a block stages: 32 KiB of LDS, four blocks per CU
@@ -35,25 +36,6 @@ enum { MF_S_BEST = 0, MF_S_SCORED, MF_S_DEGEN, MF_S_CUR, MF_S_ACCEPTED, MF_S_SKI
        MF_S_CAND_MODEL = 20 /* float32[9] in 20..24 */, MF_S_CAND_OK = 25 };
 #define MF_NSUMS 12
 
-struct MfArgs {
-    int h, w, layout, model, n_hyp, step, ws;         // ws: scored columns, ceil(w / step)
-    uint32_t n, ns;                                   // pixels, grid points (y % step == 0 && x % step == 0)
-    uint32_t k0, k1;
-    float thresh;
-    double cx, cy, s, inv;                            // the centre, 1 / P and P, P the power of two >= max(h, w)
-    const float *flow;
-    const uint8_t *exclude;
-    float *cur;                                       // d_model: the current model
-    float *models;
-    int32_t *hyp_counts;
-    unsigned long long *state;
-};
-
-__device__ static inline bool mf_part(const MfArgs &a, uint32_t i, float &U, float &V)
-{
-    return flow_good(a.flow, a.layout, (size_t)i, U, V) && !(a.exclude && a.exclude[i]);
-}
-
 // INLIER (include/dflow.h, B and D)
 __device__ __forceinline__ static bool mf_inlier(const float (&m)[9], float xf, float yf, float tx, float ty, float thresh)
 {
@@ -62,23 +44,10 @@ __device__ __forceinline__ static bool mf_inlier(const float (&m)[9], float xf, 
     return W > 0.0f && ex * ex + ey * ey <= t * t;
 }
 
-__device__ static inline void mf_load_model(const float *__restrict__ p, float (&m)[9])
-{
-#pragma unroll
-    for (int k = 0; k < 9; k++) m[k] = p[k];
-}
-
 __device__ static inline void mf_identity(float (&m)[9])
 {
 #pragma unroll
     for (int k = 0; k < 9; k++) m[k] = k % 4 == 0 ? 1.0f : 0.0f;
-}
-
-// grid point c -> its pixel
-__device__ static inline uint32_t mf_grid_pixel(const MfArgs &a, uint32_t c, int &x, int &y)
-{
-    y = (int)(c / (uint32_t)a.ws) * a.step; x = (int)(c % (uint32_t)a.ws) * a.step;
-    return (uint32_t)y * (uint32_t)a.w + (uint32_t)x;
 }
 
 // Gaussian elimination with partial pivoting of the N x (N + R) system A, the first largest pivot winning, then the back
@@ -242,19 +211,6 @@ template <bool HOMOG> __global__ void __launch_bounds__(MF_THREADS) mf_score_ker
         }
     }
     if (live && cnt) atomicAdd(&a.hyp_counts[j], cnt);
-}
-
-// how many lanes of the block have `is`, added to *slot: ballots -> LDS -> one 64-bit integer atomic per block
-__device__ static inline void mf_block_add(bool is, unsigned long long *slot)
-{
-    __shared__ int s_c;
-    if (threadIdx.x == 0) s_c = 0;
-    __syncthreads();
-    const int c = __popcll(__ballot(is));
-    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_c, c);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_c) atomicAdd(slot, (unsigned long long)s_c);
-    __syncthreads();
 }
 
 __global__ void __launch_bounds__(MF_THREADS) mf_best_kernel(MfArgs a, int round)

@@ -1141,6 +1141,74 @@ def motion_layers(flow, k, exclude=None, **fit_args):
     return models, layers
 
 
+# ---------------------------------------------------------------------- epipolar geometry (csrc/epipolar.hip)
+EPIPOLAR_FIT_COUNTS = ("scored", "inliers", "degenerate", "best_round", "best_slot", "best_count", "models_per_1000", "reserved")
+
+
+def epipolar_fit(flow, thresh=1.0, n_hyp=512, lo_rounds=1, step=1, seed=0, exclude=None, classes=False, residual=False, counts=False):
+    """The epipolar geometry of a flow field (dflow_epipolar_fit, DESIGN.md "Epipolar-geometry fit"): the fundamental matrix
+    that most vectors agree with to within a Sampson distance of thresh pixels, found from n_hyp random 7-point samples per
+    round (each gives up to three models) and lo_rounds further rounds sampled among the best model's inliers.  The model of a
+    camera moving through a rigid scene with depth; motion_fit's homography fits one plane of it.  flow is (H,W,2) float32
+    [dy,dx] or (H,W,3) float32 [U,V,valid]; exclude an (H,W) uint8 mask, non-zero = the pixel takes no part, or None.  Device
+    tensors or host arrays; host data is uploaded to the current device.  step > 1 scores only every step-th row and column.
+    Returns the (3,3) float32 device tensor F^ in the centred, scaled coordinates the header defines (epipolar_geometry turns it
+    into pixels), all zeros when no model was found (a still camera, a line of pixels, fewer than 7 vectors), or a tuple in the
+    order (model[, classes][, residual][, counts]): classes=True adds the (H,W) uint8 plane 0 no vector / 1 inlier / 2 outlier /
+    3 excluded, residual=True the (H,W) float32 Sampson distance in pixels (-1 where there is no vector), counts=True the
+    int32[8] device tensor EPIPOLAR_FIT_COUNTS.  Runs on torch's current stream and does not wait for it."""
+    fn = "epipolar_fit"
+    flow = _check(flow, fn, "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    if exclude is not None:
+        exclude = _check(exclude, fn, "exclude", torch.uint8, (H, W))
+    if not (isinstance(thresh, (int, float, np.integer, np.floating)) and np.isfinite(np.float32(thresh)) and np.float32(thresh) > 0):
+        raise ValueError("%s: thresh must be finite and > 0 as a float32, got %r" % (fn, thresh))
+    for name, v, lo, hi in (("n_hyp", n_hyp, 1, _lib.EPIPOLAR_MAX_HYP), ("lo_rounds", lo_rounds, 0, 4), ("step", step, 1, 64),
+                            ("seed", seed, 0, 2 ** 64 - 1)):
+        if not (isinstance(v, (int, np.integer)) and lo <= v <= hi):
+            raise ValueError("%s: %s must be an int in [%d, %d], got %r" % (fn, name, lo, hi, v))
+    dev = _device_of(flow, *([exclude] if exclude is not None else []))
+    ts = _on(dev, flow, *([exclude] if exclude is not None else []))
+    flow, exclude = ts[0], ts[1] if exclude is not None else None
+    out = torch.empty(9, dtype=torch.float32, device=dev)
+    models = torch.empty(3 * int(n_hyp) * 9, dtype=torch.float32, device=dev)
+    hyp_counts = torch.empty(3 * int(n_hyp), dtype=torch.int32, device=dev)
+    state = torch.empty(32, dtype=torch.int64, device=dev)
+    extra = [_out(classes, (H, W), torch.uint8, dev), _out(residual, (H, W), torch.float32, dev), _out(counts, 8, torch.int32, dev)]
+    _lib.call("dflow_epipolar_fit", H, W, flow.data_ptr(), _layout(flow), _ptr(exclude), float(thresh), int(n_hyp), int(lo_rounds),
+              int(step), int(seed), 0, out.data_ptr(), models.data_ptr(), hyp_counts.data_ptr(), state.data_ptr(), _ptr(extra[0]),
+              _ptr(extra[1]), _ptr(extra[2]), _lib.stream(dev))
+    ret = tuple(t for t in [out.view(3, 3)] + extra if t is not None)
+    return ret if len(ret) > 1 else ret[0]
+
+
+def epipolar_geometry(model, h, w):
+    """What the nine numbers of epipolar_fit mean in pixels, in host float64, after the caller has read them (model: anything
+    np.asarray takes, 9 values).  Returns a dict: F, the (3,3) fundamental matrix in pixel coordinates, T^T F^ T with the header's
+    T, so that (x',y',1) F (x,y,1)^T = 0; e1, the epipole in frame 1 (F e1 = 0), and e2, the epipole in frame 2 (F^T e2 = 0), as
+    homogeneous 3-vectors, each the cross product of the two rows (for e2: columns) of F whose product is longest; foe, e1 in
+    pixels (x, y), the focus of expansion when the camera moves forward, or None when e1 lies at infinity (a sideways motion)
+    or there is no model."""
+    m = np.asarray(model, np.float64).reshape(3, 3)
+    if not (isinstance(h, (int, np.integer)) and isinstance(w, (int, np.integer)) and 1 <= h <= 8192 and 1 <= w <= 8192):
+        raise ValueError("epipolar_geometry: h and w must be ints in [1, 8192], got %r, %r" % (h, w))
+    P = 1.0
+    while P < max(h, w):
+        P *= 2.0
+    s, cx, cy = 1.0 / P, (w - 1) * 0.5, (h - 1) * 0.5
+    T = np.array([[s, 0.0, -cx * s], [0.0, s, -cy * s], [0.0, 0.0, 1.0]])
+    F = T.T @ m @ T
+
+    def null(rows):
+        products = [np.cross(rows[i], rows[j]) for i, j in ((0, 1), (0, 2), (1, 2))]
+        return max(products, key=lambda c: float(c @ c))
+    e1, e2 = null(F), null(F.T)
+    scale = float(np.abs(e1).max())
+    foe = (float(e1[0] / e1[2]), float(e1[1] / e1[2])) if scale > 0.0 and abs(e1[2]) > 1e-12 * scale else None
+    return dict(F=F, e1=e1, e2=e2, foe=foe)
+
+
 # ---------------------------------------------------------------------- point trajectories (csrc/tracks.hip)
 TRACK_STATES = ("free", "live", "left", "noflow", "noback", "inconsistent")
 TRACK_ADVANCE_COUNTS = ("live", "left", "noflow", "noback", "inconsistent", "not_live")

@@ -64,6 +64,12 @@ Without them nothing is launched that was not launched before.
 defaults, DESIGN.md "Global-motion fit"; --motion-thresh T is its inlier threshold in pixels, default 1) and writes
 residual_<pair>.flo, the forward flow minus the model's, and motion.json in DIR with the per-pair rows {pair, matrix, scored,
 inliers}.  One line per pair gives the inlier share.  Without it nothing is launched that was not launched before.
+--epipolar T fits the epipolar geometry of every pair's checked sparse field (pipeline.epipolar_fit with its defaults and the
+Sampson threshold T pixels, DESIGN.md "Epipolar-geometry fit"), after the check, --segments, --wmedian-reject and --confidence
+and before --prefilter / --epic, and writes epipolar.json in DIR with the per-pair rows {pair, model, F, e1, e2, foe and the
+counts}; with --motion homography a row also holds that fit's counts.  --epipolar-gate drops the vectors that disagree from the
+sparse field, every other vector bit for bit.  One line per pair gives the inlier share.  Without it nothing is launched that
+was not launched before.
 --confidence T takes every pass's label margin after its sweeps (DiscreteFlow.confidence, DESIGN.md "Label confidence"; --conf-mode
 local|data and --conf-sep S as in "python bcd.py", default local and 1); the margin travels to rank 0 as a third channel of the
 pass's flow.  There every pair's checked sparse field is gated with the forward margin (pipeline.flow_gate, margin >= T), after
@@ -121,6 +127,9 @@ def parser():
     ap.add_argument("--motion", default=None, metavar="MODEL",
                     help="also fit the dominant motion (affine or homography) of each forward flow; writes motion.json and residual_NN.flo")
     ap.add_argument("--motion-thresh", default=None, metavar="T", help="with --motion: the inlier threshold in pixels (default 1)")
+    ap.add_argument("--epipolar", default=None, metavar="T",
+                    help="also fit the epipolar geometry of each pair's checked sparse field (Sampson threshold T pixels); writes epipolar.json")
+    ap.add_argument("--epipolar-gate", action="store_true", help="with --epipolar: drop the vectors that disagree from the sparse field")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     mod("labelconf").add_cli_options(ap, with_threshold=True)
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
@@ -185,6 +194,40 @@ def motion_args(a):
     except ValueError:
         parser().error("--motion-thresh needs T (finite, > 0), got %r" % (a.motion_thresh,))
     return a.motion, thresh
+
+
+def epipolar_arg(a):
+    """--epipolar T -> T or None; exits with status 2 for a threshold that is not finite and > 0, or --epipolar-gate without it."""
+    if a.epipolar is None:
+        if a.epipolar_gate:
+            parser().error("--epipolar-gate needs --epipolar")
+        return None
+    try:
+        thresh = float(a.epipolar)
+        if not (np.isfinite(thresh) and thresh > 0):
+            raise ValueError
+    except ValueError:
+        parser().error("--epipolar needs T (finite, > 0), got %r" % (a.epipolar,))
+    return thresh
+
+
+def epipolar_pair(s, pair, sparse_dev):
+    """--epipolar: the fit of one pair's checked sparse field, its row of epipolar.json and its printed line; returns the field,
+    without the vectors that disagree under --epipolar-gate (the others keep their bits)."""
+    import torch
+    a, pipeline = s.a, mod("pipeline")
+    model, cls, counts = pipeline.epipolar_fit(sparse_dev, thresh=a.epipolar, classes=True, counts=True)
+    counts = dict(zip(pipeline.EPIPOLAR_FIT_COUNTS[:7], counts.cpu().tolist()))
+    model = model.cpu().numpy()
+    geo = pipeline.epipolar_geometry(model, s.H, s.W)
+    s.epipolar_rows.append(dict(pair=pair, model=model.tolist(), F=geo["F"].tolist(), e1=geo["e1"].tolist(), e2=geo["e2"].tolist(),
+                                foe=geo["foe"], **counts))
+    print("pair %d: epipolar geometry: %d of %d checked vectors within %g px (%.2f%%)%s"
+          % (pair, counts["inliers"], counts["scored"], a.epipolar, 100.0 * counts["inliers"] / max(counts["scored"], 1),
+             "" if counts["best_slot"] >= 0 else "; no model was found"))
+    if a.epipolar_gate:
+        sparse_dev = torch.where((cls == 2)[..., None], torch.zeros_like(sparse_dev), sparse_dev)
+    return sparse_dev
 
 
 def midframe_args(a):
@@ -414,6 +457,8 @@ def write_pair(s, pair, fwd, bwd, margin=None):
         sparse_dev, gate_counts = pipeline.flow_gate(sparse_dev, margin, lo=a.confidence, counts=True)
         print("pair %d: confidence gate at margin >= %g: %d of %d checked vectors stay" % ((pair, a.confidence) + tuple(gate_counts.cpu().tolist()[::-1])))
         np.save(os.path.join(a.out, "margin_%02d.npy" % pair), margin.cpu().numpy())
+    if a.epipolar is not None:
+        sparse_dev = epipolar_pair(s, pair, sparse_dev)
     sparse_raw = sparse_dev                     # --prefilter hands a filtered copy to the interpolation
     sparse = sparse_dev.cpu().numpy()
     for backward, f in ((0, fwd), (1, bwd)):
@@ -458,6 +503,7 @@ def write_out(s, flows):
     photo_rows, photo_totals = [], {}
     mid_rows = []
     motion_rows = []
+    s.epipolar_rows = []
     for pair in range(a.pairs):
         fwd, bwd, margin = flows[2 * pair], flows[2 * pair + 1], None
         if a.confidence is not None:            # [dy, dx, margin] per pass
@@ -496,6 +542,13 @@ def write_out(s, flows):
         import json
         with open(os.path.join(a.out, "motion.json"), "w") as f:
             json.dump(dict(head, model=a.motion, thresh=a.motion_thresh, pairs=motion_rows), f, indent=1)
+    if a.epipolar is not None:
+        import json
+        if a.motion == "homography":            # both fits' counts side by side, nothing more: the homography is fitted to the forward flow
+            for row, m in zip(s.epipolar_rows, motion_rows):
+                row["homography"] = dict(scored=m["scored"], inliers=m["inliers"], thresh=a.motion_thresh)
+        with open(os.path.join(a.out, "epipolar.json"), "w") as f:
+            json.dump(dict(head, thresh=a.epipolar, gate=bool(a.epipolar_gate), pairs=s.epipolar_rows), f, indent=1)
     if a.midframe:
         import json
         with open(os.path.join(a.out, "midframe.json"), "w") as f:
@@ -531,6 +584,7 @@ def main(argv=None):
         a.wmedian_reject = wmedian_reject_arg(a.wmedian_reject)
     a.mid_fill_rounds, a.mid_occl_thresh = midframe_args(a)
     a.motion, a.motion_thresh = motion_args(a)
+    a.epipolar = epipolar_arg(a)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)

@@ -166,3 +166,36 @@ def make_mid(H, W, seed=0, t=0.5, amp_x=40.0, amp_y=20.0, style="dense", iters=6
 def pair_seed(pair_idx, backward):
     """Seed convention of SURVEY 8(d): 1000 * pair_idx + direction."""
     return 1000 * int(pair_idx) + int(backward)
+
+
+def rigid_flow(H, W, seed, t, rot, objects=()):
+    """The exact flow of a pinhole camera that moves through a rigid scene, which the smooth warps of make_pair are not: they
+    obey no epipolar geometry.  The camera has focal length max(H, W) pixels and its principal point at the frame's centre; the
+    scene is a smooth depth map Z(x, y) in [4.5, 12.5] drawn from `seed`; the point seen at pixel (x, y) is X = Z K^-1 (x, y, 1),
+    the second camera sees it at K (R X + t), R the rotation by the axis-angle vector `rot` (radians), t in the units of Z.
+    objects: rectangles (y0, x0, y1, x1, du, dv) whose pixels carry the extra motion (du, dv) pixels on top of the scene's.
+    Returns (flow, mask): (H,W,3) float64 [U, V, 1] and the (H,W) bool mask of the rectangles.  t = (0, 0, tz) and rot = 0 put
+    the epipole (the focus of expansion) at ((W-1)/2, (H-1)/2); t = (tx, 0, 0) puts it at infinity."""
+    rng = np.random.default_rng(seed + 104729)
+    f, cx, cy = float(max(H, W)), (W - 1) * 0.5, (H - 1) * 0.5
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    Z = np.full((H, W), 8.5)
+    for amp in (2.0, 1.25, 0.75):
+        fx, fy = rng.uniform(0.5, 2.0, 2)
+        p0, p1 = rng.uniform(0, 2 * np.pi, 2)
+        Z = Z + amp * np.sin(2 * np.pi * fx * xx / W + p0) * np.cos(2 * np.pi * fy * yy / H + p1)
+    rx, ry, rz = (float(v) for v in rot)
+    th = (rx * rx + ry * ry + rz * rz) ** 0.5
+    K = np.array([[0.0, -rz, ry], [rz, 0.0, -rx], [-ry, rx, 0.0]])
+    R = np.eye(3) if th == 0.0 else np.eye(3) + (np.sin(th) / th) * K + ((1.0 - np.cos(th)) / (th * th)) * (K @ K)
+    X = np.stack([(xx - cx) / f * Z, (yy - cy) / f * Z, Z], axis=-1)
+    Y = X @ R.T + np.asarray(t, np.float64)
+    if not (Y[..., 2] > 0).all():
+        raise ValueError("rigid_flow: the motion puts a scene point behind the second camera")
+    U, V = f * Y[..., 0] / Y[..., 2] + cx - xx, f * Y[..., 1] / Y[..., 2] + cy - yy
+    mask = np.zeros((H, W), bool)
+    for y0, x0, y1, x1, du, dv in objects:
+        U[y0:y1, x0:x1] += du
+        V[y0:y1, x0:x1] += dv
+        mask[y0:y1, x0:x1] = True
+    return np.stack([U, V, np.ones((H, W))], axis=-1), mask
