@@ -77,6 +77,8 @@
  *                                   d_err, d_counts 4
  *       dflow_track_seed            d_pos 8; d_state, d_birth, d_n, d_scan, d_counts 4; d_mask 1
  *       dflow_track_flow            d_pos_a, d_pos_b 8; d_state_a, d_state_b, d_owner, d_out, d_counts 4
+ *       dflow_superpixels           d_label, d_centers, d_slic, d_counts, d_sums, d_comp, d_size, d_final, d_scan 4; d_bgr 1
+ *       dflow_segment_fit           d_acc 8; d_flow, d_label, d_models, d_seg_counts, d_out, d_counts 4; d_class 1
  *     A plane below its number returns DFLOW_EINVAL ("NAME is not N-byte aligned", the batch forms name the entry NAME[i]) before
  *     anything is launched, after the NULL checks and before the workspace is looked at (the batch forms of the sweeps check the
  *     one size of their workspaces before any per-pass pointer, as they always have).
@@ -1068,6 +1070,101 @@ int dflow_track_seed(int32_t h, int32_t w, int32_t cap, int32_t step, int32_t fr
 int dflow_track_flow(int32_t h, int32_t w, int32_t cap, const float *d_pos_a, const int32_t *d_state_a, const float *d_pos_b,
                      const int32_t *d_state_b, int32_t *d_owner /* (h,w) int32 */, float *d_out /* (h,w,3) */,
                      int32_t *d_counts /* NULL or int32[3] */, void *stream);
+
+/* Superpixels (DESIGN.md "Superpixels and per-segment flow models"): an over-segmentation of an image into compact regions of
+ * similar colour, an integer variant of gSLIC (Achanta et al.; Ren and Reid) whose segments are 4-connected and numbered 0 ..
+ * n_seg-1.  This build's definition; the reference has no counterpart.  1 <= h, w <= 8192, n = h*w; d_bgr is (h,w,3) uint8 [b,g,r];
+ * S = step, 4 <= S <= 64; m = compactness, 0 <= m <= 255; 1 <= iters <= 32; 0 <= min_size <= 2^26.  All arithmetic is unsigned
+ * integer: the result depends on no order of arrival, and two calls give the same bytes.
+ *   GRID.  gw = ceil(w/S), gh = ceil(h/S), K = gw*gh <= 2^22.  Centre k = gy*gw + gx is five numbers at 1/16 resolution, (cx16,
+ *     cy16, b16, g16, r16), and starts as 16 times the position and the colours of pixel (x, y) = (min(gx*S + S/2, w-1), min(gy*S +
+ *     S/2, h-1)).
+ *   ASSIGNMENT.  Pixel (x, y) with colours (b, g, r) lies in cell (gy, gx) = (y/S, x/S) and considers the centres k of the cells
+ *     (gy+dy, gx+dx), |dy|, |dx| <= 1, that exist.  dc2 = (16b - b16)^2 + (16g - g16)^2 + (16r - r16)^2, ds2 = (16x - cx16)^2 + (16y -
+ *     cy16)^2, D' = S*S*dc2 + m*m*ds2, key = D' << 22 | k; the pixel takes the k of its smallest key, so at equal distance the
+ *     smaller k wins.  Bounds: a centre is the rounded mean of pixels of its own 3x3 cells, so every coordinate difference is
+ *     below 4*S*16 <= 2^12 and every colour difference below 2^12: dc2 < 2^26 and ds2 < 2^25 fit 32 bits, D' < 2^12 * 2^26 + 2^16 *
+ *     2^25 < 2^42, and the key fits 64 bits.
+ *   UPDATE.  Per centre: n, the number of its pixels, and the sums of x, y, b, g, r over them (each below 2^32: at most 9*S*S
+ *     pixels).  Each of the five numbers becomes (16*sum + (n >> 1)) / n, a 64-bit integer division; a centre with n == 0 keeps
+ *     its numbers.
+ *   An ITERATION is one assignment followed by one update.  The raw labels are the assignment of iteration `iters`, the centres
+ *     those after its update.
+ *   COMPONENTS.  The 4-connected components of equal raw label.  A component's ROOT is its smallest raster index y*w + x, its size
+ *     its number of pixels; it is SMALL if size < min_size.  The TARGET of a small component with root pixel (y0, x0) is the
+ *     component of pixel (y0, x0-1) if x0 > 0, else of (y0-1, x0) if y0 > 0, else there is none.  That pixel is not of the
+ *     component and the target's root is smaller, so targets form a forest.  A small component joins the component at the end of
+ *     its chain of targets: the first that is not small, or the one that holds pixel 0.  (The order-independent counterpart of
+ *     SLIC's "merge into the label seen just before".)  So every final segment is 4-connected, every final segment but possibly
+ *     the one that holds pixel 0 has at least min_size pixels, and min_size 0 or 1 merges nothing.
+ *   NUMBERING.  The final segments are numbered 0 .. n_seg-1 in the order of their smallest raster index.
+ * Outputs: d_label (h,w) int32, the final segment number.  d_centers (K,8) int32: [cx16, cy16, b16, g16, r16, n of the last
+ * assignment, 0, 0].  d_slic (NULL to skip) (h,w) int32: the raw label k.  d_counts (NULL to skip) int32[8], zeroed by the call on
+ * the stream = {K, centres with n == 0 in the last assignment, components, small components (the one that holds pixel 0
+ * included if it is small), pixels of components that joined another, n_seg, the size of the largest final segment, 0}.
+ * There is no d_ws: the scratch is the caller's typed planes, all int32 and 4-byte aligned: d_sums (K,8), d_comp (h,w), d_size
+ * (h,w), d_final (h,w) and d_scan, ceil(h*w / 256) + 1 elements.  What they hold afterwards is unspecified.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; step outside [4,64];
+ * compactness outside [0,255]; iters outside [1,32]; min_size outside [0,67108864]; any flag bit (there are none yet); a NULL
+ * d_bgr, d_label, d_centers, d_sums, d_comp, d_size, d_final or d_scan; an int32 plane not 4-byte aligned; an output or scratch
+ * plane equal to d_bgr or to one listed before it (d_label, d_centers, d_slic, d_counts, d_sums, d_comp, d_size, d_final, d_scan).
+ * 8 + 2 iters launches (the centres; an assignment fused with the accumulation and a division per iteration; seven for the
+ * components, the merge, the scan and the numbering) and at most one memset, whatever the image holds.  Asynchronous on `stream`,
+ * allocates nothing, reads nothing back, can be captured into a graph. */
+#define DFLOW_SEGMENTS_MAX 67108864 /* 2^26 */
+int dflow_superpixels(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t step /* 4..64 */, int32_t compactness /* 0..255 */,
+        int32_t iters /* 1..32 */, int32_t min_size /* 0..2^26 */, uint32_t flags /* none yet */,
+        int32_t *d_label   /* (h,w) */, int32_t *d_centers /* (K,8) */,
+        int32_t *d_slic    /* NULL or (h,w) */, int32_t *d_counts /* NULL or int32[8] */,
+        int32_t *d_sums    /* scratch (K,8) */, int32_t *d_comp /* scratch (h,w) */, int32_t *d_size /* scratch (h,w) */,
+        int32_t *d_final   /* scratch (h,w) */, int32_t *d_scan /* scratch int32[ceil(h*w/256) + 1] */, void *stream);
+
+/* A robust affine flow model per segment (DESIGN.md "Superpixels and per-segment flow models"): trimmed least squares over the
+ * vectors of every segment of a label plane.  This build's definition; the reference has no counterpart.  1 <= h, w <= 8192; d_flow
+ * is (h,w,.) float32 in DFLOW_EVAL_UVV or DFLOW_EVAL_DYDX layout; a vector is GOOD as in dflow_flow_consistency.  d_label is (h,w)
+ * int32, any label plane; 1 <= n_seg <= 2^26; thresh (pixels) finite and > 0; R = rounds, 1 <= R <= 6.  Pixel (x, y) with vector
+ * (U,V) and label l TAKES PART if the vector is good, 0 <= l < n_seg, and fabsf(U) <= 32768 && fabsf(V) <= 32768.  Its quantities:
+ * xf = (float)x, yf = (float)y, a = 2x - (w-1), b = 2y - (h-1), p = llrintf(U*64), q = llrintf(V*64).  Float32 and float64 chains
+ * are one IEEE operation per written operation; everything else is an integer.  The result depends on no order of arrival, and two
+ * calls give the same bytes.
+ *   A MODEL is float32[6]: Um = (m0*xf + m1*yf) + m2, Vm = (m3*xf + m4*yf) + m5 (float32).  A pixel AGREES with it at T iff, with
+ *     eu = U - Um, ev = V - Vm: eu*eu + ev*ev <= T*T (float32; a NaN anywhere makes it false).
+ *   ROUND 0.  Per segment, over the pixels of its label that take part, the int64 sums N, Sa, Sb, Saa, Sab, Sbb, Sp, Sap, Sbp, Sq,
+ *     Saq, Sbq (|a|, |b| < 2^13, |p|, |q| <= 2^21, at most 2^26 pixels: every sum stays below 2^60).  SOLVE as step E of
+ *     dflow_motion_fit does: each sum is converted to float64 (one rounding), then c00 = Sbb*N - Sb*Sb, c01 = Sb*Sa - Sab*N, c02 =
+ *     Sab*Sb - Sbb*Sa, c11 = Saa*N - Sa*Sa, c12 = Sa*Sab - Saa*Sb, c22 = Saa*Sbb - Sab*Sab, det = (Saa*c00 + Sab*c01) + Sa*c02; for
+ *     (r0,r1,r2) = (Sap, Sbp, Sp): x0 = ((c00*r0 + c01*r1) + c02*r2)/det, x1 = ((c01*r0 + c11*r1) + c12*r2)/det, x2 = ((c02*r0 +
+ *     c12*r1) + c22*r2)/det, m0 = (float)(x0*0.03125), m1 = (float)(x1*0.03125), m2 = (float)(((x2 - x0*(w-1)) - x1*(h-1))*0.015625);
+ *     m3..m5 likewise from (Saq, Sbq, Sq).  p and q are the flow, not the target: the model is the flow's.  The solve FAILS with N <
+ *     3, det zero or not finite, or a coefficient not finite.  A failed solve with N >= 1 gives the translation [0, 0,
+ *     (float)(((double)Sp/(double)N)*0.015625), 0, 0, (float)(((double)Sq/(double)N)*0.015625)]; with N == 0 the segment has no
+ *     model.
+ *   ROUND r = 1 .. R-1.  The same sums over the pixels that take part and agree with the model of round r-1 at T_r = thresh *
+ *     2^(R-1-r) (one float32 multiplication); a segment without a model has none that agree.  The same solve and the same
+ *     translation; with N == 0 the model of the round before, and its kind, stay.  The last round fits what lies within thresh.
+ * Outputs: d_models (n_seg,6) float32, zeros without a model.  d_seg_counts (n_seg,4) int32 = {pixels with this label, pixels that
+ * take part, those of them that agree with the final model at thresh, the kind of the final model: 0 none, 1 translation, 2 affine}.
+ * d_out (NULL to skip) (h,w,3) float32: [Um, Vm, 1] at every pixel whose label is in range and whose segment has a model, good
+ * vector or not (holes inside a segment are filled); [0,0,0] elsewhere.  d_class (NULL to skip) (h,w) uint8: 0 takes no part, 1
+ * agrees with its segment's final model at thresh, 2 does not, 3 takes part but its segment has no model.  d_counts (NULL to skip)
+ * int32[8], zeroed by the call on the stream = {pixels that take part, of class 1, segments with a model, affine segments,
+ * translation segments, pixels whose label is out of range, good vectors outside the 32768 range (whatever their label), 0}.
+ * There is no d_ws: the scratch is the caller's typed plane d_acc (n_seg,12) int64, 8-byte aligned, which the call zeroes on the
+ * stream and every round leaves zeroed.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout; n_seg outside
+ * [1,67108864]; thresh not finite or not > 0; rounds outside [1,6]; any flag bit (there are none yet); a NULL d_flow, d_label,
+ * d_models, d_seg_counts or d_acc; d_acc not 8-byte aligned, a float or int32 plane not 4-byte aligned; an output or scratch plane
+ * equal to d_flow, d_label or to one listed before it (d_models, d_seg_counts, d_out, d_class, d_counts, d_acc).
+ * 2 rounds + 1 launches (per round the sums, a wave's adds aggregated per distinct label first, and a thread per segment that
+ * solves; then one that applies) and two or three memsets, whatever the planes hold.  Asynchronous on `stream`, allocates nothing,
+ * reads nothing back, can be captured into a graph. */
+int dflow_segment_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        const int32_t *d_label /* (h,w): any label plane */, int32_t n_seg /* 1..2^26 */,
+        float thresh, int32_t rounds /* 1..6 */, uint32_t flags /* none yet */,
+        float *d_models       /* (n_seg,6) */, int32_t *d_seg_counts /* (n_seg,4) */,
+        float *d_out          /* NULL or (h,w,3) [U,V,valid] */, uint8_t *d_class /* NULL or (h,w) */,
+        int32_t *d_counts     /* NULL or int32[8] */,
+        int64_t *d_acc        /* scratch int64 (n_seg,12), 8-byte aligned */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ CONF_COUNTS = 6                             # DFLOW_CONF_COUNTS
 TRACK_FREE, TRACK_LIVE, TRACK_LEFT, TRACK_NOFLOW, TRACK_NOBACK, TRACK_INCONSISTENT = range(6)
 TRACK_CAP_MAX = 1 << 26                     # a track set's largest capacity
 EPIPOLAR_MAX_HYP = 21845                    # DFLOW_EPIPOLAR_MAX_HYP: three slots per sample in a 16-bit index
+SEGMENTS_MAX = 1 << 26                      # DFLOW_SEGMENTS_MAX: the most segments, and the largest min_size
 
 
 class DflowError(RuntimeError):
@@ -153,7 +154,14 @@ _SIGNATURES_EPIPOLAR = {
     "dflow_epipolar_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _f32, _i32, _i32, _i32, _u64, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp]),
 }
-SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS) + tuple(_SIGNATURES_EPIPOLAR)
+# Superpixels and the per-segment fit (csrc/superpixels.hip): shared checks alone, their refusals pinned by
+# tests/test_abi_superpixels.py.
+_SIGNATURES_SUPERPIXELS = {
+    "dflow_superpixels": (C.c_int, [_i32, _i32, _vp, _i32, _i32, _i32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_segment_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+SYMBOLS = (tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS) + tuple(_SIGNATURES_EPIPOLAR)
+           + tuple(_SIGNATURES_SUPERPIXELS))
 
 
 def build(force=False):
@@ -179,7 +187,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR):
+        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR, _SIGNATURES_SUPERPIXELS):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -24,6 +24,14 @@ int launch_track_seed(int H, int W, int cap, int step, int frame, const uint8_t 
 int launch_track_flow(int H, int W, int cap, const float *pos_a, const int32_t *state_a, const float *pos_b, const int32_t *state_b,
                       int32_t *owner, float *out, int32_t *counts, hipStream_t s);
 
+// superpixels.hip: the integer SLIC with connected, compactly numbered segments, 8 + 2 iters launches, and the per-segment affine
+// fit, 2 rounds + 1 launches, whatever the planes hold (arguments validated by the caller); slic, out, cls and counts may be NULL
+int launch_superpixels(int H, int W, const uint8_t *bgr, int step, int compactness, int iters, int min_size, int32_t *label,
+                       int32_t *centers, int32_t *slic, int32_t *counts, int32_t *sums, int32_t *comp, int32_t *size, int32_t *fin,
+                       int32_t *scan, hipStream_t s);
+int launch_segment_fit(int H, int W, const float *flow, int layout, const int32_t *label, int n_seg, float thresh, int rounds,
+                       float *models, int32_t *seg_counts, float *out, uint8_t *cls, int32_t *counts, int64_t *acc, hipStream_t s);
+
 static thread_local char g_err[512] = "";
 
 int dflow_set_error(int code, const char *fmt, ...)
@@ -993,6 +1001,58 @@ int dflow_track_flow(int32_t h, int32_t w, int32_t cap, const float *d_pos_a, co
                         {{"d_owner", d_owner}, {"d_out", d_out}, {"d_counts", d_counts}});
     if (rc) return rc;
     return launch_track_flow(h, w, cap, d_pos_a, d_state_a, d_pos_b, d_state_b, d_owner, d_out, d_counts, (hipStream_t)stream);
+}
+
+// the largest number of segments and the largest min_size: the pixels of the largest frame
+#define SEGMENTS_MAX (1 << 26)
+
+int dflow_superpixels(int32_t h, int32_t w, const uint8_t *d_bgr, int32_t step, int32_t compactness, int32_t iters, int32_t min_size,
+                      uint32_t flags, int32_t *d_label, int32_t *d_centers, int32_t *d_slic, int32_t *d_counts, int32_t *d_sums,
+                      int32_t *d_comp, int32_t *d_size, int32_t *d_final, int32_t *d_scan, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "step", step, 4, 64))) return rc;
+    if ((rc = check_int_range(__func__, "compactness", compactness, 0, 255))) return rc;
+    if ((rc = check_int_range(__func__, "iters", iters, 1, 32))) return rc;
+    if ((rc = check_int_range(__func__, "min_size", min_size, 0, SEGMENTS_MAX))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_bgr); CHECK_PTR(d_label); CHECK_PTR(d_centers); CHECK_PTR(d_sums); CHECK_PTR(d_comp); CHECK_PTR(d_size);
+    CHECK_PTR(d_final); CHECK_PTR(d_scan);
+    rc = check_aligned(__func__, {{"d_label", d_label, 4}, {"d_centers", d_centers, 4}, {"d_slic", d_slic, 4}, {"d_counts", d_counts, 4},
+                                  {"d_sums", d_sums, 4}, {"d_comp", d_comp, 4}, {"d_size", d_size, 4}, {"d_final", d_final, 4},
+                                  {"d_scan", d_scan, 4}});
+    if (rc) return rc;
+    // the image is read in every iteration, and every plane is read by a launch after the one that wrote it
+    rc = check_distinct(__func__, {{"d_bgr", d_bgr}},
+                        {{"d_label", d_label}, {"d_centers", d_centers}, {"d_slic", d_slic}, {"d_counts", d_counts}, {"d_sums", d_sums},
+                         {"d_comp", d_comp}, {"d_size", d_size}, {"d_final", d_final}, {"d_scan", d_scan}});
+    if (rc) return rc;
+    return launch_superpixels(h, w, d_bgr, step, compactness, iters, min_size, d_label, d_centers, d_slic, d_counts, d_sums, d_comp,
+                              d_size, d_final, d_scan, (hipStream_t)stream);
+}
+
+int dflow_segment_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout, const int32_t *d_label, int32_t n_seg, float thresh,
+                      int32_t rounds, uint32_t flags, float *d_models, int32_t *d_seg_counts, float *d_out, uint8_t *d_class,
+                      int32_t *d_counts, int64_t *d_acc, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_int_range(__func__, "n_seg", n_seg, 1, SEGMENTS_MAX))) return rc;
+    if ((rc = check_finite_gt0(__func__, "thresh", thresh))) return rc;
+    if ((rc = check_int_range(__func__, "rounds", rounds, 1, 6))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_flow); CHECK_PTR(d_label); CHECK_PTR(d_models); CHECK_PTR(d_seg_counts); CHECK_PTR(d_acc);
+    // the sums are updated with 64-bit atomics
+    rc = check_aligned(__func__, {{"d_acc", d_acc, 8}, {"d_flow", d_flow, 4}, {"d_label", d_label, 4}, {"d_models", d_models, 4},
+                                  {"d_seg_counts", d_seg_counts, 4}, {"d_out", d_out, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the field and the labels are read in every launch
+    rc = check_distinct(__func__, {{"d_flow", d_flow}, {"d_label", d_label}},
+                        {{"d_models", d_models}, {"d_seg_counts", d_seg_counts}, {"d_out", d_out}, {"d_class", d_class},
+                         {"d_counts", d_counts}, {"d_acc", d_acc}});
+    if (rc) return rc;
+    return launch_segment_fit(h, w, d_flow, layout, d_label, n_seg, thresh, rounds, d_models, d_seg_counts, d_out, d_class, d_counts,
+                              d_acc, (hipStream_t)stream);
 }
 
 int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1, float tresh, int32_t min_segment_size)

@@ -1209,6 +1209,129 @@ def epipolar_geometry(model, h, w):
     return dict(F=F, e1=e1, e2=e2, foe=foe)
 
 
+# ---------------------------------------------------------------------- superpixels and per-segment models (csrc/superpixels.hip)
+SUPERPIXEL_COUNTS = ("centres", "empty_centres", "components", "small", "pixels_merged", "n_seg", "largest", "reserved")
+SEGMENT_FIT_COUNTS = ("part", "agree", "with_model", "affine", "translation", "bad_label", "out_of_range", "reserved")
+
+
+def _int_in(fn, name, v, lo, hi):
+    if not (isinstance(v, (int, np.integer)) and not isinstance(v, bool) and lo <= v <= hi):
+        raise ValueError("%s: %s must be an int in [%d, %d], got %r" % (fn, name, lo, hi, v))
+    return int(v)
+
+
+def _superpixels_gate(fn, img, step, compactness, iters, min_size):
+    """The arguments of superpixels through the input gate, before any device is touched: (img, min_size)."""
+    img = _check(img, fn, "img", torch.uint8, (None, None, 3))
+    H, W, _ = img.shape
+    if not (1 <= H <= 8192 and 1 <= W <= 8192):
+        raise ValueError("%s: img must be between 1x1 and 8192x8192, got %dx%d" % (fn, W, H))
+    step = _int_in(fn, "step", step, 4, 64)
+    _int_in(fn, "compactness", compactness, 0, 255)
+    _int_in(fn, "iters", iters, 1, 32)
+    return img, step * step // 4 if min_size is None else _int_in(fn, "min_size", min_size, 0, _lib.SEGMENTS_MAX)
+
+
+def _segment_fit_gate(fn, flow, thresh, rounds, shape=None):
+    """flow, thresh and rounds of segment_fit through the input gate: the flow, of frame size `shape` if that is given."""
+    flow = _check(flow, fn, "flow", torch.float32, (None, None, (2, 3)) if shape is None else (shape[0], shape[1], (2, 3)))
+    if not (1 <= flow.shape[0] <= 8192 and 1 <= flow.shape[1] <= 8192):
+        raise ValueError("%s: flow must be between 1x1 and 8192x8192, got %dx%d" % (fn, flow.shape[1], flow.shape[0]))
+    if not (isinstance(thresh, (int, float, np.integer, np.floating)) and np.isfinite(np.float32(thresh)) and np.float32(thresh) > 0):
+        raise ValueError("%s: thresh must be finite and > 0 as a float32, got %r" % (fn, thresh))
+    _int_in(fn, "rounds", rounds, 1, 6)
+    return flow
+
+
+def superpixel_grid(h, w, step):
+    """(gh, gw, K) of dflow_superpixels: the rows, the columns and the number of the grid's centres."""
+    gh, gw = -(-int(h) // int(step)), -(-int(w) // int(step))
+    return gh, gw, gh * gw
+
+
+def _superpixels_call(img, step, compactness, iters, min_size, slic, counts):
+    """One dflow_superpixels on a device image into new planes: (labels, centers, slic or None, counts or None)."""
+    H, W, _ = img.shape
+    dev = img.device
+    K = superpixel_grid(H, W, step)[2]
+    i32 = torch.int32
+    label, centers = torch.empty((H, W), dtype=i32, device=dev), torch.empty((K, 8), dtype=i32, device=dev)
+    raw, cnt = _out(slic, (H, W), i32, dev), _out(counts, 8, i32, dev)
+    sums, scan = torch.empty((K, 8), dtype=i32, device=dev), torch.empty(-(-(H * W) // 256) + 1, dtype=i32, device=dev)
+    comp, size, fin = (torch.empty((H, W), dtype=i32, device=dev) for _ in range(3))
+    _lib.call("dflow_superpixels", H, W, img.data_ptr(), int(step), int(compactness), int(iters), int(min_size), 0, label.data_ptr(),
+              centers.data_ptr(), _ptr(raw), _ptr(cnt), sums.data_ptr(), comp.data_ptr(), size.data_ptr(), fin.data_ptr(),
+              scan.data_ptr(), _lib.stream(dev))
+    return label, centers, raw, cnt
+
+
+def superpixels(img, step=16, compactness=10, iters=10, min_size=None, centers=False, slic=False, counts=False):
+    """An over-segmentation of an image into compact regions of similar colour (dflow_superpixels, DESIGN.md "Superpixels and
+    per-segment flow models"): an integer gSLIC on a grid of `step` pixels, `iters` iterations, spatial weight `compactness`
+    (0: colour alone), whose segments are 4-connected, have at least min_size pixels (None: step*step//4; but for the segment
+    that holds pixel 0) and are numbered 0 .. n_seg-1 in raster order of their first pixels.  img is an (H,W,3) uint8 BGR device
+    tensor or host array; host data is uploaded to the current device.  Returns the (H,W) int32 device plane of segment numbers,
+    or a tuple in the order (labels[, centers][, slic][, counts]): centers=True adds the (K,8) int32 centres [cx16, cy16, b16,
+    g16, r16, n, 0, 0], slic=True the raw (H,W) int32 SLIC labels, counts=True the int32[8] device tensor SUPERPIXEL_COUNTS, whose
+    entry 5 is n_seg.  Runs on torch's current stream and does not wait for it."""
+    img, min_size = _superpixels_gate("superpixels", img, step, compactness, iters, min_size)
+    dev = _device_of(img)
+    img, = _on(dev, img)
+    label, cen, raw, cnt = _superpixels_call(img, step, compactness, iters, min_size, slic, counts)
+    ret = (label,) + tuple(t for t, want in ((cen, centers), (raw, slic), (cnt, counts)) if want)
+    return ret if len(ret) > 1 else label
+
+
+def _segment_fit_call(flow, labels, n_seg, thresh, rounds, out, classes, counts):
+    """One dflow_segment_fit on device tensors into new planes: (models, seg_counts, [out, classes, counts] or Nones)."""
+    H, W, _ = flow.shape
+    dev = flow.device
+    models = torch.empty((n_seg, 6), dtype=torch.float32, device=dev)
+    seg_counts = torch.empty((n_seg, 4), dtype=torch.int32, device=dev)
+    acc = torch.empty((n_seg, 12), dtype=torch.int64, device=dev)
+    extra = [_out(out, (H, W, 3), torch.float32, dev), _out(classes, (H, W), torch.uint8, dev), _out(counts, 8, torch.int32, dev)]
+    _lib.call("dflow_segment_fit", H, W, flow.data_ptr(), _layout(flow), labels.data_ptr(), int(n_seg), float(thresh), int(rounds), 0,
+              models.data_ptr(), seg_counts.data_ptr(), _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]), acc.data_ptr(), _lib.stream(dev))
+    return models, seg_counts, extra
+
+
+def segment_fit(flow, labels, n_seg, thresh=1.0, rounds=3, out=False, classes=False, counts=False):
+    """A robust affine flow model per segment (dflow_segment_fit, DESIGN.md "Superpixels and per-segment flow models"): least
+    squares over the vectors of each segment, trimmed in `rounds` rounds whose thresholds halve down to thresh pixels; a segment
+    with fewer than three vectors or with vectors on one line gets their mean, one with none no model.  flow is (H,W,2) float32
+    [dy,dx] or (H,W,3) float32 [U,V,valid]; labels an (H,W) int32 plane, any labelling (superpixels', a mask, a motion layer
+    plane cast to int32), of which the values in [0, n_seg) are segments.  Device tensors or host arrays; host data is uploaded
+    to the current device.  Returns (models, seg_counts), the (n_seg,6) float32 models [m0..m5], U = m0 x + m1 y + m2, V = m3 x +
+    m4 y + m5, and the (n_seg,4) int32 {pixels, vectors that take part, those that agree, kind: 0 none / 1 translation / 2
+    affine}, followed in this order by what is asked for: out=True the (H,W,3) float32 [U,V,valid] flow of the models (holes
+    inside a segment are filled), classes=True the (H,W) uint8 plane 0 takes no part / 1 agrees / 2 disagrees / 3 no model,
+    counts=True the int32[8] device tensor SEGMENT_FIT_COUNTS.  Runs on torch's current stream and does not wait for it."""
+    fn = "segment_fit"
+    flow = _segment_fit_gate(fn, flow, thresh, rounds)
+    labels = _check(labels, fn, "labels", torch.int32, (flow.shape[0], flow.shape[1]))
+    n_seg = _int_in(fn, "n_seg", n_seg, 1, _lib.SEGMENTS_MAX)
+    dev = _device_of(flow, labels)
+    flow, labels = _on(dev, flow, labels)
+    models, seg_counts, extra = _segment_fit_call(flow, labels, n_seg, thresh, rounds, out, classes, counts)
+    return (models, seg_counts) + tuple(t for t in extra if t is not None)
+
+
+def superpixel_flow(img, flow, step=16, compactness=10, iters=10, min_size=None, thresh=1.0, rounds=3, classes=False, counts=False):
+    """superpixels on img, then segment_fit of flow on its segments: the piecewise-affine version of a flow field.  The
+    per-segment planes are sized from the n_seg this function reads back once (it waits for the stream there); the library reads
+    nothing back.  Returns (labels, models, seg_counts, out[, classes][, counts]) as the two functions define them; n_seg is
+    models.shape[0]."""
+    fn = "superpixel_flow"
+    img, min_size = _superpixels_gate(fn, img, step, compactness, iters, min_size)
+    flow = _segment_fit_gate(fn, flow, thresh, rounds, shape=img.shape)
+    dev = _device_of(img, flow)
+    img, flow = _on(dev, img, flow)
+    label, _, _, cnt = _superpixels_call(img, step, compactness, iters, min_size, False, True)
+    n_seg = int(cnt[5].item())
+    models, seg_counts, extra = _segment_fit_call(flow, label, n_seg, thresh, rounds, True, classes, counts)
+    return (label, models, seg_counts) + tuple(t for t in extra if t is not None)
+
+
 # ---------------------------------------------------------------------- point trajectories (csrc/tracks.hip)
 TRACK_STATES = ("free", "live", "left", "noflow", "noback", "inconsistent")
 TRACK_ADVANCE_COUNTS = ("live", "left", "noflow", "noback", "inconsistent", "not_live")
