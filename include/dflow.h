@@ -79,6 +79,7 @@
  *       dflow_track_flow            d_pos_a, d_pos_b 8; d_state_a, d_state_b, d_owner, d_out, d_counts 4
  *       dflow_superpixels           d_label, d_centers, d_slic, d_counts, d_sums, d_comp, d_size, d_final, d_scan 4; d_bgr 1
  *       dflow_segment_fit           d_acc 8; d_flow, d_label, d_models, d_seg_counts, d_out, d_counts 4; d_class 1
+ *       dflow_two_view              d_pose, d_state 8; d_flow, d_model, d_depth, d_err, d_counts 4; d_part, d_class 1
  *     A plane below its number returns DFLOW_EINVAL ("NAME is not N-byte aligned", the batch forms name the entry NAME[i]) before
  *     anything is launched, after the NULL checks and before the workspace is looked at (the batch forms of the sweeps check the
  *     one size of their workspaces before any per-pass pointer, as they always have).
@@ -940,6 +941,71 @@ int dflow_epipolar_fit(int32_t h, int32_t w, const float *d_flow, int32_t layout
         int32_t *d_hyp_counts /* scratch+output int32[3*n_hyp]: their inlier counts, 0 for a degenerate one */,
         int64_t *d_state     /* scratch+output int64[32], 8-byte aligned */,
         uint8_t *d_class     /* NULL or (h,w) */, float *d_residual /* NULL or (h,w) */,
+        int32_t *d_counts    /* NULL or int32[8] */, void *stream);
+
+/* Two-view reconstruction (DESIGN.md "Two-view reconstruction"): from the F^ that dflow_epipolar_fit leaves on the device and the
+ * camera's intrinsics, the rotation and the unit translation of the second camera, X2 = R X1 + t, a depth per pixel in units of
+ * the baseline |t| = 1, a reprojection error, and a class plane in which "behind a camera" marks what moves against the epipolar
+ * direction, the fit's blind spot.  This build's definition; the reference has no counterpart.  1 <= h, w <= 8192, n = h*w.
+ * d_flow, GOOD, xf, yf, the float32 targets tx, ty, P, s and step are dflow_epipolar_fit's, unchanged; its centre is called
+ * (cxF, cyF) = ((w-1)/2, (h-1)/2) here.  fx, fy (pixels, finite and > 0) and cx, cy (finite) are the pinhole camera of both
+ * frames.  d_model is float32[9], F^ in the fit's coordinates, read on the device.  d_part (NULL: every pixel) is (h,w) uint8: a
+ * pixel VOTES iff it is GOOD, y % step == 0 && x % step == 0 and, with d_part, its byte == 1 (the fit's inlier class).  All
+ * arithmetic is float64, one IEEE operation (+ - * / sqrt) per written operation; everything else is an integer.  The result
+ * depends on no order of arrival, and two calls give the same bytes.
+ *   A. ESSENTIAL MATRIX.  With F the float32 entries widened, a00 = s*fx, a02 = s*(cx - cxF), a11 = s*fy, a12 = s*(cy - cyF) (A =
+ *     [[a00,0,a02],[0,a11,a12],[0,0,1]] takes camera coordinates to the fit's): G = F A, G[i][0] = F[i][0]*a00, G[i][1] =
+ *     F[i][1]*a11, G[i][2] = (F[i][0]*a02 + F[i][1]*a12) + F[i][2]; E = A^T G, E[0][j] = a00*G[0][j], E[1][j] = a11*G[1][j],
+ *     E[2][j] = (a02*G[0][j] + a12*G[1][j]) + G[2][j].  x2^T E x1 = 0 for the camera coordinates below.
+ *   B. DECOMPOSITION.  M = E^T E, M[i][j] = M[j][i] = (E[0][i]*E[0][j] + E[1][i]*E[1][j]) + E[2][i]*E[2][j] for i <= j; V = I.
+ *     8 cyclic Jacobi sweeps (a fixed number and no tolerance: Jacobi converges quadratically, and nothing is tested), each over the
+ *     pairs (p,q) = (0,1), (0,2), (1,2) with r the third index: apq = M[p][q]; apq == 0 skips the pair; theta = (M[q][q] -
+ *     M[p][p]) / (2*apq); t = 1 / (|theta| + sqrt(theta*theta + 1)), negated if theta < 0 (a theta that overflowed gives t = 0,
+ *     the identity rotation); c = 1 / sqrt(t*t + 1), sn = t*c; M[p][p] = M[p][p] - t*apq, M[q][q] = M[q][q] + t*apq, M[p][q] =
+ *     M[q][p] = 0; with arp = M[r][p], arq = M[r][q]: M[r][p] = M[p][r] = c*arp - sn*arq, M[r][q] = M[q][r] = sn*arp + c*arq; for
+ *     k = 0..2 with vkp = V[k][p], vkq = V[k][q]: V[k][p] = c*vkp - sn*vkq, V[k][q] = sn*vkp + c*vkq.  The eigenpairs (M[i][i],
+ *     column i of V) are sorted by descending eigenvalue, ties to the smaller index (an insertion sort with a strict >): v1, v2,
+ *     v3.  det = (v1[0]*(v2[1]*v3[2] - v3[1]*v2[2]) - v2[0]*(v1[1]*v3[2] - v3[1]*v1[2])) + v3[0]*(v1[1]*v2[2] - v2[1]*v1[2]); det <
+ *     0 negates v3.  (E v)[i] = (E[i][0]*v[0] + E[i][1]*v[1]) + E[i][2]*v[2], a.b = (a[0]*b[0] + a[1]*b[1]) + a[2]*b[2], |a| =
+ *     sqrt(a.a).  w1 = E v1, sigma1 = |w1|, u1 = w1 / sigma1; w2 = E v2, g = w2.u1, w2[i] = w2[i] - g*u1[i], sigma2 = |w2|, u2 =
+ *     w2 / sigma2; u3 = u1 x u2 (u3[0] = u1[1]*u2[2] - u1[2]*u2[1], cyclic); sigma3 = |E v3|.  R_a = U W V^T and R_b = U W^T V^T
+ *     with W = [[0,-1,0],[1,0,0],[0,0,1]]: R_a[i][j] = (u2[i]*v1[j] - u1[i]*v2[j]) + u3[i]*v3[j], R_b[i][j] = (u1[i]*v2[j] -
+ *     u2[i]*v1[j]) + u3[i]*v3[j].  The candidates are 0: (R_a, +u3), 1: (R_a, -u3), 2: (R_b, +u3), 3: (R_b, -u3).
+ *     NO POSE: F^ all zeros; sigma1 not finite or not > 0; sigma2 not > 2^-20 * sigma1 (an F^ of rank 1); or, below, no vote.
+ *   C. VOTE.  x1 = (((double)xf - cx)/fx, ((double)yf - cy)/fy, 1), x2 = (((double)tx - cx)/fx, ((double)ty - cy)/fy, 1).  For a
+ *     candidate (R, t): r[i] = (R[i][0]*x1[0] + R[i][1]*x1[1]) + R[i][2]; c = r x x2, c0 = r1 - r2*x2[1], c1 = r2*x2[0] - r0, c2 =
+ *     r0*x2[1] - r1*x2[0]; d = (c0*c0 + c1*c1) + c2*c2; a = x2 x t, a0 = x2[1]*t2 - t1, a1 = t0 - x2[0]*t2, a2 = x2[0]*t1 -
+ *     x2[1]*t0; n1 = (a0*c0 + a1*c1) + a2*c2; b = r x t, b0 = r1*t2 - r2*t1, b1 = r2*t0 - r0*t2, b2 = r0*t1 - r1*t0; n2 = (b0*c0 +
+ *     b1*c1) + b2*c2.  The depths are Z1 = n1/d in camera 1 and Z2 = n2/d in camera 2 (Z2 x2 = Z1 r + t crossed with x2 and with
+ *     r); d = |r x x2|^2 is computed directly and not as |r|^2 |x2|^2 - (r.x2)^2, which cancels for a small parallax.  A voting
+ *     pixel gives the candidate its vote iff 0 < d < +Inf && n1 > 0 && n2 > 0: in front of both cameras, with no division.
+ *     (Negating t negates n1 and n2 exactly.)  Votes are integers in d_state[0..3].
+ *   D. SELECT.  The candidate with the most votes, ties to the smaller index; all votes zero: NO POSE.  d_pose float64[16] = {R
+ *     row-major [0..8], t [9..11], 1, sigma2/sigma1, sigma3/sigma1 [12..14], the candidate as a double [15]}; under NO POSE all
+ *     zeros with [15] = -1.
+ *   E. APPLY, every pixel whatever `step` and d_part are, each output optional (NULL to skip), with the winner's (R, t) and PARALLAX
+ *     = 0 < d < +Inf.  d_depth (h,w) float32: (float)(n1/d) at a good pixel with parallax (negative behind camera 1), else 0.
+ *     d_class (h,w) uint8: 0 not good; 1 parallax, n1 > 0 && n2 > 0; 2 parallax and not both; 3 good without parallax, and every
+ *     good pixel under NO POSE.  d_err (h,w) float32: -1 at a pixel that is not good; with Z1 = n1/d, Y[i] = Z1*r[i] + t[i]: at a
+ *     good pixel with parallax and Y[2] > 0, ex = ((fx*Y[0])/Y[2] + cx) - (double)tx, ey = ((fy*Y[1])/Y[2] + cy) - (double)ty,
+ *     (float)sqrt(ex*ex + ey*ey), the reprojection error in pixels; +Inf at any other good pixel.  d_counts int32[8], zeroed by the
+ *     call on the stream: {voting pixels, the winner's votes, the largest vote of the other three, the candidate (-1: none), pixels
+ *     of class 1, of class 2, of class 3, 0}; under NO POSE the two votes are 0.
+ * There is no d_ws: the scratch is d_state, int64[32], an output as well: [0..3] the votes, [4] the voting pixels, [5..7] the class
+ * totals, [8..30] the bits of the float64 R_a, R_b, u3, sigma2/sigma1, sigma3/sigma1 (zeros without candidates), [31] 1 when B
+ * gave candidates.
+ * DFLOW_EINVAL before anything is launched, checked in this order: a frame size outside [1,8192]; an unknown layout; fx, then fy,
+ * not finite or not > 0; cx, then cy, not finite; step outside [1,64]; any flag bit (there are none yet); a NULL d_flow, d_model,
+ * d_pose or d_state; d_pose or d_state not 8-byte aligned, a float or int32 plane not 4-byte aligned; an output or scratch plane
+ * equal to an input or to one listed before it.  4 launches and one or two memsets, whatever the planes hold.  Asynchronous on
+ * `stream`, allocates nothing, reads nothing back, can be captured into a graph (after dflow_epipolar_fit, on one stream). */
+int dflow_two_view(int32_t h, int32_t w, const float *d_flow, int32_t layout,
+        const float *d_model /* float32[9]: F^ as dflow_epipolar_fit leaves it */,
+        const uint8_t *d_part /* NULL or (h,w): a pixel votes iff its byte == 1 */,
+        double fx, double fy, double cx, double cy, int32_t step /* 1..64 */, uint32_t flags /* none yet */,
+        double *d_pose       /* float64[16] */,
+        int64_t *d_state     /* scratch+output int64[32], 8-byte aligned */,
+        float *d_depth       /* NULL or (h,w) */, uint8_t *d_class /* NULL or (h,w) */, float *d_err /* NULL or (h,w) */,
         int32_t *d_counts    /* NULL or int32[8] */, void *stream);
 
 /* Per-pixel confidence of a labelling (DESIGN.md "Label confidence"): how far the chosen label's local energy lies below the best

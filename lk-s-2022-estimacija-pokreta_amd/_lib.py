@@ -160,8 +160,13 @@ _SIGNATURES_SUPERPIXELS = {
     "dflow_superpixels": (C.c_int, [_i32, _i32, _vp, _i32, _i32, _i32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dflow_segment_fit": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _i32, _f32, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# The two-view reconstruction (csrc/two_view.hip): shared checks alone, its refusals pinned by tests/test_abi_two_view.py.
+_SIGNATURES_TWO_VIEW = {
+    "dflow_two_view": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp]),
+}
 SYMBOLS = (tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS) + tuple(_SIGNATURES_EPIPOLAR)
-           + tuple(_SIGNATURES_SUPERPIXELS))
+           + tuple(_SIGNATURES_SUPERPIXELS) + tuple(_SIGNATURES_TWO_VIEW))
 
 
 def build(force=False):
@@ -187,7 +192,8 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR, _SIGNATURES_SUPERPIXELS):
+        for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR, _SIGNATURES_SUPERPIXELS,
+                      _SIGNATURES_TWO_VIEW):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

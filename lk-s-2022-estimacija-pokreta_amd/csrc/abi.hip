@@ -32,6 +32,12 @@ int launch_superpixels(int H, int W, const uint8_t *bgr, int step, int compactne
 int launch_segment_fit(int H, int W, const float *flow, int layout, const int32_t *label, int n_seg, float thresh, int rounds,
                        float *models, int32_t *seg_counts, float *out, uint8_t *cls, int32_t *counts, int64_t *acc, hipStream_t s);
 
+// two_view.hip: the pose, depth, class and reprojection error of a flow field under its fundamental matrix, 4 launches whatever the
+// planes hold (arguments validated by the caller); part, depth, cls, err and counts may be NULL
+int launch_two_view(int H, int W, const float *flow, int layout, const float *model, const uint8_t *part, double fx, double fy, double cx,
+                    double cy, int step, double *pose, int64_t *state, float *depth, uint8_t *cls, float *err, int32_t *counts,
+                    hipStream_t s);
+
 static thread_local char g_err[512] = "";
 
 int dflow_set_error(int code, const char *fmt, ...)
@@ -1060,6 +1066,32 @@ int dflow_remove_small_segments_host(float *h_sparse, int32_t dim0, int32_t dim1
     if (!h_sparse) return dflow_set_error(DFLOW_EINVAL, "h_sparse is NULL");
     if (dim0 <= 0 || dim1 <= 0) return dflow_set_error(DFLOW_EINVAL, "field size %dx%d", dim0, dim1);
     return host_remove_small_segments(h_sparse, dim0, dim1, tresh, min_segment_size);
+}
+
+int dflow_two_view(int32_t h, int32_t w, const float *d_flow, int32_t layout, const float *d_model, const uint8_t *d_part, double fx,
+                   double fy, double cx, double cy, int32_t step, uint32_t flags, double *d_pose, int64_t *d_state, float *d_depth,
+                   uint8_t *d_class, float *d_err, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_layout(__func__, "layout", layout))) return rc;
+    if ((rc = check_finite_gt0(__func__, "fx", fx))) return rc;
+    if ((rc = check_finite_gt0(__func__, "fy", fy))) return rc;
+    if (!isfinite(cx)) return refuse_value(__func__, "cx", cx, "finite");
+    if (!isfinite(cy)) return refuse_value(__func__, "cy", cy, "finite");
+    if ((rc = check_int_range(__func__, "step", step, 1, 64))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_flow); CHECK_PTR(d_model); CHECK_PTR(d_pose); CHECK_PTR(d_state);
+    // the pose is float64, the votes are updated with 64-bit atomics
+    rc = check_aligned(__func__, {{"d_pose", d_pose, 8}, {"d_state", d_state, 8}, {"d_flow", d_flow, 4}, {"d_model", d_model, 4},
+                                  {"d_depth", d_depth, 4}, {"d_err", d_err, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the field, the model and the voters' plane are read in launches that follow the first writes
+    rc = check_distinct(__func__, {{"d_flow", d_flow}, {"d_model", d_model}, {"d_part", d_part}},
+                        {{"d_pose", d_pose}, {"d_state", d_state}, {"d_depth", d_depth}, {"d_class", d_class}, {"d_err", d_err},
+                         {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_two_view(h, w, d_flow, layout, d_model, d_part, fx, fy, cx, cy, step, d_pose, d_state, d_depth, d_class, d_err,
+                           d_counts, (hipStream_t)stream);
 }
 
 }  // extern "C"

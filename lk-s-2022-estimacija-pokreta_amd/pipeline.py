@@ -1209,6 +1209,80 @@ def epipolar_geometry(model, h, w):
     return dict(F=F, e1=e1, e2=e2, foe=foe)
 
 
+# ---------------------------------------------------------------------- two-view reconstruction (csrc/two_view.hip)
+TWO_VIEW_COUNTS = ("voters", "votes", "runner_up", "candidate", "front", "behind", "flat", "reserved")
+
+
+def _finite(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+
+
+def two_view_intrinsics(fn, H, W, focal, center):
+    """(fx, fy, cx, cy) as Python floats: focal a number or a pair, None = max(H, W), synth's camera; center a pair (cx, cy), None
+    = the frame's centre.  ValueError for anything else."""
+    if focal is None:
+        focal = float(max(H, W))
+    pair = tuple(focal) if isinstance(focal, (tuple, list)) else (focal, focal)
+    if len(pair) != 2 or not all(_finite(v) and v > 0 for v in pair):
+        raise ValueError("%s: focal must be a finite number > 0 or a pair of them, got %r" % (fn, focal))
+    if center is None:
+        center = ((W - 1) * 0.5, (H - 1) * 0.5)
+    if not (isinstance(center, (tuple, list)) and len(center) == 2 and all(_finite(v) for v in center)):
+        raise ValueError("%s: center must be a pair of finite numbers (cx, cy), got %r" % (fn, center))
+    return float(pair[0]), float(pair[1]), float(center[0]), float(center[1])
+
+
+def two_view(flow, model, focal=None, center=None, part=None, step=1, depth=False, classes=False, err=False, counts=False):
+    """The camera motion and the depths a flow field and its fundamental matrix imply (dflow_two_view, DESIGN.md "Two-view
+    reconstruction").  flow is (H,W,2) float32 [dy,dx] or (H,W,3) float32 [U,V,valid]; model the (3,3) or (9,) float32 F^ of
+    epipolar_fit, on the device or on the host (it is not read here); focal a number or a pair (fx, fy) in pixels, None =
+    max(H, W), synth's camera; center the principal point (cx, cy), None = the frame's centre; part an (H,W) uint8 plane, a
+    pixel votes iff its byte is 1 (epipolar_fit's classes), or None = every vector; step > 1 lets only every step-th row and
+    column vote.  Returns the float64[16] device tensor {R row-major, t, 1, sigma2/sigma1, sigma3/sigma1, candidate}, all zeros
+    with [15] = -1 when there is no pose (two_view_pose reads it on the host), or a tuple in the order (pose[, depth][,
+    classes][, err][, counts]): depth=True adds the (H,W) float32 depth in camera 1 in units of the baseline (0 without a
+    vector or without parallax), classes=True the (H,W) uint8 plane 0 no vector / 1 in front of both cameras / 2 behind one / 3
+    no parallax or no pose, err=True the (H,W) float32 reprojection error in pixels (-1 without a vector, +Inf where there is
+    none), counts=True the int32[8] device tensor TWO_VIEW_COUNTS.  Runs on torch's current stream and does not wait for it."""
+    fn = "two_view"
+    flow = _check(flow, fn, "flow", torch.float32, (None, None, (2, 3)))
+    H, W, _ = flow.shape
+    m = model if isinstance(model, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(model))
+    if m.dtype != torch.float32 or tuple(m.shape) not in ((3, 3), (9,)):
+        raise ValueError("%s: model must be float32 (3,3) or (9,), got %s %s" % (fn, tuple(m.shape), m.dtype))
+    if part is not None:
+        part = _check(part, fn, "part", torch.uint8, (H, W))
+    fx, fy, cx, cy = two_view_intrinsics(fn, H, W, focal, center)
+    step = _int_in(fn, "step", step, 1, 64)
+    given = [flow, m] + ([part] if part is not None else [])
+    dev = _device_of(*given)
+    ts = _on(dev, *given)
+    flow, m, part = ts[0], ts[1], ts[2] if part is not None else None
+    pose = torch.empty(16, dtype=torch.float64, device=dev)
+    state = torch.empty(32, dtype=torch.int64, device=dev)
+    extra = [_out(depth, (H, W), torch.float32, dev), _out(classes, (H, W), torch.uint8, dev), _out(err, (H, W), torch.float32, dev),
+             _out(counts, 8, torch.int32, dev)]
+    _lib.call("dflow_two_view", H, W, flow.data_ptr(), _layout(flow), m.data_ptr(), _ptr(part), fx, fy, cx, cy, step, 0, pose.data_ptr(),
+              state.data_ptr(), _ptr(extra[0]), _ptr(extra[1]), _ptr(extra[2]), _ptr(extra[3]), _lib.stream(dev))
+    ret = tuple(t for t in [pose] + extra if t is not None)
+    return ret if len(ret) > 1 else ret[0]
+
+
+def two_view_pose(pose):
+    """What the 16 numbers of two_view mean, in host float64, after the caller has read them.  Returns a dict: R (3,3), t (3,),
+    angle_deg and axis, the rotation's angle in [0, 180] and its unit axis (None for no rotation), singular (3,), the singular
+    values of the essential matrix over the largest, candidate (int, -1: no pose; then R and t are zeros)."""
+    p = np.asarray(pose, np.float64).reshape(-1)
+    if p.size != 16:
+        raise ValueError("two_view_pose: pose must hold 16 numbers, got %d" % p.size)
+    R, t = p[:9].reshape(3, 3).copy(), p[9:12].copy()
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sin2 = float(np.sqrt(v @ v))
+    cand = int(p[15])
+    angle = float(np.degrees(np.arctan2(0.5 * sin2, 0.5 * (np.trace(R) - 1.0)))) if cand >= 0 else 0.0
+    return dict(R=R, t=t, angle_deg=angle, axis=v / sin2 if cand >= 0 and sin2 > 0.0 else None, singular=p[12:15].copy(), candidate=cand)
+
+
 # ---------------------------------------------------------------------- superpixels and per-segment models (csrc/superpixels.hip)
 SUPERPIXEL_COUNTS = ("centres", "empty_centres", "components", "small", "pixels_merged", "n_seg", "largest", "reserved")
 SEGMENT_FIT_COUNTS = ("part", "agree", "with_model", "affine", "translation", "bad_label", "out_of_range", "reserved")

@@ -70,6 +70,10 @@ and before --prefilter / --epic, and writes epipolar.json in DIR with the per-pa
 counts}; with --motion homography a row also holds that fit's counts.  --epipolar-gate drops the vectors that disagree from the
 sparse field, every other vector bit for bit.  One line per pair gives the inlier share.  Without it nothing is launched that
 was not launched before.
+--pose FOCAL, with --epipolar, takes each pair's fit apart into the camera's motion (pipeline.two_view with the focal length FOCAL
+pixels, the principal point at the frame's centre and the fit's inliers as the voters, DESIGN.md "Two-view reconstruction"): a
+"pose" entry {R, t, angle_deg, axis, singular, candidate and the counts} in the pair's row of epipolar.json and depth_<pair>.npy,
+the (H,W) float32 depth in units of the baseline.  One line per pair.  Without it the JSON and the launches are what they were.
 --confidence T takes every pass's label margin after its sweeps (DiscreteFlow.confidence, DESIGN.md "Label confidence"; --conf-mode
 local|data and --conf-sep S as in "python bcd.py", default local and 1); the margin travels to rank 0 as a third channel of the
 pass's flow.  There every pair's checked sparse field is gated with the forward margin (pipeline.flow_gate, margin >= T), after
@@ -130,6 +134,8 @@ def parser():
     ap.add_argument("--epipolar", default=None, metavar="T",
                     help="also fit the epipolar geometry of each pair's checked sparse field (Sampson threshold T pixels); writes epipolar.json")
     ap.add_argument("--epipolar-gate", action="store_true", help="with --epipolar: drop the vectors that disagree from the sparse field")
+    ap.add_argument("--pose", default=None, metavar="FOCAL",
+                    help="with --epipolar: the camera's motion and the depths under the focal length FOCAL pixels; writes depth_NN.npy")
     mod("bcdstats").add_cli_options(ap, "--bcd-stats")
     mod("labelconf").add_cli_options(ap, with_threshold=True)
     ap.add_argument("--pyramid", type=int, default=1, metavar="L", help="coarse to fine with L levels (1: the plain pass)")
@@ -197,10 +203,13 @@ def motion_args(a):
 
 
 def epipolar_arg(a):
-    """--epipolar T -> T or None; exits with status 2 for a threshold that is not finite and > 0, or --epipolar-gate without it."""
+    """--epipolar T -> T or None; exits with status 2 for a threshold that is not finite and > 0, or --epipolar-gate or --pose
+    without it."""
     if a.epipolar is None:
         if a.epipolar_gate:
             parser().error("--epipolar-gate needs --epipolar")
+        if getattr(a, "pose", None) is not None:
+            parser().error("--pose needs --epipolar")
         return None
     try:
         thresh = float(a.epipolar)
@@ -211,17 +220,50 @@ def epipolar_arg(a):
     return thresh
 
 
+def pose_arg(a):
+    """--pose FOCAL -> FOCAL or None; exits with status 2 for a focal length that is not finite and > 0."""
+    if a.pose is None:
+        return None
+    try:
+        focal = float(a.pose)
+        if not (np.isfinite(focal) and focal > 0):
+            raise ValueError
+    except ValueError:
+        parser().error("--pose needs FOCAL (finite, > 0), got %r" % (a.pose,))
+    return focal
+
+
+def pose_pair(s, pair, sparse_dev, model, cls):
+    """--pose: the camera motion of one pair from its fit (model and classes still on the device), depth_<pair>.npy, the printed
+    line; returns the "pose" entry of the pair's row."""
+    a, pipeline = s.a, mod("pipeline")
+    pose, depth, counts = pipeline.two_view(sparse_dev, model, focal=a.pose, part=cls, depth=True, counts=True)
+    counts = dict(zip(pipeline.TWO_VIEW_COUNTS[:7], counts.cpu().tolist()))
+    info = pipeline.two_view_pose(pose.cpu().numpy())
+    np.save(os.path.join(a.out, "depth_%02d.npy" % pair), depth.cpu().numpy())
+    if info["candidate"] < 0:
+        print("pair %d: pose: none (%d voters)" % (pair, counts["voters"]))
+    else:
+        print("pair %d: pose: rotation %.4f deg, t (%s), %d of %d voters in front of both cameras"
+              % (pair, info["angle_deg"], " ".join("%.4f" % v for v in info["t"]), counts["votes"], counts["voters"]))
+    return dict(focal=a.pose, R=info["R"].tolist(), t=info["t"].tolist(), angle_deg=info["angle_deg"],
+                axis=None if info["axis"] is None else info["axis"].tolist(), singular=info["singular"].tolist(), **counts)
+
+
 def epipolar_pair(s, pair, sparse_dev):
     """--epipolar: the fit of one pair's checked sparse field, its row of epipolar.json and its printed line; returns the field,
     without the vectors that disagree under --epipolar-gate (the others keep their bits)."""
     import torch
     a, pipeline = s.a, mod("pipeline")
     model, cls, counts = pipeline.epipolar_fit(sparse_dev, thresh=a.epipolar, classes=True, counts=True)
+    posed = pose_pair(s, pair, sparse_dev, model, cls) if a.pose is not None else None
     counts = dict(zip(pipeline.EPIPOLAR_FIT_COUNTS[:7], counts.cpu().tolist()))
     model = model.cpu().numpy()
     geo = pipeline.epipolar_geometry(model, s.H, s.W)
     s.epipolar_rows.append(dict(pair=pair, model=model.tolist(), F=geo["F"].tolist(), e1=geo["e1"].tolist(), e2=geo["e2"].tolist(),
                                 foe=geo["foe"], **counts))
+    if posed is not None:
+        s.epipolar_rows[-1]["pose"] = posed
     print("pair %d: epipolar geometry: %d of %d checked vectors within %g px (%.2f%%)%s"
           % (pair, counts["inliers"], counts["scored"], a.epipolar, 100.0 * counts["inliers"] / max(counts["scored"], 1),
              "" if counts["best_slot"] >= 0 else "; no model was found"))
@@ -585,6 +627,7 @@ def main(argv=None):
     a.mid_fill_rounds, a.mid_occl_thresh = midframe_args(a)
     a.motion, a.motion_thresh = motion_args(a)
     a.epipolar = epipolar_arg(a)
+    a.pose = pose_arg(a)
     if a.pyramid < 1 or (a.pyramid == 1 and (a.coarse_bcd_times is not None or a.fine_window is not None)):
         raise SystemExit("run_batch: --pyramid L needs L >= 1, and --coarse-bcd-times and --fine-window need L > 1")
     s = setup(a)

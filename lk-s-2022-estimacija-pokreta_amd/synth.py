@@ -168,14 +168,9 @@ def pair_seed(pair_idx, backward):
     return 1000 * int(pair_idx) + int(backward)
 
 
-def rigid_flow(H, W, seed, t, rot, objects=()):
-    """The exact flow of a pinhole camera that moves through a rigid scene, which the smooth warps of make_pair are not: they
-    obey no epipolar geometry.  The camera has focal length max(H, W) pixels and its principal point at the frame's centre; the
-    scene is a smooth depth map Z(x, y) in [4.5, 12.5] drawn from `seed`; the point seen at pixel (x, y) is X = Z K^-1 (x, y, 1),
-    the second camera sees it at K (R X + t), R the rotation by the axis-angle vector `rot` (radians), t in the units of Z.
-    objects: rectangles (y0, x0, y1, x1, du, dv) whose pixels carry the extra motion (du, dv) pixels on top of the scene's.
-    Returns (flow, mask): (H,W,3) float64 [U, V, 1] and the (H,W) bool mask of the rectangles.  t = (0, 0, tz) and rot = 0 put
-    the epipole (the focus of expansion) at ((W-1)/2, (H-1)/2); t = (tx, 0, 0) puts it at infinity."""
+def rigid_depth(H, W, seed):
+    """The scene of rigid_flow(H, W, seed, ...), from the same random draws: (Z, K), the (H,W) float64 depth map in camera 1 and
+    the camera K = (f, f, cx, cy), focal length max(H, W) pixels, principal point the frame's centre."""
     rng = np.random.default_rng(seed + 104729)
     f, cx, cy = float(max(H, W)), (W - 1) * 0.5, (H - 1) * 0.5
     yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
@@ -184,6 +179,19 @@ def rigid_flow(H, W, seed, t, rot, objects=()):
         fx, fy = rng.uniform(0.5, 2.0, 2)
         p0, p1 = rng.uniform(0, 2 * np.pi, 2)
         Z = Z + amp * np.sin(2 * np.pi * fx * xx / W + p0) * np.cos(2 * np.pi * fy * yy / H + p1)
+    return Z, (f, f, cx, cy)
+
+
+def rigid_flow(H, W, seed, t, rot, objects=()):
+    """The exact flow of a pinhole camera that moves through a rigid scene, which the smooth warps of make_pair are not: they
+    obey no epipolar geometry.  The camera has focal length max(H, W) pixels and its principal point at the frame's centre; the
+    scene is a smooth depth map Z(x, y) in [4.5, 12.5] drawn from `seed`; the point seen at pixel (x, y) is X = Z K^-1 (x, y, 1),
+    the second camera sees it at K (R X + t), R the rotation by the axis-angle vector `rot` (radians), t in the units of Z.
+    objects: rectangles (y0, x0, y1, x1, du, dv) whose pixels carry the extra motion (du, dv) pixels on top of the scene's.
+    Returns (flow, mask): (H,W,3) float64 [U, V, 1] and the (H,W) bool mask of the rectangles.  t = (0, 0, tz) and rot = 0 put
+    the epipole (the focus of expansion) at ((W-1)/2, (H-1)/2); t = (tx, 0, 0) puts it at infinity."""
+    Z, (f, _, cx, cy) = rigid_depth(H, W, seed)
+    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
     rx, ry, rz = (float(v) for v in rot)
     th = (rx * rx + ry * ry + rz * rz) ** 0.5
     K = np.array([[0.0, -rz, ry], [rz, 0.0, -rx], [-ry, rx, 0.0]])
