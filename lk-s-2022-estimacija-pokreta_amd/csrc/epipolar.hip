@@ -6,8 +6,8 @@
 //   ep_hyp_kernel     one sample per lane: the Philox draws of its 7 points, the float64 elimination with complete pivoting of
 //                     the 7 x 9 system (private memory: the pivots index it), the cubic det(alpha F1 + F2), its roots over the whole
 //                     projective line by critical points and 60 bisections each, up to three float32 models into the slots
-//                     3j .. 3j+2 of d_models; a slot without a model stores zeros and marks its count EP_DEGENERATE
-//   ep_score_kernel   the hot one.  A block stages a chunk of EP_CHUNK scored pixels into LDS in normalised coordinates, two
+//                     3j .. 3j+2 of d_models; a slot without a model stores zeros and marks its count FIT_DEGENERATE
+//   ep_score_kernel   the hot one.  A block stages a chunk of FIT_CHUNK scored pixels into LDS in normalised coordinates, two
 //                     pixels per pair of 16-byte words, the pixels that take no part dropped; a lane owns a slot with its nine
 //                     coefficients in registers and walks the chunk with broadcast 16-byte LDS reads, two pixels per packed
 //                     float32 instruction; the count stays in the lane's register and ends in one integer atomic per lane.
@@ -18,21 +18,15 @@
 //   ep_finish_kernel  one lane: d_counts is written from d_state
 // 3 + 4 (lo_rounds + 1) launches and one or two memsets whatever the field holds.  Every count is an integer (exact in any order
 // of arrival); every float32 and float64 chain is one IEEE operation per written operation (-ffp-contract=off).
-// fit_common.h holds what is shared with motion_fit.hip as it stood there.  The chunk staging, the best key and the select step
-// are restated here and not shared: in motion_fit.hip they are woven into kernels that store pixel coordinates, index
-// hypotheses by j and fall back to the identity, and taking them out would have changed those kernels.
-#include <math.h>
+// fit_common.h holds what this fit shares with motion_fit.hip: the arguments, the draw of a sample point, the chunk staging, the
+// best key with its offer, its adoption and its counts, and the classes.  The coordinates a chunk holds, the slots of a sample,
+// the solve, the score loop and the model a fit without a winner falls back to (all zeros) are this file's.
 #include "fit_common.h"
 
-#define EP_THREADS 256
-#define EP_CHUNK 2048                                 // scored pixels a block stages: 32 KiB of LDS, four blocks per CU
-#define EP_ATTEMPTS 16
-#define EP_PIVOT_MIN 9.094947017729282e-13            // 2^-40, in coordinates scaled to [-1/2, 1/2]
+#define EP_STRIDE 8                                   // counter slots per round and sample: a slot per point, one to spare
 #define EP_BISECTIONS 60
-#define EP_DEGENERATE INT32_MIN
-#define EP_COUNTS 8
 // d_state: int64[32]
-enum { EP_S_BEST = 0, EP_S_SCORED, EP_S_DEGEN, EP_S_DEGEN0, EP_S_FINAL };
+enum { EP_S_BEST = FIT_S_BEST, EP_S_SCORED, EP_S_DEGEN, EP_S_DEGEN0, EP_S_FINAL };
 
 struct EpArgs {
     MfArgs f;                                         // n_hyp: samples; the slots are 3 n_hyp
@@ -136,7 +130,7 @@ __device__ static void ep_solve(double (&A)[7][9], float (&out)[3][9], bool (&ok
                 const double v = fabs(A[r][k]);
                 if (v > best) { best = v; pr = r; pk = k; }
             }
-        if (!(best >= EP_PIVOT_MIN)) return;
+        if (!(best >= FIT_PIVOT_MIN)) return;
         if (pr != c)
             for (int k = 0; k < 9; k++) { const double t = A[c][k]; A[c][k] = A[pr][k]; A[pr][k] = t; }
         if (pk != c) {
@@ -177,9 +171,9 @@ __device__ static void ep_solve(double (&A)[7][9], float (&out)[3][9], bool (&ok
     }
 }
 
-__global__ void __launch_bounds__(EP_THREADS) ep_hyp_kernel(EpArgs a, int round)
+__global__ void __launch_bounds__(FIT_THREADS) ep_hyp_kernel(EpArgs a, int round)
 {
-    const int j = blockIdx.x * EP_THREADS + threadIdx.x;
+    const int j = blockIdx.x * FIT_THREADS + threadIdx.x;
     if (j >= a.f.n_hyp) return;
     float cur[9];
     mf_load_model(a.f.cur, cur);
@@ -187,32 +181,19 @@ __global__ void __launch_bounds__(EP_THREADS) ep_hyp_kernel(EpArgs a, int round)
     double A[7][9];
     bool found_all = true;
     for (int k = 0; k < 7 && found_all; k++) {
-        bool found = false;
-        for (int att = 0; att < EP_ATTEMPTS && !found; att++) {
-            uint32_t u, u1;
-            philox4x32_10((uint32_t)j, (uint32_t)((round * 8 + k) * EP_ATTEMPTS + att), a.f.k0, a.f.k1, u, u1);
-            const uint32_t i = (uint32_t)(((uint64_t)u * (uint64_t)a.f.n) >> 32);
-            float U, V;
-            if (!mf_part(a.f, i, U, V)) continue;
-            bool dup = false;
-            for (int q = 0; q < k; q++) dup |= idx[q] == i;
-            if (dup) continue;
-            const float xf = (float)(int)(i % (uint32_t)a.f.w), yf = (float)(int)(i / (uint32_t)a.f.w);
-            if (round > 0) {
-                float ca, cb, cp, cq;
-                ep_coords(a, xf, yf, U, V, ca, cb, cp, cq);
-                if (!ep_inlier(cur, ca, cb, cp, cq, a.t2)) continue;
-            }
-            const float tx = xf + U, ty = yf + V;
-            const double da = ((double)xf - a.f.cx) * a.f.s, db = ((double)yf - a.f.cy) * a.f.s;
-            const double dp = ((double)tx - a.f.cx) * a.f.s, dq = ((double)ty - a.f.cy) * a.f.s;
-            double *row = A[k];
-            row[0] = dp * da; row[1] = dp * db; row[2] = dp; row[3] = dq * da; row[4] = dq * db; row[5] = dq;
-            row[6] = da; row[7] = db; row[8] = 1.0;
-            idx[k] = i;
-            found = true;
-        }
-        found_all = found;
+        float xf, yf, U, V;
+        found_all = fit_draw<EP_STRIDE>(a.f, j, round, k, idx, xf, yf, U, V, [&](float x, float y, float u, float v) {
+            float ca, cb, cp, cq;
+            ep_coords(a, x, y, u, v, ca, cb, cp, cq);
+            return ep_inlier(cur, ca, cb, cp, cq, a.t2);
+        });
+        if (!found_all) break;
+        const float tx = xf + U, ty = yf + V;
+        const double da = ((double)xf - a.f.cx) * a.f.s, db = ((double)yf - a.f.cy) * a.f.s;
+        const double dp = ((double)tx - a.f.cx) * a.f.s, dq = ((double)ty - a.f.cy) * a.f.s;
+        double *row = A[k];
+        row[0] = dp * da; row[1] = dp * db; row[2] = dp; row[3] = dq * da; row[4] = dq * db; row[5] = dq;
+        row[6] = da; row[7] = db; row[8] = 1.0;
     }
     float out[3][9];
     bool ok[3] = {false, false, false};
@@ -220,44 +201,20 @@ __global__ void __launch_bounds__(EP_THREADS) ep_hyp_kernel(EpArgs a, int round)
     for (int m = 0; m < 3; m++) {
         const size_t slot = (size_t)j * 3 + m;
         for (int k = 0; k < 9; k++) a.f.models[slot * 9 + k] = ok[m] ? out[m][k] : 0.0f;
-        a.f.hyp_counts[slot] = ok[m] ? 0 : EP_DEGENERATE;
+        a.f.hyp_counts[slot] = ok[m] ? 0 : FIT_DEGENERATE;
     }
 }
 
 // Two pixels per instruction: the chunk lies in LDS as pairs, (a0, a1, b0, b1) and (p0, p1, q0, q1), so that the loads land in
 // the register pairs v_pk_mul_f32 / v_pk_add_f32 take; each half is the IEEE operation of the scalar expression.
-typedef float ep_f2 __attribute__((ext_vector_type(2)));
-
-__global__ void __launch_bounds__(EP_THREADS) ep_score_kernel(EpArgs a)
+__global__ void __launch_bounds__(FIT_THREADS) ep_score_kernel(EpArgs a)
 {
-    __shared__ float4 s_px[EP_CHUNK];
+    __shared__ float4 s_px[FIT_CHUNK];
     __shared__ int s_n;
-    float *px = reinterpret_cast<float *>(s_px);
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)EP_CHUNK;
-    for (int t = threadIdx.x; t < EP_CHUNK; t += EP_THREADS) {
-        const uint32_t c = base + (uint32_t)t;
-        if (c >= a.f.ns) break;
-        int x, y;
-        const uint32_t i = mf_grid_pixel(a.f, c, x, y);
-        float U, V;
-        if (mf_part(a.f, i, U, V)) {
-            float ca, cb, cp, cq;
-            ep_coords(a, (float)x, (float)y, U, V, ca, cb, cp, cq);
-            const int slot = atomicAdd(&s_n, 1);                      // at most EP_CHUNK grid points per block
-            float *q = px + (slot >> 1) * 8 + (slot & 1);
-            q[0] = ca; q[2] = cb; q[4] = cp; q[6] = cq;
-        }
-    }
-    __syncthreads();
-    const int np = s_n;
-    if (threadIdx.x == 0 && (np & 1)) {                               // the other half of the last pair: a NaN target is no inlier
-        float *q = px + (np >> 1) * 8 + 1;
-        q[0] = 0.0f; q[2] = 0.0f; q[4] = __builtin_nanf(""); q[6] = __builtin_nanf("");
-    }
-    __syncthreads();
-    const int j = blockIdx.y * EP_THREADS + threadIdx.x;
+    const int np = fit_stage_chunk<FIT_CHUNK, FIT_THREADS>(a.f, s_px, s_n, [&](int x, int y, float U, float V, float (&v)[4]) {
+        ep_coords(a, (float)x, (float)y, U, V, v[0], v[1], v[2], v[3]);
+    });
+    const int j = blockIdx.y * FIT_THREADS + threadIdx.x;
     const bool live = j < a.slots && a.f.hyp_counts[j] >= 0;      // the sign does not change while counts are added
     if (!__any(live)) return;                                     // the wave's slots are all degenerate; no barrier follows
     float m[9];
@@ -269,28 +226,22 @@ __global__ void __launch_bounds__(EP_THREADS) ep_score_kernel(EpArgs a)
 #pragma unroll 4
     for (int k = 0; k < (np + 1) >> 1; k++) {
         const float4 v0 = s_px[2 * k], v1 = s_px[2 * k + 1];      // every lane the same address: a broadcast
-        const ep_f2 ca = {v0.x, v0.y}, cb = {v0.z, v0.w}, cp = {v1.x, v1.y}, cq = {v1.z, v1.w};
-        const ep_f2 l0 = (m[0] * ca + m[1] * cb) + m[2], l1 = (m[3] * ca + m[4] * cb) + m[5], l2 = (m[6] * ca + m[7] * cb) + m[8];
-        const ep_f2 e = (cp * l0 + cq * l1) + l2;
-        const ep_f2 m0 = (m[0] * cp + m[3] * cq) + m[6], m1 = (m[1] * cp + m[4] * cq) + m[7];
-        const ep_f2 den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
-        const ep_f2 ee = e * e, rhs = t2 * den;
+        const dflow_f2 ca = {v0.x, v0.y}, cb = {v0.z, v0.w}, cp = {v1.x, v1.y}, cq = {v1.z, v1.w};
+        const dflow_f2 l0 = (m[0] * ca + m[1] * cb) + m[2], l1 = (m[3] * ca + m[4] * cb) + m[5], l2 = (m[6] * ca + m[7] * cb) + m[8];
+        const dflow_f2 e = (cp * l0 + cq * l1) + l2;
+        const dflow_f2 m0 = (m[0] * cp + m[3] * cq) + m[6], m1 = (m[1] * cp + m[4] * cq) + m[7];
+        const dflow_f2 den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+        const dflow_f2 ee = e * e, rhs = t2 * den;
         cnt += (ep_pos_finite(den.x) && ee.x <= rhs.x ? 1 : 0) + (ep_pos_finite(den.y) && ee.y <= rhs.y ? 1 : 0);
     }
     if (live && cnt) atomicAdd(&a.f.hyp_counts[j], cnt);
 }
 
-__global__ void __launch_bounds__(EP_THREADS) ep_best_kernel(EpArgs a, int round)
+__global__ void __launch_bounds__(FIT_THREADS) ep_best_kernel(EpArgs a, int round)
 {
-    const int j = blockIdx.x * EP_THREADS + threadIdx.x;
-    bool degenerate = false;
-    if (j < a.slots) {
-        const int32_t c = a.f.hyp_counts[j];
-        if (c < 0) { a.f.hyp_counts[j] = 0; degenerate = true; }
-        else atomicMax(&a.f.state[EP_S_BEST], ((unsigned long long)(uint32_t)c << 32) | (0xFFFFFFFFu - (uint32_t)(round * 65536 + j)));
-    }
-    mf_block_add(degenerate, &a.f.state[EP_S_DEGEN]);
-    mf_block_add(degenerate && round == 0, &a.f.state[EP_S_DEGEN0]);
+    const bool degenerate = fit_offer(a.f, blockIdx.x * FIT_THREADS + threadIdx.x, a.slots, round);
+    fit_block_add({fit_wave_count(degenerate)}, &a.f.state[EP_S_DEGEN]);
+    fit_block_add({fit_wave_count(degenerate && round == 0)}, &a.f.state[EP_S_DEGEN0]);
 }
 
 __global__ void ep_select_kernel(EpArgs a, int round)
@@ -301,14 +252,12 @@ __global__ void ep_select_kernel(EpArgs a, int round)
         for (int k = 0; k < 9; k++) a.f.cur[k] = 0.0f;
         return;
     }
-    const uint32_t id = 0xFFFFFFFFu - (uint32_t)key;
-    if ((int)(id >> 16) == round)
-        for (int k = 0; k < 9; k++) a.f.cur[k] = a.f.models[(size_t)(id & 0xFFFFu) * 9 + k];
+    fit_adopt(a.f, key, round);
 }
 
-__global__ void __launch_bounds__(EP_THREADS) ep_apply_kernel(EpArgs a, uint8_t *__restrict__ cls, float *__restrict__ residual)
+__global__ void __launch_bounds__(FIT_THREADS) ep_apply_kernel(EpArgs a, uint8_t *__restrict__ cls, float *__restrict__ residual)
 {
-    const uint32_t i = blockIdx.x * EP_THREADS + threadIdx.x;
+    const uint32_t i = blockIdx.x * FIT_THREADS + threadIdx.x;
     bool scored = false, scored_in = false;
     if (i < a.f.n) {
         float m[9];
@@ -321,26 +270,19 @@ __global__ void __launch_bounds__(EP_THREADS) ep_apply_kernel(EpArgs a, uint8_t 
         ep_coords(a, (float)x, (float)y, U, V, ca, cb, cp, cq);
         ep_terms(m, ca, cb, cp, cq, ee, den);
         const bool in = good && ep_pos_finite(den) && ee <= a.t2 * den;
-        if (cls) cls[i] = (uint8_t)(!good ? 0 : excluded ? 3 : in ? 1 : 2);
+        if (cls) cls[i] = fit_class(good, excluded, in);
         if (residual) residual[i] = !good ? -1.0f : ep_pos_finite(den) ? sqrtf(ee / den) * a.Pf : INFINITY;
-        scored = good && !excluded && y % a.f.step == 0 && x % a.f.step == 0;
+        scored = fit_scored(a.f, good, excluded, x, y);
         scored_in = scored && in;
     }
-    mf_block_add(scored, &a.f.state[EP_S_SCORED]);
-    mf_block_add(scored_in, &a.f.state[EP_S_FINAL]);
+    fit_block_add({fit_wave_count(scored)}, &a.f.state[EP_S_SCORED]);
+    fit_block_add({fit_wave_count(scored_in)}, &a.f.state[EP_S_FINAL]);
 }
 
 __global__ void ep_finish_kernel(EpArgs a, int32_t *__restrict__ counts)
 {
     if (blockIdx.x || threadIdx.x || !counts) return;
-    const unsigned long long key = a.f.state[EP_S_BEST];
-    const uint32_t id = 0xFFFFFFFFu - (uint32_t)key;
-    counts[0] = (int32_t)a.f.state[EP_S_SCORED];
-    counts[1] = (int32_t)a.f.state[EP_S_FINAL];
-    counts[2] = (int32_t)a.f.state[EP_S_DEGEN];
-    counts[3] = key ? (int32_t)(id >> 16) : -1;
-    counts[4] = key ? (int32_t)(id & 0xFFFFu) : -1;
-    counts[5] = (int32_t)(key >> 32);
+    fit_counts(a.f, counts, EP_S_SCORED, EP_S_FINAL, EP_S_DEGEN);
     counts[6] = (int32_t)((1000ll * ((long long)a.slots - (long long)a.f.state[EP_S_DEGEN0])) / (long long)a.f.n_hyp);
     counts[7] = 0;
 }
@@ -350,32 +292,26 @@ int launch_epipolar_fit(int H, int W, const float *flow, int layout, const uint8
                         float *residual, int32_t *counts, hipStream_t s)
 {
     EpArgs a;
-    a.f.h = H; a.f.w = W; a.f.layout = layout; a.f.model = 0; a.f.n_hyp = n_hyp; a.f.step = step; a.f.ws = (W + step - 1) / step;
-    a.f.n = (uint32_t)H * (uint32_t)W; a.f.ns = (uint32_t)((H + step - 1) / step) * (uint32_t)a.f.ws;
-    a.f.k0 = (uint32_t)seed; a.f.k1 = (uint32_t)(seed >> 32); a.f.thresh = thresh;
-    double P = 1.0;
-    while (P < (double)(H > W ? H : W)) P *= 2.0;
-    a.f.cx = (double)(W - 1) * 0.5; a.f.cy = (double)(H - 1) * 0.5; a.f.s = 1.0 / P; a.f.inv = P;
-    a.f.flow = flow; a.f.exclude = exclude; a.f.cur = d_model; a.f.models = models; a.f.hyp_counts = hyp_counts;
-    a.f.state = reinterpret_cast<unsigned long long *>(state);
+    a.f = fit_frame(H, W, layout, step, flow, state);
+    a.f.n_hyp = n_hyp; a.f.k0 = (uint32_t)seed; a.f.k1 = (uint32_t)(seed >> 32); a.f.thresh = thresh;
+    a.f.exclude = exclude; a.f.cur = d_model; a.f.models = models; a.f.hyp_counts = hyp_counts;
     a.slots = 3 * n_hyp;
-    a.cxf = (float)a.f.cx; a.cyf = (float)a.f.cy; a.sf = (float)a.f.s; a.Pf = (float)P;       // half-integers and powers of two: exact
+    a.cxf = (float)a.f.cx; a.cyf = (float)a.f.cy; a.sf = (float)a.f.s; a.Pf = (float)a.f.inv;  // half-integers and powers of two: exact
     const float th = thresh * a.sf;
     a.t2 = th * th;
-    DFLOW_HIP(hipMemsetAsync(state, 0, 32 * sizeof(int64_t), s));
-    if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, EP_COUNTS * sizeof(int32_t), s));
-    const unsigned hyp_blocks = (unsigned)((n_hyp + EP_THREADS - 1) / EP_THREADS);
-    const unsigned slot_blocks = (unsigned)((a.slots + EP_THREADS - 1) / EP_THREADS);
-    const unsigned chunks = (a.f.ns + EP_CHUNK - 1) / EP_CHUNK;
+    if (int rc = fit_clear(state, counts, s)) return rc;
+    const unsigned hyp_blocks = (unsigned)((n_hyp + FIT_THREADS - 1) / FIT_THREADS);
+    const unsigned slot_blocks = (unsigned)((a.slots + FIT_THREADS - 1) / FIT_THREADS);
+    const unsigned chunks = (a.f.ns + FIT_CHUNK - 1) / FIT_CHUNK;
     // no model until a round has a winner: round 0 does not look at it, the rounds after it sample its inliers
     hipLaunchKernelGGL(ep_select_kernel, dim3(1), dim3(64), 0, s, a, -1);
     for (int r = 0; r <= lo_rounds; r++) {
-        hipLaunchKernelGGL(ep_hyp_kernel, dim3(hyp_blocks), dim3(EP_THREADS), 0, s, a, r);
-        hipLaunchKernelGGL(ep_score_kernel, dim3(chunks, slot_blocks), dim3(EP_THREADS), 0, s, a);
-        hipLaunchKernelGGL(ep_best_kernel, dim3(slot_blocks), dim3(EP_THREADS), 0, s, a, r);
+        hipLaunchKernelGGL(ep_hyp_kernel, dim3(hyp_blocks), dim3(FIT_THREADS), 0, s, a, r);
+        hipLaunchKernelGGL(ep_score_kernel, dim3(chunks, slot_blocks), dim3(FIT_THREADS), 0, s, a);
+        hipLaunchKernelGGL(ep_best_kernel, dim3(slot_blocks), dim3(FIT_THREADS), 0, s, a, r);
         hipLaunchKernelGGL(ep_select_kernel, dim3(1), dim3(64), 0, s, a, r);
     }
-    hipLaunchKernelGGL(ep_apply_kernel, dim3((a.f.n + EP_THREADS - 1) / EP_THREADS), dim3(EP_THREADS), 0, s, a, cls, residual);
+    hipLaunchKernelGGL(ep_apply_kernel, dim3((a.f.n + FIT_THREADS - 1) / FIT_THREADS), dim3(FIT_THREADS), 0, s, a, cls, residual);
     hipLaunchKernelGGL(ep_finish_kernel, dim3(1), dim3(64), 0, s, a, counts);
     return dflow_check_launch("epipolar fit kernels");
 }

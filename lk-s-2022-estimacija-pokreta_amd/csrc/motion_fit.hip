@@ -4,8 +4,8 @@
 //
 //   mf_hyp_kernel     one hypothesis per lane: the Philox draws of its 3 or 4 points, the float64 minimal solve (Gaussian
 //                     elimination with partial pivoting in centred, power-of-two scaled coordinates), the float32 model into
-//                     d_models; a degenerate one stores the identity and marks its count MF_DEGENERATE
-//   mf_score_kernel   the hot one.  A block stages a chunk of MF_CHUNK scored pixels into LDS, two pixels per pair of 16-byte
+//                     d_models; a degenerate one stores the identity and marks its count FIT_DEGENERATE
+//   mf_score_kernel   the hot one.  A block stages a chunk of FIT_CHUNK scored pixels into LDS, two pixels per pair of 16-byte
 //                     words, the pixels that take no part dropped; a lane owns a hypothesis with its coefficients in registers
 //                     and walks the chunk with broadcast 16-byte LDS reads, two pixels per packed float32 instruction; the count
 //                     stays in the lane's register and ends in one integer atomic per lane.  Grid = pixel chunks x groups of 256
@@ -19,22 +19,12 @@
 // 3 + 4 (lo_rounds + 1) + 4 polish launches and one or two memsets whatever the field holds.  Every count and sum is an integer
 // (exact in any order of arrival); every float32 and float64 chain is one IEEE operation per written operation
 // (-ffp-contract=off).
-#include <math.h>
-#include "plane_ops.h"
-#include "philox.h"
-#include "fit_common.h"      // MfArgs, mf_part, mf_grid_pixel, mf_load_model, mf_block_add: shared with epipolar.hip
+#include "fit_common.h"      // what every fit shares: the arguments, the draw, the chunk, the best key, the classes, step E
 
-#define MF_THREADS 256
-#define MF_CHUNK 2048                                 // scored pixels a block stages: 32 KiB of LDS, four blocks per CU
-#define MF_ATTEMPTS 16
-#define MF_PIVOT_MIN 9.094947017729282e-13            // 2^-40, in coordinates scaled to [-1/2, 1/2]
-#define MF_DEGENERATE INT32_MIN
-#define MF_POLISH_RANGE 32768.0f
-#define MF_COUNTS 8
+#define MF_STRIDE 4                                   // counter slots per round and hypothesis: a slot per point
 // d_state: int64[32]
-enum { MF_S_BEST = 0, MF_S_SCORED, MF_S_DEGEN, MF_S_CUR, MF_S_ACCEPTED, MF_S_SKIPPED, MF_S_CAND, MF_S_FINAL, MF_S_SUMS /* 8..19 */,
+enum { MF_S_BEST = FIT_S_BEST, MF_S_SCORED, MF_S_DEGEN, MF_S_CUR, MF_S_ACCEPTED, MF_S_SKIPPED, MF_S_CAND, MF_S_FINAL, MF_S_SUMS /* 8..19 */,
        MF_S_CAND_MODEL = 20 /* float32[9] in 20..24 */, MF_S_CAND_OK = 25 };
-#define MF_NSUMS 12
 
 // INLIER (include/dflow.h, B and D)
 __device__ __forceinline__ static bool mf_inlier(const float (&m)[9], float xf, float yf, float tx, float ty, float thresh)
@@ -51,7 +41,7 @@ __device__ static inline void mf_identity(float (&m)[9])
 }
 
 // Gaussian elimination with partial pivoting of the N x (N + R) system A, the first largest pivot winning, then the back
-// substitutions: x[r] solves right-hand side r.  false: a pivot below MF_PIVOT_MIN (or a NaN).
+// substitutions: x[r] solves right-hand side r.  false: a pivot below FIT_PIVOT_MIN (or a NaN).
 template <int N, int R> __device__ static bool mf_gauss(double (&A)[N][N + R], double (&x)[R][N])
 {
     for (int c = 0; c < N; c++) {
@@ -61,7 +51,7 @@ template <int N, int R> __device__ static bool mf_gauss(double (&A)[N][N + R], d
             const double v = fabs(A[r][c]);
             if (v > best) { best = v; piv = r; }
         }
-        if (!(best >= MF_PIVOT_MIN)) return false;
+        if (!(best >= FIT_PIVOT_MIN)) return false;
         if (piv != c)
             for (int k = 0; k < N + R; k++) { const double t = A[c][k]; A[c][k] = A[piv][k]; A[piv][k] = t; }
         for (int r = c + 1; r < N; r++) {
@@ -78,9 +68,9 @@ template <int N, int R> __device__ static bool mf_gauss(double (&A)[N][N + R], d
     return true;
 }
 
-__global__ void __launch_bounds__(MF_THREADS) mf_hyp_kernel(MfArgs a, int round)
+__global__ void __launch_bounds__(FIT_THREADS) mf_hyp_kernel(MfArgs a, int round)
 {
-    const int j = blockIdx.x * MF_THREADS + threadIdx.x;
+    const int j = blockIdx.x * FIT_THREADS + threadIdx.x;
     if (j >= a.n_hyp) return;
     const int m = a.model == DFLOW_MOTION_HOMOGRAPHY ? 4 : 3;
     float cur[9];
@@ -89,23 +79,11 @@ __global__ void __launch_bounds__(MF_THREADS) mf_hyp_kernel(MfArgs a, int round)
     float sx[4], sy[4], tx[4], ty[4];
     bool ok = true;
     for (int k = 0; k < m && ok; k++) {
-        bool found = false;
-        for (int att = 0; att < MF_ATTEMPTS && !found; att++) {
-            uint32_t u, u1;
-            philox4x32_10((uint32_t)j, (uint32_t)((round * 4 + k) * MF_ATTEMPTS + att), a.k0, a.k1, u, u1);
-            const uint32_t i = (uint32_t)(((uint64_t)u * (uint64_t)a.n) >> 32);
-            float U, V;
-            if (!mf_part(a, i, U, V)) continue;
-            bool dup = false;
-            for (int q = 0; q < k; q++) dup |= idx[q] == i;
-            if (dup) continue;
-            const float xf = (float)(int)(i % (uint32_t)a.w), yf = (float)(int)(i / (uint32_t)a.w);
-            const float txx = xf + U, tyy = yf + V;
-            if (round > 0 && !mf_inlier(cur, xf, yf, txx, tyy, a.thresh)) continue;
-            idx[k] = i; sx[k] = xf; sy[k] = yf; tx[k] = txx; ty[k] = tyy;
-            found = true;
-        }
-        ok = found;
+        float U, V;
+        ok = fit_draw<MF_STRIDE>(a, j, round, k, idx, sx[k], sy[k], U, V, [&](float xf, float yf, float u, float v) {
+            return mf_inlier(cur, xf, yf, xf + u, yf + v, a.thresh);
+        });
+        if (ok) { tx[k] = sx[k] + U; ty[k] = sy[k] + V; }
     }
     double nm[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 1.0}};       // the model in normalised coordinates
     if (ok) {
@@ -153,42 +131,19 @@ __global__ void __launch_bounds__(MF_THREADS) mf_hyp_kernel(MfArgs a, int round)
     }
     if (!ok) mf_identity(mo);
     for (int k = 0; k < 9; k++) a.models[(size_t)j * 9 + k] = mo[k];
-    a.hyp_counts[j] = ok ? 0 : MF_DEGENERATE;
+    a.hyp_counts[j] = ok ? 0 : FIT_DEGENERATE;
 }
 
 // Two pixels per instruction: the chunk lies in LDS as pairs, (x0, x1, y0, y1) and (tx0, tx1, ty0, ty1), so that the loads land
 // in the register pairs v_pk_mul_f32 / v_pk_add_f32 take; each half is the IEEE operation of the scalar expression.
-typedef float mf_f2 __attribute__((ext_vector_type(2)));
-
-template <bool HOMOG> __global__ void __launch_bounds__(MF_THREADS) mf_score_kernel(MfArgs a)
+template <bool HOMOG> __global__ void __launch_bounds__(FIT_THREADS) mf_score_kernel(MfArgs a)
 {
-    __shared__ float4 s_px[MF_CHUNK];
+    __shared__ float4 s_px[FIT_CHUNK];
     __shared__ int s_n;
-    float *px = reinterpret_cast<float *>(s_px);
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)MF_CHUNK;
-    for (int t = threadIdx.x; t < MF_CHUNK; t += MF_THREADS) {
-        const uint32_t c = base + (uint32_t)t;
-        if (c >= a.ns) break;
-        int x, y;
-        const uint32_t i = mf_grid_pixel(a, c, x, y);
-        float U, V;
-        if (mf_part(a, i, U, V)) {
-            const float xf = (float)x, yf = (float)y;
-            const int slot = atomicAdd(&s_n, 1);                      // at most MF_CHUNK grid points per block
-            float *q = px + (slot >> 1) * 8 + (slot & 1);
-            q[0] = xf; q[2] = yf; q[4] = xf + U; q[6] = yf + V;
-        }
-    }
-    __syncthreads();
-    const int np = s_n;
-    if (threadIdx.x == 0 && (np & 1)) {                               // the other half of the last pair: a NaN target is no inlier
-        float *q = px + (np >> 1) * 8 + 1;
-        q[0] = 0.0f; q[2] = 0.0f; q[4] = __builtin_nanf(""); q[6] = __builtin_nanf("");
-    }
-    __syncthreads();
-    const int j = blockIdx.y * MF_THREADS + threadIdx.x;
+    const int np = fit_stage_chunk<FIT_CHUNK, FIT_THREADS>(a, s_px, s_n, [](int x, int y, float U, float V, float (&v)[4]) {
+        v[0] = (float)x; v[1] = (float)y; v[2] = v[0] + U; v[3] = v[1] + V;
+    });
+    const int j = blockIdx.y * FIT_THREADS + threadIdx.x;
     const bool live = j < a.n_hyp && a.hyp_counts[j] >= 0;        // the sign does not change while counts are added
     float m[9];
     mf_identity(m);
@@ -198,31 +153,25 @@ template <bool HOMOG> __global__ void __launch_bounds__(MF_THREADS) mf_score_ker
 #pragma unroll 4
     for (int k = 0; k < (np + 1) >> 1; k++) {
         const float4 p = s_px[2 * k], q = s_px[2 * k + 1];        // every lane the same address: a broadcast
-        const mf_f2 xf = {p.x, p.y}, yf = {p.z, p.w}, tx = {q.x, q.y}, ty = {q.z, q.w};
-        const mf_f2 X = (m[0] * xf + m[1] * yf) + m[2], Y = (m[3] * xf + m[4] * yf) + m[5];
+        const dflow_f2 xf = {p.x, p.y}, yf = {p.z, p.w}, tx = {q.x, q.y}, ty = {q.z, q.w};
+        const dflow_f2 X = (m[0] * xf + m[1] * yf) + m[2], Y = (m[3] * xf + m[4] * yf) + m[5];
         if constexpr (HOMOG) {
-            const mf_f2 W = (m[6] * xf + m[7] * yf) + m[8];
-            const mf_f2 ex = X - W * tx, ey = Y - W * ty, t = thresh * W, e = ex * ex + ey * ey, tt = t * t;
+            const dflow_f2 W = (m[6] * xf + m[7] * yf) + m[8];
+            const dflow_f2 ex = X - W * tx, ey = Y - W * ty, t = thresh * W, e = ex * ex + ey * ey, tt = t * t;
             cnt += (W.x > 0.0f && e.x <= tt.x ? 1 : 0) + (W.y > 0.0f && e.y <= tt.y ? 1 : 0);
         } else {
             // W = (0 * xf + 0 * yf) + 1 = 1: W * tx = tx, thresh * W = thresh, bit for bit
-            const mf_f2 ex = X - tx, ey = Y - ty, e = ex * ex + ey * ey;
+            const dflow_f2 ex = X - tx, ey = Y - ty, e = ex * ex + ey * ey;
             cnt += (e.x <= t2 ? 1 : 0) + (e.y <= t2 ? 1 : 0);
         }
     }
     if (live && cnt) atomicAdd(&a.hyp_counts[j], cnt);
 }
 
-__global__ void __launch_bounds__(MF_THREADS) mf_best_kernel(MfArgs a, int round)
+__global__ void __launch_bounds__(FIT_THREADS) mf_best_kernel(MfArgs a, int round)
 {
-    const int j = blockIdx.x * MF_THREADS + threadIdx.x;
-    bool degenerate = false;
-    if (j < a.n_hyp) {
-        const int32_t c = a.hyp_counts[j];
-        if (c < 0) { a.hyp_counts[j] = 0; degenerate = true; }
-        else atomicMax(&a.state[MF_S_BEST], ((unsigned long long)(uint32_t)c << 32) | (0xFFFFFFFFu - (uint32_t)(round * 65536 + j)));
-    }
-    mf_block_add(degenerate, &a.state[MF_S_DEGEN]);
+    const bool degenerate = fit_offer(a, blockIdx.x * FIT_THREADS + threadIdx.x, a.n_hyp, round);
+    fit_block_add({fit_wave_count(degenerate)}, &a.state[MF_S_DEGEN]);
 }
 
 __global__ void mf_select_kernel(MfArgs a, int round)
@@ -235,41 +184,37 @@ __global__ void mf_select_kernel(MfArgs a, int round)
         for (int k = 0; k < 9; k++) a.cur[k] = m[k];
         return;
     }
-    const uint32_t id = 0xFFFFFFFFu - (uint32_t)key;
-    if ((int)(id >> 16) == round) {
-        for (int k = 0; k < 9; k++) a.cur[k] = a.models[(size_t)(id & 0xFFFFu) * 9 + k];
-        a.state[MF_S_CUR] = key >> 32;
-    }
+    if (fit_adopt(a, key, round)) a.state[MF_S_CUR] = fit_key_count(key);
 }
 
-struct MfSums { long long v[MF_NSUMS]; long long skipped; };
+struct MfSums { long long v[FIT_NSUMS]; long long skipped; };
 
-__global__ void __launch_bounds__(MF_THREADS) mf_sums_kernel(MfArgs a)
+__global__ void __launch_bounds__(FIT_THREADS) mf_sums_kernel(MfArgs a)
 {
     MfSums s = {};
     if (a.state[MF_S_BEST] != 0ull) {
         float m[9];
         mf_load_model(a.cur, m);
-        for (uint32_t c = blockIdx.x * MF_THREADS + threadIdx.x; c < a.ns; c += gridDim.x * MF_THREADS) {
+        for (uint32_t c = blockIdx.x * FIT_THREADS + threadIdx.x; c < a.ns; c += gridDim.x * FIT_THREADS) {
             int x, y;
             const uint32_t i = mf_grid_pixel(a, c, x, y);
             float U, V;
             if (!mf_part(a, i, U, V)) continue;
             const float xf = (float)x, yf = (float)y, tx = xf + U, ty = yf + V;
             if (!mf_inlier(m, xf, yf, tx, ty, a.thresh)) continue;
-            if (!(fabsf(tx) <= MF_POLISH_RANGE && fabsf(ty) <= MF_POLISH_RANGE)) { s.skipped++; continue; }
+            if (!(fabsf(tx) <= FIT_RANGE && fabsf(ty) <= FIT_RANGE)) { s.skipped++; continue; }
             const long long ca = 2 * x - (a.w - 1), cb = 2 * y - (a.h - 1), p = llrintf(tx * 64.0f), q = llrintf(ty * 64.0f);
             s.v[0] += 1; s.v[1] += ca; s.v[2] += cb; s.v[3] += ca * ca; s.v[4] += ca * cb; s.v[5] += cb * cb;
             s.v[6] += p; s.v[7] += ca * p; s.v[8] += cb * p; s.v[9] += q; s.v[10] += ca * q; s.v[11] += cb * q;
         }
     }
-    s = block_reduce<MF_THREADS / 64>(s, [](MfSums &x, const MfSums &y) {
+    s = block_reduce<FIT_THREADS / 64>(s, [](MfSums &x, const MfSums &y) {
 #pragma unroll
-        for (int k = 0; k < MF_NSUMS; k++) x.v[k] += y.v[k];
+        for (int k = 0; k < FIT_NSUMS; k++) x.v[k] += y.v[k];
         x.skipped += y.skipped;
     });
     if (threadIdx.x == 0) {
-        for (int k = 0; k < MF_NSUMS; k++)
+        for (int k = 0; k < FIT_NSUMS; k++)
             if (s.v[k]) atomicAdd(&a.state[MF_S_SUMS + k], (unsigned long long)s.v[k]);
         if (s.skipped) atomicAdd(&a.state[MF_S_SKIPPED], (unsigned long long)s.skipped);
     }
@@ -279,41 +224,26 @@ __global__ void __launch_bounds__(MF_THREADS) mf_sums_kernel(MfArgs a)
 __global__ void mf_solve_kernel(MfArgs a)
 {
     if (blockIdx.x || threadIdx.x) return;
-    double S[MF_NSUMS];
-    for (int k = 0; k < MF_NSUMS; k++) { S[k] = (double)(long long)a.state[MF_S_SUMS + k]; a.state[MF_S_SUMS + k] = 0ull; }
+    double S[FIT_NSUMS];
+    for (int k = 0; k < FIT_NSUMS; k++) { S[k] = (double)(long long)a.state[MF_S_SUMS + k]; a.state[MF_S_SUMS + k] = 0ull; }
     const long long N = (long long)S[0];
     a.state[MF_S_CAND] = 0ull;
     a.state[MF_S_CAND_OK] = 0ull;
     if (a.state[MF_S_BEST] == 0ull || N < 3) return;
-    const double n = S[0], sa = S[1], sb = S[2], saa = S[3], sab = S[4], sbb = S[5];
-    const double c00 = sbb * n - sb * sb, c01 = sb * sa - sab * n, c02 = sab * sb - sbb * sa;
-    const double c11 = saa * n - sa * sa, c12 = sa * sab - saa * sb, c22 = saa * sbb - sab * sab;
-    const double det = (saa * c00 + sab * c01) + sa * c02;
-    if (det == 0.0 || !isfinite(det)) return;
-    float *cand = reinterpret_cast<float *>(a.state + MF_S_CAND_MODEL);
-    bool ok = true;
-    for (int row = 0; row < 2; row++) {
-        const double r2 = S[6 + 3 * row], r0 = S[7 + 3 * row], r1 = S[8 + 3 * row];      // sum p, sum a p, sum b p
-        const double x0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det, x1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
-        const double x2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
-        // p / 64 = x0 (2x - (w-1)) + x1 (2y - (h-1)) + x2
-        const float m0 = (float)(x0 * 0.03125), m1 = (float)(x1 * 0.03125);
-        const float m2 = (float)(((x2 - x0 * (double)(a.w - 1)) - x1 * (double)(a.h - 1)) * 0.015625);
-        ok &= isfinite(m0) && isfinite(m1) && isfinite(m2);
-        cand[3 * row] = m0; cand[3 * row + 1] = m1; cand[3 * row + 2] = m2;
-    }
+    float (&cand)[9] = *reinterpret_cast<float (*)[9]>(a.state + MF_S_CAND_MODEL);
+    if (!fit_affine_from_sums(S, a.w, a.h, reinterpret_cast<float (&)[6]>(cand))) return;
     cand[6] = 0.0f; cand[7] = 0.0f; cand[8] = 1.0f;
-    a.state[MF_S_CAND_OK] = ok ? 1ull : 0ull;
+    a.state[MF_S_CAND_OK] = 1ull;
 }
 
 // the scored inliers of the candidate
-__global__ void __launch_bounds__(MF_THREADS) mf_count_kernel(MfArgs a)
+__global__ void __launch_bounds__(FIT_THREADS) mf_count_kernel(MfArgs a)
 {
     int cnt = 0;
     if (a.state[MF_S_CAND_OK]) {
         float m[9];
         mf_load_model(reinterpret_cast<const float *>(a.state + MF_S_CAND_MODEL), m);
-        for (uint32_t c = blockIdx.x * MF_THREADS + threadIdx.x; c < a.ns; c += gridDim.x * MF_THREADS) {
+        for (uint32_t c = blockIdx.x * FIT_THREADS + threadIdx.x; c < a.ns; c += gridDim.x * FIT_THREADS) {
             int x, y;
             const uint32_t i = mf_grid_pixel(a, c, x, y);
             float U, V;
@@ -322,7 +252,7 @@ __global__ void __launch_bounds__(MF_THREADS) mf_count_kernel(MfArgs a)
             cnt += mf_inlier(m, xf, yf, xf + U, yf + V, a.thresh) ? 1 : 0;
         }
     }
-    cnt = block_reduce<MF_THREADS / 64>(cnt, [](int &x, const int &y) { x += y; });
+    cnt = block_reduce<FIT_THREADS / 64>(cnt, [](int &x, const int &y) { x += y; });
     if (threadIdx.x == 0 && cnt) atomicAdd(&a.state[MF_S_CAND], (unsigned long long)cnt);
 }
 
@@ -336,10 +266,10 @@ __global__ void mf_accept_kernel(MfArgs a)
     a.state[MF_S_ACCEPTED] += 1ull;
 }
 
-__global__ void __launch_bounds__(MF_THREADS) mf_apply_kernel(MfArgs a, uint8_t *__restrict__ cls, float *__restrict__ model_flow,
+__global__ void __launch_bounds__(FIT_THREADS) mf_apply_kernel(MfArgs a, uint8_t *__restrict__ cls, float *__restrict__ model_flow,
                                                               float *__restrict__ residual)
 {
-    const uint32_t i = blockIdx.x * MF_THREADS + threadIdx.x;
+    const uint32_t i = blockIdx.x * FIT_THREADS + threadIdx.x;
     bool scored = false, scored_in = false;
     if (i < a.n) {
         float m[9];
@@ -356,27 +286,20 @@ __global__ void __launch_bounds__(MF_THREADS) mf_apply_kernel(MfArgs a, uint8_t 
             mf.u = X / W - xf; mf.v = Y / W - yf; mf.valid = 1.0f;
             if (good) { res.u = U - mf.u; res.v = V - mf.v; res.valid = 1.0f; }
         }
-        if (cls) cls[i] = (uint8_t)(!good ? 0 : excluded ? 3 : in ? 1 : 2);
+        if (cls) cls[i] = fit_class(good, excluded, in);
         if (model_flow) reinterpret_cast<FlowOut *>(model_flow)[i] = mf;
         if (residual) reinterpret_cast<FlowOut *>(residual)[i] = res;
-        scored = good && !excluded && y % a.step == 0 && x % a.step == 0;
+        scored = fit_scored(a, good, excluded, x, y);
         scored_in = scored && in;
     }
-    mf_block_add(scored, &a.state[MF_S_SCORED]);
-    mf_block_add(scored_in, &a.state[MF_S_FINAL]);
+    fit_block_add({fit_wave_count(scored)}, &a.state[MF_S_SCORED]);
+    fit_block_add({fit_wave_count(scored_in)}, &a.state[MF_S_FINAL]);
 }
 
 __global__ void mf_finish_kernel(MfArgs a, int32_t *__restrict__ counts)
 {
     if (blockIdx.x || threadIdx.x || !counts) return;
-    const unsigned long long key = a.state[MF_S_BEST];
-    const uint32_t id = 0xFFFFFFFFu - (uint32_t)key;
-    counts[0] = (int32_t)a.state[MF_S_SCORED];
-    counts[1] = (int32_t)a.state[MF_S_FINAL];
-    counts[2] = (int32_t)a.state[MF_S_DEGEN];
-    counts[3] = key ? (int32_t)(id >> 16) : -1;
-    counts[4] = key ? (int32_t)(id & 0xFFFFu) : -1;
-    counts[5] = (int32_t)(key >> 32);
+    fit_counts(a, counts, MF_S_SCORED, MF_S_FINAL, MF_S_DEGEN);
     counts[6] = (int32_t)a.state[MF_S_ACCEPTED];
     counts[7] = (int32_t)a.state[MF_S_SKIPPED];
 }
@@ -385,37 +308,30 @@ int launch_motion_fit(int H, int W, const float *flow, int layout, const uint8_t
                       int lo_rounds, int polish, int step, uint64_t seed, float *d_model, float *models, int32_t *hyp_counts,
                       int64_t *state, uint8_t *cls, float *model_flow, float *residual, int32_t *counts, hipStream_t s)
 {
-    MfArgs a;
-    a.h = H; a.w = W; a.layout = layout; a.model = model; a.n_hyp = n_hyp; a.step = step; a.ws = (W + step - 1) / step;
-    a.n = (uint32_t)H * (uint32_t)W; a.ns = (uint32_t)((H + step - 1) / step) * (uint32_t)a.ws;
-    a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.thresh = thresh;
-    double P = 1.0;
-    while (P < (double)(H > W ? H : W)) P *= 2.0;
-    a.cx = (double)(W - 1) * 0.5; a.cy = (double)(H - 1) * 0.5; a.s = 1.0 / P; a.inv = P;
-    a.flow = flow; a.exclude = exclude; a.cur = d_model; a.models = models; a.hyp_counts = hyp_counts;
-    a.state = reinterpret_cast<unsigned long long *>(state);
-    DFLOW_HIP(hipMemsetAsync(state, 0, 32 * sizeof(int64_t), s));
-    if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, MF_COUNTS * sizeof(int32_t), s));
-    const unsigned hyp_blocks = (unsigned)((n_hyp + MF_THREADS - 1) / MF_THREADS);
-    const unsigned chunks = (a.ns + MF_CHUNK - 1) / MF_CHUNK;
-    const unsigned grid_blocks = (a.ns + MF_THREADS - 1) / MF_THREADS;
+    MfArgs a = fit_frame(H, W, layout, step, flow, state);
+    a.model = model; a.n_hyp = n_hyp; a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32); a.thresh = thresh;
+    a.exclude = exclude; a.cur = d_model; a.models = models; a.hyp_counts = hyp_counts;
+    if (int rc = fit_clear(state, counts, s)) return rc;
+    const unsigned hyp_blocks = (unsigned)((n_hyp + FIT_THREADS - 1) / FIT_THREADS);
+    const unsigned chunks = (a.ns + FIT_CHUNK - 1) / FIT_CHUNK;
+    const unsigned grid_blocks = (a.ns + FIT_THREADS - 1) / FIT_THREADS;
     const unsigned walk_blocks = grid_blocks < PLANE_MAX_BLOCKS ? grid_blocks : PLANE_MAX_BLOCKS;
     // identity until a round has a winner: round 0 does not look at it, the rounds after it sample its inliers
     hipLaunchKernelGGL(mf_select_kernel, dim3(1), dim3(64), 0, s, a, -1);
     for (int r = 0; r <= lo_rounds; r++) {
-        hipLaunchKernelGGL(mf_hyp_kernel, dim3(hyp_blocks), dim3(MF_THREADS), 0, s, a, r);
-        if (model == DFLOW_MOTION_HOMOGRAPHY) hipLaunchKernelGGL(mf_score_kernel<true>, dim3(chunks, hyp_blocks), dim3(MF_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(mf_score_kernel<false>, dim3(chunks, hyp_blocks), dim3(MF_THREADS), 0, s, a);
-        hipLaunchKernelGGL(mf_best_kernel, dim3(hyp_blocks), dim3(MF_THREADS), 0, s, a, r);
+        hipLaunchKernelGGL(mf_hyp_kernel, dim3(hyp_blocks), dim3(FIT_THREADS), 0, s, a, r);
+        if (model == DFLOW_MOTION_HOMOGRAPHY) hipLaunchKernelGGL(mf_score_kernel<true>, dim3(chunks, hyp_blocks), dim3(FIT_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(mf_score_kernel<false>, dim3(chunks, hyp_blocks), dim3(FIT_THREADS), 0, s, a);
+        hipLaunchKernelGGL(mf_best_kernel, dim3(hyp_blocks), dim3(FIT_THREADS), 0, s, a, r);
         hipLaunchKernelGGL(mf_select_kernel, dim3(1), dim3(64), 0, s, a, r);
     }
     for (int t = 0; t < (model == DFLOW_MOTION_AFFINE ? polish : 0); t++) {
-        hipLaunchKernelGGL(mf_sums_kernel, dim3(walk_blocks), dim3(MF_THREADS), 0, s, a);
+        hipLaunchKernelGGL(mf_sums_kernel, dim3(walk_blocks), dim3(FIT_THREADS), 0, s, a);
         hipLaunchKernelGGL(mf_solve_kernel, dim3(1), dim3(64), 0, s, a);
-        hipLaunchKernelGGL(mf_count_kernel, dim3(walk_blocks), dim3(MF_THREADS), 0, s, a);
+        hipLaunchKernelGGL(mf_count_kernel, dim3(walk_blocks), dim3(FIT_THREADS), 0, s, a);
         hipLaunchKernelGGL(mf_accept_kernel, dim3(1), dim3(64), 0, s, a);
     }
-    hipLaunchKernelGGL(mf_apply_kernel, dim3((a.n + MF_THREADS - 1) / MF_THREADS), dim3(MF_THREADS), 0, s, a, cls, model_flow, residual);
+    hipLaunchKernelGGL(mf_apply_kernel, dim3((a.n + FIT_THREADS - 1) / FIT_THREADS), dim3(FIT_THREADS), 0, s, a, cls, model_flow, residual);
     hipLaunchKernelGGL(mf_finish_kernel, dim3(1), dim3(64), 0, s, a, counts);
     return dflow_check_launch("motion fit kernels");
 }

@@ -18,13 +18,12 @@
 // dflow_segment_fit, 2 rounds + 1 launches:
 //   sf_acc_kernel      a lane per pixel, a wave per 8 x 8 square: the twelve int64 sums of its segment, a wave's adds aggregated
 //                      per distinct label first (shuffle tree), then 64-bit integer atomics
-//   sf_solve_kernel    a thread per segment: the two 3x3 normal systems in float64 (step E of the motion fit, restated), or the
-//                      translation, or nothing
+//   sf_solve_kernel    a thread per segment: the two 3x3 normal systems in float64 (step E of the motion fit, fit_common.h's
+//                      fit_affine_from_sums, with the flow as the right-hand side), or the translation, or nothing
 //   sf_apply_kernel    a lane per pixel: the model's flow, the class, the counts
 // Every count and sum is an integer (exact in any order of arrival); every float32 and float64 chain is one IEEE operation per
 // written operation (-ffp-contract=off).
-#include <math.h>
-#include "plane_ops.h"
+#include "fit_common.h"
 #include "union_find.h"
 
 #define SP_TW 32
@@ -355,8 +354,6 @@ int launch_superpixels(int H, int W, const uint8_t *bgr, int step, int compactne
 }
 
 // ---------------------------------------------------------------------------------------------- the per-segment fit
-#define SF_NSUMS 12
-#define SF_RANGE 32768.0f
 #define SF_COUNTS 8
 
 struct SfArgs {
@@ -382,7 +379,7 @@ __device__ __forceinline__ static bool sf_agrees(float Um, float Vm, float U, fl
     return eu * eu + ev * ev <= T * T;
 }
 
-__device__ __forceinline__ static bool sf_in_range(float U, float V) { return fabsf(U) <= SF_RANGE && fabsf(V) <= SF_RANGE; }
+__device__ __forceinline__ static bool sf_in_range(float U, float V) { return fabsf(U) <= FIT_RANGE && fabsf(V) <= FIT_RANGE; }
 
 // round 0: every participant, and the pixels per label; round r > 0: the participants that agree with the model so far at T
 __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round, float T)
@@ -392,9 +389,9 @@ __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round,
     const int x = blockIdx.x * SP_TW + (int)(threadIdx.x >> 6) * 8 + (lane & 7), y = blockIdx.y * SP_TH + (lane >> 3);
     int l = -1;
     bool part = false;
-    long long v[SF_NSUMS - 1];
+    long long v[FIT_NSUMS - 1];
 #pragma unroll
-    for (int k = 0; k < SF_NSUMS - 1; k++) v[k] = 0;
+    for (int k = 0; k < FIT_NSUMS - 1; k++) v[k] = 0;
     if (x < a.w && y < a.h) {
         const int i = y * a.w + x;
         const int lab = a.label[i];
@@ -427,10 +424,10 @@ __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round,
         const bool mine = pending && l == r;
         const int c_all = __popcll(__ballot(mine)), c_part = __popcll(__ballot(mine && part));
         if (c_part) {                                 // uniform
-            unsigned long long *acc = a.acc + (size_t)r * SF_NSUMS;
+            unsigned long long *acc = a.acc + (size_t)r * FIT_NSUMS;
             if (lane == leader) atomicAdd(&acc[0], (unsigned long long)c_part);
 #pragma unroll
-            for (int k = 0; k < SF_NSUMS - 1; k++) {
+            for (int k = 0; k < FIT_NSUMS - 1; k++) {
                 long long sum = mine && part ? v[k] : 0;
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
@@ -442,39 +439,17 @@ __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round,
     }
 }
 
-// step E of the motion fit (motion_fit.hip: mf_solve_kernel), restated with the flow as the right-hand side
-__device__ static bool sf_affine(const double (&S)[SF_NSUMS], int w, int h, float (&m)[6])
-{
-    const double n = S[0], sa = S[1], sb = S[2], saa = S[3], sab = S[4], sbb = S[5];
-    const double c00 = sbb * n - sb * sb, c01 = sb * sa - sab * n, c02 = sab * sb - sbb * sa;
-    const double c11 = saa * n - sa * sa, c12 = sa * sab - saa * sb, c22 = saa * sbb - sab * sab;
-    const double det = (saa * c00 + sab * c01) + sa * c02;
-    if (det == 0.0 || !isfinite(det)) return false;
-    bool ok = true;
-    for (int row = 0; row < 2; row++) {
-        const double r2 = S[6 + 3 * row], r0 = S[7 + 3 * row], r1 = S[8 + 3 * row];      // sum p, sum a p, sum b p
-        const double x0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det, x1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det;
-        const double x2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det;
-        // p / 64 = x0 (2x - (w-1)) + x1 (2y - (h-1)) + x2
-        const float m0 = (float)(x0 * 0.03125), m1 = (float)(x1 * 0.03125);
-        const float m2 = (float)(((x2 - x0 * (double)(w - 1)) - x1 * (double)(h - 1)) * 0.015625);
-        ok &= isfinite(m0) && isfinite(m1) && isfinite(m2);
-        m[3 * row] = m0; m[3 * row + 1] = m1; m[3 * row + 2] = m2;
-    }
-    return ok;
-}
-
 // counts: NULL but in the last round
 __global__ void __launch_bounds__(SP_THREADS) sf_solve_kernel(SfArgs a, int round, int32_t *counts)
 {
     const int s = blockIdx.x * SP_THREADS + threadIdx.x;
     int kind = -1;
     if (s < a.n_seg) {
-        unsigned long long *acc = a.acc + (size_t)s * SF_NSUMS;
+        unsigned long long *acc = a.acc + (size_t)s * FIT_NSUMS;
         const long long N = (long long)acc[0];
-        double S[SF_NSUMS];
+        double S[FIT_NSUMS];
 #pragma unroll
-        for (int k = 0; k < SF_NSUMS; k++) { S[k] = (double)(long long)acc[k]; acc[k] = 0ull; }
+        for (int k = 0; k < FIT_NSUMS; k++) { S[k] = (double)(long long)acc[k]; acc[k] = 0ull; }
         float *mo = a.models + (size_t)s * 6;
         int32_t *sc = a.seg_counts + (size_t)s * 4;
         if (round == 0) sc[1] = (int32_t)N;
@@ -483,7 +458,7 @@ __global__ void __launch_bounds__(SP_THREADS) sf_solve_kernel(SfArgs a, int roun
         bool write = round == 0;
         if (N >= 1) {
             write = true;
-            if (N >= 3 && sf_affine(S, a.w, a.h, m)) kind = 2;
+            if (N >= 3 && fit_affine_from_sums(S, a.w, a.h, m)) kind = 2;
             else {
                 m[0] = 0.0f; m[1] = 0.0f; m[2] = (float)((S[6] / S[0]) * 0.015625);
                 m[3] = 0.0f; m[4] = 0.0f; m[5] = (float)((S[9] / S[0]) * 0.015625);
@@ -538,7 +513,7 @@ int launch_segment_fit(int H, int W, const float *flow, int layout, const int32_
     SfArgs a;
     a.h = H; a.w = W; a.layout = layout; a.n_seg = n_seg; a.n = H * W; a.thresh = thresh;
     a.flow = flow; a.label = label; a.models = models; a.seg_counts = seg_counts; a.acc = reinterpret_cast<unsigned long long *>(acc);
-    DFLOW_HIP(hipMemsetAsync(acc, 0, (size_t)n_seg * SF_NSUMS * sizeof(int64_t), s));
+    DFLOW_HIP(hipMemsetAsync(acc, 0, (size_t)n_seg * FIT_NSUMS * sizeof(int64_t), s));
     DFLOW_HIP(hipMemsetAsync(seg_counts, 0, (size_t)n_seg * 4 * sizeof(int32_t), s));
     if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, SF_COUNTS * sizeof(int32_t), s));
     const int nb = (a.n + SP_THREADS - 1) / SP_THREADS, sb = (n_seg + SP_THREADS - 1) / SP_THREADS;

@@ -9,23 +9,21 @@
 //   tv_vote_kernel       the hot one.  TV_PER_LANE grid pixels per lane, a block's pixels contiguous: x1 and x2 once, r, c = r x
 //                        x2, d, n1 and n2 for R_a and for R_b; the candidates with -t are the same numbers negated (IEEE
 //                        rounding is symmetric), so the four are scored from two evaluations.  Votes are ballots, summed by
-//                        the wave over its pixels -> LDS -> one 64-bit integer atomic per block and candidate (the pattern of
-//                        fit_common.h's mf_block_add, for five counts at once and a block of 2048 pixels: the atomics of all
-//                        blocks land on the same five words, about 12 ns each on an MI355X, and at one block per 256 pixels
-//                        they were the whole kernel's time)
+//                        the wave over its pixels -> LDS -> one 64-bit integer atomic per block and candidate (fit_common.h's
+//                        fit_block_add, for five counts at once and a block of 2048 pixels: the atomics of all blocks land
+//                        on the same five words, about 12 ns each on an MI355X, and at one block per 256 pixels they were
+//                        the whole kernel's time)
 //   tv_apply_kernel      every pixel, as many per lane: the winner is read from the four votes by every lane (ties to the
 //                        smaller index), lane 0 of block 0 writes d_pose; depth, class, error, and the three class totals
 //   tv_finish_kernel     one lane: d_counts is written from d_state
 // 4 launches and one or two memsets whatever the planes hold.  Every count is an integer (exact in any order of arrival).
-// fit_common.h holds the grid of scored pixels, the nine coefficients and the block's count as epipolar.hip uses them.
-#include <math.h>
+// fit_common.h holds the frame and the grid of scored pixels, the nine coefficients and the block's counts as the fits use them.
 #include "fit_common.h"
 
 #define TV_THREADS 256
 #define TV_PER_LANE 8                                 // pixels a lane takes: a block covers 2048 contiguous ones
 #define TV_SWEEPS 8
 #define TV_SIGMA2_MIN 9.5367431640625e-07             // 2^-20: sigma2 must exceed this times sigma1
-#define TV_COUNTS 8
 // d_state: int64[32].  [0..3] votes, [4] voters, [5..7] pixels of class 1, 2, 3, [8..30] float64 bits: R_a, R_b, t, sigma2/sigma1,
 // sigma3/sigma1, [31] 1 when the decomposition gave candidates
 enum { TV_S_VOTE = 0, TV_S_VOTERS = 4, TV_S_CLASS = 5, TV_S_RA = 8, TV_S_RB = 17, TV_S_T = 26, TV_S_SIGMA = 29, TV_S_VALID = 31 };
@@ -201,21 +199,6 @@ __device__ __forceinline__ static void tv_geometry(const double (&R)[9], const d
     n2 = (b0 * c0 + b1 * c1) + b2 * c2;
 }
 
-// N counts a wave has summed from its ballots, added to slots[0..N-1]: -> LDS -> one 64-bit integer atomic per block and count
-template <int N> __device__ __forceinline__ static void tv_block_add(const int (&w)[N], unsigned long long *slots)
-{
-    __shared__ int s_c[N];
-    if (threadIdx.x < N) s_c[threadIdx.x] = 0;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; k++)
-            if (w[k]) atomicAdd(&s_c[k], w[k]);
-    }
-    __syncthreads();
-    if (threadIdx.x < N && s_c[threadIdx.x]) atomicAdd(&slots[threadIdx.x], (unsigned long long)s_c[threadIdx.x]);
-}
-
 // whether grid point c votes at all, and its vector
 __device__ __forceinline__ static bool tv_voter(const TvArgs &a, uint32_t c, float &U, float &V)
 {
@@ -250,7 +233,7 @@ __device__ __forceinline__ static void tv_vote_pixel(const TvArgs &a, uint32_t c
 
 __global__ void __launch_bounds__(TV_THREADS) tv_vote_kernel(TvArgs a)
 {
-    static_assert(TV_S_VOTERS == TV_S_VOTE + 4, "tv_block_add: the four votes and the voters are neighbours in d_state");
+    static_assert(TV_S_VOTERS == TV_S_VOTE + 4, "fit_block_add: the four votes and the voters are neighbours in d_state");
     const bool valid = a.istate[TV_S_VALID] != 0;
     const uint32_t c0 = blockIdx.x * (TV_PER_LANE * TV_THREADS) + threadIdx.x;
     int total[5] = {0, 0, 0, 0, 0};
@@ -269,7 +252,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_vote_kernel(TvArgs a)
             for (int k = 0; k < 4; k++) total[k] += __popcll(__ballot(vote[k]));
         }
     }
-    tv_block_add(total, &a.f.state[TV_S_VOTE]);
+    fit_block_add(total, &a.f.state[TV_S_VOTE]);
 }
 
 // D. the candidate with the most votes, ties to the smaller index; -1: none
@@ -358,7 +341,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_apply_kernel(TvArgs a, float *_
 #pragma unroll
         for (int q = 1; q <= 3; q++) total[q - 1] += __popcll(__ballot(k == q));
     }
-    tv_block_add(total, &a.f.state[TV_S_CLASS]);
+    fit_block_add(total, &a.f.state[TV_S_CLASS]);
 }
 
 __global__ void tv_finish_kernel(TvArgs a, int32_t *__restrict__ counts)
@@ -385,18 +368,10 @@ int launch_two_view(int H, int W, const float *flow, int layout, const float *mo
                     hipStream_t s)
 {
     TvArgs a;
-    a.f.h = H; a.f.w = W; a.f.layout = layout; a.f.model = 0; a.f.n_hyp = 0; a.f.step = step; a.f.ws = (W + step - 1) / step;
-    a.f.n = (uint32_t)H * (uint32_t)W; a.f.ns = (uint32_t)((H + step - 1) / step) * (uint32_t)a.f.ws;
-    a.f.k0 = 0; a.f.k1 = 0; a.f.thresh = 0.0f;
-    double P = 1.0;
-    while (P < (double)(H > W ? H : W)) P *= 2.0;
-    a.f.cx = (double)(W - 1) * 0.5; a.f.cy = (double)(H - 1) * 0.5; a.f.s = 1.0 / P; a.f.inv = P;
-    a.f.flow = flow; a.f.exclude = nullptr; a.f.cur = nullptr; a.f.models = nullptr; a.f.hyp_counts = nullptr;
-    a.f.state = reinterpret_cast<unsigned long long *>(state);
+    a.f = fit_frame(H, W, layout, step, flow, state);             // no samples: nothing else of it is read
     a.part = part; a.model = model; a.fx = fx; a.fy = fy; a.px = cx; a.py = cy; a.pose = pose;
     a.istate = reinterpret_cast<long long *>(state); a.dstate = reinterpret_cast<double *>(state);
-    DFLOW_HIP(hipMemsetAsync(state, 0, 32 * sizeof(int64_t), s));
-    if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, TV_COUNTS * sizeof(int32_t), s));
+    if (int rc = fit_clear(state, counts, s)) return rc;
     hipLaunchKernelGGL(tv_decompose_kernel, dim3(1), dim3(64), 0, s, a);
     const uint32_t per_block = TV_THREADS * TV_PER_LANE;
     hipLaunchKernelGGL(tv_vote_kernel, dim3((a.f.ns + per_block - 1) / per_block), dim3(TV_THREADS), 0, s, a);

@@ -11,7 +11,7 @@ from motion_ref import Field, normalisation, philox
 
 F = np.float32
 UVV, DYDX = M.UVV, M.DYDX
-CHUNK = 2048                      # EP_CHUNK of csrc/epipolar.hip: the scored pixels a block stages
+CHUNK = 2048                      # FIT_CHUNK of csrc/fit_common.h: the scored pixels a block stages
 ATTEMPTS = 16
 PIVOT_MIN = 2.0 ** -40
 BISECTIONS = 60

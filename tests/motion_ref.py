@@ -7,7 +7,7 @@ import numpy as np
 F = np.float32
 AFFINE, HOMOGRAPHY = 0, 1
 UVV, DYDX = 0, 1
-CHUNK = 2048                      # MF_CHUNK of csrc/motion_fit.hip: the scored pixels a block stages
+CHUNK = 2048                      # FIT_CHUNK of csrc/fit_common.h: the scored pixels a block stages
 ATTEMPTS = 16
 PIVOT_MIN = 2.0 ** -40
 POLISH_RANGE = F(32768.0)

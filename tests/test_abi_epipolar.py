@@ -48,10 +48,10 @@ def test_the_header_the_binding_and_the_makefile_name_it(L):
     csrc = os.path.join(ROOT, PKG, "csrc")
     text = open(os.path.join(csrc, "epipolar.hip")).read()
     import epipolar_ref
-    assert '#include "fit_common.h"' in text and "#define EP_CHUNK %d " % epipolar_ref.CHUNK in text
-    for helper in ("bool mf_part(", "uint32_t mf_grid_pixel(", "void mf_block_add(", "void mf_load_model(", "struct MfArgs {"):
-        defs = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h")) and helper in open(os.path.join(csrc, n)).read()]
-        assert defs == ["fit_common.h"], helper
+    import fit_common_pins
+    import motion_ref
+    assert '#include "fit_common.h"' in text
+    fit_common_pins.check(csrc, epipolar_ref.CHUNK, motion_ref.CHUNK)
     # the gate adds no refusal text of its own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()
     gate = abi[abi.index("int dflow_epipolar_fit("):abi.index("int dflow_label_confidence(")]

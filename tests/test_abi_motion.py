@@ -41,11 +41,15 @@ def test_the_header_the_binding_and_the_makefile_name_it(L):
     csrc = os.path.join(ROOT, PKG, "csrc")
     defs = [name for name in sorted(os.listdir(csrc)) if name.endswith((".hip", ".h")) and "void philox4x32_10(" in open(os.path.join(csrc, name)).read()]
     assert defs == ["philox.h"]
-    for name in ("neighbour.hip", "motion_fit.hip"):
+    for name in ("neighbour.hip", "fit_common.h"):
         assert '#include "philox.h"' in open(os.path.join(csrc, name)).read()
     text = open(os.path.join(csrc, "motion_fit.hip")).read()
+    import epipolar_ref
+    import fit_common_pins
     import motion_ref
-    assert "flow_good(" in text and "#define MF_CHUNK %d " % motion_ref.CHUNK in text
+    assert "flow_good(" in text and '#include "fit_common.h"' in text and "mf_gauss(" in text
+    # what the fits share has one definition, and the one chunk is the one both restatements derive their frames from
+    fit_common_pins.check(csrc, motion_ref.CHUNK, epipolar_ref.CHUNK)
     # the gate adds no refusal text of its own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()
     gate = abi[abi.index("int dflow_motion_fit("):abi.index("int dflow_remove_small_segments_host(")]

@@ -60,6 +60,10 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
     assert "dflow_set_error(" not in gate
     text = open(os.path.join(csrc, "superpixels.hip")).read()
     assert '#include "union_find.h"' in text and "superpixel" not in open(os.path.join(csrc, "segments.hip")).read()
+    # the segment fit's affine solve is the motion fit's step E: one definition, shared
+    import fit_common_pins
+    fit_common_pins.check(csrc)
+    assert "fit_affine_from_sums(S, a.w, a.h, m)" in text and "fit_affine_from_sums(S, a.w, a.h," in open(os.path.join(csrc, "motion_fit.hip")).read()
     # the staged block of centres covers a tile and its neighbours at the smallest step
     tw, th, smin = (int(re.search(r"#define %s (\d+)" % n, text).group(1)) for n in ("SP_TW", "SP_TH", "SP_MIN_STEP"))
     assert smin == 4 and tw * th == 256 and "#define SP_LCW ((SP_TW - 1) / SP_MIN_STEP + 4)" in text

@@ -50,9 +50,8 @@ def test_the_header_the_binding_and_the_makefile_name_it(L):
     import two_view_ref as T
     assert '#include "fit_common.h"' in text and "#define TV_THREADS %d\n" % T.THREADS in text and "#define TV_PER_LANE %d " % T.PER_LANE in text and "#define TV_SWEEPS %d\n" % T.SWEEPS in text
     assert float(re.search(r"#define TV_SIGMA2_MIN (\S+)", text).group(1)) == T.SIGMA2_MIN
-    for helper in ("bool mf_part(", "uint32_t mf_grid_pixel(", "void mf_block_add(", "void mf_load_model(", "struct MfArgs {"):
-        defs = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h")) and helper in open(os.path.join(csrc, n)).read()]
-        assert defs == ["fit_common.h"], helper
+    import fit_common_pins
+    fit_common_pins.check(csrc)
     # the gate adds no refusal text of its own to abi.hip, and lies after every slice the other tests cut out of it
     abi = open(os.path.join(csrc, "abi.hip")).read()
     assert abi.index("int dflow_two_view(") > abi.index("int dflow_remove_small_segments_host(")
