@@ -1,7 +1,9 @@
 // Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
-// segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip, label_conf.hip): a block's reduction and class counts, the exchanges of a 16-lane row, the four-pixel access to a flow plane and a
-// (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce or count;
-// every kernel keeps its own loop, launch function and workspace.
+// segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip, label_conf.hip, tracks.hip, superpixels.hip and, through fit_common.h,
+// the fits; union_find.h's root step): a block's reduction and class counts, a wave's lanes grouped by key, the rank of a block's
+// flagged threads, the one-block scan of block sums, the exchanges of a 16-lane row, the four-pixel access to a flow plane and a
+// (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce, rank or
+// count; every kernel keeps its own loop, launch function and workspace.
 #pragma once
 #include "dflow_common.h"
 #include "jet_lut.h"
@@ -56,6 +58,77 @@ template <int N> __device__ static inline void block_count_class(int kind, int32
 #pragma unroll
     for (int k = 0; k < N; k++) is[k] = kind == k;
     block_count<N>(is, counts, offset);
+}
+
+// ---- a wave's lanes grouped by key (union_find.h's root step; superpixels.hip: sf_acc_kernel, sf_apply_kernel): one round per
+// distinct key among the lanes that have `pending`, in the order of each key's first lane.  f(key, mine, is_leader) is called by
+// every lane of the wave in every round (it may ballot and shuffle): `mine` for the lanes that hold the round's key, `is_leader`
+// for the first of them.  Terminates: a round retires the first pending lane and every lane that shares its key, so there are at
+// most 64 rounds.  The loop's trip count depends on other lanes: every lane of the wave must arrive here.
+template <typename F> __device__ static inline void wave_each_key(bool pending, int key, F f)
+{
+    const int lane = threadIdx.x & 63;
+    for (;;) {
+        const unsigned long long todo = __ballot(pending);
+        if (!todo) break;
+        const int leader = __ffsll((long long)todo) - 1;
+        const int r = __shfl(key, leader);
+        const bool mine = pending && key == r;
+        f(r, mine, lane == leader);
+        if (mine) pending = false;
+    }
+}
+
+// `c` added to slot[key] once per wave and distinct key among the lanes that have `on`
+__device__ static inline void wave_add_by_key(bool on, int key, int *slot, int c)
+{
+    wave_each_key(on, key, [&](int r, bool mine, bool is_leader) {
+        const int cnt = __popcll(__ballot(mine));
+        if (is_leader) atomicAdd(&slot[r], cnt * c);
+    });
+}
+
+// ---- the flagged threads of a block in thread order (superpixels.hip: sp_merge_kernel, sp_number_kernel; tracks.hip:
+// seed_block_flags): the number of flagged lanes below the caller's in its wave, and s_wave[wave] = the wave's count.  No barrier
+// here: s_wave (one int per wave) is the caller's, valid after the caller's next __syncthreads, so that several rounds share one.
+__device__ static inline int block_rank(bool flag, int *s_wave)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long b = __ballot(flag);
+    if (lane == 0) s_wave[threadIdx.x >> 6] = __popcll(b);
+    return __popcll(b & ((1ull << lane) - 1ull));
+}
+
+// ---- one block of WAVES waves: sums[0 .. nb) become their exclusive prefix sums (a contiguous chunk per thread, the chunks'
+// totals scanned through the waves); the total is returned in every thread (superpixels.hip: sp_scan_kernel; tracks.hip:
+// track_seed_scan_kernel).  Every thread of the block calls it.
+template <int WAVES> __device__ static inline int block_scan_sums(int nb, int32_t *__restrict__ sums)
+{
+    __shared__ int s_part[WAVES];
+    const int chunk = (nb + WAVES * 64 - 1) / (WAVES * 64), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
+    int sum = 0;
+    for (int j = lo; j < hi; j++) sum += sums[j];
+    int incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += t;
+    }
+    if (lane == 63) s_part[wave] = incl;
+    __syncthreads();
+    int before = incl - sum, total = 0;
+#pragma unroll
+    for (int k = 0; k < WAVES; k++) {
+        if (k < wave) before += s_part[k];
+        total += s_part[k];
+    }
+    for (int j = lo; j < hi; j++) {
+        const int v = sums[j];
+        sums[j] = before;
+        before += v;
+    }
+    return total;
 }
 
 // ---- a pixel per 16-lane DPP row (prior.hip, label_conf.hip): exchanges inside the row and the row's minimum

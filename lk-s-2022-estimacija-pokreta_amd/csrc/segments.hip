@@ -5,12 +5,15 @@
 //
 // Union-find with atomicMin (union_find.h, where the invariant and the termination arguments are): a label is the raster index
 // of a pixel of the same segment that is not larger than the pixel's own.  In global memory a find hangs its start under the
-// root it found (UF_HANG).  Four launches, whatever the field holds, and no workgroup waits for another:
-//   seg_tile_kernel    one workgroup per SEG_TW x SEG_TH tile: the tile's right and down joins merged in LDS, flattened, and
-//                      every pixel's label written as the raster index of its tile-local root (-1: no member); sizes zeroed;
-//   seg_border_kernel  one lane per join that crosses a tile border: the union of the two labels in global memory;
-//   seg_root_kernel    every pixel finds its root, which becomes its label, and adds itself to size[root], a wave's adds
-//                      aggregated per distinct root first;
+// root it found (UF_HANG).  Four launches, whatever the field holds, and no workgroup waits for another; the first three are
+// union_find.h's tile, border and root steps (the header lists their users) around this file's join test:
+//   seg_tile_kernel    one workgroup per SEG_TW x SEG_TH tile: the tile's vectors staged in LDS, then uf_tile_step: the right and
+//                      down joins merged in LDS, flattened, and every pixel's label written as the raster index of its
+//                      tile-local root (-1: no member); sizes zeroed;
+//   seg_border_kernel  one lane per join that crosses a tile border (uf_border_pair): the join re-tested from the flow and the
+//                      union of the two labels in global memory;
+//   seg_root_kernel    uf_root_step: every pixel finds its root, which becomes its label, and adds itself to size[root], a
+//                      wave's adds aggregated per distinct root first (wave_add_by_key, plane_ops.h);
 //   seg_write_kernel   d_out, the optional planes and the four counts (block_count, plane_ops.h).
 // The root of a segment is its smallest raster index.  Everything is integer or a copy of input bits; -ffp-contract=off and
 // the join test is one subtraction, fabsf and addition as written.
@@ -33,78 +36,27 @@ __global__ void __launch_bounds__(SEG_THREADS) seg_tile_kernel(int h, int w, con
                                                                int *__restrict__ label, int *__restrict__ size)
 {
     __shared__ float s_u[SEG_THREADS], s_v[SEG_THREADS];
-    __shared__ int s_lab[SEG_THREADS];                // tile-local index of a pixel of the same segment, -1: no member
     __shared__ unsigned char s_mem[SEG_THREADS];
-    const int t = threadIdx.x, lx = t % SEG_TW, ly = t / SEG_TW;
-    const int x = blockIdx.x * SEG_TW + lx, y = blockIdx.y * SEG_TH + ly;
-    const bool inside = x < w && y < h;               // ragged edge tiles: the pixels beyond the frame are no members
+    const int t = threadIdx.x, x = blockIdx.x * SEG_TW + t % SEG_TW, y = blockIdx.y * SEG_TH + t / SEG_TW;
     float u = 0.0f, v = 0.0f;
-    const bool member = inside && flow_good(flow, layout, (size_t)y * w + x, u, v);
-    s_u[t] = u; s_v[t] = v; s_mem[t] = member; s_lab[t] = member ? t : -1;
-    __syncthreads();
-    if (member) {
-        if (lx + 1 < SEG_TW && s_mem[t + 1] && seg_joined(u, v, s_u[t + 1], s_v[t + 1], thresh))
-            uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + 1);
-        if (ly + 1 < SEG_TH && s_mem[t + SEG_TW] && seg_joined(u, v, s_u[t + SEG_TW], s_v[t + SEG_TW], thresh))
-            uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + SEG_TW);
-    }
-    __syncthreads();
-    if (inside) {
-        int root = -1;
-        if (member) {
-            // the smallest tile-local index is the smallest raster index of the tile's part of the segment
-            const int r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t);
-            root = (blockIdx.y * SEG_TH + r / SEG_TW) * w + blockIdx.x * SEG_TW + r % SEG_TW;
-        }
-        label[(size_t)y * w + x] = root;
-        size[(size_t)y * w + x] = 0;
-    }
+    // ragged edge tiles: the pixels beyond the frame are no members
+    const bool member = x < w && y < h && flow_good(flow, layout, (size_t)y * w + x, u, v);
+    s_u[t] = u; s_v[t] = v; s_mem[t] = member;
+    uf_tile_step<SEG_TW, SEG_TH>(h, w, member, [&](int, int o) { return s_mem[o] && seg_joined(u, v, s_u[o], s_v[o], thresh); },
+                                 label, size);
 }
 
-// join k of the frame's tile borders: first the (ntx - 1) * h joins across vertical borders, then the (nty - 1) * w across
-// horizontal ones
 __global__ void __launch_bounds__(SEG_THREADS) seg_border_kernel(int h, int w, const float *__restrict__ flow, int layout, float thresh,
                                                                  int *label)
 {
-    const int nvert = ((w + SEG_TW - 1) / SEG_TW - 1) * h, nhorz = ((h + SEG_TH - 1) / SEG_TH - 1) * w;
-    int k = blockIdx.x * SEG_THREADS + threadIdx.x;
-    if (k >= nvert + nhorz) return;
     int p, q;
-    if (k < nvert) {
-        p = (k % h) * w + (k / h + 1) * SEG_TW - 1;   // the last column of a tile and the first of the next: below w
-        q = p + 1;
-    } else {
-        k -= nvert;
-        p = ((k / w + 1) * SEG_TH - 1) * w + k % w;   // the last row of a tile and the first of the next: below h
-        q = p + w;
-    }
+    if (!uf_border_pair<SEG_TW, SEG_TH>(h, w, blockIdx.x * SEG_THREADS + threadIdx.x, p, q)) return;
     float up, vp, uq, vq;
     if (flow_good(flow, layout, (size_t)p, up, vp) && flow_good(flow, layout, (size_t)q, uq, vq) && seg_joined(up, vp, uq, vq, thresh))
         uf_union<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(label, p, q);
 }
 
-__global__ void __launch_bounds__(SEG_THREADS) seg_root_kernel(int n, int *label, int *size)
-{
-    const int i = blockIdx.x * SEG_THREADS + threadIdx.x, lane = threadIdx.x & 63;
-    int root = -1;
-    if (i < n && __hip_atomic_load(&label[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 0) {
-        // no root changes any more; other lanes only replace a parent by the root above it, so either value leads there
-        root = uf_find<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(label, i);      // and label[i] = root (UF_HANG)
-    }
-    // one add per wave and distinct root.  Terminates: a round retires the first pending lane and every lane that shares its
-    // root, so there are at most 64 rounds.
-    bool pending = root >= 0;
-    for (;;) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int r = __shfl(root, leader);
-        const bool mine = pending && root == r;
-        const int c = __popcll(__ballot(mine));
-        if (lane == leader) atomicAdd(&size[r], c);
-        if (mine) pending = false;
-    }
-}
+__global__ void __launch_bounds__(SEG_THREADS) seg_root_kernel(int n, int *label, int *size) { uf_root_step<SEG_THREADS>(n, label, size); }
 
 #define SEG_COUNTS 4                                  // segments, segments removed, members, pixels removed
 
@@ -158,11 +110,10 @@ int launch_segment_filter(int H, int W, const float *flow, int layout, float thr
     seg_carve(ws, H, W, r);
     if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, SEG_COUNTS * sizeof(int32_t), s));
     const int n = H * W, ntx = (W + SEG_TW - 1) / SEG_TW, nty = (H + SEG_TH - 1) / SEG_TH;
-    const int nblocks = (n + SEG_THREADS - 1) / SEG_THREADS, njoins = (ntx - 1) * H + (nty - 1) * W;
+    const int nblocks = (n + SEG_THREADS - 1) / SEG_THREADS;
     hipLaunchKernelGGL(seg_tile_kernel, dim3(ntx, nty), dim3(SEG_THREADS), 0, s, H, W, flow, layout, thresh, r.label, r.size);
-    // a frame of one tile has no border joins: the grid keeps one block, whose lanes all return, so that the launches are four
-    hipLaunchKernelGGL(seg_border_kernel, dim3((njoins + SEG_THREADS - 1) / SEG_THREADS > 0 ? (njoins + SEG_THREADS - 1) / SEG_THREADS : 1),
-                       dim3(SEG_THREADS), 0, s, H, W, flow, layout, thresh, r.label);
+    hipLaunchKernelGGL(seg_border_kernel, dim3(uf_border_blocks<SEG_TW, SEG_TH>(H, W)), dim3(SEG_THREADS), 0, s, H, W, flow, layout,
+                       thresh, r.label);
     hipLaunchKernelGGL(seg_root_kernel, dim3(nblocks), dim3(SEG_THREADS), 0, s, n, r.label, r.size);
     hipLaunchKernelGGL(seg_write_kernel, dim3(nblocks), dim3(SEG_THREADS), 0, s, n, (const float *)flow, layout, min_size,
                        (int)((flags & DFLOW_SEG_KEEP_SINGLETONS) != 0), (const int *)r.label, (const int *)r.size, out, segment, size,

@@ -9,15 +9,16 @@
 //                      keys (D' << 22 | k, 64-bit) from two 32-bit squared distances; the tile's partial sums in LDS by 32-bit
 //                      integer atomics; one global integer atomic per (tile, centre, field) that is non-zero
 //   sp_update_kernel   a thread per centre: the rounded 64-bit integer mean, the sums zeroed for the next iteration
-//   sp_tile_kernel, sp_border_kernel, sp_root_kernel   the components of equal SLIC label: segments.hip's pattern (union_find.h)
-//                      with "same label" as the join test
+//   sp_tile_kernel, sp_border_kernel, sp_root_kernel   the components of equal SLIC label: union_find.h's tile, border and root
+//                      steps (uf_tile_step, uf_border_pair, uf_root_step) with "same label" as the join test
 //   sp_merge_kernel    a lane per component root: the end of its chain of targets, the count of final roots per block
-//   sp_scan_kernel     one block: the block counts become their exclusive prefix sums (tracks.hip's scan)
-//   sp_number_kernel   final roots take their number, the others add their size to their final root's
+//                      (block_rank, plane_ops.h)
+//   sp_scan_kernel     one block: the block counts become their exclusive prefix sums (block_scan_sums, plane_ops.h)
+//   sp_number_kernel   final roots take their number (block_rank again), the others add their size to their final root's
 //   sp_write_kernel    a lane per pixel: the final number, the raw label, the counts
 // dflow_segment_fit, 2 rounds + 1 launches:
 //   sf_acc_kernel      a lane per pixel, a wave per 8 x 8 square: the twelve int64 sums of its segment, a wave's adds aggregated
-//                      per distinct label first (shuffle tree), then 64-bit integer atomics
+//                      per distinct label first (wave_each_key, plane_ops.h; a shuffle tree per sum), then 64-bit integer atomics
 //   sf_solve_kernel    a thread per segment: the two 3x3 normal systems in float64 (step E of the motion fit, fit_common.h's
 //                      fit_affine_from_sums, with the flow as the right-hand side), or the translation, or nothing
 //   sf_apply_kernel    a lane per pixel: the model's flow, the class, the counts
@@ -138,75 +139,27 @@ __global__ void __launch_bounds__(SP_THREADS) sp_update_kernel(SpGrid g, int32_t
     block_count<1>(is, counts, 1);
 }
 
-// ---- the 4-connected components of equal SLIC label: every pixel is a member
+// ---- the 4-connected components of equal SLIC label (union_find.h's tile, border and root steps): every pixel of the frame is a
+// member, and a SLIC label is >= 0, so no member's equals the -1 beyond the frame
 __global__ void __launch_bounds__(SP_THREADS) sp_tile_kernel(int h, int w, const int32_t *__restrict__ slic, int *__restrict__ comp,
                                                              int *__restrict__ size)
 {
-    __shared__ int s_val[SP_THREADS];
-    __shared__ int s_lab[SP_THREADS];
-    const int t = threadIdx.x, lx = t % SP_TW, ly = t / SP_TW;
-    const int x = blockIdx.x * SP_TW + lx, y = blockIdx.y * SP_TH + ly;
+    __shared__ int s_val[SP_THREADS];                 // the SLIC label, -1 (no label) beyond the frame
+    const int t = threadIdx.x, x = blockIdx.x * SP_TW + t % SP_TW, y = blockIdx.y * SP_TH + t / SP_TW;
     const bool inside = x < w && y < h;
-    const int v = inside ? slic[(size_t)y * w + x] : -1 - t;          // beyond the frame: a value nobody shares
-    s_val[t] = v; s_lab[t] = t;
-    __syncthreads();
-    if (inside) {
-        if (lx + 1 < SP_TW && s_val[t + 1] == v) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + 1);
-        if (ly + 1 < SP_TH && s_val[t + SP_TW] == v) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t, t + SP_TW);
-    }
-    __syncthreads();
-    if (inside) {
-        const int r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, t);
-        comp[(size_t)y * w + x] = (blockIdx.y * SP_TH + r / SP_TW) * w + blockIdx.x * SP_TW + r % SP_TW;
-        size[(size_t)y * w + x] = 0;
-    }
+    const int v = inside ? slic[(size_t)y * w + x] : -1;
+    s_val[t] = v;
+    uf_tile_step<SP_TW, SP_TH>(h, w, inside, [&](int, int o) { return s_val[o] == v; }, comp, size);
 }
 
-// join k of the frame's tile borders: first the (ntx - 1) * h joins across vertical borders, then the (nty - 1) * w across
-// horizontal ones
 __global__ void __launch_bounds__(SP_THREADS) sp_border_kernel(int h, int w, const int32_t *__restrict__ slic, int *comp)
 {
-    const int nvert = ((w + SP_TW - 1) / SP_TW - 1) * h, nhorz = ((h + SP_TH - 1) / SP_TH - 1) * w;
-    int k = blockIdx.x * SP_THREADS + threadIdx.x;
-    if (k >= nvert + nhorz) return;
     int p, q;
-    if (k < nvert) {
-        p = (k % h) * w + (k / h + 1) * SP_TW - 1;
-        q = p + 1;
-    } else {
-        k -= nvert;
-        p = ((k / w + 1) * SP_TH - 1) * w + k % w;
-        q = p + w;
-    }
+    if (!uf_border_pair<SP_TW, SP_TH>(h, w, blockIdx.x * SP_THREADS + threadIdx.x, p, q)) return;
     if (slic[p] == slic[q]) uf_union<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(comp, p, q);
 }
 
-// `c` added to slot[key] once per wave and distinct key among the lanes that have `on`.  Terminates: a round retires the first
-// pending lane and every lane that shares its key, so there are at most 64 rounds.
-__device__ static inline void sp_wave_add(bool on, int key, int *slot, int c)
-{
-    const int lane = threadIdx.x & 63;
-    bool pending = on;
-    for (;;) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int r = __shfl(key, leader);
-        const bool mine = pending && key == r;
-        const int cnt = __popcll(__ballot(mine));
-        if (lane == leader) atomicAdd(&slot[r], cnt * c);
-        if (mine) pending = false;
-    }
-}
-
-__global__ void __launch_bounds__(SP_THREADS) sp_root_kernel(int n, int *comp, int *size)
-{
-    const int i = blockIdx.x * SP_THREADS + threadIdx.x;
-    int root = -1;
-    // no root changes any more; other lanes only replace a parent by the root above it, so either value leads there
-    if (i < n) root = uf_find<__HIP_MEMORY_SCOPE_AGENT, UF_HANG>(comp, i);                 // and comp[i] = root (UF_HANG)
-    sp_wave_add(root >= 0, root, size, 1);
-}
+__global__ void __launch_bounds__(SP_THREADS) sp_root_kernel(int n, int *comp, int *size) { uf_root_step<SP_THREADS>(n, comp, size); }
 
 // The end of a root's chain of targets (fin[root]); comp and size are read only.  A step goes to the root of the pixel to the
 // left of the root pixel, or above it in column 0: a smaller index, so the walk ends, at pixel 0 at the latest.
@@ -225,8 +178,7 @@ __global__ void __launch_bounds__(SP_THREADS) sp_merge_kernel(int n, int w, int 
         fin[i] = r;
         final_root = r == i;
     }
-    const int c = __popcll(__ballot(final_root));
-    if ((threadIdx.x & 63) == 0) s_fin[threadIdx.x >> 6] = c;
+    block_rank(final_root, s_fin);
     __syncthreads();
     if (threadIdx.x == 0) {
         int sum = 0;
@@ -238,34 +190,11 @@ __global__ void __launch_bounds__(SP_THREADS) sp_merge_kernel(int n, int w, int 
     block_count<2>(is, counts, 2);
 }
 
-// One block: the block sums become their exclusive prefix sums (a contiguous chunk per thread, the chunks' totals scanned through
-// the waves); block_sums[nb] and counts[5] = the total, n_seg.
+// One block: the block sums become their exclusive prefix sums (block_scan_sums, plane_ops.h); block_sums[nb] and counts[5] = the
+// total, n_seg.
 __global__ void __launch_bounds__(SP_THREADS) sp_scan_kernel(int nb, int32_t *__restrict__ block_sums, int32_t *counts)
 {
-    __shared__ int s_part[SP_WAVES];
-    const int chunk = (nb + SP_THREADS - 1) / SP_THREADS, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
-    int sum = 0;
-    for (int j = lo; j < hi; j++) sum += block_sums[j];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int before = incl - sum, total = 0;
-#pragma unroll
-    for (int k = 0; k < SP_WAVES; k++) {
-        if (k < wave) before += s_part[k];
-        total += s_part[k];
-    }
-    for (int j = lo; j < hi; j++) {
-        const int v = block_sums[j];
-        block_sums[j] = before;
-        before += v;
-    }
+    const int total = block_scan_sums<SP_WAVES>(nb, block_sums);
     if (threadIdx.x == 0) {
         block_sums[nb] = total;
         if (counts) counts[5] = total;
@@ -278,18 +207,17 @@ __global__ void __launch_bounds__(SP_THREADS) sp_number_kernel(int n, const int 
                                                                const int32_t *__restrict__ block_sums)
 {
     __shared__ int s_fin[SP_WAVES];
-    const int i = blockIdx.x * SP_THREADS + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * SP_THREADS + threadIdx.x, wave = threadIdx.x >> 6;
     bool final_root = false;
     if (i < n && comp[i] == i) {
         const int f = fin[i];
         final_root = f == i;
         if (!final_root) atomicAdd(&size[f], size[i]);
     }
-    const unsigned long long b = __ballot(final_root);
-    if (lane == 0) s_fin[wave] = __popcll(b);
+    const int rank = block_rank(final_root, s_fin);
     __syncthreads();
     if (final_root) {
-        int number = block_sums[blockIdx.x] + __popcll(b & ((1ull << lane) - 1ull));
+        int number = block_sums[blockIdx.x] + rank;
         for (int k = 0; k < wave; k++) number += s_fin[k];
         fin[i] = -1 - number;
     }
@@ -330,7 +258,6 @@ int launch_superpixels(int H, int W, const uint8_t *bgr, int step, int compactne
     static_assert(4096ull * 3 * 4080 * 4080 + 65025ull * 2 * 4096 * 4096 < 1ull << (64 - SP_KEY_BITS), "the key fits 64 bits");
     const int n = H * W, ntx = (W + SP_TW - 1) / SP_TW, nty = (H + SP_TH - 1) / SP_TH;
     const int nb = (n + SP_THREADS - 1) / SP_THREADS, kb = (g.K + SP_THREADS - 1) / SP_THREADS;
-    const int njoins = (ntx - 1) * H + (nty - 1) * W, jb = (njoins + SP_THREADS - 1) / SP_THREADS;
     uint32_t *usums = reinterpret_cast<uint32_t *>(sums);
     if (counts) DFLOW_HIP(hipMemsetAsync(counts, 0, SP_COUNTS * sizeof(int32_t), s));
     hipLaunchKernelGGL(sp_init_kernel, dim3(kb), dim3(SP_THREADS), 0, s, g, bgr, centers, usums, counts);
@@ -341,8 +268,8 @@ int launch_superpixels(int H, int W, const uint8_t *bgr, int step, int compactne
         hipLaunchKernelGGL(sp_update_kernel, dim3(kb), dim3(SP_THREADS), 0, s, g, centers, usums, last ? counts : nullptr);
     }
     hipLaunchKernelGGL(sp_tile_kernel, dim3(ntx, nty), dim3(SP_THREADS), 0, s, H, W, (const int32_t *)label, comp, size);
-    // a frame of one tile has no border joins: the grid keeps one block, whose lanes all return, so that the launches are the same
-    hipLaunchKernelGGL(sp_border_kernel, dim3(jb > 0 ? jb : 1), dim3(SP_THREADS), 0, s, H, W, (const int32_t *)label, comp);
+    hipLaunchKernelGGL(sp_border_kernel, dim3(uf_border_blocks<SP_TW, SP_TH>(H, W)), dim3(SP_THREADS), 0, s, H, W, (const int32_t *)label,
+                       comp);
     hipLaunchKernelGGL(sp_root_kernel, dim3(nb), dim3(SP_THREADS), 0, s, n, comp, size);
     hipLaunchKernelGGL(sp_merge_kernel, dim3(nb), dim3(SP_THREADS), 0, s, n, W, min_size, (const int *)comp, (const int *)size, fin, scan,
                        counts);
@@ -414,29 +341,22 @@ __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round,
             }
         }
     }
-    // one add per wave, distinct label and sum.  Terminates as sp_wave_add does.
-    bool pending = round == 0 ? l >= 0 : part;
-    for (;;) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;
-        const int leader = __ffsll((long long)todo) - 1;
-        const int r = __shfl(l, leader);
-        const bool mine = pending && l == r;
+    // one add per wave, distinct label and sum
+    wave_each_key(round == 0 ? l >= 0 : part, l, [&](int r, bool mine, bool is_leader) {
         const int c_all = __popcll(__ballot(mine)), c_part = __popcll(__ballot(mine && part));
         if (c_part) {                                 // uniform
             unsigned long long *acc = a.acc + (size_t)r * FIT_NSUMS;
-            if (lane == leader) atomicAdd(&acc[0], (unsigned long long)c_part);
+            if (is_leader) atomicAdd(&acc[0], (unsigned long long)c_part);
 #pragma unroll
             for (int k = 0; k < FIT_NSUMS - 1; k++) {
                 long long sum = mine && part ? v[k] : 0;
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-                if (lane == leader && sum) atomicAdd(&acc[1 + k], (unsigned long long)sum);
+                if (is_leader && sum) atomicAdd(&acc[1 + k], (unsigned long long)sum);
             }
         }
-        if (round == 0 && lane == leader) atomicAdd(&a.seg_counts[(size_t)r * 4], c_all);
-        if (mine) pending = false;
-    }
+        if (round == 0 && is_leader) atomicAdd(&a.seg_counts[(size_t)r * 4], c_all);
+    });
 }
 
 // counts: NULL but in the last round
@@ -501,7 +421,7 @@ __global__ void __launch_bounds__(SP_THREADS) sf_apply_kernel(SfArgs a, float *_
         if (out) reinterpret_cast<FlowOut *>(out)[i] = o;
         if (cls) cls[i] = (uint8_t)(!part ? 0 : !kind ? 3 : agree ? 1 : 2);
     }
-    sp_wave_add(agree, l * 4 + 2, a.seg_counts, 1);                  // l < 2^26
+    wave_add_by_key(agree, l * 4 + 2, a.seg_counts, 1);              // l < 2^26
     const bool is0[2] = {part, agree}, is5[2] = {bad_label, bad_range};
     block_count<2>(is0, counts, 0);
     block_count<2>(is5, counts, 5);

@@ -6,8 +6,9 @@
 // One track (track_advance_kernel, track_mark_kernel, track_claim_kernel) or one cell / pixel per lane, 256 threads per block; a
 // position is one 8-byte load, the corners of a bilinear sample through flow_good (dflow_common.h), the counts through block_count /
 // block_count_class (plane_ops.h).  One IEEE float32 operation per written operation (-ffp-contract=off).  A lane touches only its
-// own slot, so dflow_track_advance runs in place.  The seed's compaction is per-block counts, one block that scans the block sums
-// and an emit that repeats the block's own scan: no workgroup waits for another.
+// own slot, so dflow_track_advance runs in place.  The seed's compaction is per-block counts (block_rank, plane_ops.h), one block
+// that scans the block sums (block_scan_sums, plane_ops.h; superpixels.hip numbers its segments the same way) and an emit that
+// repeats the block's own ranks: no workgroup waits for another.
 #include <math.h>
 #include "plane_ops.h"
 
@@ -147,14 +148,12 @@ __device__ static inline bool seed_seedable(const SeedGrid &g, const int32_t *__
 __device__ static inline void seed_block_flags(const SeedGrid &g, const int32_t *__restrict__ cells, const uint8_t *__restrict__ mask,
                                                int32_t *counts, bool (&is)[TRK_SEED_ROUNDS], int (&rank)[TRK_SEED_ROUNDS], int *s_wave)
 {
-    const int base = blockIdx.x * TRK_SEED_CELLS, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int base = blockIdx.x * TRK_SEED_CELLS;
 #pragma unroll
     for (int k = 0; k < TRK_SEED_ROUNDS; k++) {
         bool covered;
         is[k] = seed_seedable(g, cells, mask, base + k * TRK_THREADS + (int)threadIdx.x, covered);
-        const uint64_t b = __ballot(is[k]);
-        rank[k] = __popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0) s_wave[k * TRK_WAVES + wave] = __popcll(b);
+        rank[k] = block_rank(is[k], s_wave + k * TRK_WAVES);
         block_count_class<1>(covered ? 0 : -1, counts, 0);
     }
     __syncthreads();
@@ -175,35 +174,12 @@ __global__ void __launch_bounds__(TRK_THREADS) track_seed_count_kernel(SeedGrid 
     }
 }
 
-// One block: the block sums become their exclusive prefix sums (a contiguous chunk per thread, the chunks' totals scanned through
-// the waves), the n the call started from is kept for the emit, *d_n and the counts are set.
+// One block: the block sums become their exclusive prefix sums (block_scan_sums, plane_ops.h), the n the call started from is kept
+// for the emit, *d_n and the counts are set.
 __global__ void __launch_bounds__(TRK_THREADS) track_seed_scan_kernel(int nb, int cap, int32_t *__restrict__ block_sums, int32_t *d_n,
                                                                       int32_t *counts)
 {
-    __shared__ int s_part[TRK_WAVES];
-    const int chunk = (nb + TRK_THREADS - 1) / TRK_THREADS, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
-    int sum = 0;
-    for (int j = lo; j < hi; j++) sum += block_sums[j];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_part[wave] = incl;
-    __syncthreads();
-    int before = incl - sum, total = 0;
-#pragma unroll
-    for (int k = 0; k < TRK_WAVES; k++) {
-        if (k < wave) before += s_part[k];
-        total += s_part[k];
-    }
-    for (int j = lo; j < hi; j++) {
-        const int v = block_sums[j];
-        block_sums[j] = before;
-        before += v;
-    }
+    const int total = block_scan_sums<TRK_WAVES>(nb, block_sums);
     if (threadIdx.x == 0) {
         const int n = seed_clamp_n(d_n, cap), seeded = min(total, cap - n);
         block_sums[nb] = n;

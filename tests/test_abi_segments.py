@@ -29,6 +29,9 @@ def test_the_header_declares_it(L):
     makefile = open(os.path.join(ROOT, PKG, "csrc", "Makefile")).read()
     assert "segments.hip" in makefile
     assert "dflow_segment_filter" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    # the tile, border and root steps are union_find.h's, one definition each
+    import component_pins
+    component_pins.check(os.path.join(ROOT, PKG, "csrc"))
 
 
 def test_workspace_bytes(L):

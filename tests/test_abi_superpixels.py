@@ -60,6 +60,9 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
     assert "dflow_set_error(" not in gate
     text = open(os.path.join(csrc, "superpixels.hip")).read()
     assert '#include "union_find.h"' in text and "superpixel" not in open(os.path.join(csrc, "segments.hip")).read()
+    # and the labelling steps, the leader loop, the rank and the scan the two share are one definition each, in the headers
+    import component_pins
+    component_pins.check(csrc)
     # the segment fit's affine solve is the motion fit's step E: one definition, shared
     import fit_common_pins
     fit_common_pins.check(csrc)

@@ -48,6 +48,9 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
         assert re.search(r"#define DFLOW_TRACK_%s %d\b" % (state, k), header) and getattr(L, "TRACK_" + state) == k
     text = open(os.path.join(csrc, "tracks.hip")).read()
     assert "block_count_class<" in text and "flow_good(" in text and "asm" not in text and "__launch_bounds__(TRK_THREADS)" in text
+    # the seed's rank and scan are plane_ops.h's, one definition each
+    import component_pins
+    component_pins.check(csrc)
     # the gates add no refusal text of their own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()
     gate = abi[abi.index("int dflow_track_advance("):abi.index("int dflow_remove_small_segments_host(")]

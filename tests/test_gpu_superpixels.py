@@ -2,7 +2,8 @@
 byte on every output plane and count, with every plane exact-size between guards at its lowest alignment (ws_guard.GuardedWs);
 the properties the header promises checked with this file's own search, independently of the restatement; the recovery of a
 piecewise-affine field under gross outliers; a graph capture.  Shapes are chosen where the kernels can go wrong (ragged cells
-and tiles, one row, one column, one centre, the most centres per tile), not where the workload lives.  Run with `pytest -m gpu`."""
+and tiles, one row, one column, one centre, the most centres per tile, more block sums than the scan's block has threads), not
+where the workload lives.  Run with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
@@ -111,7 +112,10 @@ CASES = [(37, 53, 8, 10, 10, 16, "synth"), (37, 53, 8, 10, 2, 64, "noise"), (37,
          (64, 96, 16, 0, 10, 64, "synth"), (64, 96, 16, 10, 10, 64, "synth"), (64, 96, 16, 255, 10, 64, "synth"),
          (64, 96, 16, 10, 2, 256, "noise"), (64, 96, 16, 10, 1, 1, "noise"), (64, 96, 16, 10, 10, 8, "stripes"),
          (48, 80, 4, 10, 10, 4, "synth"), (48, 80, 4, 10, 2, 16, "noise"), (48, 80, 4, 0, 10, 0, "noise"), (48, 80, 4, 255, 10, 8, "uniform"),
-         (33, 67, 5, 30, 2, 1 << 26, "noise")]
+         (33, 67, 5, 30, 2, 1 << 26, "noise"),
+         # the smallest frame whose 259 block sums are more than one per thread of the scan's block, the last chunk ragged;
+         # 3876 final roots over those blocks (one iteration: the restatement takes a third of a second)
+         (257, 257, 8, 10, 1, 3, "noise")]
 
 
 def own_components(lab):
