@@ -26,6 +26,7 @@
 //                      workgroups per CU (the measured optimum), so with the chains of 8 passes in one
 //                      launch the kernel runs in a throughput regime instead of waiting on one chain step at a time.
 #include "dflow_common.h"
+#include "wave_ops.h"
 
 #define BCD_THREADS 192
 #ifndef BCD_MINWAVES
@@ -126,26 +127,7 @@ static_assert(BCD_RANGE_BYTES % 256 == 0 && BCD_RANGE_BYTES >= 256 && BCD_RANGE_
 static_assert(BCD_RANGE_BYTES + BCD_RANGE_ENTRIES * BCD_RANGE_PITCH * 4 <= BCD_LISTS_WAVE_LDS && BCD_LISTS_WAVE_LDS >= 1024, "a wave's LDS");
 static_assert(BCD_RANGE_PITCH >= BCD_MASK_WORDS && BCD_RANGE_PITCH <= 8, "prefix-set entry pitch");
 
-// What one lane wrote to LDS, every lane of the same wave may read after this (LDS serves a wave's requests in order: nothing to
-// wait for, the compiler just must not move the accesses across)
-__device__ static inline void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// the value of the lane CTRL points at; 0 where there is no such lane or the row is not in ROWS
-template <int CTRL, int ROWS = 0xF> __device__ static inline uint32_t dpp_or0(uint32_t v)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xF, false);
-}
-// inclusive scans over the 64 lanes: row_shr 1, 2, 4, 8, then lane 15 of a row into the next row, lane 31 into rows 2 and 3
-__device__ static inline uint32_t wave_scan_add(uint32_t x)
-{
-    x += dpp_or0<0x111>(x); x += dpp_or0<0x112>(x); x += dpp_or0<0x114>(x); x += dpp_or0<0x118>(x);
-    x += dpp_or0<0x142, 0xA>(x); x += dpp_or0<0x143, 0xC>(x);
-    return x;
-}
+// the inclusive OR scan of a label set over the 64 lanes, with the steps of wave_scan_add (wave_ops.h)
 // (the words of a set step by step side by side: a DPP operand wants two idle states after its write, other words fill them)
 template <int CTRL, int ROWS = 0xF> __device__ static inline void sets_or_step(uint32_t (&x)[BCD_MASK_WORDS])
 {
@@ -154,18 +136,8 @@ template <int CTRL, int ROWS = 0xF> __device__ static inline void sets_or_step(u
 }
 __device__ static inline void wave_scan_or(uint32_t (&x)[BCD_MASK_WORDS])
 {
-    sets_or_step<0x111>(x); sets_or_step<0x112>(x); sets_or_step<0x114>(x); sets_or_step<0x118>(x);
-    sets_or_step<0x142, 0xA>(x); sets_or_step<0x143, 0xC>(x);
-}
-template <int CTRL, int ROWS = 0xF> __device__ static inline int dpp_min(int v)
-{
-    return min(v, __builtin_amdgcn_update_dpp(v, v, CTRL, ROWS, 0xF, false));
-}
-__device__ static inline int wave_min(int x)                 // wave-uniform
-{
-    x = dpp_min<0x111>(x); x = dpp_min<0x112>(x); x = dpp_min<0x114>(x); x = dpp_min<0x118>(x);
-    x = dpp_min<0x142, 0xA>(x); x = dpp_min<0x143, 0xC>(x);
-    return __builtin_amdgcn_readlane(x, 63);
+    sets_or_step<DPP_ROW_SHR(1)>(x); sets_or_step<DPP_ROW_SHR(2)>(x); sets_or_step<DPP_ROW_SHR(4)>(x); sets_or_step<DPP_ROW_SHR(8)>(x);
+    sets_or_step<DPP_ROW_BCAST15, 0xA>(x); sets_or_step<DPP_ROW_BCAST31, 0xC>(x);
 }
 __device__ static inline void sets_load(const uint32_t *e, uint32_t (&w)[BCD_MASK_WORDS])
 {
@@ -395,7 +367,7 @@ __global__ void __launch_bounds__(256, BCD_LISTS_WAVES) bcd_lists_kernel(int H, 
             wave_scan_or(a[2]);                              // the lane's last entry is final with that
 #pragma unroll
             for (int w = 0; w < BCD_MASK_WORDS; w++) {
-                const uint32_t lower_lanes = dpp_or0<0x138>(a[2][w]);                    // wave_shr:1
+                const uint32_t lower_lanes = dpp_or0<DPP_WAVE_SHR1>(a[2][w]);
                 a[0][w] |= lower_lanes; a[1][w] |= lower_lanes;
             }
 #pragma unroll
@@ -502,7 +474,9 @@ __global__ void __launch_bounds__(256, BCD_LISTS_WAVES) bcd_lists_kernel(int H, 
         // n..14 are cleared here (4 n <= 60), before the flag bits go into the first block's cost field
         const unsigned long long pp = (((unsigned long long)c1 << 32) | c0) & ~(~0ull << (4 * n));
         // second / third blocks: compacted per 64-label wave of a pixel in lane order (rank = number of lower lanes of the
-        // same pixel that own one); the first BCD_CAP_B / BCD_CAP_C owners get a slot
+        // same pixel that own one); the first BCD_CAP_B / BCD_CAP_C owners get a slot.  The three ranks of this lambda are
+        // wave_ops.h's lane_rank(mask) written out: calling it here changes this kernel's instruction sequence (DESIGN.md,
+        // "Wave primitives")
         const unsigned long long hasB = __ballot(cnt > BCD_BLK), hasC = __ballot(cnt > 2 * BCD_BLK);
         uint32_t rankB = __builtin_amdgcn_mbcnt_hi((uint32_t)(hasB >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hasB, 0u));
         uint32_t rankC = __builtin_amdgcn_mbcnt_hi((uint32_t)(hasC >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hasC, 0u));
@@ -587,25 +561,19 @@ template <int CTRL> __device__ static inline void cand_dpp(const Cand &a, double
 {
     // lanes without a source keep their own value (bound_ctrl = false, old = self)
     const int lo = __double2loint(a.v), hi = __double2hiint(a.v);
-    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
-    ok = __builtin_amdgcn_update_dpp(a.k, a.k, CTRL, 0xF, 0xF, false);
+    const int olo = dpp_i<CTRL>(lo), ohi = dpp_i<CTRL>(hi);
+    ok = dpp_i<CTRL>(a.k);
     ov = __hiloint2double(ohi, olo);
 }
-
-#define DPP_ROW_SHL1 0x101
-#define DPP_ROW_SHL2 0x102
-#define DPP_ROW_SHL4 0x104
-#define DPP_ROW_SHL8 0x108
 
 // lexicographic minimum over the 64 lanes of a wave, valid in lane 0
 __device__ static inline void wave_min_lane0(Cand &pm)
 {
     double ov; int ok;
-    cand_dpp<DPP_ROW_SHL1>(pm, ov, ok); cand_min(pm, ov, ok);
-    cand_dpp<DPP_ROW_SHL2>(pm, ov, ok); cand_min(pm, ov, ok);
-    cand_dpp<DPP_ROW_SHL4>(pm, ov, ok); cand_min(pm, ov, ok);
-    cand_dpp<DPP_ROW_SHL8>(pm, ov, ok); cand_min(pm, ov, ok);
+    cand_dpp<DPP_ROW_SHL(1)>(pm, ov, ok); cand_min(pm, ov, ok);
+    cand_dpp<DPP_ROW_SHL(2)>(pm, ov, ok); cand_min(pm, ov, ok);
+    cand_dpp<DPP_ROW_SHL(4)>(pm, ov, ok); cand_min(pm, ov, ok);
+    cand_dpp<DPP_ROW_SHL(8)>(pm, ov, ok); cand_min(pm, ov, ok);
     const int lo = __double2loint(pm.v), hi = __double2hiint(pm.v);
 #pragma unroll
     for (int r = 1; r < 4; r++) {
@@ -652,11 +620,6 @@ __device__ static inline unsigned long long wave_key_min_asm(unsigned long long 
     }
     *first_lane = fl;
     return ((unsigned long long)mh << 32) | ml;
-}
-
-__device__ static inline uint32_t lane_rank(unsigned long long mask)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 // One thread per label: 192 threads (3 waves) cover up to DFLOW_MAX_LABELS labels.

@@ -3,6 +3,7 @@
 // Dijkstra over the seed graph.
 #pragma once
 #include "dflow_common.h"
+#include "wave_ops.h"
 
 #define EPIC_CHUNK 4                        // Voronoi rounds launched between two reads of their change counters
 #define EPIC_ID_BITS 26                     // seed ids < 8192 * 8192
@@ -52,19 +53,6 @@ __device__ static inline bool is_seed(const float *__restrict__ sparse, int p)
 {
     const float u = sparse[3 * (size_t)p], v = sparse[3 * (size_t)p + 1], valid = sparse[3 * (size_t)p + 2];
     return valid > 0.5f && isfinite(u) && isfinite(v);
-}
-
-__device__ static inline uint64_t wave_min_u64(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t u = __shfl_xor(v, o); v = u < v ? u : v; }
-    return v;
-}
-__device__ static inline uint64_t wave_max_u64(uint64_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint64_t u = __shfl_xor(v, o); v = u > v ? u : v; }
-    return v;
 }
 
 // One wave walks the seed graph from seed s: the nn seeds nearest to s by (G, id), s itself first, in that order; every

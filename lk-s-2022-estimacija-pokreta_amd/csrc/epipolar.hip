@@ -22,6 +22,7 @@
 // best key with its offer, its adoption and its counts, and the classes.  The coordinates a chunk holds, the slots of a sample,
 // the solve, the score loop and the model a fit without a winner falls back to (all zeros) are this file's.
 #include "fit_common.h"
+#include "wave_ops.h"
 
 #define EP_STRIDE 8                                   // counter slots per round and sample: a slot per point, one to spare
 #define EP_BISECTIONS 60
@@ -240,8 +241,8 @@ __global__ void __launch_bounds__(FIT_THREADS) ep_score_kernel(EpArgs a)
 __global__ void __launch_bounds__(FIT_THREADS) ep_best_kernel(EpArgs a, int round)
 {
     const bool degenerate = fit_offer(a.f, blockIdx.x * FIT_THREADS + threadIdx.x, a.slots, round);
-    fit_block_add({fit_wave_count(degenerate)}, &a.f.state[EP_S_DEGEN]);
-    fit_block_add({fit_wave_count(degenerate && round == 0)}, &a.f.state[EP_S_DEGEN0]);
+    fit_block_add({wave_count(degenerate)}, &a.f.state[EP_S_DEGEN]);
+    fit_block_add({wave_count(degenerate && round == 0)}, &a.f.state[EP_S_DEGEN0]);
 }
 
 __global__ void ep_select_kernel(EpArgs a, int round)
@@ -275,8 +276,8 @@ __global__ void __launch_bounds__(FIT_THREADS) ep_apply_kernel(EpArgs a, uint8_t
         scored = fit_scored(a.f, good, excluded, x, y);
         scored_in = scored && in;
     }
-    fit_block_add({fit_wave_count(scored)}, &a.f.state[EP_S_SCORED]);
-    fit_block_add({fit_wave_count(scored_in)}, &a.f.state[EP_S_FINAL]);
+    fit_block_add({wave_count(scored)}, &a.f.state[EP_S_SCORED]);
+    fit_block_add({wave_count(scored_in)}, &a.f.state[EP_S_FINAL]);
 }
 
 __global__ void ep_finish_kernel(EpArgs a, int32_t *__restrict__ counts)

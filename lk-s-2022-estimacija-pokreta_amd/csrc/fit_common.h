@@ -135,13 +135,11 @@ __device__ __forceinline__ static int fit_stage_chunk(const MfArgs &a, float4 (&
     return np;
 }
 
-// how many lanes of the wave have `is`
-__device__ __forceinline__ static int fit_wave_count(bool is) { return (int)__popcll(__ballot(is)); }
-
 // N counts a wave has summed from its ballots, added to slots[0..N-1]: -> LDS -> one 64-bit integer atomic per block and count.
-// A single flag: fit_block_add({fit_wave_count(is)}, slot).  Calls may follow one another without a barrier between them: outside
-// the two barriers word k is touched by thread k alone, which reads it here before it clears it in the next call, and no wave
-// of the next call adds before thread k has come to that call's first barrier.  (Calls with another N have words of their own.)
+// A single flag: fit_block_add({wave_count(is)}, slot), with wave_ops.h's count.  Calls may follow one another without a barrier
+// between them: outside the two barriers word k is touched by thread k alone, which reads it here before it clears it in the next
+// call, and no wave of the next call adds before thread k has come to that call's first barrier.  (Calls with another N have
+// words of their own.)
 template <int N> __device__ __forceinline__ static void fit_block_add(const int (&w)[N], unsigned long long *slots)
 {
     __shared__ int s_c[N];

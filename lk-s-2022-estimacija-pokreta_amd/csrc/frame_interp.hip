@@ -15,6 +15,7 @@
 // per written operation (-ffp-contract=off).
 #include <math.h>
 #include "plane_ops.h"
+#include "wave_ops.h"
 
 #define FI_THREADS 256
 #define FI_FREE 0xFFFFFFFFFFFFFFFFull
@@ -84,7 +85,7 @@ __global__ void __launch_bounds__(FI_THREADS) fi_resolve_kernel(FiArgs a, float 
         reinterpret_cast<FlowOut *>(motion)[i] = m;
     }
     if (a.counts) {
-        const int c = __popcll(__ballot(won));
+        const int c = wave_count(won);
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_won, c);
         __syncthreads();
         if (threadIdx.x == 0 && s_won) atomicSub(&a.counts[FI_COUNTS - 1], s_won);

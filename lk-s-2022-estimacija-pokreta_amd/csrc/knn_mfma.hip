@@ -59,6 +59,7 @@
 #include "dflow_common.h"
 #include "knn_pca.h"
 #include "row_stage.h"
+#include "wave_ops.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -335,7 +336,7 @@ __global__ void __launch_bounds__(256) knn_cell_post_kernel(_Float16 *__restrict
         unsigned long long m = ~0ull;
 #pragma unroll
         for (int i = 4; i >= 0; i--) if (first || k5[i] > last) m = k5[i];              // smallest of mine above the last winner
-        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(m, off); m = o < m ? o : m; }
+        m = wave_min_u64(m);
         if (lane == 0) wmin[wave] = m;
         __syncthreads();
         m = wmin[0];
@@ -963,10 +964,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
             if (t < nA) en = t < 64 ? pre_a : ev[(size_t)t * 64];
             else if (t < nA + nB) { en = t - nA < 64 ? shb : ev[(size_t)(t - nA) * 64 + 32]; h = 1; }
             const int cntl = t < nA + nB ? __popc(en & 0xFFFFu) : 0;
-            int incl = cntl;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
-            const int nc = __shfl(incl, 63);                    // candidates of this batch (<= 1024)
+            const int incl = (int)wave_scan_add((uint32_t)cntl), nc = __shfl(incl, 63);      // nc: candidates of this batch (<= 1024)
             {
                 int o = incl - cntl;
                 const int tile = (int)(en >> 16);
@@ -991,9 +989,7 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
         unsigned long long rkey = KM_NO_KEY;
         float rcost = 0.0f;
         for (int r = 0; r < 5; r++) {
-            unsigned long long m = keys[0];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(m, off); m = o < m ? o : m; }
+            const unsigned long long m = wave_min_u64(keys[0]);
             const unsigned long long own = __ballot(keys[0] == m && m != KM_NO_KEY);
             float c = 0.0f;
             if (own) {
@@ -1018,8 +1014,8 @@ __global__ void __launch_bounds__(64, 2) knn_resolve_heavy_kernel(KmGeom a, KmRe
 // the (cost, slot) of the lane DPP control word CTRL selects, merged into this lane's lexicographic minimum
 template <int CTRL> __device__ static inline void dpp_lexmin(float &mind, int &best)
 {
-    const float om = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, mind), __builtin_bit_cast(int, mind), CTRL, 0xF, 0xF, false));
-    const int ob = __builtin_amdgcn_update_dpp(best, best, CTRL, 0xF, 0xF, false);
+    const float om = dpp_f<CTRL>(mind);
+    const int ob = dpp_i<CTRL>(best);
     if (om < mind || (om == mind && ob < best)) { mind = om; best = ob; }
 }
 __global__ void __launch_bounds__(256) knn_finalize_kernel(Geom g, int LP, uint32_t *__restrict__ proposals, float *__restrict__ lcosts,
@@ -1042,7 +1038,7 @@ __global__ void __launch_bounds__(256) knn_finalize_kernel(Geom g, int LP, uint3
 #pragma unroll
     for (int j = 0; j < DFLOW_MAX_LABELS / 16; j++) if (cs[j] < mind) { mind = cs[j]; best = sub + 16 * j; }
     // row_shl 1, 2, 4, 8: lane 0 of every 16-lane row ends with the row minimum
-    dpp_lexmin<0x101>(mind, best); dpp_lexmin<0x102>(mind, best); dpp_lexmin<0x104>(mind, best); dpp_lexmin<0x108>(mind, best);
+    dpp_lexmin<DPP_ROW_SHL(1)>(mind, best); dpp_lexmin<DPP_ROW_SHL(2)>(mind, best); dpp_lexmin<DPP_ROW_SHL(4)>(mind, best); dpp_lexmin<DPP_ROW_SHL(8)>(mind, best);
     if (ok) {
         if (sub == 0) { nprop[pix] = n; bestlabels[pix] = best == 0x7fffffff ? 0 : best; }
         for (int l = n + sub; l < LP; l += 16) { proposals[(size_t)pix * LP + l] = DFLOW_FILL_PROPOSAL; lcosts[(size_t)pix * LP + l] = DFLOW_FILL_COST; }
@@ -1214,9 +1210,9 @@ __global__ void __launch_bounds__(128) knn_stats_lists_kernel(KmGeom a, const ui
         const uint32_t *e = ev + lid * KM_LIST_WORDS(evrows) + (size_t)gq * evrows * 64 + lane;
         for (int i = 0; i < cnt; i++) events += (unsigned long long)__popc(e[i * 64] & 0xFFFFu);
     }
-    unsigned long long mx = entries;
-    for (int off = 32; off > 0; off >>= 1) { entries += __shfl_xor(entries, off); events += __shfl_xor(events, off); const unsigned long long o = __shfl_xor(mx, off); mx = o > mx ? o : mx; }
-    if (lane == 0) { atomicAdd(out + 0, entries); atomicAdd(out + 1, events); atomicMax(out + 2, mx); }
+    const auto add = [](unsigned long long &a, unsigned long long b) { a += b; };
+    const unsigned long long n_entries = wave_reduce_all(entries, add), n_events = wave_reduce_all(events, add), mx = wave_max_u64(entries);
+    if (lane == 0) { atomicAdd(out + 0, n_entries); atomicAdd(out + 1, n_events); atomicMax(out + 2, mx); }
 }
 
 __global__ void __launch_bounds__(256) knn_stats_rows_kernel(const float2 *__restrict__ qs, int npix, const uint8_t *__restrict__ zflag,

@@ -19,6 +19,7 @@
 // so d_out may be d_flow under [U,V,valid].
 #include <math.h>
 #include "plane_ops.h"
+#include "wave_ops.h"
 
 #define LC_TW 32
 #define LC_TH 8

@@ -20,6 +20,7 @@
 // (exact in any order of arrival); every float32 and float64 chain is one IEEE operation per written operation
 // (-ffp-contract=off).
 #include "fit_common.h"      // what every fit shares: the arguments, the draw, the chunk, the best key, the classes, step E
+#include "wave_ops.h"
 
 #define MF_STRIDE 4                                   // counter slots per round and hypothesis: a slot per point
 // d_state: int64[32]
@@ -171,7 +172,7 @@ template <bool HOMOG> __global__ void __launch_bounds__(FIT_THREADS) mf_score_ke
 __global__ void __launch_bounds__(FIT_THREADS) mf_best_kernel(MfArgs a, int round)
 {
     const bool degenerate = fit_offer(a, blockIdx.x * FIT_THREADS + threadIdx.x, a.n_hyp, round);
-    fit_block_add({fit_wave_count(degenerate)}, &a.state[MF_S_DEGEN]);
+    fit_block_add({wave_count(degenerate)}, &a.state[MF_S_DEGEN]);
 }
 
 __global__ void mf_select_kernel(MfArgs a, int round)
@@ -292,8 +293,8 @@ __global__ void __launch_bounds__(FIT_THREADS) mf_apply_kernel(MfArgs a, uint8_t
         scored = fit_scored(a, good, excluded, x, y);
         scored_in = scored && in;
     }
-    fit_block_add({fit_wave_count(scored)}, &a.state[MF_S_SCORED]);
-    fit_block_add({fit_wave_count(scored_in)}, &a.state[MF_S_FINAL]);
+    fit_block_add({wave_count(scored)}, &a.state[MF_S_SCORED]);
+    fit_block_add({wave_count(scored_in)}, &a.state[MF_S_FINAL]);
 }
 
 __global__ void mf_finish_kernel(MfArgs a, int32_t *__restrict__ counts)

@@ -1,16 +1,20 @@
 // Leaf device helpers of the image-plane stages (flow_eval.hip, flow_picture.hip, bcd_stats.hip, pyramid.hip, consistency.hip,
 // segments.hip, prior.hip, frame_interp.hip, flow_wmedian.hip, label_conf.hip, tracks.hip, superpixels.hip and, through fit_common.h,
 // the fits; union_find.h's root step): a block's reduction and class counts, a wave's lanes grouped by key, the rank of a block's
-// flagged threads, the one-block scan of block sums, the exchanges of a 16-lane row, the four-pixel access to a flow plane and a
-// (b, g, r) picture, and the bilinear sample of a picture with its photometric error.  They load, pack, sample, reduce, rank or
-// count; every kernel keeps its own loop, launch function and workspace.
+// flagged threads, the one-block scan of block sums, the four-pixel access to a flow plane and a (b, g, r) picture, and the bilinear
+// sample of a picture with its photometric error.  They load, pack, sample, reduce, rank or count; every kernel keeps its own
+// loop, launch function and workspace.  What else happens inside one wave (the scan, the count and rank of a
+// ballot, the exchanges and the minimum of a 16-lane DPP row that prior.hip and label_conf.hip use) is wave_ops.h's, included here.
 #pragma once
 #include "dflow_common.h"
 #include "jet_lut.h"
+#include "wave_ops.h"
 
 // ---- block reduce: the block's total of `a` in thread 0 (the other threads hold partial results).  A shuffle tree per wave
 // (64 lanes: offsets 32 .. 1), then lane 0 of every wave through LDS and thread 0 merges waves 1 .. WAVES - 1 in that order:
-// the order of every merge is fixed, so a double sum keeps its bits from call to call.  T travels dword by dword.
+// the order of every merge is fixed, so a double sum keeps its bits from call to call.  T travels dword by dword.  The tree stays
+// written out here, not a function of wave_ops.h: through a call mf_sums_kernel (motion_fit.hip) gets other device code
+// ("Wave primitives").
 template <int WAVES, typename T, typename Merge> __device__ static T block_reduce(T a, Merge merge)
 {
     static_assert(sizeof(T) % 4 == 0, "block_reduce shuffles whole dwords");
@@ -45,7 +49,7 @@ template <int N> __device__ static inline void block_count(const bool (&is)[N], 
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < N; k++) {
-        const int c = __popcll(__ballot(is[k]));
+        const int c = wave_count(is[k]);
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[k], c);
     }
     __syncthreads();
@@ -83,7 +87,7 @@ template <typename F> __device__ static inline void wave_each_key(bool pending, 
 __device__ static inline void wave_add_by_key(bool on, int key, int *slot, int c)
 {
     wave_each_key(on, key, [&](int r, bool mine, bool is_leader) {
-        const int cnt = __popcll(__ballot(mine));
+        const int cnt = wave_count(mine);
         if (is_leader) atomicAdd(&slot[r], cnt * c);
     });
 }
@@ -93,10 +97,9 @@ __device__ static inline void wave_add_by_key(bool on, int key, int *slot, int c
 // here: s_wave (one int per wave) is the caller's, valid after the caller's next __syncthreads, so that several rounds share one.
 __device__ static inline int block_rank(bool flag, int *s_wave)
 {
-    const int lane = threadIdx.x & 63;
     const unsigned long long b = __ballot(flag);
-    if (lane == 0) s_wave[threadIdx.x >> 6] = __popcll(b);
-    return __popcll(b & ((1ull << lane) - 1ull));
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(b);
+    return (int)lane_rank(b);
 }
 
 // ---- one block of WAVES waves: sums[0 .. nb) become their exclusive prefix sums (a contiguous chunk per thread, the chunks'
@@ -109,12 +112,7 @@ template <int WAVES> __device__ static inline int block_scan_sums(int nb, int32_
     const int lo = min((int)threadIdx.x * chunk, nb), hi = min(lo + chunk, nb);
     int sum = 0;
     for (int j = lo; j < hi; j++) sum += sums[j];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
+    const int incl = (int)wave_scan_add((uint32_t)sum);
     if (lane == 63) s_part[wave] = incl;
     __syncthreads();
     int before = incl - sum, total = 0;
@@ -129,24 +127,6 @@ template <int WAVES> __device__ static inline int block_scan_sums(int nb, int32_
         before += v;
     }
     return total;
-}
-
-// ---- a pixel per 16-lane DPP row (prior.hip, label_conf.hip): exchanges inside the row and the row's minimum
-// DPP controls (GFX9 encoding): quad_perm, row_ror:n, row_half_mirror
-#define DPP_QUAD_PERM(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
-#define DPP_ROW_ROR(n) (0x120 + (n))
-#define DPP_ROW_HALF_MIRROR 0x141
-template <int CTRL> __device__ static inline int dpp_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xF, 0xF, false); }
-template <int CTRL> __device__ static inline float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-
-// the minimum over the 16 lanes of a row, in every lane of it
-__device__ static inline int row_min16(int v)
-{
-    v = min(v, dpp_i<DPP_ROW_ROR(8)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(4)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(2)>(v));
-    v = min(v, dpp_i<DPP_ROW_ROR(1)>(v));
-    return v;
 }
 
 // ---- a plane as a flat array of h*w pixels, four pixels per lane and step, grid-stride over at most PLANE_MAX_BLOCKS blocks

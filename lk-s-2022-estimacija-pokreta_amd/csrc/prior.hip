@@ -11,6 +11,7 @@
 // hold the same bits), then the four-element tail in sequence.
 #include <math.h>
 #include "plane_ops.h"
+#include "wave_ops.h"
 
 #define PRIOR_THREADS 256
 #define PRIOR_ROW 16                                  // lanes per pixel: one DPP row
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(ADV_THREADS) advance_resolve_kernel(int H, int
         o[0] = u; o[1] = v; o[2] = valid;
     }
     if (counts) {
-        const int c = __popcll(__ballot(claimed));
+        const int c = wave_count(claimed);
         if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt, c);
         __syncthreads();
         if (threadIdx.x == 0 && s_cnt) { atomicAdd(&counts[0], s_cnt); atomicSub(&counts[1], s_cnt); }

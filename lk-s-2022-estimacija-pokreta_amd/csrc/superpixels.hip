@@ -26,6 +26,7 @@
 // written operation (-ffp-contract=off).
 #include "fit_common.h"
 #include "union_find.h"
+#include "wave_ops.h"
 
 #define SP_TW 32
 #define SP_TH 8
@@ -343,15 +344,13 @@ __global__ void __launch_bounds__(SP_THREADS) sf_acc_kernel(SfArgs a, int round,
     }
     // one add per wave, distinct label and sum
     wave_each_key(round == 0 ? l >= 0 : part, l, [&](int r, bool mine, bool is_leader) {
-        const int c_all = __popcll(__ballot(mine)), c_part = __popcll(__ballot(mine && part));
+        const int c_all = wave_count(mine), c_part = wave_count(mine && part);
         if (c_part) {                                 // uniform
             unsigned long long *acc = a.acc + (size_t)r * FIT_NSUMS;
             if (is_leader) atomicAdd(&acc[0], (unsigned long long)c_part);
 #pragma unroll
             for (int k = 0; k < FIT_NSUMS - 1; k++) {
-                long long sum = mine && part ? v[k] : 0;
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+                const long long sum = wave_reduce_all(mine && part ? v[k] : 0ll, [](long long &a, long long b) { a += b; });
                 if (is_leader && sum) atomicAdd(&acc[1 + k], (unsigned long long)sum);
             }
         }

@@ -19,6 +19,7 @@
 // 4 launches and one or two memsets whatever the planes hold.  Every count is an integer (exact in any order of arrival).
 // fit_common.h holds the frame and the grid of scored pixels, the nine coefficients and the block's counts as the fits use them.
 #include "fit_common.h"
+#include "wave_ops.h"
 
 #define TV_THREADS 256
 #define TV_PER_LANE 8                                 // pixels a lane takes: a block covers 2048 contiguous ones
@@ -242,14 +243,14 @@ __global__ void __launch_bounds__(TV_THREADS) tv_vote_kernel(TvArgs a)
 #pragma unroll
     for (int it = 0; it < TV_PER_LANE; it++) cover[it] = tv_voter(a, c0 + it * TV_THREADS, U[it], V[it]);    // every load in flight
 #pragma unroll
-    for (int it = 0; it < TV_PER_LANE; it++) total[4] += __popcll(__ballot(cover[it]));
+    for (int it = 0; it < TV_PER_LANE; it++) total[4] += wave_count(cover[it]);
     if (valid) {
 #pragma unroll 1
         for (int it = 0; it < TV_PER_LANE; it++) {
             bool vote[4] = {false, false, false, false};
             if (cover[it]) tv_vote_pixel(a, c0 + it * TV_THREADS, U[it], V[it], vote);
 #pragma unroll
-            for (int k = 0; k < 4; k++) total[k] += __popcll(__ballot(vote[k]));
+            for (int k = 0; k < 4; k++) total[k] += wave_count(vote[k]);
         }
     }
     fit_block_add(total, &a.f.state[TV_S_VOTE]);
@@ -339,7 +340,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_apply_kernel(TvArgs a, float *_
         const uint32_t i = i0 + it * TV_THREADS;
         const int k = i < a.f.n ? tv_apply_pixel(a, i, good[it], U[it], V[it], best, R, t, depth, cls, err) : 0;
 #pragma unroll
-        for (int q = 1; q <= 3; q++) total[q - 1] += __popcll(__ballot(k == q));
+        for (int q = 1; q <= 3; q++) total[q - 1] += wave_count(k == q);
     }
     fit_block_add(total, &a.f.state[TV_S_CLASS]);
 }

@@ -1,7 +1,8 @@
 """What csrc/union_find.h and csrc/plane_ops.h hold for segments.hip, superpixels.hip and tracks.hip, as source text: the grid steps
 of the component labelling, the leader loop, the in-block rank and the one-block scan are each defined once, in their header and
-nowhere else under csrc/; the telling line of each body occurs nowhere else (a copy under another name would carry it); the copies
-that were folded into them are gone; every kernel is still there under its own name.  The ABI tests of the three stages call this."""
+nowhere else under csrc/; the telling line of each body occurs nowhere else (a copy under another name would carry it; the scan
+step and the rank below a lane are wave_ops.h's wave_scan_add and lane_rank); the copies that were folded into them are gone; every
+kernel is still there under its own name.  The ABI tests of the three stages call this."""
 import os
 import re
 
@@ -9,16 +10,17 @@ import re
 DEFINITIONS = {"union_find.h": ("void uf_tile_step(", "int uf_border_joins(", "int uf_border_blocks(", "bool uf_border_pair(",
                                 "void uf_root_step(", "int uf_find(", "void uf_union("),
                "plane_ops.h": ("void wave_each_key(", "void wave_add_by_key(", "int block_rank(", "int block_scan_sums(")}
-# a line of each body: the leader pick, the scan step, the rank below a lane, the vertical- and horizontal-border index, the
-# never-zero grid, the hang
-BODIES = {"__ffsll((long long)todo) - 1": "plane_ops.h", "__shfl_up(incl, off, 64)": "plane_ops.h",
-          "b & ((1ull << lane) - 1ull)": "plane_ops.h", "(k % h) * w + (k / h + 1) *": "union_find.h",
+# a line of each body: the leader pick, the scan's last step, the rank below a lane, the vertical- and horizontal-border index,
+# the never-zero grid, the hang
+BODIES = {"__ffsll((long long)todo) - 1": "plane_ops.h", "x += dpp_or0<DPP_ROW_BCAST31, 0xC>(x)": "wave_ops.h",
+          "__builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)": "wave_ops.h", "(k % h) * w + (k / h + 1) *": "union_find.h",
           "- 1) * w + k % w": "union_find.h", "b > 0 ? b : 1": "union_find.h",
           "__hip_atomic_fetch_min(&L[start], x,": "union_find.h"}
 # the tile-local root as a raster index, whatever the tile's constants are called
 TILE_ROOT = re.compile(r"r / \w+\) \* w \+ .*r % \w+")
 GONE = ("sp_wave_add",)
-USERS = {"union_find.h": ("segments.hip", "superpixels.hip", "edges.hip"), "plane_ops.h": ("segments.hip", "tracks.hip", "union_find.h")}
+USERS = {"union_find.h": ("segments.hip", "superpixels.hip", "edges.hip"), "plane_ops.h": ("segments.hip", "tracks.hip", "union_find.h"),
+         "wave_ops.h": ("plane_ops.h",)}
 # every kernel keeps its file and its name, and is launched once in its launch function
 KERNELS = {"segments.hip": ("seg_tile_kernel", "seg_border_kernel", "seg_root_kernel", "seg_write_kernel"),
            "superpixels.hip": ("sp_tile_kernel", "sp_border_kernel", "sp_root_kernel", "sp_merge_kernel", "sp_scan_kernel",
@@ -36,6 +38,7 @@ CALLS = {"segments.hip": ("uf_tile_step<SEG_TW, SEG_TH>(", "uf_border_pair<SEG_T
 
 def check(csrc):
     texts = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h"))}
+    body = lambda t, start: t[t.index(start):t.index("\n}\n", t.index(start))]                  # noqa: E731
     for header, names in DEFINITIONS.items():
         for words in names:
             assert [n for n, t in texts.items() if words in t] == [header], words
@@ -55,11 +58,13 @@ def check(csrc):
         for k in kernels:
             assert len(re.findall(r"__global__ void __launch_bounds__\(\w+\) %s\(" % k, texts[n])) == 1, k
             assert texts[n].count("hipLaunchKernelGGL(%s," % k) == 1, k
+    # the rank and the scan are built on the wave's
+    assert "return (int)lane_rank(b);" in body(texts["plane_ops.h"], "int block_rank(")
+    assert "(int)wave_scan_add((uint32_t)sum)" in body(texts["plane_ops.h"], "int block_scan_sums(")
     for n, calls in CALLS.items():
         for words in calls:
             assert words in texts[n], (n, words)
     # the helpers place no barrier but the tile step's pair and the scan's one: seed_block_flags keeps its single one for four rounds
-    body = lambda t, start: t[t.index(start):t.index("\n}\n", t.index(start))]                  # noqa: E731
     assert "__syncthreads" not in body(texts["plane_ops.h"], "int block_rank(")
     assert "__syncthreads" not in body(texts["plane_ops.h"], "void wave_each_key(")
     assert body(texts["tracks.hip"], "void seed_block_flags(").count("__syncthreads()") == 1

@@ -133,6 +133,12 @@ def test_no_cpu_fallback(L):
         pkg("pipeline").DiscreteFlow(64, 64, 8, 8)
 
 
+def test_wave_primitives_have_one_definition_each():
+    # the DPP steps, reductions, scan, count and rank of the kNN, BCD and EPIC kernels are csrc/wave_ops.h's
+    import wave_ops_pins
+    wave_ops_pins.check(os.path.join(ROOT, pkg().__name__, "csrc"))
+
+
 def test_lamda_and_tphi_contract(L):
     """lamda and tphi must be finite and >= 0, and max(pich, picw) (3 tpsi + lamda tphi) < 800000 (include/dflow.h,
     DFLOW_DP_SENTINEL): outside it the chain kernel's unsigned minimum over tpsi + dp stops ordering like the doubles, or the

@@ -44,10 +44,11 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
     assert "#define DFLOW_CONF_LOCAL 0" in header and L.CONF_LOCAL == 0
     assert "#define DFLOW_CONF_DATA  1" in header and L.CONF_DATA == 1
     assert "#define DFLOW_CONF_COUNTS 6" in header and L.CONF_COUNTS == 6
-    # one copy of the row helpers, in plane_ops.h, and both users include it
+    # one copy of the row helpers, in wave_ops.h, and both users include it
     defs = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h")) and "int row_min16(" in open(os.path.join(csrc, n)).read()]
-    assert defs == ["plane_ops.h"]
+    assert defs == ["wave_ops.h"]
     text = open(os.path.join(csrc, "label_conf.hip")).read()
+    assert '#include "wave_ops.h"' in text and '#include "wave_ops.h"' in open(os.path.join(csrc, "prior.hip")).read()
     assert "row_min16(" in text and "flow_l1_biased(" in text and "flow_load4<" in text and "asm" not in text
     # the gates add no refusal text of their own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()

@@ -50,6 +50,9 @@ def test_the_header_the_binding_and_the_makefile_name_it(L):
     assert "flow_good(" in text and '#include "fit_common.h"' in text and "mf_gauss(" in text
     # what the fits share has one definition, and the one chunk is the one both restatements derive their frames from
     fit_common_pins.check(csrc, motion_ref.CHUNK, epipolar_ref.CHUNK)
+    # the count of a wave's flagged lanes and the tree of the polish sums are wave_ops.h's
+    import wave_ops_pins
+    wave_ops_pins.check(csrc)
     # the gate adds no refusal text of its own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()
     gate = abi[abi.index("int dflow_motion_fit("):abi.index("int dflow_remove_small_segments_host(")]

@@ -63,6 +63,9 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
     # and the labelling steps, the leader loop, the rank and the scan the two share are one definition each, in the headers
     import component_pins
     component_pins.check(csrc)
+    # what they and the accumulation do inside a wave is wave_ops.h's
+    import wave_ops_pins
+    wave_ops_pins.check(csrc)
     # the segment fit's affine solve is the motion fit's step E: one definition, shared
     import fit_common_pins
     fit_common_pins.check(csrc)

@@ -51,6 +51,9 @@ def test_the_header_the_binding_and_the_makefile_name_them(L):
     # the seed's rank and scan are plane_ops.h's, one definition each
     import component_pins
     component_pins.check(csrc)
+    # and what they do inside a wave is wave_ops.h's
+    import wave_ops_pins
+    wave_ops_pins.check(csrc)
     # the gates add no refusal text of their own to abi.hip
     abi = open(os.path.join(csrc, "abi.hip")).read()
     gate = abi[abi.index("int dflow_track_advance("):abi.index("int dflow_remove_small_segments_host(")]
