@@ -17,19 +17,18 @@ a '.flo' with (0,0).  --json prints one JSON object instead of the text.
 <flow>: '.flo' (Middlebury [u,v], every pixel valid) or '.npy': (H,W,2) the hot path's [dy,dx] fields, (H,W,3) [U,V,valid].
 Usage errors and unreadable input exit with status 2 before any GPU work.
 """
-import argparse
 import importlib
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 MAX_HYP = 21845
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("flow")
     ap.add_argument("--thresh", type=float, default=1.0, metavar="T")
     ap.add_argument("--hyp", type=int, default=512, metavar="N")
@@ -57,23 +56,20 @@ def gated(flow, cls, np):
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
-    if not (a.thresh == a.thresh and 0.0 < a.thresh < float("inf")):
-        ap.error("--thresh must be finite and > 0")
+    cli.positive(ap, "--thresh", a.thresh)
     for name, v, lo, hi in (("--hyp", a.hyp, 1, MAX_HYP), ("--lo-rounds", a.lo_rounds, 0, 4), ("--step", a.step, 1, 64),
                             ("--seed", a.seed, 0, 2 ** 64 - 1)):
-        if not lo <= v <= hi:
-            ap.error("%s must lie in [%d, %d]" % (name, lo, hi))
-    for name, path, exts in (("--classes", a.classes, (".png",)), ("--residual", a.residual, (".npy",)), ("--gate", a.gate, (".flo", ".npy"))):
-        if path is not None and os.path.splitext(path)[1].lower() not in exts:
-            ap.error("%s must be a %s file" % (name, " or ".join(exts)))
+        cli.in_range(ap, name, v, lo, hi)
+    cli.extension(ap, "--classes", a.classes, ".png")
+    cli.extension(ap, "--residual", a.residual, ".npy")
+    cli.extension(ap, "--gate", a.gate, ".flo", ".npy")
     import numpy as np
-    flowio = importlib.import_module(PKG + ".flowio")
+    flowio = cli.mod("flowio")
     try:
-        flow = importlib.import_module(PKG + ".flowfilter").read_flow(a.flow, flowio, np)
-    except (ValueError, OSError) as e:
-        print("epipolar: %s" % e, file=sys.stderr)
-        return 2
-    pipeline = importlib.import_module(PKG + ".pipeline")
+        flow = flowio.read_flow(a.flow)
+    except cli.REFUSED as e:
+        return cli.refuse("epipolar", e)
+    pipeline = cli.mod("pipeline")
     m, cls, res, cnt = pipeline.epipolar_fit(flow, thresh=a.thresh, n_hyp=a.hyp, lo_rounds=a.lo_rounds, step=a.step, seed=a.seed,
                                              classes=True, residual=True, counts=True)
     cnt = dict(zip(pipeline.EPIPOLAR_FIT_COUNTS[:7], cnt.cpu().tolist()))
@@ -81,25 +77,17 @@ def main(argv=None):
     h, w = cls.shape
     geo = pipeline.epipolar_geometry(m, h, w)
     if a.classes is not None:
-        flowio.write_png8(a.classes, np.repeat((cls * 85).astype(np.uint8)[..., None], 3, axis=2))
+        flowio.write_grey(a.classes, cls, 85)
     if a.residual is not None:
         np.save(a.residual, res.cpu().numpy())
     if a.gate is not None:
-        g = gated(flow, cls, np)
-        if a.gate.lower().endswith(".npy"):
-            np.save(a.gate, g)
-        else:
-            flowio.write_flo(a.gate, np.ascontiguousarray(g[..., [1, 0]]))
-    fraction = cnt["inliers"] / cnt["scored"] if cnt["scored"] else 0.0
-    if a.json:
-        print(json.dumps(dict(model=m.tolist(), F=geo["F"].tolist(), e1=geo["e1"].tolist(), e2=geo["e2"].tolist(), foe=geo["foe"],
-                              inlier_fraction=fraction, **cnt)))
-    else:
-        print("F: %s" % " ".join("%.9g" % v for v in geo["F"].reshape(-1)))
-        print("epipoles: (%s) (%s); focus of expansion: %s" % (" ".join("%.6g" % v for v in geo["e1"]), " ".join("%.6g" % v for v in geo["e2"]),
-                                                               "none" if geo["foe"] is None else "%.2f %.2f" % geo["foe"]))
-        print("inliers: %d of %d scored vectors (%.2f%%)%s" % (cnt["inliers"], cnt["scored"], 100.0 * fraction,
-                                                               "" if cnt["best_slot"] >= 0 else "; no model was found"))
+        flowio.write_field(a.gate, gated(flow, cls, np))
+    fraction, line = cli.inliers(cnt["inliers"], cnt["scored"], cnt["best_slot"] >= 0)
+    cli.report(a.json, dict(model=m.tolist(), F=geo["F"].tolist(), e1=geo["e1"].tolist(), e2=geo["e2"].tolist(), foe=geo["foe"],
+                            inlier_fraction=fraction, **cnt),
+               ["F: %s" % " ".join("%.9g" % v for v in geo["F"].reshape(-1)),
+                "epipoles: (%s) (%s); focus of expansion: %s" % (" ".join("%.6g" % v for v in geo["e1"]), " ".join("%.6g" % v for v in geo["e2"]),
+                                                                 "none" if geo["foe"] is None else "%.2f %.2f" % geo["foe"]), line])
     return 0
 
 

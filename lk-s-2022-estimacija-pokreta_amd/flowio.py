@@ -1,6 +1,7 @@
 """On-disk contract of the hot path: the reference's .npy names/dtypes/[dy,dx] order,
 plus Middlebury .flo ([u=dx, v=dy] float32) as parsed by visualization.py:9-29.
-Also the image files of the command-line tools: read_bgr, read_image and write_picture.
+Also the files of the command-line tools: their flows (read_flow, write_field), their images and pictures (read_bgr, read_image,
+write_picture, write_grey).
 """
 import os
 
@@ -37,6 +38,12 @@ def stage_name(picindex, backward, what):
     return "Daisy output slike %s backward=%s %s.npy" % (pic_prefix(picindex), backward, what)
 
 
+def numbered_name(path, k):
+    """<stem>_KK<ext> of path: the k-th picture of a numbered sequence (midframe.py --frames)."""
+    stem, ext = os.path.splitext(path)
+    return "%s_%02d%s" % (stem, k, ext)
+
+
 def write_flo(path, flow_dydx):
     """(H,W,2) [dy,dx] -> Middlebury .flo: f32 magic, i32 w, i32 h, then h*w*2 f32 [u,v] row-major."""
     flow_dydx = np.asarray(flow_dydx)
@@ -59,6 +66,30 @@ def read_flo(path):
     if data.size != 2 * w * h:
         raise ValueError("%s: truncated .flo" % path)
     return data.reshape(h, w, 2)
+
+
+def read_flow(path):
+    """A flow file of the command-line tools -> float32 (H,W,2) [dy,dx] ('.flo', or an '.npy' of that shape) or (H,W,3)
+    [U,V,valid] (an '.npy' of that shape); ValueError for anything else."""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".flo":
+        return np.ascontiguousarray(read_flo(path)[..., ::-1])
+    if ext == ".npy":
+        flow = np.load(path)
+        if flow.ndim != 3 or flow.shape[2] not in (2, 3):
+            raise ValueError("%s: expected an (H,W,2) or (H,W,3) array, got %s" % (path, flow.shape))
+        return np.ascontiguousarray(flow, dtype=np.float32)
+    raise ValueError("unsupported flow file: %s" % path)
+
+
+def write_field(path, uvv):
+    """An (H,W,3) [U,V,valid] field (contiguous or not) -> path: a '.flo' holds [u,v] = channels 0 and 1, a pixel without a
+    vector as whatever the field holds there; any other name ('.npy') the field as it is."""
+    uvv = np.asarray(uvv)
+    if os.path.splitext(path)[1].lower() == ".flo":
+        write_flo(path, uvv[..., [1, 0]])
+    else:
+        np.save(path, uvv)
 
 
 # ------------------------------------------------------------------------------------------------ KITTI flow PNGs
@@ -179,6 +210,12 @@ def write_png8(path, bgr):
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
                 + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def write_grey(path, plane, step):
+    """An (H,W) plane of small integers -> a grey PNG, plane * step in the three channels: step 85 for the four classes of a
+    fit, 255 // K for a map of K layers."""
+    write_png8(path, np.repeat((np.asarray(plane).astype(np.int32) * step).astype(np.uint8)[..., None], 3, axis=2))
 
 
 def read_kitti_flow_png(path):

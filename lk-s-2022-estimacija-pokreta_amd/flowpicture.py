@@ -15,17 +15,17 @@ Flows are read with evaluate.ucitajFlow ('.png' KITTI, '.npy' the hot path's fie
 flowio.read_image as '.npy' ((H,W,3) uint8 BGR), '.ppm' (binary P6) or '.png' (8-bit RGB or grey); pictures are written with
 flowio.write_picture ('.png' and '.ppm' always, anything else through PIL if it can be imported).
 """
-import argparse
 import importlib
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("flow")
     ap.add_argument("picture", nargs="?", default=None, help="where the colour picture of the flow goes")
     ap.add_argument("--max-flow", type=float, default=None, help="flow length at which the colours saturate (default: the field's maximum)")
@@ -44,9 +44,7 @@ def main(argv=None):
         ap.error("nothing to do: give a picture path, --warp, or both")
     if a.warp is None and (a.warped or a.error_picture):
         ap.error("--warped and --error-picture need --warp")
-    evaluate = importlib.import_module(PKG + ".evaluate")
-    pipeline = importlib.import_module(PKG + ".pipeline")
-    flowio = importlib.import_module(PKG + ".flowio")
+    evaluate, pipeline, flowio = cli.mod("evaluate"), cli.mod("pipeline"), cli.mod("flowio")
     read_image, write_picture = flowio.read_image, flowio.write_picture
     flow = evaluate.ucitajFlow(a.flow)
     if a.picture is not None:
@@ -54,9 +52,8 @@ def main(argv=None):
     if a.warp is not None:
         img1, img2 = (read_image(p) for p in a.warp)
         if img1.shape != img2.shape or img1.shape[:2] != flow.shape[:2]:
-            print("flowpicture: the flow is %dx%d, the images %dx%d and %dx%d"
-                  % (flow.shape[1], flow.shape[0], img1.shape[1], img1.shape[0], img2.shape[1], img2.shape[0]), file=sys.stderr)
-            return 2
+            return cli.refuse("flowpicture", "the flow is %dx%d, the images %dx%d and %dx%d"
+                              % (flow.shape[1], flow.shape[0], img1.shape[1], img1.shape[0], img2.shape[1], img2.shape[0]))
         out = pipeline.warp_eval(img1, img2, flow, a.err_thresh, a.err_max, warped=a.warped is not None,
                                  image=a.error_picture is not None)
         out = out if isinstance(out, tuple) else (out,)

@@ -14,19 +14,19 @@ Per frame one line is printed: t and the eight counts {from1, from2, filled, unk
 Flows are read with evaluate.ucitajFlow ('.npy' the hot path's [dy,dx] fields or a 3-channel field, '.flo' Middlebury, '.png'
 KITTI), images with flowio.read_image, pictures are written with flowio.write_picture, as flowpicture.py does.
 """
-import argparse
 import importlib
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 
 SOURCE_BGR = ((0, 0, 0), (255, 96, 0), (0, 96, 255), (128, 128, 128))      # none, img1, img2, filled
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("img1")
     ap.add_argument("img2")
     ap.add_argument("fwd", help="the flow of img1's pixels")
@@ -50,33 +50,25 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.t is not None and a.frames is not None:
         ap.error("--t and --frames exclude each other")
-    if a.t is not None and not 0.0 < a.t < 1.0:
-        ap.error("--t must lie in (0, 1)")
-    if a.frames is not None and not 1 <= a.frames <= 99:
-        ap.error("--frames must lie in [1, 99]")
-    if not 0 <= a.fill_rounds <= 64:
-        ap.error("--fill-rounds must lie in [0, 64]")
-    if not 0.0 <= a.occl_thresh < float("inf"):
-        ap.error("--occl-thresh must be finite and >= 0")
+    cli.between(ap, "--t", a.t, 0.0, 1.0)
+    cli.in_range(ap, "--frames", a.frames, 1, 99)
+    cli.in_range(ap, "--fill-rounds", a.fill_rounds, 0, 64)
+    cli.non_negative(ap, "--occl-thresh", a.occl_thresh)
     if a.source is not None and a.frames is not None:
         ap.error("--source goes with a single frame, not with --frames")
     import numpy as np
-    evaluate = importlib.import_module(PKG + ".evaluate")
-    pipeline = importlib.import_module(PKG + ".pipeline")
-    flowio = importlib.import_module(PKG + ".flowio")
+    evaluate, pipeline, flowio = cli.mod("evaluate"), cli.mod("pipeline"), cli.mod("flowio")
     img1, img2 = flowio.read_image(a.img1), flowio.read_image(a.img2)
     fwd = evaluate.ucitajFlow(a.fwd)
     bwd = evaluate.ucitajFlow(a.backward) if a.backward is not None else None
     sizes = [x.shape[:2] for x in (img1, img2, fwd) + ((bwd,) if bwd is not None else ())]
     if len(set(sizes)) != 1:
-        print("midframe: the images and the flows differ in size: %s" % ", ".join("%dx%d" % (s[1], s[0]) for s in sizes), file=sys.stderr)
-        return 2
+        return cli.refuse("midframe", "the images and the flows differ in size: %s" % ", ".join("%dx%d" % (s[1], s[0]) for s in sizes))
     if a.frames is not None:
         frames, counts = pipeline.frame_sequence(img1, img2, fwd, bwd, n=a.frames, fill_rounds=a.fill_rounds,
                                                  occl_thresh=a.occl_thresh, counts=True)
-        stem, ext = os.path.splitext(a.out)
         for k, (frame, cnt) in enumerate(zip(frames, counts), 1):
-            flowio.write_picture("%s_%02d%s" % (stem, k, ext), frame.cpu().numpy())
+            flowio.write_picture(flowio.numbered_name(a.out, k), frame.cpu().numpy())
             print(count_line(float(np.float32(k / (a.frames + 1))), cnt.cpu().tolist()))
         return 0
     t = 0.5 if a.t is None else a.t

@@ -17,18 +17,17 @@ excluded.  --layers K fits K models one after the other, each to the vectors tha
 '.flo' outputs hold [u,v], a pixel without a vector as (0,0).  Usage errors and unreadable input exit with status 2 before any
 GPU work.
 """
-import argparse
 import importlib
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("flow")
     ap.add_argument("--model", choices=("affine", "homography"), default="affine")
     ap.add_argument("--thresh", type=float, default=1.0, metavar="T")
@@ -48,29 +47,22 @@ def parser():
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
-    if not (a.thresh == a.thresh and 0.0 < a.thresh < float("inf")):
-        ap.error("--thresh must be finite and > 0")
+    cli.positive(ap, "--thresh", a.thresh)
     for name, v, lo, hi in (("--hyp", a.hyp, 1, 65536), ("--lo-rounds", a.lo_rounds, 0, 4), ("--polish", a.polish, 0, 4),
-                            ("--step", a.step, 1, 64), ("--seed", a.seed, 0, 2 ** 64 - 1)):
-        if not lo <= v <= hi:
-            ap.error("%s must lie in [%d, %d]" % (name, lo, hi))
-    if a.layers is not None and not 1 <= a.layers <= 255:
-        ap.error("--layers must lie in [1, 255]")
+                            ("--step", a.step, 1, 64), ("--seed", a.seed, 0, 2 ** 64 - 1), ("--layers", a.layers, 1, 255)):
+        cli.in_range(ap, name, v, lo, hi)
     if a.layers is not None and (a.model_flow is not None or a.residual is not None):
         ap.error("--model-flow and --residual describe one model: they do not go with --layers")
     for name, path, ext in (("--model-flow", a.model_flow, ".flo"), ("--residual", a.residual, ".flo"), ("--classes", a.classes, ".png")):
-        if path is not None and os.path.splitext(path)[1].lower() != ext:
-            ap.error("%s must be a %s file" % (name, ext))
+        cli.extension(ap, name, path, ext)
     import numpy as np
-    flowio = importlib.import_module(PKG + ".flowio")
+    flowio = cli.mod("flowio")
     try:
-        flow = importlib.import_module(PKG + ".flowfilter").read_flow(a.flow, flowio, np)
-    except (ValueError, OSError) as e:
-        print("motionfit: %s" % e, file=sys.stderr)
-        return 2
-    pipeline = importlib.import_module(PKG + ".pipeline")
+        flow = flowio.read_flow(a.flow)
+    except cli.REFUSED as e:
+        return cli.refuse("motionfit", e)
+    pipeline = cli.mod("pipeline")
     args = dict(model=a.model, thresh=a.thresh, n_hyp=a.hyp, lo_rounds=a.lo_rounds, polish=a.polish, step=a.step, seed=a.seed)
-    grey = lambda plane: np.repeat(plane[..., None], 3, axis=2)
     if a.layers is not None:
         models, layers = pipeline.motion_layers(flow, a.layers, **args)
         layers = layers.cpu().numpy()
@@ -79,29 +71,23 @@ def main(argv=None):
         good &= np.isfinite(flow[..., :2]).all(axis=2)
         shares = [float((layers == i + 1).sum()) / max(int(good.sum()), 1) for i in range(a.layers)]
         if a.classes is not None:
-            flowio.write_png8(a.classes, grey((layers.astype(np.int32) * (255 // a.layers)).astype(np.uint8)))
-        if a.json:
-            print(json.dumps(dict(model=a.model, layers=[dict(matrix=m.tolist(), share=s) for m, s in zip(models, shares)])))
-        else:
-            for i, (m, s) in enumerate(zip(models, shares)):
-                print("layer %d: %s; %.2f%% of the vectors" % (i + 1, " ".join("%.9g" % v for v in m.reshape(-1)), 100.0 * s))
+            flowio.write_grey(a.classes, layers, 255 // a.layers)
+        cli.report(a.json, dict(model=a.model, layers=[dict(matrix=m.tolist(), share=s) for m, s in zip(models, shares)]),
+                   ["layer %d: %s; %.2f%% of the vectors" % (i + 1, " ".join("%.9g" % v for v in m.reshape(-1)), 100.0 * s)
+                    for i, (m, s) in enumerate(zip(models, shares))])
         return 0
     m, cls, mflow, res, cnt = pipeline.motion_fit(flow, classes=True, model_flow=True, residual=True, counts=True, **args)
     cnt = dict(zip(pipeline.MOTION_FIT_COUNTS, cnt.cpu().tolist()))
     m = m.cpu().numpy()
     if a.model_flow is not None:
-        flowio.write_flo(a.model_flow, mflow[..., [1, 0]].cpu().numpy())
+        flowio.write_field(a.model_flow, mflow.cpu().numpy())
     if a.residual is not None:
-        flowio.write_flo(a.residual, res[..., [1, 0]].cpu().numpy())
+        flowio.write_field(a.residual, res.cpu().numpy())
     if a.classes is not None:
-        flowio.write_png8(a.classes, grey((cls.cpu().numpy() * 85).astype(np.uint8)))
-    fraction = cnt["inliers"] / cnt["scored"] if cnt["scored"] else 0.0
-    if a.json:
-        print(json.dumps(dict(model=a.model, matrix=m.tolist(), inlier_fraction=fraction, **cnt)))
-    else:
-        print("%s model: %s" % (a.model, " ".join("%.9g" % v for v in m.reshape(-1))))
-        print("inliers: %d of %d scored vectors (%.2f%%)%s" % (cnt["inliers"], cnt["scored"], 100.0 * fraction,
-                                                               "" if cnt["best_j"] >= 0 else "; no model was found"))
+        flowio.write_grey(a.classes, cls.cpu().numpy(), 85)
+    fraction, line = cli.inliers(cnt["inliers"], cnt["scored"], cnt["best_j"] >= 0)
+    cli.report(a.json, dict(model=a.model, matrix=m.tolist(), inlier_fraction=fraction, **cnt),
+               ["%s model: %s" % (a.model, " ".join("%.9g" % v for v in m.reshape(-1))), line])
     return 0
 
 

@@ -91,10 +91,12 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
+mod = cli.mod
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("--pairs", type=int, default=1)
     ap.add_argument("--bcd-times", type=int, default=4)
     ap.add_argument("--size", default="436x1024")
@@ -149,41 +151,31 @@ EVAL_ROW = ("n", "n_out_abs", "n_out_kitti", "n_nonfinite", "n_gt_valid", "n_tes
 PHOTO_ROW = ("n", "n_outside", "n_unknown", "n_above", "sum_err", "max_err", "mean_err", "above_pct")
 
 
-def mod(name):
-    return importlib.import_module(PKG + "." + name)
+def checked(needs, got, read):
+    """read()'s value; a ValueError in it exits with status 2 and "<needs>, got <got>"."""
+    try:
+        return read()
+    except ValueError:
+        parser().error("%s, got %r" % (needs, got))
 
 
 def segments_arg(tokens):
     """--segments MIN T -> (MIN, T); exits with status 2 unless MIN is an integer >= 0 and T finite and >= 0."""
     try:
-        min_size, thresh = int(tokens[0]), float(tokens[1])
-        if min_size < 0 or min_size >= 2 ** 31 or not (np.isfinite(thresh) and thresh >= 0):
-            raise ValueError
-    except ValueError:
-        parser().error("--segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (tokens,))
-    return min_size, thresh
+        return cli.segments(tokens)
+    except ValueError as e:
+        parser().error(str(e))
 
 
 def wmedian_arg(token):
     """--wmedian R -> R; exits with status 2 unless R is an integer in 1..8."""
-    try:
-        radius = int(token)
-        if not 1 <= radius <= 8:
-            raise ValueError
-    except ValueError:
-        parser().error("--wmedian needs R (an integer in 1..8), got %r" % (token,))
-    return radius
+    return checked("--wmedian needs R (an integer in 1..8)", token, lambda: cli.integer(token, 1, 8))
 
 
 def wmedian_reject_arg(tokens):
     """--wmedian-reject R T -> (R, T); exits with status 2 unless R is an integer in 1..8 and T finite and >= 0."""
-    try:
-        radius, thresh = int(tokens[0]), float(tokens[1])
-        if not 1 <= radius <= 8 or not (np.isfinite(thresh) and thresh >= 0):
-            raise ValueError
-    except ValueError:
-        parser().error("--wmedian-reject needs R (an integer in 1..8) and T (finite, >= 0), got %r" % (tokens,))
-    return radius, thresh
+    return checked("--wmedian-reject needs R (an integer in 1..8) and T (finite, >= 0)", tokens,
+                 lambda: (cli.integer(tokens[0], 1, 8), cli.real(tokens[1], False)))
 
 
 def motion_args(a):
@@ -193,13 +185,9 @@ def motion_args(a):
         parser().error("--motion-thresh needs --motion")
     if a.motion is not None and a.motion not in ("affine", "homography"):
         parser().error("--motion needs MODEL (affine or homography), got %r" % (a.motion,))
-    try:
-        thresh = 1.0 if a.motion_thresh is None else float(a.motion_thresh)
-        if not (np.isfinite(thresh) and thresh > 0):
-            raise ValueError
-    except ValueError:
-        parser().error("--motion-thresh needs T (finite, > 0), got %r" % (a.motion_thresh,))
-    return a.motion, thresh
+    if a.motion_thresh is None:
+        return a.motion, 1.0
+    return a.motion, checked("--motion-thresh needs T (finite, > 0)", a.motion_thresh, lambda: cli.real(a.motion_thresh, True))
 
 
 def epipolar_arg(a):
@@ -211,26 +199,14 @@ def epipolar_arg(a):
         if getattr(a, "pose", None) is not None:
             parser().error("--pose needs --epipolar")
         return None
-    try:
-        thresh = float(a.epipolar)
-        if not (np.isfinite(thresh) and thresh > 0):
-            raise ValueError
-    except ValueError:
-        parser().error("--epipolar needs T (finite, > 0), got %r" % (a.epipolar,))
-    return thresh
+    return checked("--epipolar needs T (finite, > 0)", a.epipolar, lambda: cli.real(a.epipolar, True))
 
 
 def pose_arg(a):
     """--pose FOCAL -> FOCAL or None; exits with status 2 for a focal length that is not finite and > 0."""
     if a.pose is None:
         return None
-    try:
-        focal = float(a.pose)
-        if not (np.isfinite(focal) and focal > 0):
-            raise ValueError
-    except ValueError:
-        parser().error("--pose needs FOCAL (finite, > 0), got %r" % (a.pose,))
-    return focal
+    return checked("--pose needs FOCAL (finite, > 0)", a.pose, lambda: cli.real(a.pose, True))
 
 
 def pose_pair(s, pair, sparse_dev, model, cls):
@@ -279,10 +255,12 @@ def midframe_args(a):
         parser().error("--mid-fill-rounds and --mid-occl-thresh need --midframe")
     rounds = 8 if a.mid_fill_rounds is None else a.mid_fill_rounds
     occl = 30.0 if a.mid_occl_thresh is None else a.mid_occl_thresh
-    if not 0 <= rounds <= 64:
-        parser().error("--mid-fill-rounds must lie in [0, 64], got %d" % rounds)
-    if not (np.isfinite(occl) and occl >= 0):
-        parser().error("--mid-occl-thresh must be finite and >= 0, got %r" % occl)
+    for name, value, read in (("--mid-fill-rounds", rounds, lambda: cli.integer(rounds, 0, 64)),
+                              ("--mid-occl-thresh", occl, lambda: cli.real(occl, False))):
+        try:
+            read()
+        except ValueError as e:
+            parser().error("%s %s, got %r" % (name, e, value))
     return rounds, occl
 
 
@@ -552,7 +530,7 @@ def write_out(s, flows):
             fwd, bwd, margin = fwd[..., :2].contiguous(), bwd[..., :2].contiguous(), fwd[..., 2].contiguous()
         if a.motion is not None:
             matrix, residual, counts = pipeline.motion_fit(fwd, model=a.motion, thresh=a.motion_thresh, residual=True, counts=True)
-            flowio.write_flo(os.path.join(a.out, "residual_%02d.flo" % pair), residual[..., [1, 0]].cpu().numpy())
+            flowio.write_field(os.path.join(a.out, "residual_%02d.flo" % pair), residual.cpu().numpy())
             counts = counts.cpu().tolist()
             motion_rows.append(dict(pair=pair, matrix=matrix.cpu().numpy().tolist(), scored=counts[0], inliers=counts[1]))
             print("pair %d: %s motion: %d of %d vectors within %g px (%.2f%%)"
@@ -561,7 +539,7 @@ def write_out(s, flows):
         dense = [("epic", epic)] if a.epic else []
         if a.wmedian is not None:
             filtered = pipeline.flow_wmedian(fwd, img1, radius=a.wmedian)
-            flowio.write_flo(os.path.join(a.out, "wmedian_%02d.flo" % pair), filtered[..., [1, 0]].cpu().numpy())
+            flowio.write_field(os.path.join(a.out, "wmedian_%02d.flo" % pair), filtered.cpu().numpy())
             dense = [("filtered", filtered)] + dense
         if a.eval:
             gt = synth.make_pair(H, W, seed=synth.pair_seed(pair, 0))[2]

@@ -79,14 +79,11 @@ def take_segments(argv):
     without them, (MIN, T) or None), or the exit status 2 after saying why."""
     if argv[6:7] != ["--segments"]:
         return argv, None
+    cli = importlib.import_module(PKG + ".cli")
     try:
-        min_size, thresh = int(argv[7]), float(argv[8])
-        if min_size < 0 or min_size >= 2 ** 31 or not (np.isfinite(thresh) and thresh >= 0):
-            raise ValueError
-    except (IndexError, ValueError):
-        print("spremiZaEpic: --segments needs MIN (an integer >= 0) and T (finite, >= 0), got %r" % (argv[7:9],), file=sys.stderr)
-        return 2
-    return argv[:6] + argv[9:], (min_size, thresh)
+        return argv[:6] + argv[9:], cli.segments(argv[7:9])
+    except ValueError as e:
+        return cli.refuse("spremiZaEpic", e)
 
 
 def take_margin(argv):

@@ -17,19 +17,18 @@ OUT.flo (or an (H,W,3) [U,V,valid] '.npy'): a piecewise-affine version of FLOW i
 FLOW: '.flo' (Middlebury [u,v], every pixel valid) or '.npy': (H,W,2) the hot path's [dy,dx] fields, (H,W,3) [U,V,valid].
 --json prints one JSON object instead of the text.  Usage errors and unreadable input exit with status 2 before any GPU work.
 """
-import argparse
 import importlib
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 MAX_MIN_SIZE = 1 << 26
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("image")
     ap.add_argument("out", metavar="OUT.npy|OUT.png")
     ap.add_argument("--step", type=int, default=16, metavar="S")
@@ -68,10 +67,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     for name, v, lo, hi in (("--step", a.step, 4, 64), ("--compactness", a.compactness, 0, 255), ("--iters", a.iters, 1, 32),
                             ("--min-size", a.min_size, 0, MAX_MIN_SIZE), ("--rounds", a.rounds, 1, 6)):
-        if v is not None and not lo <= v <= hi:
-            ap.error("%s must lie in [%d, %d]" % (name, lo, hi))
-    if a.thresh is not None and not (a.thresh == a.thresh and 0.0 < a.thresh < float("inf")):
-        ap.error("--thresh must be finite and > 0")
+        cli.in_range(ap, name, v, lo, hi)
+    cli.positive(ap, "--thresh", a.thresh)
     if (a.flow is None) != (a.fit is None):
         ap.error("--flow and --fit go together")
     if a.flow is None:
@@ -80,20 +77,18 @@ def main(argv=None):
                 ap.error("%s needs --flow and --fit" % name)
     for name, path, exts in (("OUT", a.out, (".npy", ".png")), ("--boundaries", a.boundaries, (".png",)), ("--fit", a.fit, (".flo", ".npy")),
                              ("--classes", a.classes, (".png",)), ("--models", a.models, (".npy",))):
-        if path is not None and os.path.splitext(path)[1].lower() not in exts:
-            ap.error("%s must be a %s file" % (name, " or ".join(exts)))
+        cli.extension(ap, name, path, *exts)
     thresh, rounds = 1.0 if a.thresh is None else a.thresh, 3 if a.rounds is None else a.rounds
     import numpy as np
-    flowio = importlib.import_module(PKG + ".flowio")
+    flowio = cli.mod("flowio")
     try:
         img = flowio.read_image(a.image)
-        flow = None if a.flow is None else importlib.import_module(PKG + ".flowfilter").read_flow(a.flow, flowio, np)
+        flow = None if a.flow is None else flowio.read_flow(a.flow)
         if flow is not None and flow.shape[:2] != img.shape[:2]:
             raise ValueError("%s is %dx%d, %s is %dx%d" % (a.flow, flow.shape[1], flow.shape[0], a.image, img.shape[1], img.shape[0]))
-    except (ValueError, OSError) as e:
-        print("superpixels: %s" % e, file=sys.stderr)
-        return 2
-    pipeline = importlib.import_module(PKG + ".pipeline")
+    except cli.REFUSED as e:
+        return cli.refuse("superpixels", e)
+    pipeline = cli.mod("pipeline")
     args = dict(step=a.step, compactness=a.compactness, iters=a.iters, min_size=a.min_size)
     report = {}
     if flow is None:
@@ -103,13 +98,9 @@ def main(argv=None):
                                                                                  counts=True, **args)
         cnt = None
         report = dict(zip(pipeline.SEGMENT_FIT_COUNTS[:7], fit_cnt.cpu().tolist()))
-        out = out.cpu().numpy()
-        if a.fit.lower().endswith(".npy"):
-            np.save(a.fit, out)
-        else:
-            flowio.write_flo(a.fit, np.ascontiguousarray(out[..., [1, 0]]))
+        flowio.write_field(a.fit, out.cpu().numpy())
         if a.classes is not None:
-            flowio.write_png8(a.classes, np.repeat((cls.cpu().numpy() * 85).astype(np.uint8)[..., None], 3, axis=2))
+            flowio.write_grey(a.classes, cls.cpu().numpy(), 85)
         if a.models is not None:
             np.save(a.models, models.cpu().numpy())
     labels = labels.cpu().numpy()
@@ -123,13 +114,11 @@ def main(argv=None):
         flowio.write_png8(a.out, label_picture(labels, np))
     if a.boundaries is not None:
         flowio.write_png8(a.boundaries, boundary_picture(img, labels, np))
-    if a.json:
-        print(json.dumps(report))
-    else:
-        print("segments: %d, of %d to %d pixels" % (report["n_seg"], report["smallest"], report["largest"]))
-        if flow is not None:
-            print("models: %d affine, %d translations; %d of %d vectors agree to within %g px"
-                  % (report["affine"], report["translation"], report["agree"], report["part"], thresh))
+    lines = ["segments: %d, of %d to %d pixels" % (report["n_seg"], report["smallest"], report["largest"])]
+    if flow is not None:
+        lines.append("models: %d affine, %d translations; %d of %d vectors agree to within %g px"
+                     % (report["affine"], report["translation"], report["agree"], report["part"], thresh))
+    cli.report(a.json, report, lines)
     return 0
 
 

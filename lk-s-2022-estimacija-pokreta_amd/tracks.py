@@ -17,18 +17,17 @@ none.  The counts per state after the last frame are printed, as one JSON object
 Flow files: '.flo' (Middlebury [u,v], every pixel valid) or '.npy': (H,W,2) the hot path's [dy,dx] fields, (H,W,3) [U,V,valid].
 Usage errors and unreadable input exit with status 2 before any GPU work, and before anything is written.
 """
-import argparse
 import importlib
-import json
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("forward", nargs="+", metavar="FWD.flo")
     ap.add_argument("--backward", nargs="+", default=None, metavar="BWD.flo")
     ap.add_argument("--step", type=int, default=4, metavar="S")
@@ -48,40 +47,33 @@ def main(argv=None):
     T = len(a.forward)
     if a.backward is not None and len(a.backward) != T:
         ap.error("--backward needs as many files as there are forward flows (%d), got %d" % (T, len(a.backward)))
-    if not 1 <= a.step <= 256:
-        ap.error("--step must lie in [1, 256]")
-    for name, v in (("--rel", a.rel), ("--abs", a.abs)):
-        if not (v == v and 0.0 <= v < float("inf")):
-            ap.error("%s must be finite and >= 0" % name)
-    if a.cap is not None and not 1 <= a.cap <= 1 << 26:
-        ap.error("--cap must lie in [1, 2^26]")
-    if os.path.splitext(a.out)[1].lower() != ".npz":
-        ap.error("--out must be a .npz file")
+    cli.in_range(ap, "--step", a.step, 1, 256)
+    cli.non_negative(ap, "--rel", a.rel)
+    cli.non_negative(ap, "--abs", a.abs)
+    cli.in_range(ap, "--cap", a.cap, 1, 1 << 26)
+    cli.extension(ap, "--out", a.out, ".npz")
     span = None
     if a.flow is not None:
         try:
             span = (int(a.flow[0]), int(a.flow[1]))
         except ValueError:
             ap.error("--flow needs two frame numbers and a file")
-        if not all(0 <= t <= T for t in span):
-            ap.error("--flow: frames must lie in [0, %d]" % T)
-        if os.path.splitext(a.flow[2])[1].lower() != ".flo":
-            ap.error("--flow: the output must be a .flo file")
+        for t in span:
+            cli.in_range(ap, "--flow: frames", t, 0, T)
+        cli.extension(ap, "--flow: the output", a.flow[2], ".flo")
     import numpy as np
-    flowio = importlib.import_module(PKG + ".flowio")
-    read_flow = importlib.import_module(PKG + ".flowfilter").read_flow
+    flowio = cli.mod("flowio")
     try:
-        fwd = [read_flow(p, flowio, np) for p in a.forward]
-        bwd = [read_flow(p, flowio, np) for p in a.backward] if a.backward is not None else [None] * T
+        fwd = [flowio.read_flow(p) for p in a.forward]
+        bwd = [flowio.read_flow(p) for p in a.backward] if a.backward is not None else [None] * T
         for p, f in zip(a.forward + (a.backward or []), fwd + [b for b in bwd if b is not None]):
             if f.shape[:2] != fwd[0].shape[:2]:
                 raise ValueError("%s: a %dx%d field among %dx%d ones" % (p, f.shape[1], f.shape[0], fwd[0].shape[1], fwd[0].shape[0]))
         if max(fwd[0].shape[:2]) > 8192:
             raise ValueError("%s: frames are at most 8192x8192" % a.forward[0])
-    except (ValueError, OSError) as e:
-        print("tracks: %s" % e, file=sys.stderr)
-        return 2
-    pipeline = importlib.import_module(PKG + ".pipeline")
+    except cli.REFUSED as e:
+        return cli.refuse("tracks", e)
+    pipeline = cli.mod("pipeline")
     H, W = fwd[0].shape[:2]
     ts = pipeline.TrackSet(H, W, cap=a.cap, step=a.step, rel=a.rel, abs=a.abs)
     ts.seed()
@@ -95,19 +87,16 @@ def main(argv=None):
     got = ts.read()
     np.savez(a.out, **got)
     if sparse is not None:
-        flowio.write_flo(a.flow[2], sparse[..., [1, 0]].cpu().numpy())
+        flowio.write_field(a.flow[2], sparse.cpu().numpy())
     last = got["state"][-1]
     summary = dict(frames=T + 1, tracks=int(len(last)), dropped=int(dropped.cpu()[0]),
                    **{name: int((last == k).sum()) for k, name in enumerate(pipeline.TRACK_STATES) if k})
+    lines = ["%d frames, %d tracks (%d cells dropped): %s" % (T + 1, summary["tracks"], summary["dropped"], ", ".join(
+        "%d %s" % (summary[name], name) for name in pipeline.TRACK_STATES[1:]))]
     if span is not None:
         summary["flow_vectors"] = int((sparse[..., 2] > 0.5).sum().cpu())
-    if a.json:
-        print(json.dumps(summary))
-    else:
-        print("%d frames, %d tracks (%d cells dropped): %s" % (T + 1, summary["tracks"], summary["dropped"], ", ".join(
-            "%d %s" % (summary[name], name) for name in pipeline.TRACK_STATES[1:])))
-        if span is not None:
-            print("flow %d -> %d: %d vectors" % (span[0], span[1], summary["flow_vectors"]))
+        lines.append("flow %d -> %d: %d vectors" % (span[0], span[1], summary["flow_vectors"]))
+    cli.report(a.json, summary, lines)
     return 0
 
 

@@ -18,20 +18,18 @@ object instead of the text.
 <flow>: '.flo' (Middlebury [u,v], every pixel valid) or '.npy': (H,W,2) the hot path's [dy,dx] fields, (H,W,3) [U,V,valid].
 Usage errors and unreadable input exit with status 2 before any GPU work.
 """
-import argparse
 import importlib
-import json
-import math
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PKG = os.path.basename(os.path.dirname(os.path.abspath(__file__)))
+cli = importlib.import_module(PKG + ".cli")
 MAX_HYP = 21845
 
 
 def parser():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap = cli.parser(__doc__)
     ap.add_argument("flow")
     cam = ap.add_mutually_exclusive_group()
     cam.add_argument("--focal", type=float, default=None, metavar="F")
@@ -50,39 +48,34 @@ def parser():
 
 def camera(a):
     """(focal, center) for pipeline.two_view from the parsed options, or a message."""
-    if a.intrinsics is not None:
-        fx, fy, cx, cy = a.intrinsics
-        if not (all(math.isfinite(v) for v in a.intrinsics) and fx > 0 and fy > 0):
-            return None, "--intrinsics: FX and FY must be finite and > 0, CX and CY finite"
-        return ((fx, fy), (cx, cy)), None
-    if a.focal is not None and not (math.isfinite(a.focal) and a.focal > 0):
-        return None, "--focal must be finite and > 0"
-    return (a.focal, None), None
+    try:
+        if a.intrinsics is not None:
+            fx, fy, cx, cy = a.intrinsics
+            return ((cli.real(fx, True), cli.real(fy, True)), (cli.real(cx, None), cli.real(cy, None))), None
+        return (None if a.focal is None else cli.real(a.focal, True), None), None
+    except ValueError:
+        return None, ("--focal %s" if a.intrinsics is None else "--intrinsics: FX and FY %s, CX and CY finite") % cli.POSITIVE
 
 
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
-    if not (a.thresh == a.thresh and 0.0 < a.thresh < float("inf")):
-        ap.error("--thresh must be finite and > 0")
+    cli.positive(ap, "--thresh", a.thresh)
     for name, v, lo, hi in (("--hyp", a.hyp, 1, MAX_HYP), ("--lo-rounds", a.lo_rounds, 0, 4), ("--step", a.step, 1, 64),
                             ("--seed", a.seed, 0, 2 ** 64 - 1)):
-        if not lo <= v <= hi:
-            ap.error("%s must lie in [%d, %d]" % (name, lo, hi))
+        cli.in_range(ap, name, v, lo, hi)
     cam, msg = camera(a)
     if msg:
         ap.error(msg)
     for name, path, ext in (("--depth", a.depth, ".npy"), ("--classes", a.classes, ".png"), ("--err", a.err, ".npy")):
-        if path is not None and os.path.splitext(path)[1].lower() != ext:
-            ap.error("%s must be a %s file" % (name, ext))
+        cli.extension(ap, name, path, ext)
     import numpy as np
-    flowio = importlib.import_module(PKG + ".flowio")
+    flowio = cli.mod("flowio")
     try:
-        flow = importlib.import_module(PKG + ".flowfilter").read_flow(a.flow, flowio, np)
-    except (ValueError, OSError) as e:
-        print("twoview: %s" % e, file=sys.stderr)
-        return 2
-    pipeline = importlib.import_module(PKG + ".pipeline")
+        flow = flowio.read_flow(a.flow)
+    except cli.REFUSED as e:
+        return cli.refuse("twoview", e)
+    pipeline = cli.mod("pipeline")
     import torch
     flow = torch.from_numpy(np.ascontiguousarray(flow)).cuda()
     m, fit_cls, fit_cnt = pipeline.epipolar_fit(flow, thresh=a.thresh, n_hyp=a.hyp, lo_rounds=a.lo_rounds, step=a.step, seed=a.seed,
@@ -95,21 +88,20 @@ def main(argv=None):
     if a.depth is not None:
         np.save(a.depth, depth.cpu().numpy())
     if a.classes is not None:
-        flowio.write_png8(a.classes, np.repeat((cls.cpu().numpy() * 85).astype(np.uint8)[..., None], 3, axis=2))
+        flowio.write_grey(a.classes, cls.cpu().numpy(), 85)
     if a.err is not None:
         np.save(a.err, err.cpu().numpy())
     axis = None if info["axis"] is None else info["axis"].tolist()
-    if a.json:
-        print(json.dumps(dict(model=m.cpu().numpy().tolist(), pose=pose.tolist(), R=info["R"].tolist(), t=info["t"].tolist(),
-                              angle_deg=info["angle_deg"], axis=axis, singular=info["singular"].tolist(), fit_inliers=fit_cnt[1],
-                              fit_scored=fit_cnt[0], **cnt)))
-    elif info["candidate"] < 0:
-        print("no pose: %d voters, %d of %d scored vectors agree with a fundamental matrix" % (cnt["voters"], fit_cnt[1], fit_cnt[0]))
+    if info["candidate"] < 0:
+        lines = ["no pose: %d voters, %d of %d scored vectors agree with a fundamental matrix" % (cnt["voters"], fit_cnt[1], fit_cnt[0])]
     else:
-        print("rotation: %.6f deg about (%s)" % (info["angle_deg"], "none" if axis is None else " ".join("%.6f" % v for v in axis)))
-        print("t: %s" % " ".join("%.9g" % v for v in info["t"]))
-        print("votes: %d of %d voters for candidate %d, %d for the runner-up" % (cnt["votes"], cnt["voters"], cnt["candidate"], cnt["runner_up"]))
-        print("pixels: %d in front of both cameras, %d behind one, %d without parallax" % (cnt["front"], cnt["behind"], cnt["flat"]))
+        lines = ["rotation: %.6f deg about (%s)" % (info["angle_deg"], "none" if axis is None else " ".join("%.6f" % v for v in axis)),
+                 "t: %s" % " ".join("%.9g" % v for v in info["t"]),
+                 "votes: %d of %d voters for candidate %d, %d for the runner-up" % (cnt["votes"], cnt["voters"], cnt["candidate"], cnt["runner_up"]),
+                 "pixels: %d in front of both cameras, %d behind one, %d without parallax" % (cnt["front"], cnt["behind"], cnt["flat"])]
+    cli.report(a.json, dict(model=m.cpu().numpy().tolist(), pose=pose.tolist(), R=info["R"].tolist(), t=info["t"].tolist(),
+                            angle_deg=info["angle_deg"], axis=axis, singular=info["singular"].tolist(), fit_inliers=fit_cnt[1],
+                            fit_scored=fit_cnt[0], **cnt), lines)
     return 0
 
 

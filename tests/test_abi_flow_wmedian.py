@@ -221,7 +221,7 @@ def test_command_line_refusals(L, capsys, tmp_path):
     assert ff.main([str(tmp_path / "missing.flo"), str(tmp_path / "o.flo")]) == 2 and "flowfilter:" in capsys.readouterr().err
     assert ff.main([str(tmp_path / "f.txt"), str(tmp_path / "o.flo")]) == 2 and "unsupported flow file" in capsys.readouterr().err
     flowio.write_flo(str(tmp_path / "f.flo"), np.arange(24, dtype=np.float32).reshape(3, 4, 2))
-    assert (ff.read_flow(str(tmp_path / "f.flo"), flowio, np) == np.arange(24, dtype=np.float32).reshape(3, 4, 2)).all()
+    assert (flowio.read_flow(str(tmp_path / "f.flo")) == np.arange(24, dtype=np.float32).reshape(3, 4, 2)).all()
     rb = pkg("run_batch")
     a = rb.parser().parse_args([])
     assert a.wmedian is None and a.wmedian_reject is None
