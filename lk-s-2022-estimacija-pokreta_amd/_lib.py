@@ -165,6 +165,18 @@ _SIGNATURES_TWO_VIEW = {
     "dflow_two_view": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp]),
 }
+# Sparse feature tracking (csrc/klt.hip, include/dflow_klt.h): shared checks alone, the refusals pinned by tests/test_abi_klt.py.
+# Declared in a header of their own and kept out of SYMBOLS, which is what include/dflow.h declares.
+_SIGNATURES_KLT = {
+    "dflow_klt_pyramid_bytes": (_sz, [_i32, _i32, _i32]),
+    "dflow_klt_pyramid": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "dflow_corners": (C.c_int, [_i32, _i32, _vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dflow_klt_track": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, C.c_uint32, _vp, _vp,
+                                  _vp, _vp, _vp, _vp]),
+}
+SYMBOLS_KLT = tuple(_SIGNATURES_KLT)
+TRACK_FLAT, TRACK_RESIDUAL = 6, 7             # DFLOW_TRACK_FLAT, DFLOW_TRACK_RESIDUAL: the states dflow_klt_track adds
+KLT_LEVELS_MAX = 8
 SYMBOLS = (tuple(_SIGNATURES) + tuple(_SIGNATURES_SHARED_GATE) + tuple(_SIGNATURES_TRACKS) + tuple(_SIGNATURES_EPIPOLAR)
            + tuple(_SIGNATURES_SUPERPIXELS) + tuple(_SIGNATURES_TWO_VIEW))
 
@@ -193,7 +205,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for table in (_SIGNATURES, _SIGNATURES_SHARED_GATE, _SIGNATURES_TRACKS, _SIGNATURES_EPIPOLAR, _SIGNATURES_SUPERPIXELS,
-                      _SIGNATURES_TWO_VIEW):
+                      _SIGNATURES_TWO_VIEW, _SIGNATURES_KLT):
             for name, (restype, argtypes) in table.items():
                 fn = getattr(L, name)
                 fn.restype, fn.argtypes = restype, argtypes

@@ -13,6 +13,7 @@
 #include <string.h>
 #include <initializer_list>
 #include "dflow_common.h"
+#include "../../include/dflow_klt.h"
 
 // tracks.hip: a track set carried one frame on, new tracks in the uncovered cells, the sparse flow between two snapshots (arguments
 // validated by the caller); bwd, err, mask and counts may be NULL.  Declared here: dflow_common.h is part of every device build.
@@ -37,6 +38,17 @@ int launch_segment_fit(int H, int W, const float *flow, int layout, const int32_
 int launch_two_view(int H, int W, const float *flow, int layout, const float *model, const uint8_t *part, double fx, double fy, double cx,
                     double cy, int step, double *pose, int64_t *state, float *depth, uint8_t *cls, float *err, int32_t *counts,
                     hipStream_t s);
+
+// klt.hip: the grey pyramid, the corners of its level 0 and pyramidal Lucas-Kanade over a track set (include/dflow_klt.h; arguments
+// validated by the caller); the set of launch_corners, and err, back and counts may be NULL
+size_t klt_pyramid_bytes(int H, int W, int levels);
+int launch_klt_pyramid(int H, int W, int levels, const uint8_t *bgr, uint8_t *pyr, hipStream_t s);
+int launch_corners(int H, int W, const uint8_t *grey, int rc, int min_dist, int border, float quality, float min_response, int cap,
+                   const float *pos, const int32_t *state, const int32_t *d_n, float *resp, uint8_t *mask, uint8_t *occ, uint32_t *rmax,
+                   int32_t *counts, hipStream_t s);
+int launch_klt_track(int H, int W, int levels, const uint8_t *pyr1, const uint8_t *pyr2, int cap, const float *pos_in,
+                     const int32_t *state_in, int r, int iters, float eps, float min_eig, float max_err, float fb, float *pos_out,
+                     int32_t *state_out, float *err, float *back, int32_t *counts, hipStream_t s);
 
 static thread_local char g_err[512] = "";
 
@@ -1092,6 +1104,82 @@ int dflow_two_view(int32_t h, int32_t w, const float *d_flow, int32_t layout, co
     if (rc) return rc;
     return launch_two_view(h, w, d_flow, layout, d_model, d_part, fx, fy, cx, cy, step, d_pose, d_state, d_depth, d_class, d_err,
                            d_counts, (hipStream_t)stream);
+}
+
+// ---- sparse feature tracking (include/dflow_klt.h): the shared checks alone, in the order the header states
+#define KLT_LEVELS_MAX 8
+
+size_t dflow_klt_pyramid_bytes(int32_t h, int32_t w, int32_t levels)
+{
+    if (check_frame_size(__func__, h, w) || check_int_range(__func__, "levels", levels, 1, KLT_LEVELS_MAX)) return 0;
+    return klt_pyramid_bytes(h, w, levels);
+}
+
+int dflow_klt_pyramid(int32_t h, int32_t w, int32_t levels, const uint8_t *d_bgr, uint8_t *d_pyr, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "levels", levels, 1, KLT_LEVELS_MAX))) return rc;
+    CHECK_PTR(d_bgr); CHECK_PTR(d_pyr);
+    // four pixels move at a time: three dwords in, one out
+    if ((rc = check_aligned(__func__, {{"d_bgr", d_bgr, 4}, {"d_pyr", d_pyr, 4}}))) return rc;
+    if ((rc = check_distinct(__func__, {{"d_bgr", d_bgr}}, {{"d_pyr", d_pyr}}))) return rc;
+    return launch_klt_pyramid(h, w, levels, d_bgr, d_pyr, (hipStream_t)stream);
+}
+
+int dflow_corners(int32_t h, int32_t w, const uint8_t *d_pyr, int32_t rc_win, int32_t min_dist, int32_t border, float quality,
+                  float min_response, int32_t cap, const float *d_pos, const int32_t *d_state, const int32_t *d_n, float *d_response,
+                  uint8_t *d_mask, uint8_t *d_occ, uint32_t *d_rmax, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "rc", rc_win, 1, 7))) return rc;
+    if ((rc = check_int_range(__func__, "min_dist", min_dist, 1, 32))) return rc;
+    if ((rc = check_int_range(__func__, "border", border, 0, 8192))) return rc;
+    if ((rc = check_finite_ge0(__func__, "quality", quality))) return rc;
+    if (quality > 1.0f) return refuse_value(__func__, "quality", quality, "<= 1");
+    if ((rc = check_finite_ge0(__func__, "min_response", min_response))) return rc;
+    // a track set is given whole or not at all
+    if (d_pos || d_state || d_n || d_occ) {
+        if ((rc = check_int_range(__func__, "cap", cap, 1, TRACK_CAP_MAX))) return rc;
+        CHECK_PTR(d_pos); CHECK_PTR(d_state); CHECK_PTR(d_n); CHECK_PTR(d_occ);
+    }
+    CHECK_PTR(d_pyr); CHECK_PTR(d_response); CHECK_PTR(d_mask); CHECK_PTR(d_rmax);
+    rc = check_aligned(__func__, {{"d_pos", d_pos, ALIGN_FLOW2}, {"d_state", d_state, 4}, {"d_n", d_n, 4}, {"d_response", d_response, 4},
+                                  {"d_rmax", d_rmax, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // the response is read by the launch after the one that writes it, the set by the one between them
+    rc = check_distinct(__func__, {{"d_pyr", d_pyr}, {"d_pos", d_pos}, {"d_state", d_state}, {"d_n", d_n}},
+                        {{"d_response", d_response}, {"d_mask", d_mask}, {"d_occ", d_occ}, {"d_rmax", d_rmax}, {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_corners(h, w, d_pyr, rc_win, min_dist, border, quality, min_response, cap, d_pos, d_state, d_n, d_response, d_mask, d_occ,
+                          d_rmax, d_counts, (hipStream_t)stream);
+}
+
+int dflow_klt_track(int32_t h, int32_t w, int32_t levels, const uint8_t *d_pyr1, const uint8_t *d_pyr2, int32_t cap, const float *d_pos_in,
+                    const int32_t *d_state_in, int32_t r, int32_t iters, float eps, float min_eig, float max_err, float fb, uint32_t flags,
+                    float *d_pos_out, int32_t *d_state_out, float *d_err, float *d_back, int32_t *d_counts, void *stream)
+{
+    int rc = check_frame_size(__func__, h, w); if (rc) return rc;
+    if ((rc = check_int_range(__func__, "levels", levels, 1, KLT_LEVELS_MAX))) return rc;
+    if ((rc = check_int_range(__func__, "cap", cap, 1, TRACK_CAP_MAX))) return rc;
+    if ((rc = check_int_range(__func__, "r", r, 1, 10))) return rc;
+    if ((rc = check_int_range(__func__, "iters", iters, 1, 64))) return rc;
+    if ((rc = check_finite_gt0(__func__, "eps", eps))) return rc;
+    if ((rc = check_finite_ge0(__func__, "min_eig", min_eig))) return rc;
+    if ((rc = check_finite_ge0(__func__, "max_err", max_err))) return rc;
+    if ((rc = check_finite_ge0(__func__, "fb", fb))) return rc;
+    if ((rc = check_flags(__func__, flags, 0))) return rc;
+    CHECK_PTR(d_pyr1); CHECK_PTR(d_pyr2); CHECK_PTR(d_pos_in); CHECK_PTR(d_state_in); CHECK_PTR(d_pos_out); CHECK_PTR(d_state_out);
+    rc = check_aligned(__func__, {{"d_pos_in", d_pos_in, ALIGN_FLOW2}, {"d_pos_out", d_pos_out, ALIGN_FLOW2}, {"d_back", d_back, ALIGN_FLOW2},
+                                  {"d_state_in", d_state_in, 4}, {"d_state_out", d_state_out, 4}, {"d_err", d_err, 4}, {"d_counts", d_counts, 4}});
+    if (rc) return rc;
+    // a lane group reads its own slot before it writes it: d_pos_out may be d_pos_in and d_state_out may be d_state_in, nothing else
+    rc = check_distinct(__func__, {{"d_pyr1", d_pyr1}, {"d_pyr2", d_pyr2}, {"d_pos_in", d_pos_in}, {"d_state_in", d_state_in}},
+                        {{"d_pos_out", d_pos_out == d_pos_in ? nullptr : d_pos_out},
+                         {"d_state_out", d_state_out == d_state_in ? nullptr : d_state_out}, {"d_err", d_err}, {"d_back", d_back},
+                         {"d_counts", d_counts}});
+    if (rc) return rc;
+    return launch_klt_track(h, w, levels, d_pyr1, d_pyr2, cap, d_pos_in, d_state_in, r, iters, eps, min_eig, max_err, fb, d_pos_out,
+                            d_state_out, d_err, d_back, d_counts, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1587,6 +1587,37 @@ class TrackSet:
         self._counts["advance"] = cnt
         return self
 
+    def seed_corners(self, pyr, **corner_args):
+        """Starts a track at every corner of the pyramid's level 0 (corners) that no live track of the set suppresses, at the
+        current frame.  The set must have been built with step=1: a corner is a pixel, and a cell must be one."""
+        if self.step != 1:
+            raise ValueError("TrackSet.seed_corners: the set must be built with step=1 (a corner is one pixel), this one has step=%d" % self.step)
+        for name in ("tracks", "response", "counts"):
+            if name in corner_args:
+                raise ValueError("TrackSet.seed_corners: %s is not an argument here" % name)
+        mask, cnt = corners(pyr, self.h, self.w, tracks=(self.pos, self.state, self.n), counts=True, **corner_args)
+        self._counts["corners"] = cnt
+        return self.seed(mask)
+
+    def advance_klt(self, pyr1, pyr2, levels=None, **klt_args):
+        """Carries the set from the frame of pyr1 to the frame of pyr2 by pyramidal Lucas-Kanade (klt_track) and makes the result
+        the current frame: snapshots, frame counter and counts as in advance().  levels: those of the two klt_pyramid buffers;
+        None reads it off the length of pyr1."""
+        for name in ("inplace", "err", "counts"):
+            if name in klt_args:
+                raise ValueError("TrackSet.advance_klt: %s is not an argument here" % name)
+        if levels is None:
+            fit = [k for k in range(1, _lib.KLT_LEVELS_MAX + 1) if klt_pyramid_len(self.h, self.w, k) == len(pyr1)]
+            if not fit:
+                raise ValueError("TrackSet.advance_klt: pyr1 holds %d bytes, no pyramid of a %dx%d frame does" % (len(pyr1), self.w, self.h))
+            levels = fit[0]
+        pos, state, cnt = klt_track(pyr1, pyr2, self.h, self.w, levels, self.pos, self.state, counts=True, **klt_args)
+        self.pos, self.state = pos, state
+        self.snapshots.append((pos, state))
+        self.frame += 1
+        self._counts["advance"] = cnt
+        return self
+
     def flow(self, a, b, owner=False, counts=False):
         """The sparse flow from frame a to frame b (track_flow) of the tracks alive in both."""
         for name, v in (("a", a), ("b", b)):
@@ -1597,7 +1628,8 @@ class TrackSet:
 
     def counts(self):
         """The int32 device tensors of the last seed() (TRACK_SEED_COUNTS) and the last advance() (TRACK_ADVANCE_COUNTS), None
-        where there was none: {"seed": ..., "advance": ...}.  Nothing is read back."""
+        where there was none: {"seed": ..., "advance": ...}.  After seed_corners() there is "corners" (CORNER_COUNTS) as well, and
+        after advance_klt() "advance" holds KLT_TRACK_COUNTS.  Nothing is read back."""
         return dict(self._counts)
 
     def read(self):
@@ -1610,6 +1642,141 @@ class TrackSet:
         birth = self.birth[:n].cpu().numpy()
         pos[np.arange(len(self.snapshots))[:, None] < birth[None, :]] = np.nan
         return dict(pos=pos, state=state, birth=birth, length=(state == _lib.TRACK_LIVE).sum(0).astype(np.int32))
+
+
+# ---------------------------------------------------------------------- sparse feature tracking (csrc/klt.hip)
+TRACK_STATES_KLT = TRACK_STATES + ("flat", "residual")
+CORNER_COUNTS = ("candidates", "maxima", "suppressed", "corners")
+KLT_TRACK_COUNTS = ("live", "left", "flat", "residual", "inconsistent", "not_live", "converged", "reserved")
+
+
+def klt_pyramid_len(h, w, levels):
+    """The bytes of the grey pyramid of an (h, w) frame: level l is ((h_l+1)//2, (w_l+1)//2) of level l-1, one after the other."""
+    total = 0
+    for _ in range(int(levels)):
+        total += int(h) * int(w)
+        h, w = (int(h) + 1) // 2, (int(w) + 1) // 2
+    return total
+
+
+def _klt_levels(fn, levels):
+    if not (isinstance(levels, (int, np.integer)) and 1 <= levels <= _lib.KLT_LEVELS_MAX):
+        raise ValueError("%s: levels must be an int in [1, %d], got %r" % (fn, _lib.KLT_LEVELS_MAX, levels))
+    return int(levels)
+
+
+def _klt_float(fn, name, v, positive=False):
+    ok = isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(np.float32(v))
+    if not ok or not (np.float32(v) > 0 if positive else np.float32(v) >= 0):
+        raise ValueError("%s: %s must be finite and %s 0 as a float32, got %r" % (fn, name, ">" if positive else ">=", v))
+    return float(np.float32(v))
+
+
+def klt_pyramid(img, levels=3):
+    """The grey pyramid of a (H,W,3) uint8 BGR image (dflow_klt_pyramid, DESIGN.md "Sparse feature tracking"): level 0 is
+    (29 b + 150 g + 77 r + 128) >> 8, every further level pyr_down's 5x5 binomial of the one before at half the size.  Returns one
+    uint8 device tensor of klt_pyramid_len(H, W, levels) bytes, the levels one after the other: what corners and klt_track take.
+    A device tensor or a host array; runs on torch's current stream and does not wait for it."""
+    fn = "klt_pyramid"
+    img = _check(img, fn, "img", torch.uint8, (None, None, 3))
+    levels = _klt_levels(fn, levels)
+    H, W = _track_frame(fn, img.shape[0], img.shape[1])
+    dev = _device_of(img)
+    img, = _on(dev, img)
+    pyr = torch.empty(klt_pyramid_len(H, W, levels), dtype=torch.uint8, device=dev)
+    _lib.call("dflow_klt_pyramid", H, W, levels, img.data_ptr(), pyr.data_ptr(), _lib.stream(dev))
+    return pyr
+
+
+def _klt_pyr(fn, name, pyr, h, w, levels):
+    pyr = _check(pyr, fn, name, torch.uint8, (None,))
+    if pyr.numel() < klt_pyramid_len(h, w, levels):
+        raise ValueError("%s: %s holds %d bytes, a %dx%d pyramid of %d levels has %d" % (fn, name, pyr.numel(), w, h, levels,
+                                                                                          klt_pyramid_len(h, w, levels)))
+    return pyr
+
+
+def corners(pyr, h, w, rc=2, min_dist=4, border=4, quality=0.01, min_response=0.0, tracks=None, response=False, counts=False):
+    """Shi-Tomasi corners of level 0 of a pyramid (dflow_corners): R is the smaller eigenvalue of the structure tensor of the
+    central differences over the (2 rc + 1)^2 window; a corner is a pixel at least `border` from the frame's edge with R > 0,
+    R >= quality * max R and R >= min_response that is the maximum of its (2 min_dist + 1)^2 neighbourhood (ties: the smaller
+    raster index) and has no live track of `tracks` = (pos, state, n), a track set as track_seed takes it, in that
+    neighbourhood.  Returns the (h,w) uint8 mask, 255 at a corner: what track_seed(step=1, mask=...) turns into tracks, in raster
+    order; or a tuple (mask[, response][, counts]): the (h,w) float32 plane of R, the int32[4] device tensor CORNER_COUNTS.
+    Runs on torch's current stream and does not wait for it."""
+    fn = "corners"
+    h, w = _track_frame(fn, h, w)
+    pyr = _klt_pyr(fn, "pyr", pyr, h, w, 1)
+    rc, min_dist, border = _int_in(fn, "rc", rc, 1, 7), _int_in(fn, "min_dist", min_dist, 1, 32), _int_in(fn, "border", border, 0, 8192)
+    quality, min_response = _klt_float(fn, "quality", quality), _klt_float(fn, "min_response", min_response)
+    if quality > 1:
+        raise ValueError("%s: quality must be in [0, 1], got %r" % (fn, quality))
+    pos = state = n = None
+    if tracks is not None:
+        pos, state = _track_set(fn, tracks[0], tracks[1])
+        n = tracks[2]
+        if isinstance(n, (int, np.integer)):
+            n = torch.tensor([min(max(int(n), -2 ** 31), 2 ** 31 - 1)], dtype=torch.int32)
+        n = _check(n, fn, "n", torch.int32, (1,))
+    dev = _device_of(pyr, *([pos, state, n] if tracks is not None else []))
+    pyr, = _on(dev, pyr)
+    occ = None
+    if tracks is not None:
+        pos, state, n = _track_planes(dev, pos, state, n)
+        occ = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    resp = torch.empty((h, w), dtype=torch.float32, device=dev)
+    mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    rmax = torch.empty(1, dtype=torch.int32, device=dev)
+    cnt = _out(counts, 4, torch.int32, dev)
+    _lib.call("dflow_corners", h, w, pyr.data_ptr(), rc, min_dist, border, quality, min_response, pos.shape[0] if tracks is not None else 0,
+              _ptr(pos), _ptr(state), _ptr(n), resp.data_ptr(), mask.data_ptr(), _ptr(occ), rmax.data_ptr(), _ptr(cnt), _lib.stream(dev))
+    ret = tuple(t for t in (mask, resp if response else None, cnt) if t is not None)
+    return ret if len(ret) > 1 else mask
+
+
+def klt_track(pyr1, pyr2, h, w, levels, pos, state, r=7, iters=20, eps=0.01, min_eig=1.0, max_err=0.0, fb=0.5, inplace=False,
+              err=False, counts=False):
+    """A track set carried from the frame of pyr1 to the frame of pyr2 by pyramidal Lucas-Kanade (dflow_klt_track): every LIVE
+    track is followed through the `levels` levels of the two klt_pyramid buffers with a (2r+1)^2 window, at most `iters`
+    Gauss-Newton steps per level, stopping below `eps` pixels.  It ends, keeping its position, when it leaves the frame (LEFT), when
+    the smaller eigenvalue of its window's gradient matrix is below min_eig grey^2/px^2 at level 0 (FLAT), when its mean absolute
+    residual exceeds max_err grey levels (RESIDUAL; 0: no test), or when tracking back from pyr2 to pyr1 does not return within fb
+    pixels (INCONSISTENT; 0: no backward pass).  pos (cap,2) float32 [x,y], state (cap) int32 (TRACK_STATES_KLT); device tensors
+    or host arrays.  Returns (pos, state[, err][, counts]) as track_advance does: err=True adds the (cap) float32 residual (-1
+    where none was formed), counts=True the int32[8] device tensor KLT_TRACK_COUNTS.  Runs on torch's current stream and does not
+    wait for it."""
+    fn = "klt_track"
+    h, w = _track_frame(fn, h, w)
+    levels = _klt_levels(fn, levels)
+    pyr1, pyr2 = _klt_pyr(fn, "pyr1", pyr1, h, w, levels), _klt_pyr(fn, "pyr2", pyr2, h, w, levels)
+    pos, state = _track_set(fn, pos, state)
+    r, iters = _int_in(fn, "r", r, 1, 10), _int_in(fn, "iters", iters, 1, 64)
+    eps = _klt_float(fn, "eps", eps, positive=True)
+    min_eig, max_err, fb = _klt_float(fn, "min_eig", min_eig), _klt_float(fn, "max_err", max_err), _klt_float(fn, "fb", fb)
+    dev = _device_of(pos, state, pyr1, pyr2)
+    pyr1, pyr2 = _on(dev, pyr1, pyr2)
+    pos, state = _track_planes(dev, pos, state)
+    cap = pos.shape[0]
+    pos_out, state_out = (pos, state) if inplace else (torch.empty_like(pos), torch.empty_like(state))
+    extra = [_out(err, cap, torch.float32, dev), _out(counts, 8, torch.int32, dev)]
+    _lib.call("dflow_klt_track", h, w, levels, pyr1.data_ptr(), pyr2.data_ptr(), cap, pos.data_ptr(), state.data_ptr(), r, iters, eps,
+              min_eig, max_err, fb, 0, pos_out.data_ptr(), state_out.data_ptr(), _ptr(extra[0]), None, _ptr(extra[1]), _lib.stream(dev))
+    return tuple(t for t in [pos_out, state_out] + extra if t is not None)
+
+
+def klt_sparse_flow(img1, img2, levels=3, cap=None, corner_args=None, **klt_args):
+    """The sparse flow img1 -> img2 without a dense pass: pyramids -> corners -> klt_track -> track_flow.  Returns the (H,W,3)
+    float32 [U,V,valid] device tensor epic_interpolate, motion_fit, epipolar_fit, segment_filter and flow_eval take, valid at the
+    corners of img1 whose track is live in img2.  cap: the most corners that are followed (default: one per 16 pixels)."""
+    fn = "klt_sparse_flow"
+    img1 = _check(img1, fn, "img1", torch.uint8, (None, None, 3))
+    H, W = img1.shape[0], img1.shape[1]
+    img2 = _check(img2, fn, "img2", torch.uint8, (H, W, 3))
+    ts = TrackSet(H, W, cap=cap if cap is not None else max(1, H * W // 16), step=1, device=_device_of(img1, img2))
+    pyr1, pyr2 = klt_pyramid(img1, levels), klt_pyramid(img2, levels)
+    ts.seed_corners(pyr1, **(corner_args or {}))
+    ts.advance_klt(pyr1, pyr2, levels=levels, **klt_args)
+    return ts.flow(0, 1)
 
 
 def pyramid_levels(pich, picw, levels=2, cellh=None, cellw=None, fine_window=None, **overrides):
